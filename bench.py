@@ -20,6 +20,13 @@ there are (always strong).
 Plain `python bench.py --gpus N` with N > 1 starts its own N ranks (fresh children under torch.distributed.run, before this process
 touches the GPU) and relays rank 0's line; under torch.distributed.run it is one of the ranks.
 
+A plain run only sets up, warms up, times the --steps launches and prints the line.  Everything else it can measure -- the CPU baseline,
+the replay kernels, the other estimators, configs 3 and 5, the shard timings, the end-to-end sweep, the drop-in latency, power under load,
+the strong series of a weak multi-rank run -- runs only with --full.  --dump-outputs DIR writes what the last timed launch computed as
+DIR/<name>.npy (float64): `stats` [trials][ISE, IAE, ITAE], `status` and `k_done` of every trial (a seeded sample of 65 536 trials when
+there are more), and the per-step streams `x`, `err`, `q` as [trial][step][comp] for a seeded sample of trials (at most 256, fewer where
+the streams of 256 trials would exceed 48 MB).
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields, incl. `roofline` and `cpu_baseline`).
 """
 import argparse
@@ -530,6 +537,38 @@ def compact_line(line):
     return walk(line, ())
 
 
+DUMP_ROW_TRIALS = 65536              # per-trial rows of at most this many trials (2.6 MB)
+DUMP_STREAM_TRIALS = 256             # per-step streams of at most this many trials ...
+DUMP_STREAM_BYTES = 48 << 20         # ... and at most this many bytes: the whole dump stays below 64 MB
+
+
+def dump_outputs(out_dir, torch, engine, bufs, layout, stats, status, k_done, gathered=None):
+    """--dump-outputs: what the last timed launch handed its caller, as float64 DIR/<name>.npy, so that two builds can be compared output for
+    output.  Per-trial rows -- `stats` [ISE, IAE, ITAE], `status`, `k_done`, and with ranks the all-gathered `trial_rows` [ISE, IAE, ITAE,
+    status] -- of every trial, or of a seeded sample of DUMP_ROW_TRIALS; the per-step streams `x`, `err`, `q` as [trial][step][comp] of a
+    seeded sample of trials.  The samples depend on the trial count alone: the same arguments pick the same trials."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(n, cap):
+        return np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+
+    def save(name, t, idx):
+        np.save(os.path.join(out_dir, name + '.npy'), t[torch.as_tensor(idx, device=t.device)].to(torch.float64).cpu().numpy())
+
+    T = stats.shape[0]
+    rows = sample(T, DUMP_ROW_TRIALS)
+    for name, t in (('stats', stats), ('status', status), ('k_done', k_done)):
+        save(name, t, rows)
+    if gathered is not None:
+        save('trial_rows', gathered, sample(gathered.shape[0], DUMP_ROW_TRIALS))
+    if bufs is not None:
+        tkc = {name: engine.as_tkc(t, layout) for name, t in bufs.items()}
+        per_trial = sum(t.shape[1] * t.shape[2] for t in tkc.values()) * 8
+        idx = sample(T, max(1, min(DUMP_STREAM_TRIALS, DUMP_STREAM_BYTES // per_trial)))
+        for name, t in tkc.items():
+            save(name, t, idx)
+
+
 PROFILER_ENV_PREFIXES = ('ROCP', 'ROCTRACER', 'HSA_TOOLS', 'ROCTX')
 
 
@@ -628,13 +667,18 @@ def main():
     ap.add_argument('--e2e', action='store_true', help='only the headline and the end-to-end sweep side object')
     ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end sweep side object (counter passes: its 49 launches of the headline kernel on other noise would be averaged in)')
     ap.add_argument('--backend', default=None, choices=['nccl', 'gloo'], help='torch.distributed backend (default: nccl = RCCL when every rank has a GPU of its own, gloo when ranks must share cards -- a 1-GPU box)')
-    ap.add_argument('--latency', action='store_true', help='UVS_OPT_LATENCY on the timed launch: plain four-lane kernels for shards that do not fill the chip (a few % faster than the default small-batch kernels; results differ from the default mapping in the last bits)')
+    ap.add_argument('--latency', action='store_true', help='UVS_OPT_LATENCY on the timed launch: plain four-lane kernels for shards that do not fill the chip (a few %% faster than the default small-batch kernels; results differ from the default mapping in the last bits)')
     ap.add_argument('--no-strong-series', action='store_true', help='N > 1, weak: skip the strong-series side measurement')
     ap.add_argument('--no-power', action='store_true', help='skip the power / clock samples under load (about 3 s of extra launches)')
     ap.add_argument('--stats-only', action='store_true', help='do not write the per-step X / err / q streams (separate line, B = noise read only)')
     ap.add_argument('--host-noise', action='store_true', help='generate the noise streams with numpy on the host (default: HIP generator)')
     ap.add_argument('--layout', default=None, choices=['kct', 'ktc', 'tkc'], help='physical layout of the per-step streams (default: trial-fastest kct; config 5: per-trial records ktc)')
+    ap.add_argument('--full', action='store_true', help='also run every side measurement (CPU baseline, replay, other estimators, configs 3 / 5, shard timings, '
+                                                        'end-to-end sweep, drop-in latency, power, strong series); the --no-* options above trim this set')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed launch computed as DIR/<name>.npy (float64, < 64 MB in all)')
     args = ap.parse_args()
+    if args.e2e:                                                  # names a side object: only --full runs it
+        args.full = True
     if under_profiler():                                          # rocprofv3 pass: no helper children from a GPU-initialised process, no 49 extra launches in the counters
         args.no_power = args.no_e2e = True
 
@@ -676,7 +720,7 @@ def main():
     workers = max(1, cores // max(1, world))
     cpu = None
     assert not (args.host_noise and args.config not in (2, 4)), '--host-noise is wired for the config-2 inputs only'
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 2:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 2:
         cpu = cpu_baseline(plan.q_start)
     noise_host, gen_s = None, 0.0
     if args.host_noise:
@@ -711,10 +755,12 @@ def main():
         else:                                                     # NoiseProfiler-compatible streams generated on the GPU
             noise = batch.device_noise(cfg, plan, lo, hi, K, dev, share=False)          # first call: + one-time table upload / torch warm-up
             torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            noise = batch.device_noise(cfg, plan, lo, hi, K, dev, share=False)          # what one more sweep cell costs
-            torch.cuda.synchronize()
-            gen_s = time.perf_counter() - t1
+            gen_s = None
+            if args.full:
+                t1 = time.perf_counter()
+                noise = batch.device_noise(cfg, plan, lo, hi, K, dev, share=False)      # what one more sweep cell costs
+                torch.cuda.synchronize()
+                gen_s = time.perf_counter() - t1
         if args.layout != 'kct':                                  # generated as [step][comp][trial]
             noise = noise.permute({'ktc': (0, 2, 1), 'tkc': (2, 0, 1)}[args.layout]).contiguous()
         q0 = torch.as_tensor(plan.q_start[lo:hi].copy(), device=dev)
@@ -808,9 +854,12 @@ def main():
     else:
         total_updates, failed_total = updates_per_launch, failed_local
     value = total_updates * args.steps / wall
+    if args.dump_outputs and rank == 0:                           # before any side measurement: they re-use these buffers
+        dump_outputs(args.dump_outputs, torch, engine, None if args.stats_only else bufs, args.layout, stats, status, k_done,
+                     gathered if dist_on else None)
 
     strong_side = None
-    if dist_on and world > 1 and scaling == 'weak' and args.config == 2 and not args.stats_only and not args.no_strong_series:
+    if args.full and dist_on and world > 1 and scaling == 'weak' and args.config == 2 and not args.stats_only and not args.no_strong_series:
         # north_star's series -- ONE 65 536-trial batch over the N ranks -- timed in the same job, with the same barriers and the same gather,
         # right after the weak run (side object: never `value`).  Rank r owns dist.shard_range(65 536, r, N) of the global enumeration.
         cfg_s = config2()
@@ -894,9 +943,9 @@ def main():
                         'fp64_flops': (fl / (avg_ms * 1e-3)) if fl else None, 'fp64_peak_flops': FP64_VECTOR_PEAK_FLOPS,
                         'fp64_frac': (fl / (avg_ms * 1e-3) / FP64_VECTOR_PEAK_FLOPS) if fl else None,
                         'source': 'instruction counts per launch from the committed PMC passes (SQ_INSTS_VALU, SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64), divided by this run\'s kernel time'}
-        side_ok = world == 1 and headline_shape and not args.no_side
+        side_ok = args.full and world == 1 and headline_shape and not args.no_side
         replay = None
-        if world == 1 and args.config == 2 and not args.no_replay and not args.e2e and not args.stats_only and args.layout == 'kct' and args.lanes in (0, 2):
+        if args.full and world == 1 and args.config == 2 and not args.no_replay and not args.e2e and not args.stats_only and args.layout == 'kct' and args.lanes in (0, 2):
             replay = replay_side_measurement(torch, engine, uvs_amd, fp, plant, q0, bufs['x'], bufs['err'], T, K, M, N)
         others = None
         if side_ok and not args.e2e:
@@ -1020,7 +1069,7 @@ def main():
                     entry[mode] = {'kernel_ms': float(np.mean(ms)), 'lanes_per_filter': int(uvs_amd.lib().uvs_rmckf_closed_loop_lanes(C.byref(fp_m), C.byref(plant), Ts))}
                 shard_model['mckf'][f'N={n_ranks}'] = entry
         power = None
-        if world == 1 and not args.no_power:                       # after the short side measurements above (seconds of sustained load change what follows)
+        if args.full and world == 1 and not args.no_power:                     # after the short side measurements above (seconds of sustained load change what follows)
             power = power_under_load(torch, launch, torch.cuda.current_device())
         if power and valu:                                         # the issue peak at the clock the part actually sustains under this kernel
             clk = float(np.mean(power['sclk_mhz'])) * 1e6

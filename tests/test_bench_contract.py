@@ -73,9 +73,61 @@ def test_plain_gpus_n_starts_its_own_ranks_and_a_failing_rank_is_loud(tmp_path):
     assert res.returncode != 0 and 'WORLD_SIZE=3' in res.stderr and 'torch.distributed.run' in res.stderr
 
 
+@pytest.mark.parametrize('layout,M,N,T,row_cap', [('kct', 8, 6, 300, 65536), ('ktc', 32, 7, 100, 65536), ('tkc', 8, 6, 90, 64)])
+def test_dump_outputs_writes_bounded_seeded_samples(tmp_path, monkeypatch, layout, M, N, T, row_cap):
+    """--dump-outputs: float64 .npy files of what the launch returned, [trial][step][comp] streams of a seeded trial sample, under 64 MB in
+    all, the same trials on every call.  (32,7): the byte cap bounds the stream sample; row_cap < T: the per-trial rows are sampled too."""
+    import torch
+    import bench
+    from uvs_amd import engine
+    monkeypatch.setattr(bench, 'DUMP_ROW_TRIALS', row_cap)
+    K = 299
+    g = torch.Generator().manual_seed(1)
+    shape = lambda c: {'kct': (K, c, T), 'ktc': (K, T, c), 'tkc': (T, K, c)}[layout]     # noqa: E731 -- engine.alloc_stream's, on the host
+    bufs = {k: torch.rand(shape(c), generator=g, dtype=torch.float64) for k, c in (('x', M * N), ('err', M), ('q', N))}
+    stats = torch.rand((T, 3), generator=g, dtype=torch.float64)
+    status = torch.randint(0, 2, (T,), generator=g, dtype=torch.int32)
+    k_done = torch.randint(1, K + 1, (T,), generator=g, dtype=torch.int32)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), torch, engine, bufs, layout, stats, status, k_done)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b')) == ['err.npy', 'k_done.npy', 'q.npy', 'stats.npy', 'status.npy', 'x.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) < 64 << 20
+    out = {n[:-4]: np.load(tmp_path / 'a' / n) for n in names}
+    for n in names:
+        assert np.array_equal(out[n[:-4]], np.load(tmp_path / 'b' / n)) and out[n[:-4]].dtype == np.float64
+    rows = min(T, bench.DUMP_ROW_TRIALS)
+    assert out['stats'].shape == (rows, 3) and out['status'].shape == out['k_done'].shape == (rows,)
+    S = out['x'].shape[0]
+    assert 1 <= S <= min(T, bench.DUMP_STREAM_TRIALS) and out['x'].shape == (S, K, M * N) and out['err'].shape == (S, K, M) and out['q'].shape == (S, K, N)
+    tkc = engine.as_tkc(bufs['err'], layout).numpy()
+    hit = [t for t in range(T) if np.array_equal(tkc[t], out['err'][0])]     # the dumped rows are trials of the launch, whole
+    assert len(hit) == 1 and np.array_equal(engine.as_tkc(bufs['x'], layout).numpy()[hit[0]], out['x'][0])
+    if T <= bench.DUMP_ROW_TRIALS:
+        assert np.array_equal(out['stats'], stats.numpy()) and np.array_equal(out['k_done'], k_done.numpy())
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times the steps and prints the line without any side measurement; --dump-outputs writes the last step's outputs."""
+    import bench
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--trials', '4096', '--dump-outputs', str(tmp_path)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['ms_per_step'] > 0 and abs(d['value'] - 4096 * 299 / (d['ms_per_step'] * 1e-3)) / d['value'] < 1e-6
+    assert d['cpu_baseline'] is None and d['replay'] is None and d['roofline']['power'] is None and d['other_estimators'] is None
+    out = {n[:-4]: np.load(os.path.join(tmp_path, n)) for n in os.listdir(tmp_path)}
+    assert sorted(out) == ['err', 'k_done', 'q', 'stats', 'status', 'x']
+    assert out['stats'].shape == (4096, 3) and np.all(out['status'] == 0) and np.all(out['k_done'] == 299)
+    assert out['x'].shape == (bench.DUMP_STREAM_TRIALS, 299, 48) and np.all(np.isfinite(out['x'])) and np.all(np.isfinite(out['err']))
+
+
 @pytest.mark.gpu
 def test_bench_line_contract():
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--trials', '4096', '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--trials', '4096', '--no-cpu-baseline', '--full']
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]

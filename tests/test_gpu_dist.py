@@ -168,8 +168,8 @@ def _plain_bench(*bench_args, expect_rc0=True):
 def test_plain_bench_gpus_2_launches_its_own_ranks():
     """the driver's command shape with --gpus 2 on a 1-GPU box.  The parent starts two fresh ranks before touching the GPU;
     with one visible card the ranks share it and the gather falls back to gloo (said so in the line).  Default series: weak (per-GPU work
-    fixed); north_star's strong series of the same job rides along as multi_gpu.strong_series."""
-    d = _plain_bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--no-side', '--no-cpu-baseline', '--trials', '4096')
+    fixed); with --full, north_star's strong series of the same job rides along as multi_gpu.strong_series."""
+    d = _plain_bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--full', '--no-side', '--no-cpu-baseline', '--trials', '4096')
     assert d['n_gpus'] == 2 and d['config']['ranks_seen'] == 2 and d['scaling'] == 'weak' and d['config']['trials_total'] == 8192
     assert d['config']['trials_rank0'] == 4096 and d['config']['failed_trials'] == 0
     assert d['multi_gpu']['gather_ms'] > 0 and d['multi_gpu']['gather_inside_timed_region'] is True

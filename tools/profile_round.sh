@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the rocprofv3 evidence for profiles/<round>/ on the GPU box.  usage: tools/profile_round.sh <outdir under gpurun_out>
 # Kernel-trace statistics and PMC counters are separate passes (never --pmc together with other trace domains); the program after
-# `--` is python3 itself.  The traced command is the driver's: bench.py --steps 20 --warmup 5 (minus the host CPU baseline).
+# `--` is python3 itself.  The traced command is bench.py --steps 20 --warmup 5 --full (minus the host CPU baseline): the side measurements are traced too.
 set -u
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/${1:-prof}
@@ -10,9 +10,9 @@ cd /tmp && export TMPDIR=/tmp
 # which kernels these counts belong to: the library's version string carries the fingerprint of its kernel sources (csrc/src_hash.py)
 python3 -c "import sys; sys.path.insert(0, '$REPO'); import uvs_amd; print(uvs_amd.lib().uvs_version().decode())" > $OUT/library_version.txt
 # the un-profiled line first: a profiled run clocks 2-3 % lower (MI355X_MICROARCH.md, DVFS give-back)
-UVS_BENCH_FULL_JSON=$OUT/bench_full.json python3 $REPO/bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err
+UVS_BENCH_FULL_JSON=$OUT/bench_full.json python3 $REPO/bench.py --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 echo "bench line done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-power > $OUT/stats_bench.json 2> $OUT/stats_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-e2e --no-power > $OUT/stats_bench.json 2> $OUT/stats_bench.err
 echo "kernel trace done"
 i=0
 for pass in "FETCH_SIZE" "WRITE_SIZE" \
@@ -21,7 +21,7 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" \
             "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM_WR SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU" \
             "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/pmc_$i -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-power > $OUT/pmc_$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/pmc_$i -- python3 $REPO/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-e2e --no-power > $OUT/pmc_$i.log 2>&1
   echo "pmc pass $i done"
 done
 cd $REPO
