@@ -44,7 +44,8 @@ extern "C" {
 #define UVS_ERR_HIP (-3)      /* HIP runtime error (see uvs_last_error)     */
 #define UVS_ERR_METHOD (-4)   /* estimator not available on this path       */
 
-/* experiment.py:6-11 (Method) and :13-15 (ExperimentStatus) */
+/* experiment.py:6-11 (Method) and :13-15 (ExperimentStatus).  ANALYTICAL (the calibrated baseline) has its own entry point,
+ * uvs_analytical_closed_loop_f64; the estimator entry points refuse it with UVS_ERR_METHOD. */
 enum { UVS_METHOD_ANALYTICAL = 1, UVS_METHOD_KF = 2, UVS_METHOD_MCKF = 3, UVS_METHOD_IMCCKF = 4, UVS_METHOD_GMCKF = 5 };
 enum { UVS_STATUS_SUCCESS = 0, UVS_STATUS_FAIL = 1 };
 
@@ -186,6 +187,27 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
                                  uvs_view x_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out,
                                  double *stats, int32_t *status, int32_t *k_done,
                                  uvs_view x_final, uvs_view p_final, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Calibrated IBVS baseline: T closed-loop trials of Method.ANALYTICAL (experiment.py:145-162, :300-320) on the synthetic DH / pinhole plant,
+ * the same loop clock, plant and noise as uvs_rmckf_closed_loop_f64 but with the interaction matrix computed instead of estimated.  Per step:
+ * f = features + noise; J_feature = J_image(noisy raw-pixel u, v; Z = Euclidean camera-disc distance) kron(I2, R^T) J_robot (the row
+ * formulas of the analytic initial guess, experiment.py:101-112); dq = -gain pinv(J_feature) (f - desired_f) (kappa = 1); q += dq dt.
+ * A non-finite J_feature makes pinv raise in the reference: status FAIL, k_done = that step, nothing logged for it (:313-316).
+ *   fp       method must be UVS_METHOD_ANALYTICAL (else UVS_ERR_METHOD); (m, n) = (8, 6) only (else UVS_ERR_SHAPE); m, n, steps, k_max, gain,
+ *            dt, desired are read, the estimator fields are ignored; reserved: UVS_OPT_STRICT_PINV or 0 (else UVS_ERR_ARG)
+ *   plant    UVS_PLANT_DH_PINHOLE with n_points = 4, n_joints = 6 (a linear plant: UVS_ERR_ARG)
+ *   q_start  [T][1][n] in;  noise [T][K][m] in (NULL = none)
+ *   j_out    [T][K][m*n] out  J_feature the control law used at step k, row-major (NULL to skip)
+ *   err_out, q_out, f_out, dq_out, stats, k_done  out  as for uvs_rmckf_closed_loop_f64 (NULL to skip)
+ *   status   [T] int32 out  REQUIRED: carries the marks of the two-pass scheme below
+ * Two passes as for the estimators: Householder least squares with the default watches (UVS_OPT_STRICT_PINV: every solve certified by the
+ * cond_2 bound from the inverse of the triangular factor) stops a trial at its first suspect solve; a careful kernel enqueued right behind
+ * it re-runs exactly those trials with numpy's pinv semantics (SVD of the factor, numpy's cutoff).
+ */
+int uvs_analytical_closed_loop_f64(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T, uvs_view q_start, uvs_view noise,
+                                   uvs_view j_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out, double *stats,
+                                   int32_t *status, int32_t *k_done, void *stream);
 
 /*
  * Open-loop replay of recorded streams through the estimator + control law

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('UVS_LIB_PATH', os.path.join(HERE, 'libuvs_rmckf.so'))
 CSRC = os.path.join(HERE, 'csrc')
 
 UVS_MAX_M, UVS_MAX_N, UVS_MAX_POINTS = 32, 8, 16
-METHOD_KF, METHOD_MCKF, METHOD_IMCCKF, METHOD_GMCKF = 2, 3, 4, 5
+METHOD_ANALYTICAL, METHOD_KF, METHOD_MCKF, METHOD_IMCCKF, METHOD_GMCKF = 1, 2, 3, 4, 5
 PLANT_DH_PINHOLE, PLANT_LINEAR = 0, 1
 
 
@@ -65,6 +65,7 @@ SYMBOLS = {
     'uvs_rmckf_closed_loop_segments': (C.c_int, [C.POINTER(FilterParams), C.POINTER(Plant), _I64]),
     'uvs_rmckf_closed_loop_workspace_bytes': (C.c_size_t, [C.POINTER(FilterParams), C.POINTER(Plant), _I64]),
     'uvs_rmckf_closed_loop_fallback_offset': (C.c_size_t, [C.POINTER(FilterParams), C.POINTER(Plant), _I64]),
+    'uvs_analytical_closed_loop_f64': (C.c_int, [C.POINTER(FilterParams), C.POINTER(Plant), _I64] + [View] * 7 + [_VP] * 3 + [_VP]),
     'uvs_rmckf_replay_f64': (C.c_int, [C.POINTER(FilterParams), _I64] + [View] * 7 + [_VP] * 2 + [View] * 2 + [_VP]),
     'uvs_rmckf_replay_f32': (C.c_int, [C.POINTER(FilterParams), _I64] + [View] * 5 + [_VP] * 2 + [_VP]),
     'uvs_rmckf_step_f64': (C.c_int, [C.POINTER(FilterParams), _I64] + [_VP] * 5 + [_I32, _I32] + [_VP] * 4 + [_VP]),

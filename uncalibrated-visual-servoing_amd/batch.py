@@ -136,6 +136,16 @@ def device_noise(cfg, plan, lo, hi, steps, device='cuda', share=True):
     return out
 
 
+def _check_analytical(method, lanes, latency):
+    """True for the calibrated baseline (Method.ANALYTICAL, engine.analytical_closed_loop: one lane per trial, so the estimators' lane options
+    do not apply); the reference's Experiment.run() crashes there (R unbound, experiment.py:121) in two lines only the estimators use."""
+    if method != Method.ANALYTICAL:
+        return False
+    if lanes or latency:
+        raise ValueError('lanes / latency select estimator kernels; the ANALYTICAL closed loop has one mapping (strict_pinv applies)')
+    return True
+
+
 def run_batch(cfg, plant=None, cells=None, epoch=None, rank=0, world=1, want=('err',), lanes=0, noise_tensor=None,
               device='cuda', noise_on_device=True, strict_pinv=False, latency=False):
     """Run this rank's shard of the sweep on its GPU.  Returns a BatchResult whose tensors stay on the device.
@@ -147,16 +157,15 @@ def run_batch(cfg, plant=None, cells=None, epoch=None, rank=0, world=1, want=('e
     cfg = load_config(cfg)
     ex, est = cfg['experiments'], cfg['estimator']
     method = Method[est['method']]
-    if method == Method.ANALYTICAL:
-        raise NotImplementedError('ANALYTICAL is not an estimator (and crashes in the reference: R is unbound, experiment.py:121)')
+    analytical = _check_analytical(method, lanes, latency)
     plant = SyntheticPlant.ur10(ex['desired_f']) if plant is None else plant
     plan = plan_trials(cfg, cells, epoch)
     lo, hi = dist.shard_range(len(plan), rank, world)
-    p = est['estimator_params']
+    p = est.get('estimator_params') or {}
     m, n = len(ex['desired_f']), plant.n_joints
     fp = engine.make_params(m, n, method.name, p.get('kernel_bw', 1.0), p.get('annealing', False), ex['dt'], ex['t_max'],
-                            ex['ibvs_gain'], ex['desired_f'], p['initial_guess'], lanes, None, p.get('fpi_threshold', 0.1),
-                            p.get('fpi_epoch_max', 1000))
+                            ex['ibvs_gain'], ex['desired_f'], p.get('initial_guess', True) if analytical else p['initial_guess'], lanes, None,
+                            p.get('fpi_threshold', 0.1), p.get('fpi_epoch_max', 1000))
     fp.reserved = (1 if strict_pinv else 0) | (2 if latency else 0)
     t_log = engine.loop_clock(ex['dt'], ex['t_max'])
     K, Tl = len(t_log), hi - lo
@@ -170,13 +179,16 @@ def run_batch(cfg, plant=None, cells=None, epoch=None, rank=0, world=1, want=('e
             noise_tensor = torch.as_tensor(host, device=dev)
         q0 = torch.as_tensor(plan.q_start[lo:hi].copy(), device=dev)
         x0 = None
-        if not p['initial_guess']:
+        if not analytical and not p['initial_guess']:
             x0 = torch.as_tensor(np.asarray(p['x0'], float).reshape(1, m * n).repeat(Tl, 0), device=dev)
-        out = engine.closed_loop(fp, plant.to_struct(), q0, noise_tensor, x0, want=want)
+        if analytical:
+            out = engine.analytical_closed_loop(fp, plant.to_struct(), q0, noise_tensor, want=want)
+        else:
+            out = engine.closed_loop(fp, plant.to_struct(), q0, noise_tensor, x0, want=want)
     start, stop = out['events']                                     # HIP events around the kernel launch (output allocation excluded)
     stop.synchronize()
     return BatchResult(plan, lo, hi, t_log, out['stats'], out['status'], out['k_done'],
-                       {k: out[k] for k in ('x', 'err', 'q', 'f', 'dq') if out.get(k) is not None}, noise_tensor,
+                       {k: out[k] for k in ('x', 'j', 'err', 'q', 'f', 'dq') if out.get(k) is not None}, noise_tensor,
                        start.elapsed_time(stop) * 1e-3)
 
 
@@ -232,6 +244,7 @@ def run_sweep(cfg, plant=None, cells=None, epoch=None, rank=0, world=1, want=(),
     """See _run_sweep.  The engine launches on the CURRENT device's current stream: the sweep runs with ``device`` made current, so that the events
     that order the row copies against the kernels are recorded on the stream the kernels are launched on."""
     import torch
+    _check_analytical(Method[load_config(cfg)['estimator']['method']], lanes, latency)    # (before any device work)
     dev = torch.device(device)
     with torch.cuda.device(dev if dev.index is not None else torch.cuda.current_device()):
         return _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, torch.device('cuda', torch.cuda.current_device()), max_trials, share_noise,
@@ -253,8 +266,7 @@ def _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, device, max_t
     cfg = load_config(cfg)
     ex, est, nz = cfg['experiments'], cfg['estimator'], cfg['noise']
     method = Method[est['method']]
-    if method == Method.ANALYTICAL:
-        raise NotImplementedError('ANALYTICAL is not an estimator (and crashes in the reference: R is unbound, experiment.py:121)')
+    analytical = _check_analytical(method, lanes, latency)
     plant = SyntheticPlant.ur10(ex['desired_f']) if plant is None else plant
     if plan is None:
         plan = plan_trials(cfg, cells, epoch)
@@ -267,11 +279,11 @@ def _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, device, max_t
                 (len(plan) and not ex['change_q_start'] and not np.array_equal(plan.q_start[0], np.asarray(ex['q_start'], float))):
             raise ValueError('run_sweep(plan=...): the plan does not belong to this config / cells / epoch')
     lo, hi = dist.shard_range(len(plan), rank, world)
-    p = est['estimator_params']
+    p = est.get('estimator_params') or {}
     m, n = len(ex['desired_f']), plant.n_joints
     fp = engine.make_params(m, n, method.name, p.get('kernel_bw', 1.0), p.get('annealing', False), ex['dt'], ex['t_max'],
-                            ex['ibvs_gain'], ex['desired_f'], p['initial_guess'], lanes, None, p.get('fpi_threshold', 0.1),
-                            p.get('fpi_epoch_max', 1000))
+                            ex['ibvs_gain'], ex['desired_f'], p.get('initial_guess', True) if analytical else p['initial_guess'], lanes, None,
+                            p.get('fpi_threshold', 0.1), p.get('fpi_epoch_max', 1000))
     fp.reserved = (1 if strict_pinv else 0) | (2 if latency else 0)
     K = len(engine.loop_clock(ex['dt'], ex['t_max']))
     dev = torch.device(device)
@@ -288,13 +300,14 @@ def _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, device, max_t
     plant_struct = plant.to_struct()
     q0 = torch.as_tensor(plan.q_start[lo:hi].copy(), device=dev)
     x0 = None
-    if not p['initial_guess']:
+    if not analytical and not p['initial_guess']:
         x0 = torch.as_tensor(np.asarray(p['x0'], float).reshape(1, m * n).repeat(Tmax, 0), device=dev)
     seeds_dev = torch.as_tensor(np.ascontiguousarray(plan.seed[lo:hi], dtype=np.uint64).view(np.int64), device=dev)
     # two sets of per-trial outputs (a set is copied out while the next piece writes the other), one set of streams, one noise buffer
     S = Tmax + noise_device.SEED_STEP * (m - 1)
     noise_buf = torch.empty(K * max(S, m * Tmax), dtype=torch.float64, device=dev)
-    streams = {k_: engine.alloc_stream(Tmax, K, c, 'kct', dev) for k_, c in (('x', m * n), ('err', m), ('q', n), ('f', m), ('dq', n)) if k_ in want}
+    streams = {k_: engine.alloc_stream(Tmax, K, c, 'kct', dev) for k_, c in (('x', m * n), ('j', m * n), ('err', m), ('q', n), ('f', m), ('dq', n))
+               if k_ in want}
     sets = []
     for _ in range(2):                                             # the streams are allocated ONCE and shared by both sets (7.5 GB of X per 65 536 trials)
         d = dict(streams)
@@ -322,7 +335,10 @@ def _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, device, max_t
             noise_device.generate(noise_type, params, seeds_dev[a - lo:b - lo], m, K, nz['hold'], hold_cnt, 'kct', out=noise, device=dev)
         if i >= 2:
             main.wait_event(copied[i - 2])                          # this set's previous rows have left the device
-        out = engine.closed_loop(fp, plant_struct, q0[a - lo:b - lo], noise, None if x0 is None else x0[:T], want=want, reuse=sets[i % 2])
+        if analytical:
+            out = engine.analytical_closed_loop(fp, plant_struct, q0[a - lo:b - lo], noise, want=want, reuse=sets[i % 2])
+        else:
+            out = engine.closed_loop(fp, plant_struct, q0[a - lo:b - lo], noise, None if x0 is None else x0[:T], want=want, reuse=sets[i % 2])
         done = torch.cuda.Event()
         done.record(main)
         copier.wait_event(done)

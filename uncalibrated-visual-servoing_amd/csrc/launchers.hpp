@@ -6,7 +6,7 @@
 #include <cstdint>
 #include "rmckf_device.hpp"
 
-namespace uvs { struct ReplayArgs32; }
+namespace uvs { struct ReplayArgs32; struct AnalyticalArgs; }
 
 // (m, n, lanes-per-filter) instantiations of the generic templates; the first listed L of a shape is its default.
 #ifdef UVS_QUICK                      // experiment builds (make quick): the headline shape only, compiles in seconds
@@ -66,6 +66,8 @@ bool replay_rows_cmd(int m, int n, int method, int64_t T, hipStream_t s, const u
 bool replay_rows(int m, int n, int method, bool bywave, bool xo, bool eo, int64_t T, hipStream_t s, const uvs::ReplayArgs &A);
 // single-precision estimator-only replay (rmckf_replay_f32.hpp): (8,6), KF / IMCC-KF / RMCKF
 bool replay_f32(int m, int n, int method, int64_t T, hipStream_t s, const uvs::ReplayArgs32 &A);
+// calibrated IBVS baseline (analytical.hpp): (8,6), DH plant; careful = the second pass over the trials marked UVS_STATUS_SUSPECT
+bool analytical(int m, int n, bool careful, int64_t T, hipStream_t s, const uvs::AnalyticalArgs &A);
 // everything else
 void stats(long long T, int K, int m, uvs::View err, const double *t, const int *k_done, double *stats, hipStream_t s);
 void debug_math(int which, long long n, const double *x, double *y, hipStream_t s);

@@ -874,14 +874,11 @@ UVS_DEV void plant_features(const uvs_plant &pl, const double (&q)[N], int sub, 
     }
 }
 
-// Analytic initial guess X0 = J_img kron(I2, R^T) J_robot for this lane's rows, plus the noise-free f
-// at q (experiment.py:86-114; geometric Jacobian ur10_simulation.py:112-139).
-template <int M, int N, int L>
-UVS_DEV void initial_guess(const uvs_plant &pl, const double (&q)[N], int sub, double (&x)[M / L][N], double (&f)[M / L]) {
-    constexpr int R = M / L;
-    double rot[9], pos[3], zs[N][3], ps[N][3];
+// Camera-frame twist Jacobian Jc = kron(I2, R^T) J_robot at joints q (geometric Jacobian ur10_simulation.py:112-139), with the camera pose.
+template <int N>
+UVS_DEV void camera_jacobian(const uvs_plant &pl, const double (&q)[N], double (&rot)[9], double (&pos)[3], double (&Jc)[6][N]) {
+    double zs[N][3], ps[N][3];
     forward_kinematics<N, true>(pl, q, rot, pos, zs, ps);
-    double Jc[6][N];                                                        // camera-frame twist Jacobian kron(I2, R^T) J
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         double z[3], o[3];
@@ -898,6 +895,40 @@ UVS_DEV void initial_guess(const uvs_plant &pl, const double (&q)[N], int sub, d
             Jc[3 + r][i] = fma(rot[r], z[0], fma(rot[3 + r], z[1], rot[6 + r] * z[2]));
         }
     }
+}
+
+// computeZ: Euclidean distance |cam - disc| (not a z-depth)
+UVS_DEV double point_depth(const double (&pos)[3], const double *w) {
+    const double ddx = pos[0] - w[0], ddy = pos[1] - w[1], ddz = pos[2] - w[2];
+    return sqrt(fma(ddx, ddx, fma(ddy, ddy, ddz * ddz)));
+}
+
+// Row `row` of the image Jacobian at pixel coordinates (u, v) -- raw pixels, no principal-point shift -- and depth, then the feature
+// Jacobian row x = ji Jc (experiment.py:101-112 for the initial guess, :151-162 for Method.ANALYTICAL).
+template <int N>
+UVS_DEV void feature_jacobian_row(double F, double u, double v, double depth, int row, const double (&Jc)[6][N], double (&x)[N]) {
+    double ji[6];
+    if ((row & 1) == 0) {                                                    // experiment.py:101-109 (u row)
+        ji[0] = -F / depth; ji[1] = 0.0; ji[2] = u / depth; ji[3] = u * v / F; ji[4] = -(F * F + u * u) / F; ji[5] = v;
+    } else {                                                                 // experiment.py:102-110 (v row)
+        ji[0] = 0.0; ji[1] = -F / depth; ji[2] = v / depth; ji[3] = (F * F + v * v) / F; ji[4] = -u * v / F; ji[5] = -u;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc = fma(ji[k], Jc[k][j], acc);
+        x[j] = acc;
+    }
+}
+
+// Analytic initial guess X0 = J_img kron(I2, R^T) J_robot for this lane's rows, plus the noise-free f
+// at q (experiment.py:86-114; geometric Jacobian ur10_simulation.py:112-139).
+template <int M, int N, int L>
+UVS_DEV void initial_guess(const uvs_plant &pl, const double (&q)[N], int sub, double (&x)[M / L][N], double (&f)[M / L]) {
+    constexpr int R = M / L;
+    double rot[9], pos[3], Jc[6][N];                                        // camera-frame twist Jacobian kron(I2, R^T) J
+    camera_jacobian<N>(pl, q, rot, pos, Jc);
     const double F = pl.focal;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -905,23 +936,8 @@ UVS_DEV void initial_guess(const uvs_plant &pl, const double (&q)[N], int sub, d
         const double *w = pl.points[row >> 1];
         const double u = project_axis(rot, pos, w, 0, F, pl.center);
         const double v = project_axis(rot, pos, w, 1, F, pl.center);
-        const double ddx = pos[0] - w[0], ddy = pos[1] - w[1], ddz = pos[2] - w[2];
-        const double depth = sqrt(fma(ddx, ddx, fma(ddy, ddy, ddz * ddz)));  // computeZ: |cam - disc|
-        double ji[6];
-        if ((row & 1) == 0) {                                                // experiment.py:101-109 (u row)
-            ji[0] = -F / depth; ji[1] = 0.0; ji[2] = u / depth; ji[3] = u * v / F; ji[4] = -(F * F + u * u) / F; ji[5] = v;
-            f[r] = u;
-        } else {                                                             // experiment.py:102-110 (v row)
-            ji[0] = 0.0; ji[1] = -F / depth; ji[2] = v / depth; ji[3] = (F * F + v * v) / F; ji[4] = -u * v / F; ji[5] = -u;
-            f[r] = v;
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) acc = fma(ji[k], Jc[k][j], acc);
-            x[r][j] = acc;
-        }
+        feature_jacobian_row<N>(F, u, v, point_depth(pos, w), row, Jc, x[r]);
+        f[r] = (row & 1) == 0 ? u : v;
     }
 }
 

@@ -13,6 +13,7 @@
 #include "uvs_rmckf.h"
 #include "launchers.hpp"
 #include "rmckf_replay_f32.hpp"
+#include "analytical.hpp"
 
 #ifndef UVS_MCKF_TAPER_PCT               // length of the last segment of an MCKF trial in % of the first (linear in between): 100 / 50 / 25 / 10 % measured
 #define UVS_MCKF_TAPER_PCT 10            // 4.32 / 4.12 / 4.07 / 4.04 ms at 8 segments (unsegmented 4.43), 4.96 / 4.91 / 4.73 / 4.64 on alpha = 1.0 (5.51)
@@ -256,6 +257,35 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
     if (!(closed_careful_a(fp->m, fp->n, T, s, A) || closed_careful_b(fp->m, fp->n, T, s, A)))
         return fail(UVS_ERR_SHAPE, "%s", "(m, n) has no careful closed-loop instantiation in libuvs_rmckf");
     return check_launch("closed_loop_kernel (careful pass)");
+}
+
+int uvs_analytical_closed_loop_f64(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T, uvs_view q_start, uvs_view noise,
+                                   uvs_view j_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out, double *stats,
+                                   int32_t *status, int32_t *k_done, void *stream) {
+    if (!fp) return fail(UVS_ERR_ARG, "%s", "filter params are NULL");
+    if (fp->method != UVS_METHOD_ANALYTICAL) return fail(UVS_ERR_METHOD, "%s", "uvs_analytical_closed_loop_f64 runs Method.ANALYTICAL only");
+    if (fp->m != 8 || fp->n != 6) return fail(UVS_ERR_SHAPE, "%s", "the calibrated closed loop is instantiated for (m, n) = (8, 6) only");
+    if (T <= 0) return fail(UVS_ERR_ARG, "%s", "T must be positive");
+    if (fp->steps < 0 || fp->k_max <= 0) return fail(UVS_ERR_ARG, "%s", "steps must be >= 0 and k_max > 0");
+    if (fp->reserved & ~UVS_OPT_STRICT_PINV) return fail(UVS_ERR_ARG, "%s", "only UVS_OPT_STRICT_PINV applies to the calibrated closed loop");
+    if (!plant) return fail(UVS_ERR_ARG, "%s", "plant is NULL");
+    if (plant->kind != UVS_PLANT_DH_PINHOLE) return fail(UVS_ERR_ARG, "%s", "the calibrated closed loop needs the DH/pinhole plant");
+    if (plant->n_joints != fp->n || plant->n_points * 2 != fp->m) return fail(UVS_ERR_ARG, "%s", "plant does not match (m, n)");
+    if (!q_start.base) return fail(UVS_ERR_ARG, "%s", "q_start view is NULL");
+    if (!status) return fail(UVS_ERR_ARG, "%s", "status is required (it also carries the suspect marks between the two passes)");
+    uvs::AnalyticalArgs A;
+    A.fp = *fp;
+    A.plant = *plant;
+    A.T = T;
+    A.q_start = uvs::to_view(q_start); A.noise = uvs::to_view(noise); A.j_out = uvs::to_view(j_out);
+    A.err_out = uvs::to_view(err_out); A.q_out = uvs::to_view(q_out); A.f_out = uvs::to_view(f_out); A.dq_out = uvs::to_view(dq_out);
+    A.stats = stats; A.status = status; A.k_done = k_done;
+    hipStream_t s = (hipStream_t)stream;
+    if (!analytical(fp->m, fp->n, false, T, s, A)) return fail(UVS_ERR_SHAPE, "%s", "(m, n) is not instantiated in libuvs_rmckf");
+    if (int rc = check_launch("analytical_kernel")) return rc;
+    // second pass: trials whose first pass met a suspect (or, under UVS_OPT_STRICT_PINV, an uncertified) solve, redone with numpy's pinv
+    analytical(fp->m, fp->n, true, T, s, A);
+    return check_launch("analytical_kernel (careful pass)");
 }
 
 int uvs_rmckf_replay_f64(const uvs_filter_params *fp, int64_t T, uvs_view f, uvs_view dq, uvs_view x0, uvs_view x_out,

@@ -21,3 +21,4 @@
 #include "tu_replay_tuned.hip"
 #include "tu_replay_f32.hip"
 #include "tu_misc.hip"
+#include "tu_analytical.hip"

@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import FilterParams, View, NULL_VIEW
 
-METHOD_CODES = {'KF': 2, 'MCKF': 3, 'IMCCKF': 4, 'GMCKF': 5}
+METHOD_CODES = {'ANALYTICAL': 1, 'KF': 2, 'MCKF': 3, 'IMCCKF': 4, 'GMCKF': 5}
 REG = 0.001 ** 2            # experiment.py:280
 ANNEAL_SPAN = 100.0         # experiment.py:271
 
@@ -174,6 +174,40 @@ def closed_loop(fp, plant_struct, q_start, noise=None, x0=None, want=('x', 'err'
         stream_view(out['f'], layout), stream_view(out['dq'], layout),
         out['stats'].data_ptr(), out['status'].data_ptr(), out['k_done'].data_ptr(),
         flat(out['x_final']), flat(out['p_final']), ws, ws_bytes, _stream())
+    stop.record()
+    _lib.check(rc)
+    out['events'] = (start, stop)
+    return out
+
+
+def analytical_closed_loop(fp, plant_struct, q_start, noise=None, want=('err', 'q'), layout='kct', reuse=None):
+    """Launch T closed-loop trials of the calibrated IBVS baseline (Method.ANALYTICAL, uvs_analytical_closed_loop_f64): the interaction matrix
+    is computed from the plant at every step instead of estimated.  Arguments and the returned dict as for ``closed_loop``, with the stream
+    ``'j'`` (J_feature the control law used, m*n per step) in place of ``'x'``; ``fp.method`` must be ANALYTICAL (make_params(..., 'ANALYTICAL'))."""
+    torch = _torch()
+    T, K, m, n = q_start.shape[0], fp.steps, fp.m, fp.n
+    dev = q_start.device
+    out = {'x': None}
+    tdim = {'kct': 2, 'ktc': 1, 'tkc': 0}[layout]
+    for key, comp in (('j', m * n), ('err', m), ('q', n), ('f', m), ('dq', n)):
+        if key not in want:
+            out[key] = None
+        elif reuse is not None:
+            out[key] = reuse[key].narrow(tdim, 0, T)
+        else:
+            out[key] = alloc_stream(T, K, comp, layout, dev)           # rows at and after k_done are unspecified
+    if reuse is not None:
+        out['stats'], out['status'], out['k_done'] = reuse['stats'][:T], reuse['status'][:T], reuse['k_done'][:T]
+    else:
+        out['stats'] = torch.zeros((T, 3), dtype=torch.float64, device=dev)
+        out['status'] = torch.zeros(T, dtype=torch.int32, device=dev)
+        out['k_done'] = torch.zeros(T, dtype=torch.int32, device=dev)
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    rc = _lib.lib().uvs_analytical_closed_loop_f64(
+        C.byref(fp), C.byref(plant_struct), T, View(q_start.data_ptr(), q_start.stride(0), 0, q_start.stride(1)), stream_view(noise, layout),
+        stream_view(out['j'], layout), stream_view(out['err'], layout), stream_view(out['q'], layout), stream_view(out['f'], layout),
+        stream_view(out['dq'], layout), out['stats'].data_ptr(), out['status'].data_ptr(), out['k_done'].data_ptr(), _stream())
     stop.record()
     _lib.check(rc)
     out['events'] = (start, stop)
