@@ -78,20 +78,58 @@ def test_strict_pinv_replay_matches_reference_everywhere(uvs, name, lanes):
     assert set(out['status'].cpu().numpy().tolist()) == {0} and int(out['k_done'][0]) == K
 
 
-@pytest.mark.parametrize('lanes,strict', [(0, False), (2, False), (4, False), (1, False), (-2, False), (0, True)])
-def test_closed_loop_on_the_kahan_fixture(uvs, lanes, strict):
-    """Closed loop from the Kahan-like X0 (VERDICT r4 #5): the reference's trajectory -- its truncated command is ~1e-5 rad/s, the plain
-    least-squares one is hundreds of times larger -- in the DEFAULT mode on every lane mapping (the growth watch marks the trial at its first
-    solve), and with UVS_OPT_STRICT_PINV as before."""
-    g = load_golden(KAHAN)
-    K = len(g['t'])
+def _kahan_closed_loop(uvs, g, fp, T=3):
     plant = uvs.SyntheticPlant.ur10(scene_desired(g)).to_struct()
-    args = (plant, _cuda(np.tile(g['q_start'], (3, 1))), _cuda(np.repeat(g['noise'][:, :, None], 3, axis=2)), _cuda(np.tile(g['X'][0], (3, 1))))
-    out = uvs.engine.closed_loop(_fp(uvs, g, lanes, strict=strict), *args, want=('x', 'err', 'q', 'dq'))
+    args = (plant, _cuda(np.tile(g['q_start'], (T, 1))), _cuda(np.repeat(g['noise'][:, :, None], T, axis=2)), _cuda(np.tile(g['X'][0], (T, 1))))
+    return uvs.engine.closed_loop(fp, *args, want=('x', 'err', 'q', 'dq'))
+
+
+def _assert_follows_the_reference(g, out):
+    K = len(g['t'])
     assert out['status'].cpu().tolist() == [0] * 3 and out['k_done'].cpu().tolist() == [K] * 3
     err, q, X, dq = (out[k].cpu().numpy()[:, :, 1] for k in ('err', 'q', 'x', 'dq'))
     assert rel_err(err, g['err']) <= 1e-7 and rel_err(q, g['q']) <= 1e-7 and rel_err(X[g['X_steps']], g['X']) <= 1e-7
     assert rel_err(dq[:K - 1], g['dq_prev'][1:]) <= 1e-6
+
+
+@pytest.mark.parametrize('lanes,strict', [(0, False), (2, False), (4, False), (1, False), (-2, False), (0, True), (1, True), (2, True), (4, True)])
+def test_closed_loop_on_the_kahan_fixture(uvs, lanes, strict):
+    """Closed loop from the Kahan-like X0 (VERDICT r4 #5): the reference's trajectory -- its truncated command is ~1e-5 rad/s, the plain
+    least-squares one is hundreds of times larger -- in the DEFAULT mode on every lane mapping (the growth watch marks the trial at its first
+    solve), and with UVS_OPT_STRICT_PINV on every tuned lane mapping (the certificate marks it)."""
+    g = load_golden(KAHAN)
+    _assert_follows_the_reference(g, _kahan_closed_loop(uvs, g, _fp(uvs, g, lanes, strict=strict)))
+
+
+def test_kahan_fixture_on_the_small_batch_routes(uvs):
+    """Three trials run on four lanes per filter: the EMU2 kernel in the default mode, the plain four-lane kernel under UVS_OPT_LATENCY with
+    UVS_OPT_STRICT_PINV (certified first pass).  Both follow the reference."""
+    import ctypes as C
+    g = load_golden(KAHAN)
+    plant = uvs.SyntheticPlant.ur10(scene_desired(g)).to_struct()
+    for reserved in (0, 1 | 2):                                                         # default; UVS_OPT_STRICT_PINV | UVS_OPT_LATENCY
+        fp = _fp(uvs, g)
+        fp.reserved = reserved
+        assert int(uvs.lib().uvs_rmckf_closed_loop_lanes(C.byref(fp), C.byref(plant), 3)) == 4
+        _assert_follows_the_reference(g, _kahan_closed_loop(uvs, g, fp))
+
+
+@pytest.mark.parametrize('lanes', (0, 2, 4))
+@pytest.mark.parametrize('method', ('KF', 'IMCCKF', 'MCKF'))
+def test_strict_pinv_on_the_kahan_fixture_equals_the_careful_pass(uvs, method, lanes):
+    """The fixture pins RMCKF only.  For the other estimators strict mode must leave the trial to the careful pass: its first solve sees the
+    Kahan-like X0, which a certifying first pass marks.  So a strict run equals the all-careful run (lanes_per_filter = -2)."""
+    g = load_golden(KAHAN)
+    outs = []
+    for ln in (lanes, -2):
+        fp = _fp(uvs, g, ln, strict=True)
+        fp.method = {'KF': 2, 'MCKF': 3, 'IMCCKF': 4}[method]
+        outs.append(_kahan_closed_loop(uvs, g, fp))
+    a, b = outs
+    assert a['status'].cpu().tolist() == b['status'].cpu().tolist() and a['k_done'].cpu().tolist() == b['k_done'].cpu().tolist()
+    k = int(b['k_done'].min())
+    for key in ('err', 'q'):
+        assert rel_err(a[key].cpu().numpy()[:k], b[key].cpu().numpy()[:k]) <= 1e-9, key
 
 
 def test_strict_pinv_agrees_with_the_fast_path_on_healthy_trials(uvs):

@@ -1,9 +1,10 @@
 // Host-side launch functions, one translation unit per kernel family so that the library builds in parallel (make -j):
-// the C ABI (uvs_rmckf.hip) validates arguments and asks each family in turn; a launcher returns false when it has no
-// instantiation for the request.  The shape tables live here.
+// the C ABI (uvs_rmckf.hip) validates arguments, picks the family (closed loop: plan_closed_loop) and calls its launcher, which
+// returns false when it has no instantiation for the request.  The shape tables live here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 #include "rmckf_device.hpp"
 
 namespace uvs { struct ReplayArgs32; struct AnalyticalArgs; }
@@ -42,13 +43,42 @@ namespace uvs_launch {
 
 inline dim3 grid_for(int64_t T, int L) { return dim3((unsigned)((T * L + 63) / 64)); }
 
-// tuned closed loop (rmckf_tuned.hpp): method in {KF, IMCCKF, GMCKF}
+// Run-time value -> template argument: f(std::integral_constant<int, V>{}) for the V of the list that equals v; false when none does, else
+// what f returns (true for a void f).  Each family passes the list of what it instantiates (closed_wide has no MCKF kernel), so no other
+// value is ever instantiated.
+template <int... VS, class F>
+bool dispatch(int v, F &&f) {
+    auto call = [&](auto c) {
+        if constexpr (std::is_void_v<decltype(f(c))>) return (f(c), true);
+        else return f(c);
+    };
+    return ((v == VS && call(std::integral_constant<int, VS>{})) || ...);
+}
+// Run-time flags -> template arguments: f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...), every combination instantiated.
+template <class F>
+void with_flags(F &&f) { f(); }
+template <class F, class... B>
+void with_flags(F &&f, bool a, B... rest) {
+    if (a) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// Does the first pass of the tuned closed-loop kernel certify every solve under UVS_OPT_STRICT_PINV?  It does when the solve goes through
+// lstsq_tall_tuned with strict on: RMCKF reads the option at run time, KF / IMCC-KF / MCKF have CERT instantiations at (8,6), two lanes,
+// DH plant (rmckf_tuned.hpp).  EMU2 (lstsq_tall_emu2) does not, nor does the wide kernel (normal equations).  launch2 picks the CERT
+// instantiations by it, plan_closed_loop decides by it between a certified first pass and the careful pass alone.
+constexpr bool tuned_certifies(int m, int n, int L, int method, bool linear, bool emu2) {
+    return !emu2 && (method == UVS_METHOD_GMCKF || (m == 8 && n == 6 && L == 2 && !linear));
+}
+
+// tuned closed loop (rmckf_tuned.hpp): method in {KF, IMCCKF, GMCKF}, MCKF on two lanes
 bool closed_tuned_a(int m, int n, int L, int method, bool linear, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
 bool closed_tuned_b(int m, int n, int L, int method, bool linear, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
-// four lanes per filter with the two-lane kernel's bits (EMU2): (8,6), DH plant, KF / IMCC-KF / RMCKF -- the automatic choice for batches that do not fill the chip
-bool closed_tuned_emu2(int m, int n, int method, bool linear, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
-// tuned wide-shape closed loop (rmckf_wide.hpp): (32,7), lanes_per_filter = 8 (the default of that shape for the closed loop)
-bool closed_wide(int m, int n, int L, int method, bool linear, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
+// four lanes per filter with the two-lane kernel's bits (EMU2): (8,6), DH plant -- the automatic choice for batches that do not fill the chip
+bool closed_tuned_emu2(int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
+// tuned wide-shape closed loop (rmckf_wide.hpp), KF / IMCC-KF / RMCKF: (32,7) on the linear plant at 8 or 16 lanes per filter, (8,6) on the
+// DH plant at 8 (one row per lane)
+bool closed_wide(int m, int n, int L, int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
 // generic templates (rmckf_generic.hpp)
 bool closed_generic_a(int m, int n, int L, int method, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
 bool closed_generic_b(int m, int n, int L, int method, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);

@@ -9,9 +9,9 @@ namespace {
 template <int M, int N, int LL, int METHOD, int PLANT, bool EMU2 = false>
 void launch2(bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
     constexpr int PV = (LL == 2 ? M / LL / 2 : M / LL);      // L = 2 parks half of its blocks in LDS; 1 and 4 keep all in registers
-    // UVS_OPT_STRICT_PINV on KF / IMCC-KF / MCKF: the instantiations whose control law certifies every solve (a compile-time switch there, see CERT in
-    // rmckf_tuned.hpp; RMCKF reads the option at run time); MCKF as whole trials
-    if constexpr (METHOD != UVS_METHOD_GMCKF && M == 8 && N == 6 && LL == 2 && PLANT != UVS_PLANT_LINEAR && !EMU2) {
+    // UVS_OPT_STRICT_PINV on KF / IMCC-KF / MCKF: the instantiations whose control law certifies every solve (uvs_launch::tuned_certifies; a compile-time
+    // switch there, see CERT in rmckf_tuned.hpp; RMCKF reads the option at run time); MCKF as whole trials
+    if constexpr (METHOD != UVS_METHOD_GMCKF && uvs_launch::tuned_certifies(M, N, LL, METHOD, PLANT == UVS_PLANT_LINEAR, EMU2)) {
         if (A.fp.reserved & UVS_OPT_STRICT_PINV) {
             constexpr bool SEGM = (METHOD == UVS_METHOD_MCKF);
             if (xo) hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, true, false, SEGM, false, true>), g, dim3(64), 0, s, A);
@@ -68,37 +68,24 @@ void launch_dh(bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
     }
     launch2<M, N, LL, METHOD, UVS_PLANT_DH_PINHOLE, EMU2>(xo, g, s, A);
 }
-template <int M, int N, int LL>
+template <int M, int N, int LL, bool EMU2 = false>
 bool launch(int method, bool linear, bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
-    if constexpr (LL == 2) {                                       // first-pass MCKF rows: two-lane kernels only
-        if (method == UVS_METHOD_MCKF) {
-            if (!linear) launch_dh<M, N, LL, UVS_METHOD_MCKF>(xo, g, s, A);
-            else launch2<M, N, LL, UVS_METHOD_MCKF, UVS_PLANT_LINEAR>(xo, g, s, A);
-            return true;
-        }
-    }
-    if (method == UVS_METHOD_MCKF) return false;
-    if (method == UVS_METHOD_GMCKF && !linear) launch_dh<M, N, LL, UVS_METHOD_GMCKF>(xo, g, s, A);
-    else if (method == UVS_METHOD_GMCKF) launch2<M, N, LL, UVS_METHOD_GMCKF, UVS_PLANT_LINEAR>(xo, g, s, A);
-    else if (method == UVS_METHOD_IMCCKF && !linear) launch_dh<M, N, LL, UVS_METHOD_IMCCKF>(xo, g, s, A);
-    else if (method == UVS_METHOD_IMCCKF) launch2<M, N, LL, UVS_METHOD_IMCCKF, UVS_PLANT_LINEAR>(xo, g, s, A);
-    else if (!linear) launch_dh<M, N, LL, UVS_METHOD_KF>(xo, g, s, A);
-    else launch2<M, N, LL, UVS_METHOD_KF, UVS_PLANT_LINEAR>(xo, g, s, A);
-    return true;
+    auto go = [&](auto meth) {
+        constexpr int METHOD = decltype(meth)::value;
+        if (!linear) launch_dh<M, N, LL, METHOD, EMU2>(xo, g, s, A);
+        else if constexpr (!EMU2) launch2<M, N, LL, METHOD, UVS_PLANT_LINEAR>(xo, g, s, A);
+    };
+    if constexpr (LL == 2 || EMU2)                                 // first-pass MCKF rows: two-lane kernels (and EMU2) only
+        return uvs_launch::dispatch<UVS_METHOD_MCKF, UVS_METHOD_GMCKF, UVS_METHOD_IMCCKF, UVS_METHOD_KF>(method, go);
+    else
+        return uvs_launch::dispatch<UVS_METHOD_GMCKF, UVS_METHOD_IMCCKF, UVS_METHOD_KF>(method, go);
 }
 }  // namespace
 #endif
 
 #ifdef UVS_TU_EMU2                      // this translation unit also carries the four-lane kernels with the two-lane kernel's bits (rmckf_tuned.hpp, EMU2)
-bool uvs_launch::closed_tuned_emu2(int m, int n, int method, bool linear, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A) {
-    if (m != 8 || n != 6 || linear) return false;
-    const dim3 g = grid_for(T, 4);
-    if (method == UVS_METHOD_GMCKF) launch_dh<8, 6, 4, UVS_METHOD_GMCKF, true>(xo, g, s, A);
-    else if (method == UVS_METHOD_IMCCKF) launch_dh<8, 6, 4, UVS_METHOD_IMCCKF, true>(xo, g, s, A);
-    else if (method == UVS_METHOD_KF) launch_dh<8, 6, 4, UVS_METHOD_KF, true>(xo, g, s, A);
-    else if (method == UVS_METHOD_MCKF) launch_dh<8, 6, 4, UVS_METHOD_MCKF, true>(xo, g, s, A);   // (round 5: every fixed-point pass in-kernel, as on two lanes)
-    else return false;
-    return true;
+bool uvs_launch::closed_tuned_emu2(int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A) {
+    return launch<8, 6, 4, true>(method, false, xo, grid_for(T, 4), s, A);
 }
 #endif
 

@@ -20,27 +20,14 @@ void launch_latency(bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
 }
 }  // namespace
 
-bool uvs_launch::closed_wide(int m, int n, int L, int method, bool linear, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A) {
-    if (m == 8 && n == 6 && L == 8 && !linear) {                  // (explicit lanes_per_filter = 8 only: measured, not faster than four lanes)
-        const dim3 g8 = grid_for(T, L);
-        if (method == UVS_METHOD_GMCKF) launch_latency<UVS_METHOD_GMCKF>(xo, g8, s, A);
-        else if (method == UVS_METHOD_IMCCKF) launch_latency<UVS_METHOD_IMCCKF>(xo, g8, s, A);
-        else if (method == UVS_METHOD_KF) launch_latency<UVS_METHOD_KF>(xo, g8, s, A);
+bool uvs_launch::closed_wide(int m, int n, int L, int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A) {
+    const dim3 g = grid_for(T, L);
+    return dispatch<UVS_METHOD_GMCKF, UVS_METHOD_IMCCKF, UVS_METHOD_KF>(method, [&](auto meth) {
+        constexpr int METHOD = decltype(meth)::value;
+        if (m == 8 && n == 6 && L == 8) launch_latency<METHOD>(xo, g, s, A);   // (explicit lanes_per_filter = 8 only: measured, not faster than four lanes)
+        else if (m == 32 && n == 7 && L == 8) launch_wide<32, 7, 8, METHOD>(xo, g, s, A);
+        else if (m == 32 && n == 7 && L == 16) launch_wide<32, 7, 16, METHOD>(xo, g, s, A);
         else return false;
         return true;
-    }
-    if (m != 32 || n != 7 || (L != 8 && L != 16) || !linear || A.fp.initial_guess) return false;
-    const dim3 g = grid_for(T, L);
-    if (L == 8) {
-        if (method == UVS_METHOD_GMCKF) launch_wide<32, 7, 8, UVS_METHOD_GMCKF>(xo, g, s, A);
-        else if (method == UVS_METHOD_IMCCKF) launch_wide<32, 7, 8, UVS_METHOD_IMCCKF>(xo, g, s, A);
-        else if (method == UVS_METHOD_KF) launch_wide<32, 7, 8, UVS_METHOD_KF>(xo, g, s, A);
-        else return false;
-    } else {
-        if (method == UVS_METHOD_GMCKF) launch_wide<32, 7, 16, UVS_METHOD_GMCKF>(xo, g, s, A);
-        else if (method == UVS_METHOD_IMCCKF) launch_wide<32, 7, 16, UVS_METHOD_IMCCKF>(xo, g, s, A);
-        else if (method == UVS_METHOD_KF) launch_wide<32, 7, 16, UVS_METHOD_KF>(xo, g, s, A);
-        else return false;
-    }
-    return true;
+    });
 }

@@ -40,11 +40,12 @@ int check_launch(const char *what) {
     return UVS_OK;
 }
 
-int default_lanes(int m, int n, int method) {
-    // (MCKF: the tuned two-lane kernels run the first fixed-point pass and leave trials that need more to the careful second pass,
-    // whose generic template carries the Cholesky factors of the blocks -- four lanes per filter there, at two they go to scratch)
-    (void)method;
-#define X(M, N, L) if (m == M && n == N) return L;
+// lanes_per_filter resolved: |value| (a negative one forces the generic template), or the shape's default for 0; 0 = shape not instantiated.
+// (MCKF: the tuned two-lane kernels run the first fixed-point pass and leave trials that need more to the careful second pass, whose
+// generic template carries the Cholesky factors of the blocks -- four lanes per filter there, at two they go to scratch)
+int resolve_lanes(const uvs_filter_params &fp) {
+    if (fp.lanes_per_filter) return fp.lanes_per_filter < 0 ? -fp.lanes_per_filter : fp.lanes_per_filter;
+#define X(M, N, L) if (fp.m == M && fp.n == N) return L;
     UVS_SHAPES(X)
 #undef X
     return 0;
@@ -57,29 +58,117 @@ int check_params(const uvs_filter_params *fp, int64_t T, int *lanes) {
     if (fp->method != UVS_METHOD_KF && fp->method != UVS_METHOD_MCKF && fp->method != UVS_METHOD_IMCCKF && fp->method != UVS_METHOD_GMCKF)
         return fail(UVS_ERR_METHOD, "%s", "method must be KF, MCKF, IMCCKF or GMCKF");
     if (fp->method == UVS_METHOD_MCKF && fp->fpi_epoch_max < 1) return fail(UVS_ERR_ARG, "%s", "MCKF needs fpi_epoch_max >= 1");
-    const int L = fp->lanes_per_filter < 0 ? -fp->lanes_per_filter : (fp->lanes_per_filter ? fp->lanes_per_filter : default_lanes(fp->m, fp->n, fp->method));
+    const int L = resolve_lanes(*fp);
     if (L == 0) return fail(UVS_ERR_SHAPE, "%s", "(m, n) is not instantiated in libuvs_rmckf");
     *lanes = L;
     return UVS_OK;
 }
 
-// Four lanes per filter for a closed-loop batch of the (8,6) shape that four-lane wavefronts still run in one round (1024 SIMDs, one wavefront
-// each, 16 trials per wavefront): half the trials per wavefront, a shorter step, 20-28 % less time per launch.  By default
-// -- lanes_per_filter == 0, KF / IMCC-KF / RMCKF on the DH plant -- the EMU2 kernels, which reproduce the two-lane arithmetic bit for bit, so
-// the choice is invisible in the results; with UVS_OPT_LATENCY the plain four-lane kernels (3-7 % faster still, last-bit differences).  MCKF
-// (round 5) has the EMU2 kernel too -- every fixed-point pass in-kernel -- but no plain four-lane one.  Returns 0 = no change, 4 = plain four lanes,
-// -4 = four lanes with the two-lane bits.
-int small_batch_lanes(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) {
-    if (fp->lanes_per_filter != 0 || fp->m != 8 || fp->n != 6 || (T * 4 + 63) / 64 > 1024) return 0;
-    if (((fp->reserved >> 8) & 0xff) > 1) return 0;                   // a forced segment count (testing / measurements) asks for the segmented two-lane kernel
-    // (eight lanes per filter -- one row per lane on the wide kernel's DH instantiation, lanes_per_filter = 8 -- were built and measured for this
-    // role: 8 192 trials 0.92 ms against 0.88 ms on four lanes -- the plant replicated on eight lanes gives back what one row per lane saves
-    // (1 075 against 1 109 VALU instructions per wavefront-step): DESIGN.md section 6)
-    if (fp->reserved & UVS_OPT_LATENCY) return fp->method == UVS_METHOD_MCKF ? 0 : 4;   // (the plain four-lane kernels run only MCKF's first pass: no latency mapping for it)
+bool tuned_shape(int m, int n, int L) {
+#define X(M, N, LL) if (m == M && n == N && L == LL) return true;
+    UVS_TUNED_SHAPES_A(X) UVS_TUNED_SHAPES_B(X)
+#undef X
+    return false;
+}
+
+// ------------------------------------------------------------------------------------------------ closed-loop plan
+// Which kernel family runs the first pass of a closed-loop launch, on how many lanes per filter, in how many segments, and whether it
+// certifies every solve under UVS_OPT_STRICT_PINV.  Decided here once; the launch and the four query functions only read it.
+enum class Route {
+    kTuned,        // rmckf_tuned.hpp, lanes_per_filter 1 / 2 / 4 (tu_closed_tuned_{a,b}.hip)
+    kEmu2,         // the same on four lanes per filter with the two-lane kernel's bits (small (8,6) batches)
+    kWide,         // rmckf_wide.hpp: (32,7) on the linear plant, (8,6) at lanes_per_filter = 8 on the DH plant
+    kGeneric,      // rmckf_generic.hpp: any instantiated (m, n, L), every estimator (UVS_ERR_SHAPE when (m, n, L) is not instantiated)
+    kCarefulOnly,  // UVS_OPT_STRICT_PINV on a route that does not certify: every trial marked, the careful pass is the only pass
+};
+struct ClosedPlan {
+    Route route;
+    int L;           // lanes per filter (uvs_rmckf_closed_loop_lanes)
+    int n_seg;       // segments per trial (uvs_rmckf_closed_loop_segments): > 1 only on the two-lane tuned route
+    bool certified;  // UVS_OPT_STRICT_PINV: the first pass certifies every solve and marks what it cannot
+};
+
+constexpr int64_t kSimdSlots = 1024;
+
+// Segmented trials (tuned two-lane MCKF kernel, and RMCKF's SEGMENTED instantiation at (8,6)).  How many segments a launch of T trials is cut
+// into: MCKF wavefronts differ in length (a trial whose fixed-point iteration keeps iterating costs its whole wavefront the branch), so the
+// last round of a launch of whole trials leaves SIMDs idle for up to a third of a trial.  Bits 8-15 of fp.reserved override (1 = never,
+// n = n segments).
+int segments(const uvs_filter_params &fp, int64_t T) {
+    const int64_t chunks = (T * 2 + 63) / 64;
+    int n = (fp.reserved >> 8) & 0xff;
+    if (!n && fp.method == UVS_METHOD_MCKF) {
+        // measured on MI355X (DESIGN.md section 4; 32 trials per wavefront, one wavefront per SIMD): one round or less -- nothing to balance;
+        // up to three rounds -- 8 segments (49 152 trials 4.02 -> 3.15 ms, 65 536: 4.43 -> 4.04, 98 304: 6.46 -> 5.94); beyond -- 4
+        // (131 072: 8.24 -> 7.66, 262 144: 15.6 -> 15.0), where 8 hand-overs per chunk cost more than the shorter tail returns
+        n = chunks <= kSimdSlots ? 1 : (chunks <= 3 * kSimdSlots ? 8 : 4);
+    }
+    if (!n) {
+        // RMCKF wavefronts all take the same time, so only a launch that is NOT a whole number of rounds has something to balance: 1.5 rounds take
+        // two rounds' time as whole trials (49 152 trials 2.97 -> 2.65 ms, 81 920: 4.49 -> 4.11 in four segments); whole rounds (the BASELINE configs)
+        // and launches beyond six rounds keep whole trials and the instantiation without the hand-over code
+        const int64_t over = chunks % kSimdSlots;
+        n = (chunks > kSimdSlots && chunks < 6 * kSimdSlots && over >= kSimdSlots / 10 && over <= kSimdSlots - kSimdSlots / 10) ? 4 : 1;
+    }
+    if (n > 16) n = 16;
+    if (n > 1 && fp.steps < 8 * n) n = 1;                        // nothing to cut in a short trial
+    return n < 1 ? 1 : n;
+}
+
+ClosedPlan plan_closed_loop(const uvs_filter_params &fp, const uvs_plant &plant, int64_t T) {
+    const bool mckf = fp.method == UVS_METHOD_MCKF, strict = (fp.reserved & UVS_OPT_STRICT_PINV) != 0;
+    const bool dh = plant.kind == UVS_PLANT_DH_PINHOLE, linear = plant.kind == UVS_PLANT_LINEAR;
+    ClosedPlan p{Route::kGeneric, resolve_lanes(fp), 1, false};
+    // lanes_per_filter 1 / 2 / 4 select the tuned kernel (rmckf_tuned.hpp) where it exists; a negative value forces the generic
+    // template with |value| lanes (kept as an in-library cross-check of the tuned code).  MCKF has tuned kernels on two lanes only.
+    const bool tuned = fp.lanes_per_filter >= 0 && (fp.method == UVS_METHOD_GMCKF || fp.method == UVS_METHOD_KF || fp.method == UVS_METHOD_IMCCKF ||
+                                                    (mckf && p.L == 2));
+    // Four lanes per filter for a closed-loop batch of the (8,6) shape that four-lane wavefronts still run in one round (1024 SIMDs, one wavefront
+    // each, 16 trials per wavefront): half the trials per wavefront, a shorter step, 20-28 % less time per launch.  By default
+    // -- lanes_per_filter == 0, DH plant -- the EMU2 kernels, which reproduce the two-lane arithmetic bit for bit, so the choice is invisible in the
+    // results (MCKF too, round 5: every fixed-point pass in-kernel); with UVS_OPT_LATENCY the plain four-lane kernels (3-7 % faster still, last-bit
+    // differences), which run only MCKF's first pass: no latency mapping for it.  A forced segment count (testing / measurements) asks for the
+    // segmented two-lane kernel.  (Eight lanes per filter -- one row per lane on the wide kernel's DH instantiation, lanes_per_filter = 8 -- were
+    // built and measured for this role: 8 192 trials 0.92 ms against 0.88 ms on four lanes -- the plant replicated on eight lanes gives back what
+    // one row per lane saves (1 075 against 1 109 VALU instructions per wavefront-step): DESIGN.md section 6.)
+    if (fp.lanes_per_filter == 0 && fp.m == 8 && fp.n == 6 && (T * 4 + 63) / 64 <= kSimdSlots && ((fp.reserved >> 8) & 0xff) <= 1) {
+        if (fp.reserved & UVS_OPT_LATENCY) {
+            if (!mckf) p.L = 4;
+        }
 #ifdef UVS_HAVE_EMU2
-    if (plant->kind == UVS_PLANT_DH_PINHOLE && !(fp->reserved & UVS_OPT_STRICT_PINV)) return -4;
+        else if (dh && !strict) {
+            p.route = Route::kEmu2;
+            p.L = 4;
+            return p;
+        }
 #endif
-    return 0;
+    }
+    if (fp.lanes_per_filter == 0 && fp.m == 32 && fp.n == 7 && linear && !fp.initial_guess && !mckf) p.L = 8;   // wide-shape tuned kernel
+    if (tuned && !mckf && ((fp.m == 8 && fp.n == 6 && p.L == 8 && dh) || (fp.m == 32 && fp.n == 7 && (p.L == 8 || p.L == 16) && linear)))
+        p.route = Route::kWide;
+    else if (tuned && tuned_shape(fp.m, fp.n, p.L))
+        p.route = Route::kTuned;
+    if (strict) {
+        // numpy's pinv on every solve.  A tuned QR kernel that certifies (uvs_launch::tuned_certifies) bounds the condition number of every solve
+        // rigorously from the inverse of the triangular factor and marks what it cannot certify: one fast pass plus the careful pass for the marked
+        // trials (round 6; ~1.1 x the default mode).  Every other route: no first pass, every trial marked, the careful pass is the only pass (an
+        // order of magnitude slower).  Nothing to cut into segments either way.
+        p.certified = p.route == Route::kTuned && uvs_launch::tuned_certifies(fp.m, fp.n, p.L, fp.method, linear, false);
+        if (!p.certified) p.route = Route::kCarefulOnly;
+    } else if (p.route == Route::kTuned && p.L == 2 && dh && (mckf || (fp.method == UVS_METHOD_GMCKF && fp.m == 8 && fp.n == 6))) {
+        p.n_seg = segments(fp, T);
+    }
+    return p;
+}
+ClosedPlan plan_or_none(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) {   // (the queries answer NULL arguments with "no segments")
+    return fp && plant && T > 0 ? plan_closed_loop(*fp, *plant, T) : ClosedPlan{Route::kGeneric, 0, 1, false};
+}
+
+size_t seg_flag_bytes(int64_t chunks) { return (size_t)(((chunks + 1) * sizeof(int) + 255) / 256) * 256; }   // one counter per chunk + the fallback count
+size_t seg_workspace_bytes(const uvs_filter_params &fp, int64_t T, int n_seg) {
+    if (n_seg <= 1) return 0;
+    const int64_t chunks = (T * 2 + 63) / 64;
+    return seg_flag_bytes(chunks) + (size_t)chunks * uvs::seg_state_doubles(fp.m, fp.n, 2) * 64 * sizeof(double);
 }
 
 }  // namespace
@@ -100,64 +189,21 @@ int uvs_supported_lanes(int32_t m, int32_t n, int32_t *lanes, int32_t cap) {
     return cnt;
 }
 
-// Segmented trials (tuned two-lane MCKF kernel).  How many segments a launch of T trials is cut into: MCKF wavefronts differ in length (a
-// trial whose fixed-point iteration keeps iterating costs its whole wavefront the branch), so the last round of a launch of whole trials
-// leaves SIMDs idle for up to a third of a trial.  Bits 8-15 of fp->reserved override (1 = never, n = n segments).
-namespace {
-constexpr int64_t kSimdSlots = 1024;
-int segments_for(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) {
-    if (!fp || !plant || T <= 0 || fp->lanes_per_filter < 0 || plant->kind != UVS_PLANT_DH_PINHOLE) return 1;
-    const bool mckf = fp->method == UVS_METHOD_MCKF, rmckf = fp->method == UVS_METHOD_GMCKF && fp->m == 8 && fp->n == 6;
-    if (!mckf && !rmckf) return 1;
-    if (fp->reserved & UVS_OPT_STRICT_PINV) return 1;                // (every trial goes to the careful kernels: nothing to cut)
-    const int L = fp->lanes_per_filter ? fp->lanes_per_filter : default_lanes(fp->m, fp->n, fp->method);
-    bool tuned2 = false;
-#define X(M, N, LL) if (fp->m == M && fp->n == N && L == LL && LL == 2) tuned2 = true;
-    UVS_TUNED_SHAPES_A(X) UVS_TUNED_SHAPES_B(X)
-#undef X
-    if (!tuned2) return 1;
-    const int forced = (fp->reserved >> 8) & 0xff;
-    int n = forced;
-    const int64_t chunks = (T * L + 63) / 64;
-    if (!n && mckf) {
-        // measured on MI355X (DESIGN.md section 4; 32 trials per wavefront, one wavefront per SIMD): one round or less -- nothing to balance;
-        // up to three rounds -- 8 segments (49 152 trials 4.02 -> 3.15 ms, 65 536: 4.43 -> 4.04, 98 304: 6.46 -> 5.94); beyond -- 4
-        // (131 072: 8.24 -> 7.66, 262 144: 15.6 -> 15.0), where 8 hand-overs per chunk cost more than the shorter tail returns
-        n = chunks <= kSimdSlots ? 1 : (chunks <= 3 * kSimdSlots ? 8 : 4);
-    }
-    if (!n && rmckf) {
-        // RMCKF wavefronts all take the same time, so only a launch that is NOT a whole number of rounds has something to balance: 1.5 rounds take
-        // two rounds' time as whole trials (49 152 trials 2.97 -> 2.65 ms, 81 920: 4.49 -> 4.11 in four segments); whole rounds (the BASELINE configs)
-        // and launches beyond six rounds keep whole trials and the instantiation without the hand-over code
-        const int64_t over = chunks % kSimdSlots;
-        n = (chunks > kSimdSlots && chunks < 6 * kSimdSlots && over >= kSimdSlots / 10 && over <= kSimdSlots - kSimdSlots / 10) ? 4 : 1;
-    }
-    if (small_batch_lanes(fp, plant, T)) n = 1;                      // (small batches run on four lanes per filter: no segmented kernel there, none needed)
-    if (n > 16) n = 16;
-    if (n > 1 && fp->steps < 8 * n) n = 1;                        // nothing to cut in a short trial
-    return n < 1 ? 1 : n;
-}
-size_t seg_flag_bytes(int64_t chunks) { return (size_t)(((chunks + 1) * sizeof(int) + 255) / 256) * 256; }   // one counter per chunk + the fallback count
-}  // namespace
-
-int uvs_rmckf_closed_loop_segments(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) { return segments_for(fp, plant, T); }
+int uvs_rmckf_closed_loop_segments(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) { return plan_or_none(fp, plant, T).n_seg; }
 
 int uvs_rmckf_closed_loop_lanes(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) {
     int L = 0;
     if (!fp || !plant || T <= 0 || check_params(fp, T, &L) != UVS_OK) return 0;
-    if (fp->lanes_per_filter == 0 && fp->m == 32 && fp->n == 7 && plant->kind == UVS_PLANT_LINEAR && !fp->initial_guess && fp->method != UVS_METHOD_MCKF) return 8;
-    return small_batch_lanes(fp, plant, T) ? 4 : L;
+    return plan_closed_loop(*fp, *plant, T).L;
 }
 
 size_t uvs_rmckf_closed_loop_workspace_bytes(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) {
-    const int n = segments_for(fp, plant, T);
-    if (n <= 1) return 0;
-    const int64_t chunks = (T * 2 + 63) / 64;
-    return seg_flag_bytes(chunks) + (size_t)chunks * uvs::seg_state_doubles(fp->m, fp->n, 2) * 64 * sizeof(double);
+    const int n_seg = plan_or_none(fp, plant, T).n_seg;
+    return n_seg > 1 ? seg_workspace_bytes(*fp, T, n_seg) : 0;
 }
 
 size_t uvs_rmckf_closed_loop_fallback_offset(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) {
-    if (segments_for(fp, plant, T) <= 1) return 0;
+    if (plan_or_none(fp, plant, T).n_seg <= 1) return 0;
     return (size_t)((T * 2 + 63) / 64) * sizeof(int);
 }
 
@@ -186,8 +232,7 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
     if (!q_start.base) return fail(UVS_ERR_ARG, "%s", "q_start view is NULL");
     if (!status) return fail(UVS_ERR_ARG, "%s", "status is required (it also carries the suspect marks between the two passes)");
     if (!fp->initial_guess && !x0.base) return fail(UVS_ERR_ARG, "%s", "x0 view is required when initial_guess == 0");
-    const int small = small_batch_lanes(fp, plant, T);
-    if (small == 4) L = 4;
+    const ClosedPlan plan = plan_closed_loop(*fp, *plant, T);
     uvs::ClosedArgs A;
     A.fp = *fp;
     A.plant = *plant;
@@ -199,9 +244,9 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
     A.stats = stats; A.status = status; A.k_done = k_done;
     if (workspace) {                                               // segmented trials, when the caller lent enough memory for them
         if (((uintptr_t)workspace & 7u) != 0) return fail(UVS_ERR_ARG, "%s", "workspace must be 8-byte aligned");
-        const size_t need = uvs_rmckf_closed_loop_workspace_bytes(fp, plant, T);
+        const size_t need = seg_workspace_bytes(*fp, T, plan.n_seg);
         if (need > 0 && workspace_bytes >= need) {
-            A.n_seg = segments_for(fp, plant, T);
+            A.n_seg = plan.n_seg;
             // Segment lengths taper linearly towards the end of the trial (the last one UVS_MCKF_TAPER_PCT % of the first): what is left
             // unbalanced at the end of the launch is one short work item per slot instead of one of average length.
             const int taper = UVS_MCKF_TAPER_PCT;
@@ -221,32 +266,21 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
         }
     }
     hipStream_t s = (hipStream_t)stream;
-    bool launched = false;
-    // lanes_per_filter 1 / 2 / 4 select the tuned kernel (rmckf_tuned.hpp) where it exists; a negative value forces the generic
-    // template with |value| lanes (kept as an in-library cross-check of the tuned code).
-    const bool tuned_ok = (fp->method == UVS_METHOD_GMCKF || fp->method == UVS_METHOD_KF || fp->method == UVS_METHOD_IMCCKF ||
-                           (fp->method == UVS_METHOD_MCKF && L == 2)) && fp->lanes_per_filter >= 0;
+    const int m = fp->m, n = fp->n, method = fp->method;
     const bool linear = plant->kind == UVS_PLANT_LINEAR, xo = x_out.base != nullptr;
-    if (fp->lanes_per_filter == 0 && fp->m == 32 && fp->n == 7 && tuned_ok && linear && !fp->initial_guess) L = 8;   // wide-shape tuned kernel
-    if (fp->reserved & UVS_OPT_STRICT_PINV) {
-        // numpy's pinv on every solve.  The tuned QR kernels (lanes 1 / 2 / 4 per filter; not the wide shape's normal equations) CERTIFY every
-        // solve themselves in this mode -- a rigorous upper bound of the condition number from the inverse of the triangular factor, rmckf_tuned.hpp
-        // lstsq_tall_tuned -- and mark what they cannot certify: one fast pass plus the careful pass for the marked trials (round 6; ~1.1 x the
-        // default mode).  Everything else: mark every trial, the careful pass below is the only pass (an order of magnitude slower).
-        const bool wide_takes = (fp->m == 8 && fp->n == 6 && L == 8 && !linear) || (fp->m == 32 && fp->n == 7 && (L == 8 || L == 16) && linear);
-        const bool has_cert = fp->method == UVS_METHOD_GMCKF || (fp->m == 8 && fp->n == 6 && L == 2 && !linear);   // (tu_closed_tuned.inc: the CERT instantiations)
-        bool certified_pass = false;
-        if (tuned_ok && !wide_takes && has_cert)
-            certified_pass = closed_tuned_a(fp->m, fp->n, L, fp->method, linear, xo, T, s, A) || closed_tuned_b(fp->m, fp->n, L, fp->method, linear, xo, T, s, A);
-        if (!certified_pass) uvs_launch::fill_i32(status, uvs::UVS_STATUS_SUSPECT, (long long)T, s);
-        launched = true;
-    }
+    bool launched = true;
+    switch (plan.route) {
+    case Route::kTuned:
+        launched = closed_tuned_a(m, n, plan.L, method, linear, xo, T, s, A) || closed_tuned_b(m, n, plan.L, method, linear, xo, T, s, A);
+        break;
 #ifdef UVS_HAVE_EMU2
-    if (!launched && tuned_ok && small == -4) launched = closed_tuned_emu2(fp->m, fp->n, fp->method, linear, xo, T, s, A);
+    case Route::kEmu2: launched = closed_tuned_emu2(method, xo, T, s, A); break;
 #endif
-    if (!launched && tuned_ok) launched = closed_wide(fp->m, fp->n, L, fp->method, linear, xo, T, s, A);
-    if (!launched && tuned_ok) launched = closed_tuned_a(fp->m, fp->n, L, fp->method, linear, xo, T, s, A) || closed_tuned_b(fp->m, fp->n, L, fp->method, linear, xo, T, s, A);
-    if (!launched) launched = closed_generic_a(fp->m, fp->n, L, fp->method, T, s, A) || closed_generic_b(fp->m, fp->n, L, fp->method, T, s, A);
+    case Route::kWide: launched = closed_wide(m, n, plan.L, method, xo, T, s, A); break;
+    case Route::kCarefulOnly: uvs_launch::fill_i32(status, uvs::UVS_STATUS_SUSPECT, (long long)T, s); break;
+    default:
+        launched = closed_generic_a(m, n, plan.L, method, T, s, A) || closed_generic_b(m, n, plan.L, method, T, s, A);
+    }
     if (!launched) return fail(UVS_ERR_SHAPE, "%s", "(m, n, lanes_per_filter) is not instantiated in libuvs_rmckf");
     if (int rc = check_launch("closed_loop_kernel")) return rc;
 #ifdef UVS_NO_CAREFUL                  // diagnostic build: leave the marks of the first pass in `status` (how many trials does the second pass redo?)
@@ -305,22 +339,20 @@ int uvs_rmckf_replay_f64(const uvs_filter_params *fp, int64_t T, uvs_view f, uvs
     A.status = status; A.k_done = k_done;
     hipStream_t s = (hipStream_t)stream;
     bool launched = false;
-    // two lanes per filter (the default) at (8,6): tuned kernel; a negative lanes_per_filter forces the generic template
-    const bool tuned_method = fp->method == UVS_METHOD_GMCKF || fp->method == UVS_METHOD_KF || fp->method == UVS_METHOD_IMCCKF ||
-                              fp->method == UVS_METHOD_MCKF;
-    const bool tuned_ok = tuned_method && fp->lanes_per_filter >= 0 && L == 2;
+    // (every estimator check_params accepts has tuned replay kernels)
     // without the commanded dq there is no least-squares solve and nothing couples a filter's rows: four lanes per filter, state in
     // registers, two wavefronts per SIMD (library default, or lanes_per_filter = 4)
-    if (tuned_method && !dqcmd_out.base && (fp->lanes_per_filter == 0 || fp->lanes_per_filter == 4))
+    if (!dqcmd_out.base && (fp->lanes_per_filter == 0 || fp->lanes_per_filter == 4))
         launched = replay_rows(fp->m, fp->n, fp->method, fp->lanes_per_filter == 0, x_out.base != nullptr, err_out.base != nullptr, T, s, A);
     if ((fp->reserved & UVS_OPT_STRICT_PINV) && dqcmd_out.base) {   // numpy's pinv on every solve: the careful pass below is the only pass
         uvs_launch::fill_i32(status, uvs::UVS_STATUS_SUSPECT, (long long)T, s);
         launched = true;
     }
     // with the commanded dq (library default lanes, KF / RMCKF, X and err wanted too): the same estimator wavefronts + control wavefronts
-    if (!launched && tuned_method && dqcmd_out.base && x_out.base && err_out.base && fp->lanes_per_filter == 0)
+    if (!launched && dqcmd_out.base && x_out.base && err_out.base && fp->lanes_per_filter == 0)
         launched = replay_rows_cmd(fp->m, fp->n, fp->method, T, s, A);
-    if (!launched && tuned_ok) launched = replay_tuned(fp->m, fp->n, fp->method, x_out.base != nullptr, dqcmd_out.base != nullptr, T, s, A);
+    // two lanes per filter (the default) at (8,6): tuned kernel; a negative lanes_per_filter forces the generic template
+    if (!launched && fp->lanes_per_filter >= 0 && L == 2) launched = replay_tuned(fp->m, fp->n, fp->method, x_out.base != nullptr, dqcmd_out.base != nullptr, T, s, A);
     if (!launched) launched = replay_generic_a(fp->m, fp->n, L, fp->method, T, s, A) || replay_generic_b(fp->m, fp->n, L, fp->method, T, s, A);
     if (!launched) return fail(UVS_ERR_SHAPE, "%s", "(m, n, lanes_per_filter) is not instantiated in libuvs_rmckf");
     if (int rc = check_launch("replay_kernel")) return rc;
