@@ -189,6 +189,36 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
                                  uvs_view x_final, uvs_view p_final, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Per-trial estimator parameters: a hyperparameter grid in ONE launch.  The same closed loop as uvs_rmckf_closed_loop_ws_f64, but trial t runs
+ * with its own correntropy bandwidth sigma_0 (experiment.py:37, :267-271), servo gain (:26, :312), regulariser (:280), fixed-point threshold
+ * (:38) and desired features (:21) -- what a user of these estimators tunes, where the reference's driver (main.py) can only sweep the noise.
+ * annealing, anneal_span, dt, steps, k_max, fpi_epoch_max, initial_guess and method stay launch-wide (fp).
+ *   tp->kernel_bw, gain, reg, fpi_threshold   DEVICE arrays of T doubles; NULL = fp's value for every trial
+ *   tp->desired   [T][1][m] DEVICE view; base NULL = fp->desired
+ *   tp->source    DEVICE array of T int32: trial t reads q_start / noise / x0 of trial source[t] (NULL = t) and writes every output at t, so H
+ *                 grid cells over the same E trials (common random numbers) need the inputs of E trials, not of H x E.  Values outside
+ *                 [0, number of trials the input views hold) are the caller's error: they are not checked and read out of bounds.
+ * Every value is used exactly where the uniform kernels use fp's, the same operations in the same order: trial t's results are BIT-IDENTICAL to
+ * those of a uniform launch (two lanes per filter, or the small-batch mapping, which has the same bits) with t's values; a tp of NULL members
+ * equals uvs_rmckf_closed_loop_ws_f64.  The careful second pass reads the same per-trial values and the same source index.
+ * Scope: (m, n) = (8, 6) on the DH / pinhole plant with lanes_per_filter 0 or 2, KF / MCKF / IMCC-KF / RMCKF -- always the two-lane tuned kernel:
+ * the four-lane small-batch kernels have no per-trial flavour, so grids of at most 16 384 trials run on two lanes as well (same bits, the
+ * small-batch speed-up forgone).  Anything else is refused, never run with launch-wide values: tp NULL -> UVS_ERR_ARG; ANALYTICAL ->
+ * UVS_ERR_METHOD; another shape, lanes_per_filter or a linear plant -> UVS_ERR_SHAPE; UVS_OPT_STRICT_PINV, UVS_OPT_LATENCY or
+ * UVS_OPT_DIAG_DROP_SEG_FLAG -> UVS_ERR_ARG.  Workspace size, segment count and fallback offset are those of the queries above for (fp, plant, T).
+ */
+typedef struct uvs_trial_params {
+    const double *kernel_bw, *gain, *reg, *fpi_threshold;
+    uvs_view desired;
+    const int32_t *source;
+} uvs_trial_params;
+int uvs_rmckf_closed_loop_grid_f64(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T, const uvs_trial_params *tp,
+                                   uvs_view q_start, uvs_view noise, uvs_view x0,
+                                   uvs_view x_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out,
+                                   double *stats, int32_t *status, int32_t *k_done,
+                                   uvs_view x_final, uvs_view p_final, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Calibrated IBVS baseline: T closed-loop trials of Method.ANALYTICAL (experiment.py:145-162, :300-320) on the synthetic DH / pinhole plant,
  * the same loop clock, plant and noise as uvs_rmckf_closed_loop_f64 but with the interaction matrix computed instead of estimated.  Per step:
  * f = features + noise; J_feature = J_image(noisy raw-pixel u, v; Z = Euclidean camera-disc distance) kron(I2, R^T) J_robot (the row

@@ -3,16 +3,18 @@
 # Kernel-trace statistics and PMC counters are separate passes (never --pmc together with other trace domains); the program after
 # `--` is python3 itself.  The traced command is bench.py --steps 20 --warmup 5 --full (minus the host CPU baseline): the side measurements are traced too.
 set -u
+# every GPU step runs under a time limit of its own, and the first one that fails ends the script: nothing more is started on a card after a fault
+step() { timeout -k 10 "$@" || { echo "step failed (rc $?): $*" | cut -c1-300; exit 1; }; }
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/${1:-prof}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # which kernels these counts belong to: the library's version string carries the fingerprint of its kernel sources (csrc/src_hash.py)
-python3 -c "import sys; sys.path.insert(0, '$REPO'); import uvs_amd; print(uvs_amd.lib().uvs_version().decode())" > $OUT/library_version.txt
+step 120 python3 -c "import sys; sys.path.insert(0, '$REPO'); import uvs_amd; print(uvs_amd.lib().uvs_version().decode())" > $OUT/library_version.txt
 # the un-profiled line first: a profiled run clocks 2-3 % lower (MI355X_MICROARCH.md, DVFS give-back)
-UVS_BENCH_FULL_JSON=$OUT/bench_full.json python3 $REPO/bench.py --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench_line.err
+UVS_BENCH_FULL_JSON=$OUT/bench_full.json step 600 python3 $REPO/bench.py --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 echo "bench line done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-e2e --no-power > $OUT/stats_bench.json 2> $OUT/stats_bench.err
+step 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-e2e --no-power > $OUT/stats_bench.json 2> $OUT/stats_bench.err
 echo "kernel trace done"
 i=0
 for pass in "FETCH_SIZE" "WRITE_SIZE" \
@@ -21,7 +23,7 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" \
             "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM_WR SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU" \
             "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/pmc_$i -- python3 $REPO/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-e2e --no-power > $OUT/pmc_$i.log 2>&1
+  step 300 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/pmc_$i -- python3 $REPO/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-e2e --no-power > $OUT/pmc_$i.log 2>&1
   echo "pmc pass $i done"
 done
 cd $REPO

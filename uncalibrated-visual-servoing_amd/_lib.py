@@ -38,6 +38,13 @@ class FilterParams(C.Structure):
                 ('desired', C.c_double * UVS_MAX_M)]
 
 
+class TrialParams(C.Structure):
+    """uvs_trial_params: per-trial kernel_bw / gain / reg / fpi_threshold (device arrays of T doubles), desired ([T][1][m]) and the source trial of
+    the inputs (device array of T int32); a NULL member = the launch-wide value of FilterParams (source: the trial itself)."""
+    _fields_ = [('kernel_bw', C.c_void_p), ('gain', C.c_void_p), ('reg', C.c_void_p), ('fpi_threshold', C.c_void_p), ('desired', View),
+                ('source', C.c_void_p)]
+
+
 class NoiseParams(C.Structure):
     _fields_ = [('type', C.c_int32), ('m', C.c_int32), ('steps', C.c_int32), ('hold_cnt', C.c_int32)] + \
                [(k, C.c_double) for k in ('std', 'mean', 'rho', 'alpha', 'beta', 'gamma', 'delta', 'inv_alpha', 'expo', 'one_minus_alpha',
@@ -61,6 +68,8 @@ SYMBOLS = {
     'uvs_supported_lanes': (C.c_int, [_I32, _I32, C.POINTER(_I32), _I32]),
     'uvs_rmckf_closed_loop_f64': (C.c_int, [C.POINTER(FilterParams), C.POINTER(Plant), _I64] + [View] * 8 + [_VP] * 3 + [View] * 2 + [_VP]),
     'uvs_rmckf_closed_loop_ws_f64': (C.c_int, [C.POINTER(FilterParams), C.POINTER(Plant), _I64] + [View] * 8 + [_VP] * 3 + [View] * 2 + [_VP, C.c_size_t, _VP]),
+    'uvs_rmckf_closed_loop_grid_f64': (C.c_int, [C.POINTER(FilterParams), C.POINTER(Plant), _I64, C.POINTER(TrialParams)] + [View] * 8 + [_VP] * 3 + [View] * 2 +
+                                       [_VP, C.c_size_t, _VP]),
     'uvs_rmckf_closed_loop_lanes': (C.c_int, [C.POINTER(FilterParams), C.POINTER(Plant), _I64]),
     'uvs_rmckf_closed_loop_segments': (C.c_int, [C.POINTER(FilterParams), C.POINTER(Plant), _I64]),
     'uvs_rmckf_closed_loop_workspace_bytes': (C.c_size_t, [C.POINTER(FilterParams), C.POINTER(Plant), _I64]),

@@ -356,6 +356,153 @@ def _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, device, max_t
     return SweepResult(plan, lo, hi, host['stats'].numpy(), host['status'].numpy(), host['k_done'].numpy(), pieces, seconds)
 
 
+GRID_KEYS = ('kernel_bw', 'ibvs_gain', 'fpi_threshold')          # config names of what a grid may vary -> trial_params 'kernel_bw', 'gain', 'fpi_threshold'
+
+
+@dataclass
+class GridPlan:
+    """A hyperparameter grid over the trials of one noise cell: grid cell h has the values ``values[h]`` (one column per axis of ``axes``, the
+    product of the axes in the order given, last axis fastest), launch ``pieces[i] = (h_lo, h_hi)`` runs grid cells [h_lo, h_hi) as
+    (h_hi - h_lo) x epoch trials, trial t of a launch reading the inputs of trial ``t % epoch`` of the noise cell (``source``)."""
+    axes: dict               # name -> list of values, as given
+    values: np.ndarray       # (H, len(axes))
+    epoch: int
+    pieces: list
+
+    def __len__(self):
+        return len(self.values)
+
+    def source(self, h_lo, h_hi):
+        return np.tile(np.arange(self.epoch, dtype=np.int32), h_hi - h_lo)
+
+    def column(self, name, h_lo, h_hi):
+        """Per-trial values of axis ``name`` for the launch of grid cells [h_lo, h_hi)."""
+        return np.repeat(self.values[h_lo:h_hi, list(self.axes).index(name)], self.epoch)
+
+    def substituted(self, cfg, h):
+        """The config whose uniform sweep grid cell ``h`` reproduces bit for bit."""
+        cfg = json.loads(json.dumps(load_config(cfg)))
+        for name, v in zip(self.axes, self.values[h]):
+            if name == 'ibvs_gain':
+                cfg['experiments']['ibvs_gain'] = float(v)
+            else:
+                cfg['estimator']['estimator_params'][name] = float(v)
+        return cfg
+
+
+def plan_grid(grid, epoch, max_trials=None):
+    """GridPlan of ``grid`` (a dict mapping any of GRID_KEYS to a list of values) over ``epoch`` trials per cell; launches of at most
+    ``max_trials`` trials, cut at grid-cell boundaries (at least one grid cell per launch)."""
+    unknown = [k for k in grid if k not in GRID_KEYS]
+    if unknown or not grid:
+        raise ValueError(f'run_grid: grid maps any of {GRID_KEYS} to a list of values, got {list(grid)}')
+    axes = {k: [float(v) for v in vs] for k, vs in grid.items()}
+    if any(len(vs) == 0 for vs in axes.values()):
+        raise ValueError('run_grid: an axis of the grid is empty')
+    mesh = np.meshgrid(*axes.values(), indexing='ij')
+    values = np.stack([g.reshape(-1) for g in mesh], axis=1)
+    H = len(values)
+    per = H if not max_trials else max(1, int(max_trials) // int(epoch))
+    return GridPlan(axes, values, int(epoch), [(h, min(H, h + per)) for h in range(0, H, per)])
+
+
+@dataclass
+class GridResult:
+    """Per-trial rows of run_grid on the host, indexed (noise cell, grid cell, trial of the cell)."""
+    plan: TrialPlan
+    grid: GridPlan
+    stats: np.ndarray        # (C, H, epoch, 3)
+    status: np.ndarray       # (C, H, epoch) int32
+    k_done: np.ndarray       # (C, H, epoch) int32
+    seconds: float = 0.0
+
+    def rows(self):
+        """(C, H, epoch, 5) fp64 [ISE, IAE, ITAE, status, k_done]."""
+        return np.concatenate([self.stats, self.status[..., None].astype(float), self.k_done[..., None].astype(float)], axis=-1)
+
+    def cell_summary(self):
+        """{(noise cell, grid cell): stats.cell_summary's entry}."""
+        from . import stats as _stats
+        out = {}
+        for c in range(self.stats.shape[0]):
+            H, E = self.status.shape[1:]
+            summ = _stats.cell_summary(self.stats[c].reshape(H * E, 3), self.status[c].reshape(-1), np.repeat(np.arange(H), E))
+            out.update({(c, h): v for h, v in summ.items()})
+        return out
+
+
+def run_grid(cfg, grid, cells=None, epoch=None, want=(), lanes=0, device='cuda', plant=None, max_trials=None, on_piece=None):
+    """A hyperparameter study in one launch per noise cell: every grid cell of ``grid`` (plan_grid: kernel_bw x ibvs_gain x fpi_threshold, any subset)
+    over the SAME trials -- plan_trials' seeds and start-pose jitter, unchanged -- instead of one sweep per grid cell.  For every noise cell the noise
+    of its ``epoch`` trials is generated once (the shared T + 70 streams where they alias, as run_sweep does), then ONE launch of H x epoch trials
+    with per-trial parameters reads them through ``source = t % epoch`` (engine.closed_loop(trial_params=...); pieces of at most ``max_trials``
+    trials, cut at grid-cell boundaries).  Contract: grid cell h equals run_sweep on ``GridPlan.substituted(cfg, h)``, bit for bit.
+    ``on_piece(c, h_lo, h_hi, out)`` is called after each launch has finished (c: noise cell) with engine.closed_loop's dict, where a sink reads the
+    ``want`` streams.  Method.ANALYTICAL has no per-trial kernel: ValueError (as have strict_pinv and latency, which this function does not offer)."""
+    import time
+    import torch
+    cfg = load_config(cfg)
+    ex, est, nz = cfg['experiments'], cfg['estimator'], cfg['noise']
+    method = Method[est['method']]
+    if method == Method.ANALYTICAL:
+        raise ValueError('run_grid: Method.ANALYTICAL has no per-trial parameters (no bandwidth, and no per-trial kernel for its gain)')
+    if lanes not in (0, 2):
+        raise ValueError('run_grid: lanes must be 0 or 2 (the per-trial kernels run two lanes per filter)')
+    plan = plan_trials(cfg, cells, epoch)
+    E = int(ex['epoch'] if epoch is None else epoch)
+    gp = plan_grid(grid, E, max_trials)
+    C_, H = len(plan.cells), len(gp)
+    stats = np.empty((C_, H, E, 3))
+    status = np.empty((C_, H, E), np.int32)
+    k_done = np.empty((C_, H, E), np.int32)
+    dev = torch.device(device)
+    with torch.cuda.device(dev if dev.index is not None else torch.cuda.current_device()):
+        dev = torch.device('cuda', torch.cuda.current_device())
+        plant = SyntheticPlant.ur10(ex['desired_f']) if plant is None else plant
+        p = est.get('estimator_params') or {}
+        m, n = len(ex['desired_f']), plant.n_joints
+        fp = engine.make_params(m, n, method.name, p.get('kernel_bw', 1.0), p.get('annealing', False), ex['dt'], ex['t_max'], ex['ibvs_gain'],
+                                ex['desired_f'], p['initial_guess'], lanes, None, p.get('fpi_threshold', 0.1), p.get('fpi_epoch_max', 1000))
+        K = len(engine.loop_clock(ex['dt'], ex['t_max']))
+        noise_type = NoiseType[nz['type']]
+        hold_cnt = int(nz['hold_time'] / ex['dt'])
+        key = 'alpha' if noise_type == NoiseType.ALPHA_STABLE else 'rho'
+        plant_struct = plant.to_struct()
+        q0 = torch.as_tensor(plan.q_start.copy(), device=dev)
+        x0 = None if p['initial_guess'] else torch.as_tensor(np.asarray(p['x0'], float).reshape(1, m * n).repeat(E, 0), device=dev)
+        seeds_dev = torch.as_tensor(np.ascontiguousarray(plan.seed, dtype=np.uint64).view(np.int64), device=dev)
+        names = {'kernel_bw': 'kernel_bw', 'ibvs_gain': 'gain', 'fpi_threshold': 'fpi_threshold'}
+        launches = []                                              # per piece: trial_params on the device, made once
+        for h_lo, h_hi in gp.pieces:
+            tp = {names[k_]: torch.as_tensor(gp.column(k_, h_lo, h_hi), device=dev) for k_ in gp.axes}
+            tp['source'] = torch.as_tensor(gp.source(h_lo, h_hi), device=dev)
+            launches.append(tp)
+        reuse = None
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for c in range(C_):
+            a, b = c * E, (c + 1) * E
+            params = dict(nz['noise_params'])
+            params[key] = float(plan.cells[c])
+            if noise_device.shares_streams(noise_type, nz['hold'], plan.seed[a:b]):
+                noise = noise_device.generate_shared(noise_type, params, int(plan.seed[a]), E, m, K, device=dev)[1]
+            else:
+                noise = torch.empty((K, m, E), dtype=torch.float64, device=dev)
+                noise_device.generate(noise_type, params, seeds_dev[a:b], m, K, nz['hold'], hold_cnt, 'kct', out=noise, device=dev)
+            for (h_lo, h_hi), tp in zip(gp.pieces, launches):
+                out = engine.closed_loop(fp, plant_struct, q0[a:b], noise, x0, want=want, reuse=reuse, trial_params=tp)
+                if reuse is None:
+                    reuse = out                                    # the first piece is the largest: later ones write into its tensors
+                hc = h_hi - h_lo
+                stats[c, h_lo:h_hi] = out['stats'].cpu().numpy().reshape(hc, E, 3)
+                status[c, h_lo:h_hi] = out['status'].cpu().numpy().reshape(hc, E)
+                k_done[c, h_lo:h_hi] = out['k_done'].cpu().numpy().reshape(hc, E)
+                if on_piece is not None:
+                    on_piece(c, h_lo, h_hi, out)
+        torch.cuda.synchronize(dev)
+    return GridResult(plan, gp, stats, status, k_done, time.perf_counter() - t0)
+
+
 CSV_COLUMNS = (['experiment_id', 'status', 'rho', 't'] + [f'q_{i}' for i in range(1, 7)] +
                ['camera_x', 'camera_y', 'camera_z', 'camera_roll', 'camera_pitch', 'camera_yaw'] +
                [f'f_{i}' for i in range(1, 9)] + [f'desired_f_{i}' for i in range(1, 9)] + [f'noise_{i}' for i in range(1, 9)] + ['kernel_bw'])

@@ -76,6 +76,11 @@ bool closed_tuned_a(int m, int n, int L, int method, bool linear, bool xo, int64
 bool closed_tuned_b(int m, int n, int L, int method, bool linear, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
 // four lanes per filter with the two-lane kernel's bits (EMU2): (8,6), DH plant -- the automatic choice for batches that do not fill the chip
 bool closed_tuned_emu2(int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);
+// per-trial parameters (uvs_rmckf_closed_loop_grid_f64): the tuned two-lane kernel at (8,6) on the DH plant, RMCKF + KF / MCKF + IMCC-KF
+// (tu_closed_grid_{a,b}.hip), and the careful second pass behind it (tu_careful_grid.hip)
+bool closed_grid_a(int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedGridArgs &A);
+bool closed_grid_b(int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedGridArgs &A);
+bool closed_grid_careful(int64_t T, hipStream_t s, const uvs::ClosedGridArgs &A);
 // tuned wide-shape closed loop (rmckf_wide.hpp), KF / IMCC-KF / RMCKF: (32,7) on the linear plant at 8 or 16 lanes per filter, (8,6) on the
 // DH plant at 8 (one row per lane)
 bool closed_wide(int m, int n, int L, int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A);

@@ -124,6 +124,38 @@ struct ClosedArgs {
     int n_seg = 1;
     int seg_first[kMaxSegments + 1] = {};       // segment s covers steps [seg_first[s], seg_first[s + 1])
 };
+// Per-trial estimator parameters (uvs_rmckf_closed_loop_grid_f64): DEVICE arrays of T values, nullptr = the launch-wide value of fp.  `source`
+// names the trial whose q_start / noise / x0 trial t reads (nullptr = t); outputs are written at t.  Carried by a derived argument block that only
+// the per-trial kernels take, so that every other closed-loop kernel reads its arguments where it always did.
+struct TrialParams {
+    const double *kernel_bw = nullptr, *gain = nullptr, *reg = nullptr, *fpi_threshold = nullptr;
+    View desired = {nullptr, 0, 0, 0};          // [T][1][m]
+    const int *source = nullptr;
+};
+struct ClosedGridArgs : ClosedArgs {
+    TrialParams tp;
+};
+// One kernel text, two flavours, chosen per TRANSLATION UNIT: compiled with UVS_PER_TRIAL (tu_closed_grid_{a,b}.hip, tu_careful_grid.hip) the tuned and
+// the generic closed-loop kernel are the per-trial entries closed_loop_grid_kernel / closed_loop_grid_generic_kernel taking ClosedGridArgs, with the
+// switch PTP on; everywhere else they are the uniform kernels they always were -- same names, same argument block, same machine code (a shared
+// __device__ body behind two __global__ wrappers moved the register allocation of about half of the existing instantiations).
+#ifdef UVS_PER_TRIAL
+constexpr bool kPerTrial = true;
+using ClosedKernelArgs = ClosedGridArgs;
+#define UVS_CLOSED_TUNED_KERNEL closed_loop_grid_kernel
+#define UVS_CLOSED_GENERIC_KERNEL closed_loop_grid_generic_kernel
+#else
+constexpr bool kPerTrial = false;
+using ClosedKernelArgs = ClosedArgs;
+#define UVS_CLOSED_TUNED_KERNEL closed_loop_tuned_kernel
+#define UVS_CLOSED_GENERIC_KERNEL closed_loop_kernel
+#endif
+UVS_DEV const TrialParams *trial_params_of(const ClosedArgs &) { return nullptr; }
+UVS_DEV const TrialParams *trial_params_of(const ClosedGridArgs &a) { return &a.tp; }
+// sigma_k with the trial's own sigma_0: bandwidth() below, operation for operation
+UVS_DEV double bandwidth_of(const uvs_filter_params &fp, double kernel_bw, int k) {
+    return fp.annealing ? kernel_bw + fp.anneal_span * (1.0 - (double)k / (double)fp.k_max) : kernel_bw;
+}
 // Doubles per lane that one trial-chunk state occupies in the workspace (an upper bound over the kernel variants of a shape, so that the
 // C ABI can size the workspace without knowing which one runs): joints + their sines / cosines, command, previous features, clock,
 // covariance blocks, X, the twelve statistics accumulators, one word of flags.

@@ -30,16 +30,32 @@ UVS_DEV void store_final(const Rows<M, N, L> &st, const View &xf, const View &pf
 // CAREFUL = true is the second pass behind any closed-loop kernel: it re-runs, from their first step, exactly the trials the first pass
 // marked UVS_STATUS_SUSPECT (a numerically rank-deficient Jacobian showed up in the control law) with numpy's pinv semantics, and
 // overwrites their outputs; wavefronts without such a trial exit at once.
+// PTP: compiled with UVS_PER_TRIAL this is closed_loop_grid_generic_kernel(ClosedGridArgs), the careful pass behind uvs_rmckf_closed_loop_grid_f64,
+// which redoes a marked trial with that trial's own parameters and inputs, like the first pass (rmckf_tuned.hpp).
 template <int M, int N, int L, int METHOD_T, bool CAREFUL = false>
-__global__ __launch_bounds__(64) void closed_loop_kernel(const ClosedArgs A) {
+__global__ __launch_bounds__(64) void UVS_CLOSED_GENERIC_KERNEL(const ClosedKernelArgs A) {
+    constexpr bool PTP = kPerTrial;
     constexpr int R = M / L;
     const long long gl = (long long)blockIdx.x * 64 + threadIdx.x;
     long long trial = gl / L;
     const int sub = (int)(gl % L);
     const bool valid = trial < A.T;
     if (!valid) trial = A.T - 1;                    // padding lanes shadow the last trial so group shuffles stay uniform
-    const uvs_filter_params &fp = A.fp;
-    const int K = fp.steps;
+    // PTP: a per-lane copy of the parameter block with the trial's own scalars (only those four members differ between lanes)
+    uvs_filter_params fp_trial;
+    __shared__ double lds_tp[PTP ? 4 : 1][64];
+    long long src = trial;
+    if constexpr (PTP) {
+        const TrialParams &tp = *trial_params_of(A);
+        fp_trial = A.fp;
+        if (tp.source) src = tp.source[trial];
+        lds_tp[0][threadIdx.x] = tp.kernel_bw ? tp.kernel_bw[trial] : A.fp.kernel_bw;
+        lds_tp[1][threadIdx.x] = tp.gain ? tp.gain[trial] : A.fp.gain;
+        lds_tp[2][threadIdx.x] = tp.reg ? tp.reg[trial] : A.fp.reg;
+        lds_tp[3][threadIdx.x] = tp.fpi_threshold ? tp.fpi_threshold[trial] : A.fp.fpi_threshold;
+    }
+    const uvs_filter_params &fp = PTP ? fp_trial : A.fp;
+    const int K = A.fp.steps;
     bool mine = true, flagged = false;
     if constexpr (CAREFUL) {
         mine = A.status[trial] == UVS_STATUS_SUSPECT;
@@ -48,13 +64,20 @@ __global__ __launch_bounds__(64) void closed_loop_kernel(const ClosedArgs A) {
 
     double q[N], dq[N];
 #pragma unroll
-    for (int j = 0; j < N; ++j) { q[j] = *A.q_start.at(trial, 0, j); dq[j] = 0.0; }
+    for (int j = 0; j < N; ++j) { q[j] = *A.q_start.at(src, 0, j); dq[j] = 0.0; }
 
     Rows<M, N, L> st;
     st.init_cov();
     double f_prev[R], des[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) des[r] = fp.desired[sub * R + r];
+    for (int r = 0; r < R; ++r) des[r] = A.fp.desired[sub * R + r];
+    if constexpr (PTP) {
+        const View &tp_des = trial_params_of(A)->desired;
+        if (tp_des.p) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) des[r] = *tp_des.at(trial, 0, sub * R + r);
+        }
+    }
     if (fp.initial_guess) {
         initial_guess<M, N, L>(A.plant, q, sub, st.x, f_prev);
     } else {
@@ -62,7 +85,7 @@ __global__ __launch_bounds__(64) void closed_loop_kernel(const ClosedArgs A) {
         for (int r = 0; r < R; ++r) {
             f_prev[r] = 0.0;                                                    // f = zeros(m) (experiment.py:56)
 #pragma unroll
-            for (int j = 0; j < N; ++j) st.x[r][j] = *A.x0.at(trial, 0, (sub * R + r) * N + j);
+            for (int j = 0; j < N; ++j) st.x[r][j] = *A.x0.at(src, 0, (sub * R + r) * N + j);
         }
     }
 
@@ -75,12 +98,18 @@ __global__ __launch_bounds__(64) void closed_loop_kernel(const ClosedArgs A) {
 
     double nz[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) nz[r] = (A.noise.on() && K > 0) ? *A.noise.at(trial, 0, sub * R + r) : 0.0;
+    for (int r = 0; r < R; ++r) nz[r] = (A.noise.on() && K > 0) ? *A.noise.at(src, 0, sub * R + r) : 0.0;
 
     for (int k = 0; k < K; ++k) {
+        if constexpr (PTP) {                        // the trial's scalars wait in LDS (this kernel uses none otherwise) and are read where a step needs them:
+            asm volatile("" ::: "memory");          // at 509 of 512 registers there is no room to hold them across the step
+            fp_trial.kernel_bw = lds_tp[0][threadIdx.x];
+            fp_trial.reg = lds_tp[2][threadIdx.x];
+            fp_trial.fpi_threshold = lds_tp[3][threadIdx.x];
+        }
         double nz_next[R];                          // prefetch the next step's noise under this step's arithmetic
 #pragma unroll
-        for (int r = 0; r < R; ++r) nz_next[r] = (A.noise.on() && k + 1 < K) ? *A.noise.at(trial, k + 1, sub * R + r) : 0.0;
+        for (int r = 0; r < R; ++r) nz_next[r] = (A.noise.on() && k + 1 < K) ? *A.noise.at(src, k + 1, sub * R + r) : 0.0;
 
         double f[R], z[R], err[R], kap[R];
         plant_features<M, N, L>(A.plant, q, sub, f);
@@ -98,7 +127,7 @@ __global__ __launch_bounds__(64) void closed_loop_kernel(const ClosedArgs A) {
             k_done = k;
         }
         if (!__any(alive)) break;
-        const bool suspect = control_law<M, N, L, CAREFUL>(st, kap, err, fp.gain, sub, dq);
+        const bool suspect = control_law<M, N, L, CAREFUL>(st, kap, err, PTP ? lds_tp[PTP ? 1 : 0][threadIdx.x] : fp.gain, sub, dq);
         flagged |= alive && suspect;
 
         if (alive && valid && mine) {

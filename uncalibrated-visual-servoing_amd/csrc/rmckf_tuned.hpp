@@ -767,10 +767,17 @@ constexpr int kSharedOcc = 2;           // wavefronts per SIMD of the two-lane K
 // profiles/r06/strict_certificate_ab.txt), and the KF / IMCC-KF kernels, held to 256 registers for two wavefronts per SIMD, spilled 12 bytes over
 // it: those three take it as a compile-time switch, and the launcher picks their CERT instantiations in strict mode.
 // XPAIR (round 6; with XREC): the X stream leaves LDS as 16-byte pairs of consecutive trials into TRIAL-FASTEST rows instead of as records (store_records).
+// PTP (per-trial parameters, uvs_rmckf_closed_loop_grid_f64; a translation unit compiled with UVS_PER_TRIAL sees this kernel as closed_loop_grid_kernel
+// taking ClosedGridArgs, rmckf_device.hpp): kernel_bw, gain, reg, fpi_threshold, desired and the source trial of the inputs are read per trial in the
+// prologue (a null array = the launch-wide value) and used wherever the uniform kernel reads them from fp, the same operations in the same order: a
+// trial's bits are those of a uniform launch with its values.  With one wavefront per SIMD the allocator keeps the scalars in idle accumulator
+// registers; a later segment reads them again (inputs, not state).
 template <int M, int N, int L, int METHOD, int PLANT, int PV, bool XOUT, bool EMU2 = false, bool SEGMENTED = (METHOD == UVS_METHOD_MCKF), bool XREC = false,
           bool CERT = false, bool XPAIR = false>
 __global__ __launch_bounds__(64, (L >= 4 ? kL4Occ : ((METHOD == UVS_METHOD_KF || METHOD == UVS_METHOD_IMCCKF) && PV >= 1 && L == 2) ? kSharedOcc : 1))
-void closed_loop_tuned_kernel(const ClosedArgs A) {
+void UVS_CLOSED_TUNED_KERNEL(const ClosedKernelArgs A) {
+    constexpr bool PTP = kPerTrial;
+    static_assert(!PTP || (M == 8 && N == 6 && L == 2 && !EMU2 && !XREC && !CERT && PLANT != UVS_PLANT_LINEAR), "per-trial parameters: (8,6), two lanes, DH plant");
     static_assert(M >= N && (L == 1 || L == 2 || L == 4) && M % L == 0, "tuned kernel: tall Jacobian, 1, 2 or 4 lanes per filter");
     static_assert(!XREC || (XOUT && L == 2 && !EMU2 && M == 8 && N == 6 && METHOD != UVS_METHOD_MCKF), "record stores: the (8,6) two-lane kernels with X in LDS (MCKF rewrites rows of a step)");
     static_assert(!XPAIR || XREC, "pair stores are a flavour of the LDS store path");
@@ -799,6 +806,10 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
     __shared__ double lds_acc[3 * R][64];
     __shared__ double lds_p[(PL > 0 && !((METHOD == UVS_METHOD_KF || METHOD == UVS_METHOD_IMCCKF) && PV >= 1)) ? PL * NP : 1][64];
     __shared__ double lds_c[PC::kCount];
+    // PTP on IMCC-KF: held to 256 registers for two wavefronts per SIMD and full, the kernel spilled 12-20 B over the trial's bandwidth and gain;
+    // its workgroups leave LDS for two more rows (8 x (18 784 + 1 024) B of 160 KiB), read once per step each
+    constexpr bool TP_LDS = PTP && SHARED_P && METHOD == UVS_METHOD_IMCCKF;
+    __shared__ double lds_tp[TP_LDS ? 2 : 1][64];
 
     // diagnostics (dead code unless a kDiag* switch is on): entry time of the wavefront / work item; entry -> state ready -> steps done -> handed over
     unsigned long long wt_first = 0, it_t0 = 0, it_t1 = 0, it_t2 = 0, it_t3 = 0, it_ta = 0, it_tb = 0;
@@ -834,6 +845,18 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
     const long long trial = valid ? wave_first + tl : A.T - 1;     // padding lanes shadow the last trial
     const uvs_filter_params &fp = A.fp;
     const int K = fp.steps;
+    // the trial's own parameters and the trial its inputs come from (PTP); the uniform kernels read fp where they always did
+    long long src = trial;
+    double tp_bw = 0.0, tp_gain = 0.0, tp_reg = 0.0, tp_thr = 0.0;
+    if constexpr (PTP) {
+        const TrialParams &tp = *trial_params_of(A);
+        if (tp.source) src = tp.source[trial];
+        tp_bw = tp.kernel_bw ? tp.kernel_bw[trial] : fp.kernel_bw;
+        tp_gain = tp.gain ? tp.gain[trial] : fp.gain;
+        tp_reg = tp.reg ? tp.reg[trial] : fp.reg;
+        tp_thr = tp.fpi_threshold ? tp.fpi_threshold[trial] : fp.fpi_threshold;
+    }
+    if constexpr (TP_LDS) { lds_tp[0][lane] = tp_bw; lds_tp[1][lane] = tp_gain; }
     // segment [k_begin, k_end) of the trial; `fresh`: start from the initial state (first segment, or a later one whose predecessor did not
     // report within the spin budget -- it then recomputes the trial from step 0, writing the same rows once more: never a deadlock)
     int k_begin = 0, k_end = K, flag_early = 0;
@@ -874,7 +897,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
     };
 
     // per-lane stream cursors (advance by the step stride once per step; components are reached by adding the uniform stride)
-    const double *pn = A.noise.p ? A.noise.at(trial, 0, rb) : nullptr;
+    const double *pn = A.noise.p ? A.noise.at(src, 0, rb) : nullptr;
     double *px = A.x_out.p ? A.x_out.at(trial, 0, rb * N) : nullptr;
     double *pe = A.err_out.p ? A.err_out.at(trial, 0, rb) : nullptr;
     double *pf = A.f_out.p ? A.f_out.at(trial, 0, rb) : nullptr;
@@ -897,6 +920,13 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
     bool alive = true, flagged = false;                          // flagged: a rank-deficient Jacobian was seen -> careful second pass
 #pragma unroll
     for (int r = 0; r < R; ++r) des[r] = own_row([&](int row) { return fp.desired[row]; }, r);
+    if constexpr (PTP) {
+        const View &tp_des = trial_params_of(A)->desired;
+        if (tp_des.p) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) des[r] = *tp_des.at(trial, 0, r * RS + rb);
+        }
+    }
     double restored_word = 0.0;
     // The state of a trial chunk between two of its segments, [field][lane] in the workspace (seg_state_doubles per lane).
     auto seg_state = [&](auto saving) {
@@ -971,7 +1001,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
     } else {
         double q_all[N];
 #pragma unroll
-        for (int j = 0; j < N; ++j) { q_all[j] = *A.q_start.at(trial, 0, j); dq[j] = 0.0; }
+        for (int j = 0; j < N; ++j) { q_all[j] = *A.q_start.at(src, 0, j); dq[j] = 0.0; }
 #pragma unroll
         for (int u = 0; u < JG; ++u) {
             double cand[G];
@@ -996,7 +1026,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
             for (int r = 0; r < R; ++r) {
                 f_prev[r] = 0.0;                                   // f = zeros(m) (experiment.py:56)
 #pragma unroll
-                for (int j = 0; j < N; ++j) x0[r][j] = *A.x0.at(trial, 0, (r * RS + rb) * N + j);
+                for (int j = 0; j < N; ++j) x0[r][j] = *A.x0.at(src, 0, (r * RS + rb) * N + j);
             }
         }
 #pragma unroll
@@ -1369,7 +1399,10 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
         }
         UVS_STAMP(0);                                            // noise-load issue + plant
         if constexpr (kDiagStamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); UVS_STAMP(6); }   // slot 6: how long the oldest outstanding memory operation still takes
-        const double sigma = bandwidth(fp, k);
+        double sigma;
+        if constexpr (TP_LDS) sigma = 1.0;                        // (IMCC-KF forms its one weight from the LDS copy where it needs it, below)
+        else if constexpr (PTP) sigma = bandwidth_of(fp, tp_bw, k);
+        else sigma = bandwidth(fp, k);
         const double neg_half_inv_s2 = -0.5 * fast_rcp(sigma * sigma);
         double c_shared = 1.0;
         if constexpr (METHOD == UVS_METHOD_IMCCKF) {             // one weight for the whole filter: G(||Z - H X||) (experiment.py:258-261)
@@ -1391,6 +1424,10 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
             } else {
                 ss = pair_sum<L>(ss);
             }
+            if constexpr (TP_LDS) {                              // the trial's sigma_k, formed here so that nothing of it is live across the sums above
+                const double sigma_own = bandwidth_of(fp, lds_tp[0][lane], k);
+                c_shared = exp_nonpos(ss * (-0.5 * fast_rcp(sigma_own * sigma_own)));
+            } else
             c_shared = exp_nonpos(ss * neg_half_inv_s2);         // sqrt(.)**2 of the reference folded: G(n) = exp(-n^2 / (2 sigma^2))
         }
         double kap[R];
@@ -1439,7 +1476,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
             if constexpr (SHARED_P) {                                // one covariance block per lane (KF, IMCC-KF): p[0]
                 if (r == 0) {
                     NoHook none;
-                    rmckf_row<N, METHOD>(x, p[0], dq, zi, neg_half_inv_s2, c_shared, fp.reg, kap[r], chk, fpi, none, share);
+                    rmckf_row<N, METHOD>(x, p[0], dq, zi, neg_half_inv_s2, c_shared, PTP ? tp_reg : fp.reg, kap[r], chk, fpi, none, share);
                 } else {
                     rmckf_row_follow<N>(x, share, dq, zi, chk);
                     kap[r] = 1.0;
@@ -1448,7 +1485,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
 #pragma unroll
                 for (int e = 0; e < NP; ++e) pb[e] = (r < PV) ? p[r < PV ? r : 0][e] : lds_p[(r >= PV ? r - PV : 0) * NP + e][lane];
                 if constexpr (METHOD == UVS_METHOD_MCKF) { fpi.known = true; fpi.known_nu = pre_nu[r]; fpi.known_arg = pre_arg[r]; }
-                rmckf_row<N, METHOD>(x, pb, dq, zi, neg_half_inv_s2, c_shared, fp.reg, kap[r], chk, fpi);
+                rmckf_row<N, METHOD>(x, pb, dq, zi, neg_half_inv_s2, c_shared, PTP ? tp_reg : fp.reg, kap[r], chk, fpi);
             }
             if constexpr (METHOD == UVS_METHOD_MCKF) { m_gamma[r] = fpi.row_gamma; m_a[r] = fpi.row_a; m_nu[r] = fpi.row_nu; m_z[r] = zi; e_s2[r] = fpi.row_s2; e_gg[r] = fpi.row_gg; }
 #pragma unroll
@@ -1489,7 +1526,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
                 fpi.num = pair_sum<L>(fpi.num);
                 fpi.den = pair_sum<L>(fpi.den);
             }
-            const double thr2 = fp.fpi_threshold * fp.fpi_threshold;
+            const double thr2 = (PTP ? tp_thr : fp.fpi_threshold) * (PTP ? tp_thr : fp.fpi_threshold);
             bool more = alive && !fpi.skip && !fpi.poison && (fpi.num > thr2 * fpi.den);  // ||Xc - X|| / ||X|| > threshold; NaN ends the iteration like the reference's while
             if (__builtin_expect(__any(more), 0)) {
                 // ---- the fixed-point branch, spread over the wavefront (round 5).  Round 4 ran it where the state lives: the two lanes of an
@@ -1543,6 +1580,9 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
                     double x[N], pp[NP], h[N], kk[N];
                     // (then the four undo scalars -- their 4 R sources die with the pulls -- and the command)
                     double r_gamma, r_a, r_nu, r_z;
+                    // PTP: the row iterates with ITS trial's bandwidth and threshold, fetched from the owner like the rest of its state
+                    double r_nh = neg_half_inv_s2, r_thr2 = thr2;
+                    if constexpr (PTP) { r_nh = in_reg(pull(sa, neg_half_inv_s2)); r_thr2 = in_reg(pull(sa, thr2)); }
                     {                                                         // the four undo scalars of the row: R candidates each, two batches
                         auto pull2 = [&](const double (&u)[R], const double (&v)[R], double &ru, double &rv) {
                             double cu[R], cv[R];
@@ -1616,7 +1656,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
                         bool bad2 = false;
 #pragma unroll
                         for (int l = 0; l < N; ++l) { dd[l] = 0.0; xcv[l] = 0.0; kn[l] = 0.0; }
-                        if (more_t) mckf_iterate_row<N>(x, Lc, ljj, h, r_z, neg_half_inv_s2, kk, kn, dd, xcv, bad2);
+                        if (more_t) mckf_iterate_row<N>(x, Lc, ljj, h, r_z, r_nh, kk, kn, dd, xcv, bad2);
                         // ||Xn - Xc||^2 and ||Xc||^2 in the owner lanes' order: local rows 0 .. R-1 of a parity as one chain, passed down the slot
                         double cn = 0.0, cd = 0.0;
                         constexpr int CH = M / 2;                                 // local rows of a parity in the two-lane numbering
@@ -1640,7 +1680,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
                                 for (int j = 0; j < N; ++j) kk[j] = kn[j];
                                 ++it_t;
                                 if (it_t == fp.fpi_epoch_max) skip2 = true;       // :246-250
-                                again = !skip2 && (num2 > thr2 * den2) && it_t < fp.fpi_epoch_max;
+                                again = !skip2 && (num2 > r_thr2 * den2) && it_t < fp.fpi_epoch_max;
                             }
                         }
                         // the verdict of the lanes that hold the complete sums, for the whole slot
@@ -1736,7 +1776,7 @@ void closed_loop_tuned_kernel(const ClosedArgs A) {
             }
             flagged |= alive && suspect;
 #pragma unroll
-            for (int j = 0; j < N; ++j) dq[j] = -fp.gain * sol[j];
+            for (int j = 0; j < N; ++j) dq[j] = -(TP_LDS ? lds_tp[TP_LDS ? 1 : 0][lane] : PTP ? tp_gain : fp.gain) * sol[j];
         }
         if (!__any(alive)) break;                                // the last live trial of the wavefront just FAILed: nothing left to log
         UVS_STAMP(2);                                            // control law

@@ -3,6 +3,7 @@
 // Kernels (all fp64, wave64, 64-thread workgroups so that each wavefront is scheduled independently) live in headers and are
 // instantiated by one translation unit per family (launchers.hpp) so that the library builds in parallel:
 //   rmckf_tuned.hpp          closed_loop_tuned_kernel: whole servo trial per filter, headline shapes (tu_closed_tuned_{a,b}.hip)
+//                            closed_loop_grid_kernel: the same body with per-trial estimator parameters (UVS_PER_TRIAL; tu_closed_grid_{a,b}.hip)
 //   rmckf_replay_tuned.hpp   replay_tuned_kernel / replay_rows_kernel: estimator (+ control law) over recorded streams (tu_replay_tuned.hip)
 //   rmckf_generic.hpp        closed_loop_kernel / replay_kernel / step_kernel: any shape, every estimator incl. MCKF; stats_kernel
 //                            (tu_generic_{a,b}.hip, tu_misc.hip)
@@ -20,6 +21,14 @@
 #endif
 
 using namespace uvs_launch;
+
+#ifdef UVS_NO_PER_TRIAL                   // single-translation-unit diagnostic builds (uvs_unity.hip): a translation unit holds ONE flavour of the kernel text,
+namespace uvs_launch {                   // so they carry no per-trial kernels and uvs_rmckf_closed_loop_grid_f64 answers UVS_ERR_SHAPE
+bool closed_grid_a(int, bool, int64_t, hipStream_t, const uvs::ClosedGridArgs &) { return false; }
+bool closed_grid_b(int, bool, int64_t, hipStream_t, const uvs::ClosedGridArgs &) { return false; }
+bool closed_grid_careful(int64_t, hipStream_t, const uvs::ClosedGridArgs &) { return false; }
+}  // namespace uvs_launch
+#endif
 
 // ================================================================================================ C ABI
 namespace {
@@ -171,6 +180,11 @@ size_t seg_workspace_bytes(const uvs_filter_params &fp, int64_t T, int n_seg) {
     return seg_flag_bytes(chunks) + (size_t)chunks * uvs::seg_state_doubles(fp.m, fp.n, 2) * 64 * sizeof(double);
 }
 
+int closed_loop_impl(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T, const uvs_trial_params *tp, uvs_view q_start, uvs_view noise,
+                     uvs_view x0, uvs_view x_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out,
+                     double *stats, int32_t *status, int32_t *k_done, uvs_view x_final, uvs_view p_final,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 }  // namespace
 
 extern "C" {
@@ -218,6 +232,35 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
                                  uvs_view x0, uvs_view x_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out,
                                  double *stats, int32_t *status, int32_t *k_done, uvs_view x_final, uvs_view p_final,
                                  void *workspace, size_t workspace_bytes, void *stream) {
+    return closed_loop_impl(fp, plant, T, nullptr, q_start, noise, x0, x_out, err_out, q_out, f_out, dq_out, stats, status, k_done, x_final, p_final,
+                            workspace, workspace_bytes, stream);
+}
+
+int uvs_rmckf_closed_loop_grid_f64(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T, const uvs_trial_params *tp, uvs_view q_start,
+                                   uvs_view noise, uvs_view x0, uvs_view x_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out,
+                                   double *stats, int32_t *status, int32_t *k_done, uvs_view x_final, uvs_view p_final,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    if (!fp) return fail(UVS_ERR_ARG, "%s", "filter params are NULL");
+    if (!tp) return fail(UVS_ERR_ARG, "%s", "trial params are NULL (uvs_rmckf_closed_loop_ws_f64 is the call without them)");
+    if (fp->method == UVS_METHOD_ANALYTICAL) return fail(UVS_ERR_METHOD, "%s", "per-trial parameters: KF, MCKF, IMCCKF and GMCKF only, not the calibrated baseline");
+    if (fp->m != 8 || fp->n != 6 || (fp->lanes_per_filter != 0 && fp->lanes_per_filter != 2))
+        return fail(UVS_ERR_SHAPE, "%s", "per-trial parameters are instantiated for (m, n) = (8, 6) with lanes_per_filter 0 or 2 only");
+    if (plant && plant->kind != UVS_PLANT_DH_PINHOLE) return fail(UVS_ERR_SHAPE, "%s", "per-trial parameters are instantiated for the DH / pinhole plant only");
+    if (fp->reserved & (UVS_OPT_STRICT_PINV | UVS_OPT_LATENCY | UVS_OPT_DIAG_DROP_SEG_FLAG))
+        return fail(UVS_ERR_ARG, "%s", "per-trial parameters: UVS_OPT_STRICT_PINV, UVS_OPT_LATENCY and UVS_OPT_DIAG_DROP_SEG_FLAG are not available");
+    return closed_loop_impl(fp, plant, T, tp, q_start, noise, x0, x_out, err_out, q_out, f_out, dq_out, stats, status, k_done, x_final, p_final,
+                            workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+namespace {
+// The closed-loop launch behind uvs_rmckf_closed_loop_ws_f64 (tp == nullptr) and uvs_rmckf_closed_loop_grid_f64 (tp: per-trial parameters; the
+// entry point has already refused what has no per-trial kernel): one set of checks, one plan, one workspace layout.
+int closed_loop_impl(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T, const uvs_trial_params *tp, uvs_view q_start, uvs_view noise,
+                     uvs_view x0, uvs_view x_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out,
+                     double *stats, int32_t *status, int32_t *k_done, uvs_view x_final, uvs_view p_final,
+                     void *workspace, size_t workspace_bytes, void *stream) {
     int L = 0;
     if (int rc = check_params(fp, T, &L)) return rc;
     if (!plant) return fail(UVS_ERR_ARG, "%s", "plant is NULL");
@@ -232,8 +275,17 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
     if (!q_start.base) return fail(UVS_ERR_ARG, "%s", "q_start view is NULL");
     if (!status) return fail(UVS_ERR_ARG, "%s", "status is required (it also carries the suspect marks between the two passes)");
     if (!fp->initial_guess && !x0.base) return fail(UVS_ERR_ARG, "%s", "x0 view is required when initial_guess == 0");
-    const ClosedPlan plan = plan_closed_loop(*fp, *plant, T);
-    uvs::ClosedArgs A;
+    ClosedPlan plan = plan_closed_loop(*fp, *plant, T);
+    // per-trial parameters: the two-lane tuned kernel only.  Where the plan picks the four-lane small-batch kernels (whole trials, the two-lane
+    // kernel's bits) the grid runs on two lanes, whole trials as planned.
+    if (tp && plan.route == Route::kEmu2) { plan.route = Route::kTuned; plan.L = 2; }
+    if (tp && (plan.route != Route::kTuned || plan.L != 2)) return fail(UVS_ERR_SHAPE, "%s", "per-trial parameters: no kernel for this plan");
+    uvs::ClosedGridArgs A;                                         // (the uniform kernels take its ClosedArgs base)
+    if (tp) {
+        A.tp.kernel_bw = tp->kernel_bw; A.tp.gain = tp->gain; A.tp.reg = tp->reg; A.tp.fpi_threshold = tp->fpi_threshold;
+        A.tp.desired = uvs::to_view(tp->desired);
+        A.tp.source = tp->source;
+    }
     A.fp = *fp;
     A.plant = *plant;
     A.T = T;
@@ -269,6 +321,9 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
     const int m = fp->m, n = fp->n, method = fp->method;
     const bool linear = plant->kind == UVS_PLANT_LINEAR, xo = x_out.base != nullptr;
     bool launched = true;
+    if (tp) {
+        launched = closed_grid_a(method, xo, T, s, A) || closed_grid_b(method, xo, T, s, A);
+    } else
     switch (plan.route) {
     case Route::kTuned:
         launched = closed_tuned_a(m, n, plan.L, method, linear, xo, T, s, A) || closed_tuned_b(m, n, plan.L, method, linear, xo, T, s, A);
@@ -288,10 +343,13 @@ int uvs_rmckf_closed_loop_ws_f64(const uvs_filter_params *fp, const uvs_plant *p
 #endif
     // second pass: trials in which the control law met a numerically rank-deficient Jacobian (status left at UVS_STATUS_SUSPECT) are
     // re-run with numpy's pinv semantics (experiment.py:312); wavefronts without such a trial exit at once
-    if (!(closed_careful_a(fp->m, fp->n, T, s, A) || closed_careful_b(fp->m, fp->n, T, s, A)))
+    if (!(tp ? closed_grid_careful(T, s, A) : (closed_careful_a(fp->m, fp->n, T, s, A) || closed_careful_b(fp->m, fp->n, T, s, A))))
         return fail(UVS_ERR_SHAPE, "%s", "(m, n) has no careful closed-loop instantiation in libuvs_rmckf");
     return check_launch("closed_loop_kernel (careful pass)");
 }
+}  // namespace
+
+extern "C" {
 
 int uvs_analytical_closed_loop_f64(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T, uvs_view q_start, uvs_view noise,
                                    uvs_view j_out, uvs_view err_out, uvs_view q_out, uvs_view f_out, uvs_view dq_out, double *stats,

@@ -1,5 +1,6 @@
 // Single-translation-unit view of the library for the diagnostic builds (make quick / stamps / ablate / asm), which pass one set of
 // -D flags to everything.  The shipped library is built from the separate translation units (make, make -j).
+#define UVS_NO_PER_TRIAL                  // (the per-trial kernels are the same text compiled with UVS_PER_TRIAL: separate translation units only)
 #include "uvs_rmckf.hip"
 #include "tu_closed_tuned_a.hip"
 #undef UVS_TU_SHAPES

@@ -132,7 +132,32 @@ def launch_closed_loop(fp, plant_struct, T, *args, device=None):
     return _lib.lib().uvs_rmckf_closed_loop_ws_f64(C.byref(fp), C.byref(plant_struct), T, *args, ws, ws_bytes, _stream())
 
 
-def closed_loop(fp, plant_struct, q_start, noise=None, x0=None, want=('x', 'err', 'q'), layout='kct', final_state=False, x_layout=None, reuse=None):
+TRIAL_PARAM_KEYS = ('kernel_bw', 'gain', 'reg', 'fpi_threshold', 'desired', 'source')
+
+
+def trial_params_struct(trial_params, T, m, device):
+    """uvs_trial_params over the tensors of ``trial_params`` (closed_loop's argument of that name), after checking their dtypes, shapes and device."""
+    import torch
+    unknown = set(trial_params) - set(TRIAL_PARAM_KEYS)
+    if unknown:
+        raise ValueError(f'trial_params: unknown keys {sorted(unknown)}; known: {TRIAL_PARAM_KEYS}')
+    tp = _lib.TrialParams(None, None, None, None, NULL_VIEW, None)
+    for key, value in trial_params.items():
+        if value is None:
+            continue
+        shape, dtype = ((T, m), torch.float64) if key == 'desired' else ((T,), torch.int32 if key == 'source' else torch.float64)
+        if tuple(value.shape) != shape or value.dtype != dtype or value.device != device or not value.is_contiguous():
+            raise ValueError(f'trial_params[{key!r}]: a contiguous {dtype} tensor of shape {shape} on {device} is needed, got '
+                             f'{value.dtype} {tuple(value.shape)} on {value.device}')
+        if key == 'desired':
+            tp.desired = View(value.data_ptr(), value.stride(0), 0, value.stride(1))
+        else:
+            setattr(tp, key, value.data_ptr())
+    return tp
+
+
+def closed_loop(fp, plant_struct, q_start, noise=None, x0=None, want=('x', 'err', 'q'), layout='kct', final_state=False, x_layout=None, reuse=None,
+                trial_params=None):
     """Launch T closed-loop trials.  ``q_start``: (T, n) cuda tensor; ``noise``: stream tensor in ``layout`` or None;
     ``x0``: (T, m*n) cuda tensor when fp.initial_guess == 0.  Returns a dict of output tensors (streams in ``layout``).
     ``x_layout``: another layout for the X stream alone.  The default -- X trial-fastest like every stream -- is what the kernels are tuned for (since round 6
@@ -141,10 +166,17 @@ def closed_loop(fp, plant_struct, q_start, noise=None, x0=None, want=('x', 'err'
     IMCC-KF.  Only there: RMCKF and MCKF keep their strided stores whatever the view, and smaller batches run on the four-lane kernels, for which 'ktc' is an
     uncoalesced, slower path.
     ``reuse``: the dict an earlier call with at least as many trials returned -- its tensors are written again ([..., :T] of the streams,
-    [:T] of the per-trial arrays) instead of allocating new ones (batch.run_sweep: cell after cell through one set of buffers)."""
+    [:T] of the per-trial arrays) instead of allocating new ones (batch.run_sweep: cell after cell through one set of buffers).
+    ``trial_params``: per-trial estimator parameters, ONE launch for a whole hyperparameter grid (uvs_rmckf_closed_loop_grid_f64; (8,6), DH plant, two
+    lanes per filter): a dict with any of 'kernel_bw', 'gain', 'reg', 'fpi_threshold' ((T,) fp64 cuda tensors), 'desired' ((T, m)) and 'source' ((T,)
+    int32: trial t reads q_start / noise / x0 of trial source[t]; its values must index the trials those tensors hold -- they are not checked on the
+    device).  With 'source' T is len(source) and q_start / noise / x0 may hold fewer trials.  A trial's results are bit-identical to those of a uniform
+    launch with its values.  None (the default) is the uniform call."""
     x_layout = x_layout or layout
     torch = _torch()
     T, K, m, n = q_start.shape[0], fp.steps, fp.m, fp.n
+    if trial_params is not None and trial_params.get('source') is not None:
+        T = trial_params['source'].shape[0]
     dev = q_start.device
     out = {}
     tdim = lambda lay: {'kct': 2, 'ktc': 1, 'tkc': 0}[lay]         # noqa: E731
@@ -167,13 +199,17 @@ def closed_loop(fp, plant_struct, q_start, noise=None, x0=None, want=('x', 'err'
     flat = lambda t: NULL_VIEW if t is None else View(t.data_ptr(), t.stride(0), 0, t.stride(1))      # noqa: E731
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)           # around the launch only: the
     ws, ws_bytes = workspace(fp, plant_struct, T, dev)
+    args = (flat(q_start), stream_view(noise, layout), flat(x0),
+            stream_view(out['x'], x_layout), stream_view(out['err'], layout), stream_view(out['q'], layout),
+            stream_view(out['f'], layout), stream_view(out['dq'], layout),
+            out['stats'].data_ptr(), out['status'].data_ptr(), out['k_done'].data_ptr(),
+            flat(out['x_final']), flat(out['p_final']), ws, ws_bytes, _stream())
+    tp = trial_params_struct(trial_params, T, m, dev) if trial_params is not None else None
     start.record()                                                                                     # allocations above are not kernel time
-    rc = _lib.lib().uvs_rmckf_closed_loop_ws_f64(
-        C.byref(fp), C.byref(plant_struct), T, flat(q_start), stream_view(noise, layout), flat(x0),
-        stream_view(out['x'], x_layout), stream_view(out['err'], layout), stream_view(out['q'], layout),
-        stream_view(out['f'], layout), stream_view(out['dq'], layout),
-        out['stats'].data_ptr(), out['status'].data_ptr(), out['k_done'].data_ptr(),
-        flat(out['x_final']), flat(out['p_final']), ws, ws_bytes, _stream())
+    if tp is not None:
+        rc = _lib.lib().uvs_rmckf_closed_loop_grid_f64(C.byref(fp), C.byref(plant_struct), T, C.byref(tp), *args)
+    else:
+        rc = _lib.lib().uvs_rmckf_closed_loop_ws_f64(C.byref(fp), C.byref(plant_struct), T, *args)
     stop.record()
     _lib.check(rc)
     out['events'] = (start, stop)
