@@ -373,6 +373,8 @@ def test_lost_hand_over_falls_back_to_recomputation(uvs, method, segments):
         torch.cuda.synchronize()
         outs[-1]['wall'] = time.perf_counter() - t0
         outs[-1]['fallbacks'] = uvs.engine.hand_over_fallbacks(fp, plant, T)
+        named = uvs.engine.hand_over_fallbacks(fp, plant, T, device=torch.device('cuda'))    # 'cuda' is the workspace of the current 'cuda:N'
+        assert named == outs[-1]['fallbacks'] and (n == 1 or isinstance(named, int)), (named, outs[-1]['fallbacks'])
     a, b, c = outs
     # the launch counts the items that fell back (uvs_rmckf_closed_loop_fallback_offset): none on a healthy launch, every later segment of every
     # chunk when the first counter is withheld (an item that fell back hands nothing over, so its successors fall back too)

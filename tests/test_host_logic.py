@@ -408,6 +408,63 @@ def test_sweep_pieces_cover_a_shard_cell_by_cell():
     assert batch.sweep_pieces(plan, 5, 5) == []
 
 
+@pytest.mark.parametrize('path, method_code', [(os.path.join('examples', 'config.json'), 5), (os.path.join('tests', 'golden', 'config_reference.json'), 3)])
+def test_launch_setup_reads_the_config_once(uvs, path, method_code):
+    """batch.launch_setup is what run_batch, run_sweep and run_grid make of a reference config: the uvs_filter_params fields against the two committed
+    configs (literals: what the files say), the defaults of absent keys, the option bits, the noise description and the x0 / initial_guess rules."""
+    batch = uvs.batch
+    cfg = json.load(open(os.path.join(ROOT, path)))
+    s = batch.launch_setup(cfg)
+    fp = s.fp
+    assert (fp.m, fp.n, fp.method, fp.kernel_bw, fp.annealing, fp.gain, fp.dt) == (8, 6, method_code, 10.0, 0, 0.2, 0.05)
+    assert (fp.k_max, fp.steps, fp.reg, fp.fpi_threshold, fp.fpi_epoch_max) == (int(15 / 0.05), 299, 1e-6, 0.1, 1000)
+    assert (fp.initial_guess, fp.lanes_per_filter, fp.reserved) == (1, 0, 0)
+    assert list(fp.desired[:8]) == [149.0, 145.0, 125.0, 121.0, 101.0, 145.0, 125.0, 169.0] and not any(fp.desired[8:])
+    assert (s.method.name, s.analytical, s.K, s.m, s.n, s.x0) == (cfg['estimator']['method'], False, 299, 8, 6, None)
+    assert len(s.t_log) == 299 and s.t_log[0] == 0.05 and s.plant.n_joints == 6 and s.plant_struct.n_joints == 6
+    assert batch.launch_setup(cfg, lanes=2).fp.lanes_per_filter == 2
+    for strict in (False, True):
+        for latency in (False, True):
+            assert batch.launch_setup(cfg, strict_pinv=strict, latency=latency).fp.reserved == (1 if strict else 0) + (2 if latency else 0)
+    assert (uvs._lib.UVS_OPT_STRICT_PINV, uvs._lib.UVS_OPT_LATENCY) == (1, 2)          # include/uvs_rmckf.h
+    # the noise description: ALPHA_STABLE sweeps alpha, every other type rho; hold_cnt = int(hold_time / dt)
+    nd = s.noise
+    assert (nd.type.name, nd.key, nd.hold, nd.hold_cnt, nd.m) == ('ALPHA_STABLE', 'alpha', False, int(0.5 / 0.05), 8) and nd.hold_cnt == 10
+    before = dict(cfg['noise']['noise_params'])
+    assert nd.cell_params(1.5) == dict(before, alpha=1.5) and cfg['noise']['noise_params'] == before      # a cell's params are a copy
+    other = json.loads(json.dumps(cfg))
+    other['noise'].update(type='GAUSSIAN_MIXTURE', noise_params={'std': 1.0, 'mean': 0.0, 'rho': 0.5}, hold=True, hold_time=0.26)
+    nd = batch.launch_setup(other).noise
+    assert (nd.key, nd.hold, nd.hold_cnt) == ('rho', True, int(0.26 / 0.05)) and nd.cell_params(0.1) == {'std': 1.0, 'mean': 0.0, 'rho': 0.1}
+    # absent estimator keys: kernel_bw 1.0, annealing False, fpi_threshold 0.1, fpi_epoch_max 1000 -- but initial_guess is required of an estimator
+    bare = json.loads(json.dumps(cfg))
+    bare['estimator']['estimator_params'] = {'initial_guess': True}
+    fp = batch.launch_setup(bare).fp
+    assert (fp.kernel_bw, fp.annealing, fp.fpi_threshold, fp.fpi_epoch_max, fp.initial_guess) == (1.0, 0, 0.1, 1000, 1)
+    for method in ('KF', 'MCKF', 'IMCCKF', 'GMCKF'):
+        bare['estimator'].update(method=method, estimator_params={})
+        with pytest.raises(KeyError):
+            batch.launch_setup(bare)
+    # ANALYTICAL estimates nothing: initial_guess defaults to True, no x0 whatever the config says, lane options are refused, strict_pinv applies
+    bare['estimator'].update(method='ANALYTICAL', estimator_params={})
+    s = batch.launch_setup(bare, strict_pinv=True)
+    assert (s.analytical, s.fp.method, s.fp.initial_guess, s.fp.reserved, s.x0) == (True, 1, 1, 1, None)
+    bare['estimator']['estimator_params'] = {'initial_guess': False}
+    assert batch.launch_setup(bare).x0 is None
+    for kw in ({'lanes': 2}, {'latency': True}):
+        with pytest.raises(ValueError):
+            batch.launch_setup(bare, **kw)
+    # initial_guess false: the estimator starts from the config's x0, one (1, m n) row for the drivers to repeat per trial
+    own = json.loads(json.dumps(cfg))
+    x0 = np.arange(48.0).reshape(8, 6)
+    own['estimator']['estimator_params'].update(initial_guess=False, x0=x0.tolist())
+    s = batch.launch_setup(own)
+    assert s.fp.initial_guess == 0 and s.x0.shape == (1, 48) and np.array_equal(s.x0[0], x0.ravel())
+    del own['estimator']['estimator_params']['x0']
+    with pytest.raises(KeyError):
+        batch.launch_setup(own)
+
+
 def test_counter_figures_belong_to_this_library(uvs):
     """profiles/traffic_latest.json feeds bench.py's roofline.traffic / roofline.valu with PMC counts of an EARLIER profiling call.  They are valid
     only for the kernels they were counted on: the file records the fingerprint of the kernel sources it was taken with (csrc/src_hash.py:

@@ -14,6 +14,7 @@ CSRC = os.path.join(HERE, 'csrc')
 UVS_MAX_M, UVS_MAX_N, UVS_MAX_POINTS = 32, 8, 16
 METHOD_ANALYTICAL, METHOD_KF, METHOD_MCKF, METHOD_IMCCKF, METHOD_GMCKF = 1, 2, 3, 4, 5
 PLANT_DH_PINHOLE, PLANT_LINEAR = 0, 1
+UVS_OPT_STRICT_PINV, UVS_OPT_LATENCY = 1, 2                         # option bits of FilterParams.reserved
 
 
 class UvsLibraryError(RuntimeError):

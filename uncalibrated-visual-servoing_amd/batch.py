@@ -5,13 +5,14 @@ Keeps the reference's ``config.json`` schema (main.py:16-98), sweep cells (``lin
 ``seed + trial`` (main.py:137-139), the q_start jitter stream ``NoiseProfiler(2, UNIFORM, seed=experiment_seed)`` with
 the ``2 (r - 1)`` formula (main.py:118, 132-134) and the 41-column results.csv (main.py:152-196; SURVEY.md says 43, the DataFrame has 4 + 6 + 6 + 8 + 8 + 8 + 1 = 41).
 """
+import functools
 import json
 import os
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import dist, engine, noise_device
+from . import _lib, dist, engine, noise_device
 from .experiment import ExperimentStatus, Method, bandwidth_log
 from .noise import NoiseProfiler, NoiseType, noise_batch
 from .plant import SyntheticPlant
@@ -79,19 +80,25 @@ def plan_trials(cfg, cells=None, epoch=None):
     return TrialPlan(cell=np.repeat(np.arange(len(cells)), epoch), value=np.repeat(cells, epoch), seed=seeds, q_start=q0, cells=cells)
 
 
+class NoiseSpec:
+    """What a config says about the measurement noise, but for the swept value of a cell."""
+
+    def __init__(self, cfg):
+        ex, nz = cfg['experiments'], cfg['noise']
+        self.type, self.params, self.hold, self.m = NoiseType[nz['type']], nz['noise_params'], nz['hold'], len(ex['desired_f'])
+        self.key = 'alpha' if self.type == NoiseType.ALPHA_STABLE else 'rho'    # the swept parameter (main.py:104-106)
+        self.hold_cnt = int(nz['hold_time'] / ex['dt'])             # main.py:137
+
+    def cell_params(self, value):
+        return {**self.params, self.key: float(value)}              # main.py:123-126
+
+
 def trial_noise(cfg, plan, lo, hi, steps, out):
     """Fill ``out`` (logical [trial][step][m] array-like covering trials lo..hi) with the reference's noise streams."""
-    nz = cfg['noise']
-    noise_type = NoiseType[nz['type']]
-    m = len(cfg['experiments']['desired_f'])
-    hold_cnt = int(nz['hold_time'] / cfg['experiments']['dt'])      # main.py:137
-    key = 'alpha' if noise_type == NoiseType.ALPHA_STABLE else 'rho'
+    nd = NoiseSpec(cfg)
     for c in np.unique(plan.cell[lo:hi]):
         idx = np.nonzero(plan.cell[lo:hi] == c)[0]
-        params = dict(nz['noise_params'])
-        params[key] = float(plan.cells[c])                          # main.py:123-126
-        block = noise_batch(noise_type, params, plan.seed[lo:hi][idx], m, steps, nz['hold'], hold_cnt)
-        out[idx] = block
+        out[idx] = noise_batch(nd.type, nd.cell_params(plan.cells[c]), plan.seed[lo:hi][idx], nd.m, steps, nd.hold, nd.hold_cnt)
     return out
 
 
@@ -109,41 +116,98 @@ class BatchResult:
     seconds: float = 0.0
 
 
+def _upload_seeds(seeds, device):
+    """int64 device tensor of the uint64 bit patterns of ``seeds``: one upload for a shard, sliced per piece."""
+    return engine._torch().as_tensor(np.ascontiguousarray(seeds, dtype=np.uint64).view(np.int64), device=device)
+
+
+def _cell_noise(nd, value, seeds, seeds_dev, steps, device, share=True, out=None):
+    """Noise streams, [step][feature][trial], of the trials of ONE cell (swept value ``value``) whose seeds are ``seeds`` (host) / ``seeds_dev`` (their
+    _upload_seeds slice, or None: uploaded here), generated on the GPU (noise_device.py).  ``share``: where the trials' streams alias
+    (noise_device.shares_streams: consecutive seeds, no hold) generate the T + 70 distinct streams once and return an overlapping view (main.py:137-139 +
+    noise.py:70) -- bit-identical to the per-trial generation.  ``out``: None (a fresh tensor), a flat fp64 buffer of at least steps x max(T + 70, m T)
+    that either form is laid into, or -- with ``share`` off -- the [step][feature][trial] destination."""
+    T, m = len(seeds), nd.m
+    params = nd.cell_params(value)
+    flat = out is not None and out.dim() == 1
+    if share and (out is None or flat) and noise_device.shares_streams(nd.type, nd.hold, seeds):
+        S = T + noise_device.SEED_STEP * (m - 1)
+        return noise_device.generate_shared(nd.type, params, int(seeds[0]), T, m, steps, out=out[:steps * S].view(steps, S) if flat else None, device=device)[1]
+    if out is None:
+        out = engine.alloc_stream(T, steps, m, 'kct', device)
+    elif flat:
+        out = out[:steps * m * T].view(steps, m, T)
+    return noise_device.generate(nd.type, params, seeds if seeds_dev is None else seeds_dev, m, steps, nd.hold, nd.hold_cnt, 'kct', out=out, device=device)
+
+
 def device_noise(cfg, plan, lo, hi, steps, device='cuda', share=True):
-    """Noise streams of trials lo..hi generated on the GPU (noise_device.py), [step][feature][trial].  ``share``: where the trials' streams
-    alias (noise_device.shares_streams) generate each distinct stream once and return an overlapping view."""
-    nz = cfg['noise']
-    noise_type = NoiseType[nz['type']]
-    m = len(cfg['experiments']['desired_f'])
-    hold_cnt = int(nz['hold_time'] / cfg['experiments']['dt'])      # main.py:137
-    key = 'alpha' if noise_type == NoiseType.ALPHA_STABLE else 'rho'
-    torch = engine._torch()
-    cells_here = np.unique(plan.cell[lo:hi])
-    if share and len(cells_here) == 1 and noise_device.shares_streams(noise_type, nz['hold'], plan.seed[lo:hi]):
-        # one cell, consecutive seeds, no hold: the T + 70 distinct streams once, read through an overlapping [step][feature][trial] view
-        # (main.py:137-139 + noise.py:70; a shard's rank generates seeds lo ... hi + 70) -- bit-identical to the per-trial generation below
-        params = dict(nz['noise_params'])
-        params[key] = float(plan.cells[cells_here[0]])
-        return noise_device.generate_shared(noise_type, params, int(plan.seed[lo]), hi - lo, m, steps, device=device)[1]
-    out = engine.alloc_stream(hi - lo, steps, m, 'kct', device)
-    seeds_dev = torch.as_tensor(np.ascontiguousarray(plan.seed[lo:hi], dtype=np.uint64).view(np.int64), device=device)   # one upload for the shard
-    for c in np.unique(plan.cell[lo:hi]):
-        idx = np.nonzero(plan.cell[lo:hi] == c)[0]                  # cells are contiguous runs of trials (main.py:121-127)
-        params = dict(nz['noise_params'])
-        params[key] = float(plan.cells[c])                          # main.py:123-126
-        a, b = int(idx[0]), int(idx[-1]) + 1
-        noise_device.generate(noise_type, params, seeds_dev[a:b], m, steps, nz['hold'], hold_cnt, 'kct', out=out[:, :, a:b], device=device)
+    """Noise streams of trials lo..hi generated on the GPU, [step][feature][trial] (_cell_noise).  ``share``: where the shard is one cell whose trials'
+    streams alias, generate each distinct stream once and return an overlapping view."""
+    nd = NoiseSpec(cfg)
+    runs = sweep_pieces(plan, lo, hi)                               # cells are contiguous runs of trials (main.py:121-127)
+    if len(runs) == 1:
+        return _cell_noise(nd, plan.cells[runs[0][2]], plan.seed[lo:hi], None, steps, device, share)
+    out = engine.alloc_stream(hi - lo, steps, nd.m, 'kct', device)
+    seeds_dev = _upload_seeds(plan.seed[lo:hi], device)
+    for a, b, c in runs:
+        _cell_noise(nd, plan.cells[c], plan.seed[a:b], seeds_dev[a - lo:b - lo], steps, device, False, out[:, :, a - lo:b - lo])
     return out
 
 
-def _check_analytical(method, lanes, latency):
-    """True for the calibrated baseline (Method.ANALYTICAL, engine.analytical_closed_loop: one lane per trial, so the estimators' lane options
-    do not apply); the reference's Experiment.run() crashes there (R unbound, experiment.py:121) in two lines only the estimators use."""
-    if method != Method.ANALYTICAL:
-        return False
-    if lanes or latency:
+@dataclass
+class LaunchSetup:
+    """What a reference config means to a launch (launch_setup)."""
+    cfg: dict                # validated (load_config)
+    method: Method
+    analytical: bool
+    plant: object
+    fp: object               # uvs_filter_params, option bits in ``reserved``
+    t_log: np.ndarray        # engine.loop_clock: the K logged times
+    K: int
+    m: int
+    n: int
+    x0: np.ndarray           # (1, m n) row of estimator_params['x0'] when initial_guess is false, else None
+    noise: NoiseSpec
+
+    @functools.cached_property
+    def plant_struct(self):
+        """uvs_plant, made on first use: a LinearPlant uploads its arrays to the device that is current then."""
+        return self.plant.to_struct()
+
+    def x0_rows(self, T, device):
+        """(T, m n) device tensor of the x0 row, or None."""
+        return None if self.x0 is None else engine._torch().as_tensor(self.x0.repeat(T, 0), device=device)
+
+    def closed_loop(self, q_start, noise, x0, want, reuse=None, trial_params=None):
+        """The engine launch of this method; ``x0``: x0_rows(...) of at least as many trials, or None."""
+        if self.analytical:
+            return engine.analytical_closed_loop(self.fp, self.plant_struct, q_start, noise, want=want, reuse=reuse)
+        return engine.closed_loop(self.fp, self.plant_struct, q_start, noise, x0, want=want, reuse=reuse, trial_params=trial_params)
+
+
+def launch_setup(cfg, plant=None, lanes=0, strict_pinv=False, latency=False):
+    """Everything run_batch, run_sweep and run_grid derive from a reference config before they touch the device -- THE place where an estimator
+    parameter, its default, an option bit or a noise rule is read.  Host only.  Raises what load_config raises, ValueError for ANALYTICAL with lane
+    options and KeyError when an estimator's ``initial_guess`` is missing (ANALYTICAL, which estimates nothing, defaults it).  ``strict_pinv`` /
+    ``latency``: the library's launch options UVS_OPT_STRICT_PINV and UVS_OPT_LATENCY -- not part of config.json, whose schema stays the reference's."""
+    cfg = load_config(cfg)
+    ex, est = cfg['experiments'], cfg['estimator']
+    method = Method[est['method']]
+    # the calibrated baseline (engine.analytical_closed_loop) runs one lane per trial, so the estimators' lane options do not apply; the reference's
+    # Experiment.run() crashes there (R unbound, experiment.py:121) in two lines only the estimators use
+    analytical = method == Method.ANALYTICAL
+    if analytical and (lanes or latency):
         raise ValueError('lanes / latency select estimator kernels; the ANALYTICAL closed loop has one mapping (strict_pinv applies)')
-    return True
+    plant = SyntheticPlant.ur10(ex['desired_f']) if plant is None else plant
+    p = est.get('estimator_params') or {}
+    m, n = len(ex['desired_f']), plant.n_joints
+    initial_guess = p.get('initial_guess', True) if analytical else p['initial_guess']
+    t_log = engine.loop_clock(ex['dt'], ex['t_max'])
+    fp = engine.make_params(m, n, method.name, p.get('kernel_bw', 1.0), p.get('annealing', False), ex['dt'], ex['t_max'], ex['ibvs_gain'],
+                            ex['desired_f'], initial_guess, lanes, len(t_log), p.get('fpi_threshold', 0.1), p.get('fpi_epoch_max', 1000))
+    fp.reserved = (_lib.UVS_OPT_STRICT_PINV if strict_pinv else 0) | (_lib.UVS_OPT_LATENCY if latency else 0)
+    x0 = None if analytical or initial_guess else np.asarray(p['x0'], float).reshape(1, m * n)
+    return LaunchSetup(cfg, method, analytical, plant, fp, t_log, len(t_log), m, n, x0, NoiseSpec(cfg))
 
 
 def run_batch(cfg, plant=None, cells=None, epoch=None, rank=0, world=1, want=('err',), lanes=0, noise_tensor=None,
@@ -151,43 +215,24 @@ def run_batch(cfg, plant=None, cells=None, epoch=None, rank=0, world=1, want=('e
     """Run this rank's shard of the sweep on its GPU.  Returns a BatchResult whose tensors stay on the device.
     ``noise_on_device``: generate the measurement noise with the HIP generator (default) or with numpy on the host.
     ``strict_pinv`` / ``latency``: the library's launch options UVS_OPT_STRICT_PINV (numpy's pinv on every control-law solve, slower) and
-    UVS_OPT_LATENCY (four lanes per filter for shards that do not fill the chip: last-bit differences) -- not part of config.json, whose
-    schema stays the reference's."""
+    UVS_OPT_LATENCY (four lanes per filter for shards that do not fill the chip: last-bit differences), see launch_setup."""
     import torch
-    cfg = load_config(cfg)
-    ex, est = cfg['experiments'], cfg['estimator']
-    method = Method[est['method']]
-    analytical = _check_analytical(method, lanes, latency)
-    plant = SyntheticPlant.ur10(ex['desired_f']) if plant is None else plant
-    plan = plan_trials(cfg, cells, epoch)
+    s = launch_setup(cfg, plant, lanes, strict_pinv, latency)
+    plan = plan_trials(s.cfg, cells, epoch)
     lo, hi = dist.shard_range(len(plan), rank, world)
-    p = est.get('estimator_params') or {}
-    m, n = len(ex['desired_f']), plant.n_joints
-    fp = engine.make_params(m, n, method.name, p.get('kernel_bw', 1.0), p.get('annealing', False), ex['dt'], ex['t_max'],
-                            ex['ibvs_gain'], ex['desired_f'], p.get('initial_guess', True) if analytical else p['initial_guess'], lanes, None,
-                            p.get('fpi_threshold', 0.1), p.get('fpi_epoch_max', 1000))
-    fp.reserved = (1 if strict_pinv else 0) | (2 if latency else 0)
-    t_log = engine.loop_clock(ex['dt'], ex['t_max'])
-    K, Tl = len(t_log), hi - lo
-    dev = torch.device(device)
-    with torch.cuda.device(dev if dev.index is not None else torch.cuda.current_device()):   # the engine launches on the CURRENT device's current stream
+    dev = engine.current_device(device)
+    with torch.cuda.device(dev):                                    # the engine launches on the CURRENT device's current stream
         if noise_tensor is None and noise_on_device:
-            noise_tensor = device_noise(cfg, plan, lo, hi, K, dev)
+            noise_tensor = device_noise(s.cfg, plan, lo, hi, s.K, dev)
         if noise_tensor is None:
-            host = np.empty((K, m, Tl))
-            trial_noise(cfg, plan, lo, hi, K, host.transpose(2, 0, 1))  # logical [trial][step][m] view of the trial-fastest buffer
+            host = np.empty((s.K, s.m, hi - lo))
+            trial_noise(s.cfg, plan, lo, hi, s.K, host.transpose(2, 0, 1))  # logical [trial][step][m] view of the trial-fastest buffer
             noise_tensor = torch.as_tensor(host, device=dev)
         q0 = torch.as_tensor(plan.q_start[lo:hi].copy(), device=dev)
-        x0 = None
-        if not analytical and not p['initial_guess']:
-            x0 = torch.as_tensor(np.asarray(p['x0'], float).reshape(1, m * n).repeat(Tl, 0), device=dev)
-        if analytical:
-            out = engine.analytical_closed_loop(fp, plant.to_struct(), q0, noise_tensor, want=want)
-        else:
-            out = engine.closed_loop(fp, plant.to_struct(), q0, noise_tensor, x0, want=want)
+        out = s.closed_loop(q0, noise_tensor, s.x0_rows(hi - lo, dev), want)
     start, stop = out['events']                                     # HIP events around the kernel launch (output allocation excluded)
     stop.synchronize()
-    return BatchResult(plan, lo, hi, t_log, out['stats'], out['status'], out['k_done'],
+    return BatchResult(plan, lo, hi, s.t_log, out['stats'], out['status'], out['k_done'],
                        {k: out[k] for k in ('x', 'j', 'err', 'q', 'f', 'dq') if out.get(k) is not None}, noise_tensor,
                        start.elapsed_time(stop) * 1e-3)
 
@@ -239,19 +284,20 @@ class SweepResult:
         return dist.gather_trial_rows(rows, len(self.plan), group).cpu().numpy()
 
 
+def _check_plan(plan, cfg, cells, epoch):
+    """A plan made earlier must be THIS sweep's: a stale one would silently run other seeds / cells."""
+    ex, nz = cfg['experiments'], cfg['noise']
+    n_cells = len(sweep_cells(NoiseType[nz['type']])) if cells is None else len(cells)
+    per_cell = int(ex['epoch'] if epoch is None else epoch)
+    first_seed = nz['seed']
+    if len(plan) != n_cells * per_cell or len(plan.cells) != n_cells or (cells is not None and not np.array_equal(plan.cells, np.asarray(cells, float))) or \
+            (first_seed is not None and len(plan) and int(plan.seed[0]) != int(first_seed)) or \
+            (len(plan) and not ex['change_q_start'] and not np.array_equal(plan.q_start[0], np.asarray(ex['q_start'], float))):
+        raise ValueError('run_sweep(plan=...): the plan does not belong to this config / cells / epoch')
+
+
 def run_sweep(cfg, plant=None, cells=None, epoch=None, rank=0, world=1, want=(), lanes=0, device='cuda', max_trials=None,
               share_noise=True, on_piece=None, strict_pinv=False, latency=False, plan=None):
-    """See _run_sweep.  The engine launches on the CURRENT device's current stream: the sweep runs with ``device`` made current, so that the events
-    that order the row copies against the kernels are recorded on the stream the kernels are launched on."""
-    import torch
-    _check_analytical(Method[load_config(cfg)['estimator']['method']], lanes, latency)    # (before any device work)
-    dev = torch.device(device)
-    with torch.cuda.device(dev if dev.index is not None else torch.cuda.current_device()):
-        return _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, torch.device('cuda', torch.cuda.current_device()), max_trials, share_noise,
-                          on_piece, strict_pinv, latency, plan)
-
-
-def _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, device, max_trials, share_noise, on_piece, strict_pinv, latency, plan):
     """The whole sweep of main.py:104-148 on this rank's GPU, cell after cell through ONE set of device buffers: for each piece (a cell, or
     ``max_trials`` trials of it) device seeding + noise generation (the T + 70 distinct streams where they alias), the closed-loop launch,
     and the per-trial [ISE, IAE, ITAE], status, k_done copied to pinned host memory on a second stream while the next piece computes.
@@ -260,99 +306,65 @@ def _run_sweep(cfg, plant, cells, epoch, rank, world, want, lanes, device, max_t
 
     ``want``: per-step streams to log on the device; they live until the next piece overwrites them, so ``on_piece(a, b, cell, out)`` --
     called after the piece has finished, with engine.closed_loop's dict -- is where a sink consumes them (it serialises the pipeline).
-    ``plan``: a TrialPlan of this config made earlier (plan_trials takes 0.3 s for 786 432 trials; the GPU idles and clocks down meanwhile)."""
+    ``plan``: a TrialPlan of this config made earlier (plan_trials takes 0.3 s for 786 432 trials; the GPU idles and clocks down meanwhile).
+    The engine launches on the CURRENT device's current stream: the sweep runs with ``device`` made current, so that the events that order the
+    row copies against the kernels are recorded on the stream the kernels are launched on."""
     import time
     import torch
-    cfg = load_config(cfg)
-    ex, est, nz = cfg['experiments'], cfg['estimator'], cfg['noise']
-    method = Method[est['method']]
-    analytical = _check_analytical(method, lanes, latency)
-    plant = SyntheticPlant.ur10(ex['desired_f']) if plant is None else plant
+    s = launch_setup(cfg, plant, lanes, strict_pinv, latency)       # (refusals before any device work)
     if plan is None:
-        plan = plan_trials(cfg, cells, epoch)
-    else:                                                          # a plan made earlier must be THIS sweep's: a stale one would silently run other seeds / cells
-        n_cells = len(sweep_cells(NoiseType[nz['type']])) if cells is None else len(cells)
-        per_cell = int(ex['epoch'] if epoch is None else epoch)
-        first_seed = nz['seed']
-        if len(plan) != n_cells * per_cell or len(plan.cells) != n_cells or (cells is not None and not np.array_equal(plan.cells, np.asarray(cells, float))) or \
-                (first_seed is not None and len(plan) and int(plan.seed[0]) != int(first_seed)) or \
-                (len(plan) and not ex['change_q_start'] and not np.array_equal(plan.q_start[0], np.asarray(ex['q_start'], float))):
-            raise ValueError('run_sweep(plan=...): the plan does not belong to this config / cells / epoch')
+        plan = plan_trials(s.cfg, cells, epoch)
+    else:
+        _check_plan(plan, s.cfg, cells, epoch)
     lo, hi = dist.shard_range(len(plan), rank, world)
-    p = est.get('estimator_params') or {}
-    m, n = len(ex['desired_f']), plant.n_joints
-    fp = engine.make_params(m, n, method.name, p.get('kernel_bw', 1.0), p.get('annealing', False), ex['dt'], ex['t_max'],
-                            ex['ibvs_gain'], ex['desired_f'], p.get('initial_guess', True) if analytical else p['initial_guess'], lanes, None,
-                            p.get('fpi_threshold', 0.1), p.get('fpi_epoch_max', 1000))
-    fp.reserved = (1 if strict_pinv else 0) | (2 if latency else 0)
-    K = len(engine.loop_clock(ex['dt'], ex['t_max']))
-    dev = torch.device(device)
     pieces = sweep_pieces(plan, lo, hi, max_trials)
-    Tl = hi - lo
-    host = dict(stats=torch.empty((Tl, 3), dtype=torch.float64).pin_memory(), status=torch.empty(Tl, dtype=torch.int32).pin_memory(),
-                k_done=torch.empty(Tl, dtype=torch.int32).pin_memory())
-    if not pieces:
-        return SweepResult(plan, lo, hi, host['stats'].numpy(), host['status'].numpy(), host['k_done'].numpy(), pieces)
-    Tmax = max(b - a for a, b, _ in pieces)
-    noise_type = NoiseType[nz['type']]
-    hold_cnt = int(nz['hold_time'] / ex['dt'])                      # main.py:137
-    key = 'alpha' if noise_type == NoiseType.ALPHA_STABLE else 'rho'
-    plant_struct = plant.to_struct()
-    q0 = torch.as_tensor(plan.q_start[lo:hi].copy(), device=dev)
-    x0 = None
-    if not analytical and not p['initial_guess']:
-        x0 = torch.as_tensor(np.asarray(p['x0'], float).reshape(1, m * n).repeat(Tmax, 0), device=dev)
-    seeds_dev = torch.as_tensor(np.ascontiguousarray(plan.seed[lo:hi], dtype=np.uint64).view(np.int64), device=dev)
-    # two sets of per-trial outputs (a set is copied out while the next piece writes the other), one set of streams, one noise buffer
-    S = Tmax + noise_device.SEED_STEP * (m - 1)
-    noise_buf = torch.empty(K * max(S, m * Tmax), dtype=torch.float64, device=dev)
-    streams = {k_: engine.alloc_stream(Tmax, K, c, 'kct', dev) for k_, c in (('x', m * n), ('j', m * n), ('err', m), ('q', n), ('f', m), ('dq', n))
-               if k_ in want}
-    sets = []
-    for _ in range(2):                                             # the streams are allocated ONCE and shared by both sets (7.5 GB of X per 65 536 trials)
-        d = dict(streams)
-        d.update(stats=torch.zeros((Tmax, 3), dtype=torch.float64, device=dev), status=torch.zeros(Tmax, dtype=torch.int32, device=dev),
-                 k_done=torch.zeros(Tmax, dtype=torch.int32, device=dev))
-        sets.append(d)
-    main = torch.cuda.current_stream(dev)
-    copier = _COPY_STREAMS.get(str(dev))                           # one per device, kept: the first use of a new stream costs ~4 ms on the host
-    if copier is None:                                             # (queue creation), during which the GPU runs dry
-        copier = _COPY_STREAMS[str(dev)] = torch.cuda.Stream(device=dev)
-        with torch.cuda.stream(copier):
-            torch.zeros(1, device=dev)
-    copied = []
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for i, (a, b, c) in enumerate(pieces):
-        T = b - a
-        params = dict(nz['noise_params'])
-        params[key] = float(plan.cells[c])                          # main.py:123-126
-        if share_noise and noise_device.shares_streams(noise_type, nz['hold'], plan.seed[a:b]):
-            St = T + noise_device.SEED_STEP * (m - 1)
-            noise = noise_device.generate_shared(noise_type, params, int(plan.seed[a]), T, m, K, out=noise_buf[:K * St].view(K, St), device=dev)[1]
-        else:
-            noise = noise_buf[:K * m * T].view(K, m, T)
-            noise_device.generate(noise_type, params, seeds_dev[a - lo:b - lo], m, K, nz['hold'], hold_cnt, 'kct', out=noise, device=dev)
-        if i >= 2:
-            main.wait_event(copied[i - 2])                          # this set's previous rows have left the device
-        if analytical:
-            out = engine.analytical_closed_loop(fp, plant_struct, q0[a - lo:b - lo], noise, want=want, reuse=sets[i % 2])
-        else:
-            out = engine.closed_loop(fp, plant_struct, q0[a - lo:b - lo], noise, None if x0 is None else x0[:T], want=want, reuse=sets[i % 2])
-        done = torch.cuda.Event()
-        done.record(main)
-        copier.wait_event(done)
-        with torch.cuda.stream(copier):
-            for k_ in ('stats', 'status', 'k_done'):
-                host[k_][a - lo:b - lo].copy_(out[k_], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(copier)
-        copied.append(ev)
-        if on_piece is not None:
-            done.synchronize()
-            on_piece(a, b, c, out)
-    torch.cuda.synchronize(dev)
-    seconds = time.perf_counter() - t0
+    K, m, n, Tl = s.K, s.m, s.n, hi - lo
+    dev = engine.current_device(device)
+    with torch.cuda.device(dev):
+        host = dict(stats=torch.empty((Tl, 3), dtype=torch.float64).pin_memory(), status=torch.empty(Tl, dtype=torch.int32).pin_memory(),
+                    k_done=torch.empty(Tl, dtype=torch.int32).pin_memory())
+        if not pieces:
+            return SweepResult(plan, lo, hi, host['stats'].numpy(), host['status'].numpy(), host['k_done'].numpy(), pieces)
+        Tmax = max(b - a for a, b, _ in pieces)
+        q0 = torch.as_tensor(plan.q_start[lo:hi].copy(), device=dev)
+        x0 = s.x0_rows(Tmax, dev)
+        seeds_dev = _upload_seeds(plan.seed[lo:hi], dev)
+        # two sets of per-trial outputs (a set is copied out while the next piece writes the other), one set of streams, one noise buffer
+        S = Tmax + noise_device.SEED_STEP * (m - 1)
+        noise_buf = torch.empty(K * max(S, m * Tmax), dtype=torch.float64, device=dev)
+        streams = {k_: engine.alloc_stream(Tmax, K, c, 'kct', dev) for k_, c in (('x', m * n), ('j', m * n), ('err', m), ('q', n), ('f', m), ('dq', n))
+                   if k_ in want}
+        # the streams are allocated ONCE and shared by both sets (7.5 GB of X per 65 536 trials)
+        sets = [dict(streams, stats=torch.zeros((Tmax, 3), dtype=torch.float64, device=dev), status=torch.zeros(Tmax, dtype=torch.int32, device=dev),
+                     k_done=torch.zeros(Tmax, dtype=torch.int32, device=dev)) for _ in range(2)]
+        main = torch.cuda.current_stream(dev)
+        copier = _COPY_STREAMS.get(str(dev))                       # one per device, kept: the first use of a new stream costs ~4 ms on the host
+        if copier is None:                                         # (queue creation), during which the GPU runs dry
+            copier = _COPY_STREAMS[str(dev)] = torch.cuda.Stream(device=dev)
+            with torch.cuda.stream(copier):
+                torch.zeros(1, device=dev)
+        copied = []
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for i, (a, b, c) in enumerate(pieces):
+            noise = _cell_noise(s.noise, plan.cells[c], plan.seed[a:b], seeds_dev[a - lo:b - lo], K, dev, share_noise, noise_buf)
+            if i >= 2:
+                main.wait_event(copied[i - 2])                      # this set's previous rows have left the device
+            out = s.closed_loop(q0[a - lo:b - lo], noise, None if x0 is None else x0[:b - a], want, reuse=sets[i % 2])
+            done = torch.cuda.Event()
+            done.record(main)
+            copier.wait_event(done)
+            with torch.cuda.stream(copier):
+                for k_ in ('stats', 'status', 'k_done'):
+                    host[k_][a - lo:b - lo].copy_(out[k_], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(copier)
+            copied.append(ev)
+            if on_piece is not None:
+                done.synchronize()
+                on_piece(a, b, c, out)
+        torch.cuda.synchronize(dev)
+        seconds = time.perf_counter() - t0
     return SweepResult(plan, lo, hi, host['stats'].numpy(), host['status'].numpy(), host['k_done'].numpy(), pieces, seconds)
 
 
@@ -442,35 +454,23 @@ def run_grid(cfg, grid, cells=None, epoch=None, want=(), lanes=0, device='cuda',
     import time
     import torch
     cfg = load_config(cfg)
-    ex, est, nz = cfg['experiments'], cfg['estimator'], cfg['noise']
-    method = Method[est['method']]
-    if method == Method.ANALYTICAL:
+    if Method[cfg['estimator']['method']] == Method.ANALYTICAL:
         raise ValueError('run_grid: Method.ANALYTICAL has no per-trial parameters (no bandwidth, and no per-trial kernel for its gain)')
     if lanes not in (0, 2):
         raise ValueError('run_grid: lanes must be 0 or 2 (the per-trial kernels run two lanes per filter)')
     plan = plan_trials(cfg, cells, epoch)
-    E = int(ex['epoch'] if epoch is None else epoch)
+    E = int(cfg['experiments']['epoch'] if epoch is None else epoch)
     gp = plan_grid(grid, E, max_trials)
+    s = launch_setup(cfg, plant, lanes)
     C_, H = len(plan.cells), len(gp)
     stats = np.empty((C_, H, E, 3))
     status = np.empty((C_, H, E), np.int32)
     k_done = np.empty((C_, H, E), np.int32)
-    dev = torch.device(device)
-    with torch.cuda.device(dev if dev.index is not None else torch.cuda.current_device()):
-        dev = torch.device('cuda', torch.cuda.current_device())
-        plant = SyntheticPlant.ur10(ex['desired_f']) if plant is None else plant
-        p = est.get('estimator_params') or {}
-        m, n = len(ex['desired_f']), plant.n_joints
-        fp = engine.make_params(m, n, method.name, p.get('kernel_bw', 1.0), p.get('annealing', False), ex['dt'], ex['t_max'], ex['ibvs_gain'],
-                                ex['desired_f'], p['initial_guess'], lanes, None, p.get('fpi_threshold', 0.1), p.get('fpi_epoch_max', 1000))
-        K = len(engine.loop_clock(ex['dt'], ex['t_max']))
-        noise_type = NoiseType[nz['type']]
-        hold_cnt = int(nz['hold_time'] / ex['dt'])
-        key = 'alpha' if noise_type == NoiseType.ALPHA_STABLE else 'rho'
-        plant_struct = plant.to_struct()
+    dev = engine.current_device(device)
+    with torch.cuda.device(dev):
         q0 = torch.as_tensor(plan.q_start.copy(), device=dev)
-        x0 = None if p['initial_guess'] else torch.as_tensor(np.asarray(p['x0'], float).reshape(1, m * n).repeat(E, 0), device=dev)
-        seeds_dev = torch.as_tensor(np.ascontiguousarray(plan.seed, dtype=np.uint64).view(np.int64), device=dev)
+        x0 = s.x0_rows(E, dev)
+        seeds_dev = _upload_seeds(plan.seed, dev)
         names = {'kernel_bw': 'kernel_bw', 'ibvs_gain': 'gain', 'fpi_threshold': 'fpi_threshold'}
         launches = []                                              # per piece: trial_params on the device, made once
         for h_lo, h_hi in gp.pieces:
@@ -482,15 +482,9 @@ def run_grid(cfg, grid, cells=None, epoch=None, want=(), lanes=0, device='cuda',
         t0 = time.perf_counter()
         for c in range(C_):
             a, b = c * E, (c + 1) * E
-            params = dict(nz['noise_params'])
-            params[key] = float(plan.cells[c])
-            if noise_device.shares_streams(noise_type, nz['hold'], plan.seed[a:b]):
-                noise = noise_device.generate_shared(noise_type, params, int(plan.seed[a]), E, m, K, device=dev)[1]
-            else:
-                noise = torch.empty((K, m, E), dtype=torch.float64, device=dev)
-                noise_device.generate(noise_type, params, seeds_dev[a:b], m, K, nz['hold'], hold_cnt, 'kct', out=noise, device=dev)
+            noise = _cell_noise(s.noise, plan.cells[c], plan.seed[a:b], seeds_dev[a:b], s.K, dev)      # a fresh tensor per noise cell
             for (h_lo, h_hi), tp in zip(gp.pieces, launches):
-                out = engine.closed_loop(fp, plant_struct, q0[a:b], noise, x0, want=want, reuse=reuse, trial_params=tp)
+                out = s.closed_loop(q0[a:b], noise, x0, want, reuse=reuse, trial_params=tp)
                 if reuse is None:
                     reuse = out                                    # the first piece is the largest: later ones write into its tensors
                 hc = h_hi - h_lo

@@ -60,7 +60,19 @@ def _stream():
     return C.c_void_p(_torch().cuda.current_stream().cuda_stream)
 
 
-_DIMS = {'kct': (2, 0, 1), 'ktc': (1, 0, 2), 'tkc': (0, 1, 2)}
+_DIMS = {'kct': (2, 0, 1), 'ktc': (1, 0, 2), 'tkc': (0, 1, 2)}    # layout -> the tensor axes that play (trial, step, comp): THE layout table
+
+
+def _shape(T, K, comp, layout):
+    """Tensor shape of a [trial][step][comp] stream in ``layout``."""
+    return tuple(size for _, size in sorted(zip(_DIMS[layout], (T, K, comp))))
+
+
+def current_device(device=None):
+    """``device`` ('cuda', 'cuda:1', a torch.device; None = 'cuda') as an INDEXED torch.device: one without an index names the current device."""
+    torch = _torch()
+    dev = torch.device('cuda' if device is None else device)
+    return dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device())
 
 
 def alloc_stream(T, K, comp, layout='kct', device='cuda', zero=False):
@@ -71,20 +83,23 @@ def alloc_stream(T, K, comp, layout='kct', device='cuda', zero=False):
     and two of the eight slots drain 17 % slower on MI355X; walking the slots from row to row measured -1 % (config 3), -2 % (IMCC-KF),
     +/-0 (headline) and +8 % (replay) on one box -- DESIGN.md appendix A.1 -- so dense rows stay the default."""
     torch = _torch()
-    pad = int(os.environ.get('UVS_ROW_PAD', '0'))
-    if layout == 'kct' and pad:
-        return (torch.zeros if zero else torch.empty)((K, comp, T + pad), dtype=torch.float64, device=device)[:, :, :T]
-    shape = {'kct': (K, comp, T), 'ktc': (K, T, comp), 'tkc': (T, K, comp)}[layout]
-    return (torch.zeros if zero else torch.empty)(shape, dtype=torch.float64, device=device)
+    pad = int(os.environ.get('UVS_ROW_PAD', '0')) if layout == 'kct' else 0
+    tensor = (torch.zeros if zero else torch.empty)(_shape(T + pad, K, comp, layout), dtype=torch.float64, device=device)
+    return tensor.narrow(_DIMS[layout][0], 0, T) if pad else tensor
 
 
 def stream_view(tensor, layout='kct'):
     return NULL_VIEW if tensor is None else _lib.view_of(tensor, _DIMS[layout])
 
 
+def _flat(tensor):
+    """uvs_view of a per-trial (T, comp) tensor (no step axis), NULL_VIEW for None."""
+    return NULL_VIEW if tensor is None else View(tensor.data_ptr(), tensor.stride(0), 0, tensor.stride(1))
+
+
 def as_tkc(tensor, layout='kct'):
     """Logical [trial][step][comp] view (no copy) of a stream tensor."""
-    return tensor.permute({'kct': (2, 0, 1), 'ktc': (1, 0, 2), 'tkc': (0, 1, 2)}[layout])
+    return tensor.permute(_DIMS[layout])
 
 
 def supported_lanes(m, n):
@@ -98,12 +113,13 @@ _WORKSPACES = {}
 
 def workspace(fp, plant_struct, T, device):
     """(pointer, bytes) of the scratch buffer uvs_rmckf_closed_loop_ws_f64 wants for this launch -- (None, 0) when it wants none.  One
-    buffer per device and stream, grown on demand and kept: the library allocates nothing itself."""
+    buffer per (indexed) device and stream, grown on demand and kept: the library allocates nothing itself."""
     need = int(_lib.lib().uvs_rmckf_closed_loop_workspace_bytes(C.byref(fp), C.byref(plant_struct), T))
     if need == 0:
         return None, 0
     torch = _torch()
-    key = (str(device), torch.cuda.current_stream().cuda_stream)
+    device = current_device(device)                                # 'cuda', None and 'cuda:0' are one workspace
+    key = (device, torch.cuda.current_stream().cuda_stream)
     buf = _WORKSPACES.get(key)
     if buf is None or buf.numel() < need:
         buf = _WORKSPACES[key] = torch.empty(need, dtype=torch.uint8, device=device)
@@ -117,8 +133,7 @@ def hand_over_fallbacks(fp, plant_struct, T, device=None):
     off = int(_lib.lib().uvs_rmckf_closed_loop_fallback_offset(C.byref(fp), C.byref(plant_struct), T))
     if off == 0:
         return None
-    device = device if device is not None else torch.device('cuda', torch.cuda.current_device())
-    buf = _WORKSPACES.get((str(device), torch.cuda.current_stream().cuda_stream))
+    buf = _WORKSPACES.get((current_device(device), torch.cuda.current_stream().cuda_stream))
     if buf is None:
         return None
     return int(buf[off:off + 4].view(torch.int32).item())
@@ -127,8 +142,7 @@ def hand_over_fallbacks(fp, plant_struct, T, device=None):
 def launch_closed_loop(fp, plant_struct, T, *args, device=None):
     """uvs_rmckf_closed_loop_ws_f64 on torch's current stream with this process's cached workspace: ``args`` are the views / pointers of
     uvs_rmckf_closed_loop_f64 between ``T`` and ``stream``, in the header's order.  Returns the library's return code."""
-    torch = _torch()
-    ws, ws_bytes = workspace(fp, plant_struct, T, device if device is not None else torch.device('cuda', torch.cuda.current_device()))
+    ws, ws_bytes = workspace(fp, plant_struct, T, device)
     return _lib.lib().uvs_rmckf_closed_loop_ws_f64(C.byref(fp), C.byref(plant_struct), T, *args, ws, ws_bytes, _stream())
 
 
@@ -156,6 +170,29 @@ def trial_params_struct(trial_params, T, m, device):
     return tp
 
 
+def _outputs(fp, T, dev, head, want, layout, head_layout, reuse, final_state=None):
+    """The dict a closed-loop launch of T trials writes: the per-step streams ``head`` ('x' or 'j', m*n per step, in ``head_layout``), 'err', 'q', 'f', 'dq'
+    (in ``layout``; None unless in ``want``), the per-trial 'stats', 'status', 'k_done' and -- unless ``final_state`` is None -- 'x_final' / 'p_final'
+    (None when False).  ``reuse``: a dict this function returned for at least T trials, narrowed to T instead of allocating."""
+    torch = _torch()
+    K, m, n = fp.steps, fp.m, fp.n
+    out = {}
+    for key, comp in ((head, m * n), ('err', m), ('q', n), ('f', m), ('dq', n)):
+        lay = head_layout if key == head else layout
+        if key not in want:
+            out[key] = None
+        elif reuse is not None:
+            out[key] = reuse[key].narrow(_DIMS[lay][0], 0, T)
+        else:
+            out[key] = alloc_stream(T, K, comp, lay, dev)          # rows at and after k_done are unspecified
+    for key, shape, dtype in (('stats', (T, 3), torch.float64), ('status', (T,), torch.int32), ('k_done', (T,), torch.int32)):
+        out[key] = reuse[key][:T] if reuse is not None else torch.zeros(shape, dtype=dtype, device=dev)
+    if final_state is not None:
+        out['x_final'] = torch.empty((T, m * n), dtype=torch.float64, device=dev) if final_state else None
+        out['p_final'] = torch.empty((T, m * n * n), dtype=torch.float64, device=dev) if final_state else None
+    return out
+
+
 def closed_loop(fp, plant_struct, q_start, noise=None, x0=None, want=('x', 'err', 'q'), layout='kct', final_state=False, x_layout=None, reuse=None,
                 trial_params=None):
     """Launch T closed-loop trials.  ``q_start``: (T, n) cuda tensor; ``noise``: stream tensor in ``layout`` or None;
@@ -174,38 +211,20 @@ def closed_loop(fp, plant_struct, q_start, noise=None, x0=None, want=('x', 'err'
     launch with its values.  None (the default) is the uniform call."""
     x_layout = x_layout or layout
     torch = _torch()
-    T, K, m, n = q_start.shape[0], fp.steps, fp.m, fp.n
+    T = q_start.shape[0]
     if trial_params is not None and trial_params.get('source') is not None:
         T = trial_params['source'].shape[0]
     dev = q_start.device
-    out = {}
-    tdim = lambda lay: {'kct': 2, 'ktc': 1, 'tkc': 0}[lay]         # noqa: E731
-    for key, comp in (('x', m * n), ('err', m), ('q', n), ('f', m), ('dq', n)):
-        lay = x_layout if key == 'x' else layout
-        if key not in want:
-            out[key] = None
-        elif reuse is not None:
-            out[key] = reuse[key].narrow(tdim(lay), 0, T)
-        else:
-            out[key] = alloc_stream(T, K, comp, lay, dev)          # rows at and after k_done are unspecified
-    if reuse is not None:
-        out['stats'], out['status'], out['k_done'] = reuse['stats'][:T], reuse['status'][:T], reuse['k_done'][:T]
-    else:
-        out['stats'] = torch.zeros((T, 3), dtype=torch.float64, device=dev)
-        out['status'] = torch.zeros(T, dtype=torch.int32, device=dev)
-        out['k_done'] = torch.zeros(T, dtype=torch.int32, device=dev)
-    out['x_final'] = torch.empty((T, m * n), dtype=torch.float64, device=dev) if final_state else None
-    out['p_final'] = torch.empty((T, m * n * n), dtype=torch.float64, device=dev) if final_state else None
-    flat = lambda t: NULL_VIEW if t is None else View(t.data_ptr(), t.stride(0), 0, t.stride(1))      # noqa: E731
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)           # around the launch only: the
+    out = _outputs(fp, T, dev, 'x', want, layout, x_layout, reuse, final_state)
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)           # around the launch only:
     ws, ws_bytes = workspace(fp, plant_struct, T, dev)
-    args = (flat(q_start), stream_view(noise, layout), flat(x0),
+    args = (_flat(q_start), stream_view(noise, layout), _flat(x0),
             stream_view(out['x'], x_layout), stream_view(out['err'], layout), stream_view(out['q'], layout),
             stream_view(out['f'], layout), stream_view(out['dq'], layout),
             out['stats'].data_ptr(), out['status'].data_ptr(), out['k_done'].data_ptr(),
-            flat(out['x_final']), flat(out['p_final']), ws, ws_bytes, _stream())
-    tp = trial_params_struct(trial_params, T, m, dev) if trial_params is not None else None
-    start.record()                                                                                     # allocations above are not kernel time
+            _flat(out['x_final']), _flat(out['p_final']), ws, ws_bytes, _stream())
+    tp = trial_params_struct(trial_params, T, fp.m, dev) if trial_params is not None else None
+    start.record()                                                                                     # allocation and the workspace lookup are not kernel time
     if tp is not None:
         rc = _lib.lib().uvs_rmckf_closed_loop_grid_f64(C.byref(fp), C.byref(plant_struct), T, C.byref(tp), *args)
     else:
@@ -221,27 +240,13 @@ def analytical_closed_loop(fp, plant_struct, q_start, noise=None, want=('err', '
     is computed from the plant at every step instead of estimated.  Arguments and the returned dict as for ``closed_loop``, with the stream
     ``'j'`` (J_feature the control law used, m*n per step) in place of ``'x'``; ``fp.method`` must be ANALYTICAL (make_params(..., 'ANALYTICAL'))."""
     torch = _torch()
-    T, K, m, n = q_start.shape[0], fp.steps, fp.m, fp.n
-    dev = q_start.device
-    out = {'x': None}
-    tdim = {'kct': 2, 'ktc': 1, 'tkc': 0}[layout]
-    for key, comp in (('j', m * n), ('err', m), ('q', n), ('f', m), ('dq', n)):
-        if key not in want:
-            out[key] = None
-        elif reuse is not None:
-            out[key] = reuse[key].narrow(tdim, 0, T)
-        else:
-            out[key] = alloc_stream(T, K, comp, layout, dev)           # rows at and after k_done are unspecified
-    if reuse is not None:
-        out['stats'], out['status'], out['k_done'] = reuse['stats'][:T], reuse['status'][:T], reuse['k_done'][:T]
-    else:
-        out['stats'] = torch.zeros((T, 3), dtype=torch.float64, device=dev)
-        out['status'] = torch.zeros(T, dtype=torch.int32, device=dev)
-        out['k_done'] = torch.zeros(T, dtype=torch.int32, device=dev)
+    T, dev = q_start.shape[0], q_start.device
+    out = _outputs(fp, T, dev, 'j', want, layout, layout, reuse)
+    out['x'] = None
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     start.record()
     rc = _lib.lib().uvs_analytical_closed_loop_f64(
-        C.byref(fp), C.byref(plant_struct), T, View(q_start.data_ptr(), q_start.stride(0), 0, q_start.stride(1)), stream_view(noise, layout),
+        C.byref(fp), C.byref(plant_struct), T, _flat(q_start), stream_view(noise, layout),
         stream_view(out['j'], layout), stream_view(out['err'], layout), stream_view(out['q'], layout), stream_view(out['f'], layout),
         stream_view(out['dq'], layout), out['stats'].data_ptr(), out['status'].data_ptr(), out['k_done'].data_ptr(), _stream())
     stop.record()
@@ -264,12 +269,11 @@ def replay(fp, f, dq, x0, want=('x', 'err', 'kappa', 'dqcmd'), layout='kct', fin
     out['k_done'] = torch.zeros(T, dtype=torch.int32, device=dev)
     out['x_final'] = torch.empty((T, m * n), dtype=torch.float64, device=dev) if final_state else None
     out['p_final'] = torch.empty((T, m * n * n), dtype=torch.float64, device=dev) if final_state else None
-    flat = lambda t: NULL_VIEW if t is None else View(t.data_ptr(), t.stride(0), 0, t.stride(1))      # noqa: E731
     rc = _lib.lib().uvs_rmckf_replay_f64(
-        C.byref(fp), T, stream_view(f, in_layout), stream_view(dq, in_layout), flat(x0),
+        C.byref(fp), T, stream_view(f, in_layout), stream_view(dq, in_layout), _flat(x0),
         stream_view(out['x'], layout), stream_view(out['err'], layout), stream_view(out['kappa'], layout),
         stream_view(out['dqcmd'], layout), out['status'].data_ptr(), out['k_done'].data_ptr(),
-        flat(out['x_final']), flat(out['p_final']), _stream())
+        _flat(out['x_final']), _flat(out['p_final']), _stream())
     _lib.check(rc)
     return out
 
@@ -281,11 +285,10 @@ def replay_f32(fp, f, dq, x0, want=('x', 'err'), layout='kct'):
     assert f.dtype == dq.dtype == x0.dtype == torch.float32
     T, K, m, n = x0.shape[0], fp.steps, fp.m, fp.n
     dev = x0.device
-    shape = lambda c: {'kct': (K, c, T), 'ktc': (K, T, c), 'tkc': (T, K, c)}[layout]      # noqa: E731
-    out = {'x': torch.empty(shape(m * n), dtype=torch.float32, device=dev) if 'x' in want else None,
-           'err': torch.empty(shape(m), dtype=torch.float32, device=dev) if 'err' in want else None,
+    out = {'x': torch.empty(_shape(T, K, m * n, layout), dtype=torch.float32, device=dev) if 'x' in want else None,
+           'err': torch.empty(_shape(T, K, m, layout), dtype=torch.float32, device=dev) if 'err' in want else None,
            'status': torch.zeros(T, dtype=torch.int32, device=dev), 'k_done': torch.zeros(T, dtype=torch.int32, device=dev)}
-    rc = _lib.lib().uvs_rmckf_replay_f32(C.byref(fp), T, stream_view(f, layout), stream_view(dq, layout), View(x0.data_ptr(), x0.stride(0), 0, x0.stride(1)),
+    rc = _lib.lib().uvs_rmckf_replay_f32(C.byref(fp), T, stream_view(f, layout), stream_view(dq, layout), _flat(x0),
                                          stream_view(out['x'], layout), stream_view(out['err'], layout), out['status'].data_ptr(), out['k_done'].data_ptr(), _stream())
     _lib.check(rc)
     return out
