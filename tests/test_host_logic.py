@@ -50,6 +50,30 @@ def test_argument_errors_are_reported_not_thrown(uvs):
     assert lib.uvs_supported_lanes(8, 6, None, 0) >= 4 and lib.uvs_supported_lanes(7, 7, None, 0) == 0
 
 
+def test_step_entry_point_refuses_before_it_launches(uvs):
+    """uvs_rmckf_step_f64: every refusal is decided on the host, ahead of the launch -- the buffers here are host arrays no kernel could use."""
+    lib = uvs.lib()
+    T, m, n = 3, 8, 6
+    sizes = dict(X=T * m * n, P=T * m * n * n, f=T * m, f_old=T * m, dq_prev=T * n, dq_out=T * n, err_out=T * m, kappa_out=T * m)
+    bufs = {k: (ctypes.c_double * v)() for k, v in sizes.items()}
+    bufs['status'] = (ctypes.c_int32 * T)()
+    ptr = {k: ctypes.cast(v, ctypes.c_void_p) for k, v in bufs.items()}
+
+    def call(fp, T_=T, null=None):
+        p = dict(ptr, **({null: None} if null else {}))
+        return lib.uvs_rmckf_step_f64(ctypes.byref(fp), T_, p['X'], p['P'], p['f'], p['f_old'], p['dq_prev'], 1, 0, p['dq_out'], p['err_out'],
+                                      p['kappa_out'], p['status'], None)
+
+    fp = uvs.engine.make_params(m, n, 'GMCKF', desired=np.zeros(m), steps=0)
+    assert call(fp, T_=0) == -1 and b'T must be positive' in lib.uvs_last_error()       # UVS_ERR_ARG
+    for name in ptr:                                                                       # any one NULL buffer
+        assert call(fp, null=name) == -1 and b'step buffers' in lib.uvs_last_error(), name
+    fp.method = 1                                                                          # ANALYTICAL is not an estimator
+    assert call(fp) == -4                                                                  # UVS_ERR_METHOD
+    assert call(uvs.engine.make_params(5, 3, 'GMCKF', desired=np.zeros(5), steps=0)) == -2     # UVS_ERR_SHAPE: (5,3) is not instantiated
+    assert not any(bufs['status']) and not any(bufs['dq_out'])
+
+
 def test_workspace_query_is_host_logic(uvs):
     """uvs_rmckf_closed_loop_workspace_bytes: which launches the library would cut into segments (MCKF on the tuned two-lane kernel, DH plant,
     more than one round of wavefronts) and how much caller-owned scratch that takes -- no GPU involved."""
