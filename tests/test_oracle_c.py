@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import closed_shapes_common as shapes
 from conftest import golden_names, load_golden, rel_err
 from oracle import c_oracle
 
@@ -65,3 +66,27 @@ def test_c_oracle_replay_reproduces_reference(name):
     assert rel_err(out['dq_cmd'][0, :-1], g['dq_prev'][1:]) <= 1e-8
     if 'fpi_epochs' in g:
         assert np.array_equal(out['fpi'][0], g['fpi_epochs'][:k])
+
+
+# ---------------------------------------------------------------------------------------------- the shapes the reference cannot run
+@pytest.mark.parametrize('case,method,anneal', shapes.configurations())
+def test_c_oracle_agrees_with_the_block_oracle_at_the_other_shapes(case, method, anneal):
+    """Closed loop at (6,6) and (2,6) on the DH plant (3 points / 1 point; (6,6) also from a supplied X0) and at (8,6) and (6,6) on the
+    linear plant: oracle/c (batch speed) against oracle/rmckf_block (numpy pinv, the authority) on the trials shapes.sampled(case), every
+    estimator, annealing off and on, MCKF with fpi_threshold 1e-4 (its fixed-point loop iterates).  Gate 1e-11 on X, q and err, status and
+    k_done exact.  A trial may miss it -- closed-loop sensitivity of the square (6,6) estimate -- only if shapes.EXCLUDED lists it (the list
+    has a decade of margin, so it may also name trials that pass here); the GPU parity module leaves the listed trials out, and no
+    configuration lists more than 10 % of its sampled trials."""
+    agreement = shapes.oracle_agreement(case, method, anneal)
+    apart = tuple(sorted(t for t, d in agreement.items() if not d <= shapes.AGREE_TOL))
+    listed = tuple(shapes.EXCLUDED.get((case, method, anneal), ()))
+    close = [d for t, d in agreement.items() if t not in apart]
+    print(f'{case} {method} annealing {anneal}: {len(close)} trials agree to {max(close):.1e}; left out', {t: f'{agreement[t]:.1e}' for t in listed})
+    assert set(apart) <= set(listed), {t: agreement[t] for t in apart if t not in listed}
+    assert len(listed) <= shapes.MAX_EXCLUDED_FRACTION * len(agreement)
+    assert not set(listed) & set(shapes.TWINS)                          # the bit-identity trials stay in the comparison
+    ref = shapes.c_reference(case, method, anneal)
+    if method == 'MCKF':
+        assert ref['fpi'].max() >= 3                                    # the fixed-point loop does iterate
+    if shapes.CASES[case][2] == 'linear':
+        assert not ref['status'].any() and np.all(ref['k_done'] == shapes.K)
