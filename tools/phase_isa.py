@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction classes of the headline kernel's step loop, phase by phase: the -DUVS_STAMPS build pins an s_memtime between scheduling
-fences at every phase boundary (rmckf_tuned.hpp, UVS_STAMP), so the assembly between two stamps is what that phase issues.
+fences at every phase boundary (rmckf_diag.hpp, UVS_STAMP), so the assembly between two stamps is what that phase issues.
 usage: hipcc ... -DUVS_QUICK -DUVS_STAMPS -S --cuda-device-only uvs_unity.hip -o /tmp/stamps.s ; tools/phase_isa.py /tmp/stamps.s"""
 import collections
 import re

@@ -1,5 +1,5 @@
 // Which lane does each DPP control code used by the kernels read from?  Every lane moves its own lane id through the code and the host
-// checks the permutation against what rmckf_device.hpp / rmckf_tuned.hpp assume (quad_perm butterflies, row_half_mirror, row_mirror,
+// checks the permutation against what rmckf_device.hpp / rmckf_rows.hpp assume (quad_perm butterflies, row_half_mirror, row_mirror,
 // row_newbcast).  build: hipcc -O3 --offload-arch=gfx950 tools/ubench/dpp_test.hip -o tools/ubench/dpp_test
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -14,7 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rmckf_device.hpp"
-#include "rmckf_tuned.hpp"
+#include "rmckf_lstsq.hpp"
 
 namespace uvs {
 

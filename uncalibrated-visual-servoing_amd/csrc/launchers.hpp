@@ -64,7 +64,7 @@ void with_flags(F &&f, bool a, B... rest) {
 }
 
 // Does the first pass of the tuned closed-loop kernel certify every solve under UVS_OPT_STRICT_PINV?  It does when the solve goes through
-// lstsq_tall_tuned with strict on: RMCKF reads the option at run time, KF / IMCC-KF / MCKF have CERT instantiations at (8,6), two lanes,
+// lstsq_tall_tuned (rmckf_lstsq.hpp) with strict on: RMCKF reads the option at run time, KF / IMCC-KF / MCKF have CERT instantiations at (8,6), two lanes,
 // DH plant (rmckf_tuned.hpp).  EMU2 (lstsq_tall_emu2) does not, nor does the wide kernel (normal equations).  launch2 picks the CERT
 // instantiations by it, plan_closed_loop decides by it between a certified first pass and the careful pass alone.
 constexpr bool tuned_certifies(int m, int n, int L, int method, bool linear, bool emu2) {

@@ -322,7 +322,7 @@ struct Rows {
             const double cy = gaussian_kernel(nu0[r], sigma);                    // first pass: Xc = X
             bad |= (cy == 0.0);
             // a subnormal weight whose reciprocal overflows (cy <= 2^-1024): inv(Cy) = inf, 0 * inf = NaN in the reference's dense
-            // Br @ inv(Cy) @ Br.T (:232) -- the gain is NaN, the state follows and the trial FAILs (see kRcpOverflowsAtOrBelow, rmckf_tuned.hpp)
+            // Br @ inv(Cy) @ Br.T (:232) -- the gain is NaN, the state follows and the trial FAILs (see kRcpOverflowsAtOrBelow, rmckf_rows.hpp)
             const double gain = (cy <= 0x1p-1024) ? __builtin_nan("") : 1.0 / (a + 1.0 / cy);
 #pragma unroll
             for (int l = 0; l < N; ++l) {

@@ -8,7 +8,8 @@
 // Store discipline as in the closed loop: straight-line step body, padding lanes shadow the last trial, a FAILed trial keeps running on
 // NaNs and its rows at and after k_done are unspecified (the generic replay_kernel leaves them untouched instead).
 #pragma once
-#include "rmckf_tuned.hpp"
+#include "rmckf_rows.hpp"
+#include "rmckf_lstsq.hpp"
 
 namespace uvs {
 

@@ -15,7 +15,8 @@
 //   * plant matrix rows and desired features in LDS, joints replicated on the 8 lanes (no exchange), stream cursors instead of
 //     per-element address arithmetic, next step's noise fetched one step ahead.
 #pragma once
-#include "rmckf_tuned.hpp"
+#include "rmckf_diag.hpp"
+#include "rmckf_rows.hpp"
 
 namespace uvs {
 
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(64, 1) void closed_loop_wide_kernel(const ClosedArg
     __shared__ double lc[DH ? 1 : M], ldes[M];                     // f0 - J q0, desired_f
     __shared__ double lt[XREC ? TPW * RECP : 1];                   // transposition buffer of the X records
     __shared__ double lacc[3 * R][64], lfp[R][64];                 // lane-private: ISE / IAE / ITAE accumulators, previous noisy features
-    // KF and IMCC-KF weigh every row of a filter alike, so all their covariance blocks stay identical (RowShare, rmckf_tuned.hpp): a lane keeps
+    // KF and IMCC-KF weigh every row of a filter alike, so all their covariance blocks stay identical (RowShare, rmckf_rows.hpp): a lane keeps
     // ONE block, its other rows only move their x.  RMCKF: PV of the lane's R blocks stay in registers, the others live in LDS and pass
     // through registers while their row is updated: with all four in registers (L = 8) the compiler overflows VGPRs + AGPRs and spills
     // ~60 dwords per lane to scratch.

@@ -1,4 +1,6 @@
-// Shared body of tu_closed_tuned_{a,b}.hip: UVS_TU_SHAPES and UVS_TU_NAME are defined by the including file.
+// Shared body of tu_closed_tuned_{a,b}.hip (which define UVS_TU_SHAPES and UVS_TU_NAME) and of tu_closed_grid_{a,b}.hip (UVS_PER_TRIAL, UVS_TU_NAME and
+// UVS_TU_METHODS): there UVS_CLOSED_TUNED_KERNEL / ClosedKernelArgs are the per-trial flavour (closed_loop_grid_kernel / ClosedGridArgs, rmckf_device.hpp),
+// which exists at (8,6), two lanes, DH plant only.  One launcher text, so a grid launch picks the instantiation of the uniform launch it replaces.
 #include "launchers.hpp"
 #include "rmckf_tuned.hpp"
 
@@ -7,15 +9,15 @@
 namespace {
 // estimator, plant kind and "X stream wanted" are compile-time in the tuned kernel
 template <int M, int N, int LL, int METHOD, int PLANT, bool EMU2 = false>
-void launch2(bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
+void launch2(bool xo, dim3 g, hipStream_t s, const uvs::ClosedKernelArgs &A) {
     constexpr int PV = (LL == 2 ? M / LL / 2 : M / LL);      // L = 2 parks half of its blocks in LDS; 1 and 4 keep all in registers
     // UVS_OPT_STRICT_PINV on KF / IMCC-KF / MCKF: the instantiations whose control law certifies every solve (uvs_launch::tuned_certifies; a compile-time
-    // switch there, see CERT in rmckf_tuned.hpp; RMCKF reads the option at run time); MCKF as whole trials
-    if constexpr (METHOD != UVS_METHOD_GMCKF && uvs_launch::tuned_certifies(M, N, LL, METHOD, PLANT == UVS_PLANT_LINEAR, EMU2)) {
+    // switch there, see CERT in rmckf_tuned.hpp; RMCKF reads the option at run time); MCKF as whole trials.  (No per-trial CERT / XREC / XPAIR kernels.)
+    if constexpr (!uvs::kPerTrial && METHOD != UVS_METHOD_GMCKF && uvs_launch::tuned_certifies(M, N, LL, METHOD, PLANT == UVS_PLANT_LINEAR, EMU2)) {
         if (A.fp.reserved & UVS_OPT_STRICT_PINV) {
             constexpr bool SEGM = (METHOD == UVS_METHOD_MCKF);
-            if (xo) hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, true, false, SEGM, false, true>), g, dim3(64), 0, s, A);
-            else hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, false, false, SEGM, false, true>), g, dim3(64), 0, s, A);
+            if (xo) hipLaunchKernelGGL((uvs::UVS_CLOSED_TUNED_KERNEL<M, N, LL, METHOD, PLANT, PV, true, false, SEGM, false, true>), g, dim3(64), 0, s, A);
+            else hipLaunchKernelGGL((uvs::UVS_CLOSED_TUNED_KERNEL<M, N, LL, METHOD, PLANT, PV, false, false, SEGM, false, true>), g, dim3(64), 0, s, A);
             return;
         }
     }
@@ -25,8 +27,8 @@ void launch2(bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
             uvs_launch::fill_i32(A.ws_flags, 0, (long long)g.x + 1, s);      // the chunks' counters + the fallback count (a kernel, not a memset node: launchers.hpp)
             g.x *= (unsigned)A.n_seg;
             if constexpr (METHOD == UVS_METHOD_GMCKF) {
-                if (xo) hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, true, false, true>), g, dim3(64), 0, s, A);
-                else hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, false, false, true>), g, dim3(64), 0, s, A);
+                if (xo) hipLaunchKernelGGL((uvs::UVS_CLOSED_TUNED_KERNEL<M, N, LL, METHOD, PLANT, PV, true, false, true>), g, dim3(64), 0, s, A);
+                else hipLaunchKernelGGL((uvs::UVS_CLOSED_TUNED_KERNEL<M, N, LL, METHOD, PLANT, PV, false, false, true>), g, dim3(64), 0, s, A);
                 return;
             }
         }
@@ -35,7 +37,7 @@ void launch2(bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
     // (measured, profiles/r05/record_layout.txt: KF 2.605 -> 2.54 ms, IMCC-KF 2.69 -> 2.67; RMCKF -- one wavefront per SIMD, nothing to hide the twelve
     // bank-conflicted LDS reads behind -- loses 10 % and keeps its strided stores whatever the view; 16-byte stores straight from the rows' registers,
     // without the transposition, cost KF + 25 %)
-    if constexpr (M == 8 && N == 6 && LL == 2 && !EMU2 && (METHOD == UVS_METHOD_KF || METHOD == UVS_METHOD_IMCCKF) && PLANT != UVS_PLANT_LINEAR) {
+    if constexpr (!uvs::kPerTrial && M == 8 && N == 6 && LL == 2 && !EMU2 && (METHOD == UVS_METHOD_KF || METHOD == UVS_METHOD_IMCCKF) && PLANT != UVS_PLANT_LINEAR) {
         const bool aligned = (reinterpret_cast<uintptr_t>(A.x_out.p) & 15u) == 0 && A.x_out.sk % 2 == 0;
         const bool records = A.x_out.sc == 1 && A.x_out.st == M * N;
         // (round 6) trial-fastest rows -- the package's default layout -- leave LDS as 16-byte pairs of consecutive trials (XPAIR): 12 stores per lane-step
@@ -43,16 +45,16 @@ void launch2(bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
         // wavefront per SIMD, nothing to hide the LDS reads and the burst of stores behind -- loses 4.6 % with it (same file) and keeps its 8-byte stores.
         const bool pairs = A.x_out.st == 1 && A.x_out.sc % 2 == 0 && A.T % 2 == 0;
         if (xo && aligned && records) {
-            hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, true, false, false, true>), g, dim3(64), 0, s, A);
+            hipLaunchKernelGGL((uvs::UVS_CLOSED_TUNED_KERNEL<M, N, LL, METHOD, PLANT, PV, true, false, false, true>), g, dim3(64), 0, s, A);
             return;
         }
         if (xo && aligned && pairs) {
-            hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, true, false, false, true, false, true>), g, dim3(64), 0, s, A);
+            hipLaunchKernelGGL((uvs::UVS_CLOSED_TUNED_KERNEL<M, N, LL, METHOD, PLANT, PV, true, false, false, true, false, true>), g, dim3(64), 0, s, A);
             return;
         }
     }
-    if (xo) hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, true, EMU2>), g, dim3(64), 0, s, A);
-    else hipLaunchKernelGGL((uvs::closed_loop_tuned_kernel<M, N, LL, METHOD, PLANT, PV, false, EMU2>), g, dim3(64), 0, s, A);
+    if (xo) hipLaunchKernelGGL((uvs::UVS_CLOSED_TUNED_KERNEL<M, N, LL, METHOD, PLANT, PV, true, EMU2>), g, dim3(64), 0, s, A);
+    else hipLaunchKernelGGL((uvs::UVS_CLOSED_TUNED_KERNEL<M, N, LL, METHOD, PLANT, PV, false, EMU2>), g, dim3(64), 0, s, A);
 }
 // UR10-like DH table: the tuned two-lane kernel has an instantiation that knows the zeros of its first and last links per lane group
 inline bool axis_aligned(const uvs_plant &p) {
@@ -62,14 +64,14 @@ inline bool axis_aligned(const uvs_plant &p) {
     return true;
 }
 template <int M, int N, int LL, int METHOD, bool EMU2 = false>
-void launch_dh(bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
+void launch_dh(bool xo, dim3 g, hipStream_t s, const uvs::ClosedKernelArgs &A) {
     if constexpr ((LL == 2 || EMU2) && N == 6 && M == 8) {
         if (axis_aligned(A.plant)) { launch2<M, N, LL, METHOD, uvs::kPlantDhAxisAligned, EMU2>(xo, g, s, A); return; }
     }
     launch2<M, N, LL, METHOD, UVS_PLANT_DH_PINHOLE, EMU2>(xo, g, s, A);
 }
 template <int M, int N, int LL, bool EMU2 = false>
-bool launch(int method, bool linear, bool xo, dim3 g, hipStream_t s, const uvs::ClosedArgs &A) {
+bool launch(int method, bool linear, bool xo, dim3 g, hipStream_t s, const uvs::ClosedKernelArgs &A) {
     auto go = [&](auto meth) {
         constexpr int METHOD = decltype(meth)::value;
         if (!linear) launch_dh<M, N, LL, METHOD, EMU2>(xo, g, s, A);
@@ -83,6 +85,11 @@ bool launch(int method, bool linear, bool xo, dim3 g, hipStream_t s, const uvs::
 }  // namespace
 #endif
 
+#ifdef UVS_PER_TRIAL
+bool uvs_launch::UVS_TU_NAME(int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedGridArgs &A) {
+    return dispatch<UVS_TU_METHODS>(method, [&](auto meth) { launch_dh<8, 6, 2, decltype(meth)::value>(xo, grid_for(T, 2), s, A); });
+}
+#else
 #ifdef UVS_TU_EMU2                      // this translation unit also carries the four-lane kernels with the two-lane kernel's bits (rmckf_tuned.hpp, EMU2)
 bool uvs_launch::closed_tuned_emu2(int method, bool xo, int64_t T, hipStream_t s, const uvs::ClosedArgs &A) {
     return launch<8, 6, 4, true>(method, false, xo, grid_for(T, 4), s, A);
@@ -96,3 +103,4 @@ bool uvs_launch::UVS_TU_NAME(int m, int n, int L, int method, bool linear, bool 
 #undef X
     return false;
 }
+#endif

@@ -4,6 +4,8 @@
 // instantiated by one translation unit per family (launchers.hpp) so that the library builds in parallel:
 //   rmckf_tuned.hpp          closed_loop_tuned_kernel: whole servo trial per filter, headline shapes (tu_closed_tuned_{a,b}.hip)
 //                            closed_loop_grid_kernel: the same body with per-trial estimator parameters (UVS_PER_TRIAL; tu_closed_grid_{a,b}.hip)
+//   rmckf_rows.hpp           lane exchanges, rmckf_row, MCKF row pieces; rmckf_lstsq.hpp: lstsq_tall_tuned / _emu2; rmckf_diag.hpp: diagnostic clocks
+//   rmckf_wide.hpp           closed_loop_wide_kernel: (32,7), and (8,6) with one row per lane (tu_closed_wide.hip)
 //   rmckf_replay_tuned.hpp   replay_tuned_kernel / replay_rows_kernel: estimator (+ control law) over recorded streams (tu_replay_tuned.hip)
 //   rmckf_generic.hpp        closed_loop_kernel / replay_kernel / step_kernel: any shape, every estimator incl. MCKF; stats_kernel
 //                            (tu_generic_{a,b}.hip, tu_misc.hip)
@@ -98,13 +100,14 @@ struct ClosedPlan {
 };
 
 constexpr int64_t kSimdSlots = 1024;
+int64_t two_lane_chunks(int64_t T) { return (T * 2 + 63) / 64; }   // wavefronts (trial chunks) of the two-lane layout: 32 trials each
 
 // Segmented trials (tuned two-lane MCKF kernel, and RMCKF's SEGMENTED instantiation at (8,6)).  How many segments a launch of T trials is cut
 // into: MCKF wavefronts differ in length (a trial whose fixed-point iteration keeps iterating costs its whole wavefront the branch), so the
 // last round of a launch of whole trials leaves SIMDs idle for up to a third of a trial.  Bits 8-15 of fp.reserved override (1 = never,
 // n = n segments).
 int segments(const uvs_filter_params &fp, int64_t T) {
-    const int64_t chunks = (T * 2 + 63) / 64;
+    const int64_t chunks = two_lane_chunks(T);
     int n = (fp.reserved >> 8) & 0xff;
     if (!n && fp.method == UVS_METHOD_MCKF) {
         // measured on MI355X (32 trials per wavefront, one wavefront per SIMD): one round or less -- nothing to balance;
@@ -176,7 +179,7 @@ ClosedPlan plan_or_none(const uvs_filter_params *fp, const uvs_plant *plant, int
 size_t seg_flag_bytes(int64_t chunks) { return (size_t)(((chunks + 1) * sizeof(int) + 255) / 256) * 256; }   // one counter per chunk + the fallback count
 size_t seg_workspace_bytes(const uvs_filter_params &fp, int64_t T, int n_seg) {
     if (n_seg <= 1) return 0;
-    const int64_t chunks = (T * 2 + 63) / 64;
+    const int64_t chunks = two_lane_chunks(T);
     return seg_flag_bytes(chunks) + (size_t)chunks * uvs::seg_state_doubles(fp.m, fp.n, 2) * 64 * sizeof(double);
 }
 
@@ -218,7 +221,7 @@ size_t uvs_rmckf_closed_loop_workspace_bytes(const uvs_filter_params *fp, const 
 
 size_t uvs_rmckf_closed_loop_fallback_offset(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T) {
     if (plan_or_none(fp, plant, T).n_seg <= 1) return 0;
-    return (size_t)((T * 2 + 63) / 64) * sizeof(int);
+    return (size_t)two_lane_chunks(T) * sizeof(int);
 }
 
 int uvs_rmckf_closed_loop_f64(const uvs_filter_params *fp, const uvs_plant *plant, int64_t T, uvs_view q_start, uvs_view noise,
@@ -314,7 +317,7 @@ int closed_loop_impl(const uvs_filter_params *fp, const uvs_plant *plant, int64_
             }
             A.seg_first[A.n_seg] = fp->steps;
             A.ws_flags = (int *)workspace;
-            A.ws_state = (double *)((char *)workspace + seg_flag_bytes((T * 2 + 63) / 64));
+            A.ws_state = (double *)((char *)workspace + seg_flag_bytes(two_lane_chunks(T)));
         }
     }
     hipStream_t s = (hipStream_t)stream;
