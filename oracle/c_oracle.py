@@ -7,6 +7,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PATH = os.path.join(HERE, 'c', 'liboracle_rmckf.so')
+REG = 0.001 ** 2                                                    # experiment.py:280
 METHOD = {'KF': 2, 'MCKF': 3, 'IMCCKF': 4, 'GMCKF': 5}
 
 
@@ -60,7 +61,7 @@ def linear_plant(J, f0, q0):
 
 
 def closed_loop_batch(q_start, noise, desired, method='GMCKF', kernel_bw=10.0, annealing=False, dt=0.05, t_max=15.0, gain=0.2,
-                      steps=None, want_x=False, plant=None, fpi_threshold=0.1, fpi_epoch_max=1000, x0=None):
+                      steps=None, want_x=False, plant=None, fpi_threshold=0.1, fpi_epoch_max=1000, x0=None, reg=REG, anneal_span=100.0):
     """q_start (T, n), noise (T, K, m) -> dict(err (T,K,m), q (T,K,n), X (T,K,mn)?, stats (T,3), status, k_done, fpi (T,K) MCKF passes per step)."""
     q_start, noise = np.ascontiguousarray(q_start, float), np.ascontiguousarray(noise, float)
     T, K, m = noise.shape
@@ -68,7 +69,7 @@ def closed_loop_batch(q_start, noise, desired, method='GMCKF', kernel_bw=10.0, a
     fp = Params()
     fp.m, fp.n, fp.method, fp.annealing, fp.k_max = m, n, METHOD[method], int(annealing), int(t_max / dt)
     fp.steps, fp.initial_guess = K if steps is None else steps, int(x0 is None)
-    fp.kernel_bw, fp.anneal_span, fp.gain, fp.dt, fp.reg = kernel_bw, 100.0, gain, dt, 0.001 ** 2
+    fp.kernel_bw, fp.anneal_span, fp.gain, fp.dt, fp.reg = kernel_bw, anneal_span, gain, dt, reg
     fp.fpi_threshold, fp.fpi_epoch_max = fpi_threshold, fpi_epoch_max
     for i, v in enumerate(desired):
         fp.desired[i] = v
@@ -92,14 +93,15 @@ def closed_loop_batch(q_start, noise, desired, method='GMCKF', kernel_bw=10.0, a
     return dict(err=err, q=q, X=X, stats=stats, status=status, k_done=k_done, fpi=fpi)
 
 
-def replay_batch(f_seq, dq_seq, x0, desired, method='GMCKF', kernel_bw=10.0, annealing=False, k_max=300, gain=0.2, fpi_threshold=0.1, fpi_epoch_max=1000):
+def replay_batch(f_seq, dq_seq, x0, desired, method='GMCKF', kernel_bw=10.0, annealing=False, k_max=300, gain=0.2, fpi_threshold=0.1, fpi_epoch_max=1000,
+                 reg=REG, anneal_span=100.0):
     """f_seq (T, K+1, m), dq_seq (T, K, n), x0 (T, m n) -> dict(X (T,K,mn), dq_cmd (T,K,n), kappa (T,K,m), status, k_done, fpi (T,K))."""
     f_seq, dq_seq, x0 = (np.ascontiguousarray(a, float) for a in (f_seq, dq_seq, x0))
     T, K, n = dq_seq.shape
     m = f_seq.shape[2]
     fp = Params()
     fp.m, fp.n, fp.method, fp.annealing, fp.k_max, fp.steps, fp.initial_guess = m, n, METHOD[method], int(annealing), int(k_max), K, 0
-    fp.kernel_bw, fp.anneal_span, fp.gain, fp.dt, fp.reg = kernel_bw, 100.0, gain, 0.0, 0.001 ** 2
+    fp.kernel_bw, fp.anneal_span, fp.gain, fp.dt, fp.reg = kernel_bw, anneal_span, gain, 0.0, reg
     fp.fpi_threshold, fp.fpi_epoch_max = fpi_threshold, fpi_epoch_max
     for i, v in enumerate(desired):
         fp.desired[i] = v

@@ -5,7 +5,7 @@ Because ``H = kron(I_m, dq^T)`` (experiment.py:188) and ``P0 = Q = I``, ``R = I`
 block diagonal: m independent n x n blocks that share the regressor ``h = dq``
 (SURVEY.md fact 4).  This module evaluates the same recursion row by row:
 
-    P_i += I;  nu_i = Z_i - x_i.h;  c_i = exp(-nu_i^2 / (2 sigma^2));  r_i = 1/(c_i + 1e-6)
+    P_i += I;  nu_i = Z_i - x_i.h;  c_i = exp(-nu_i^2 / (2 sigma^2));  r_i = 1/(c_i + reg)
     g_i = P_i h;  s_i = h.g_i + r_i;  k_i = g_i / s_i;  x_i += k_i nu_i
     P_i = (I - k_i h^T) P_i (I - k_i h^T)^T + k_i k_i^T          (Joseph, R = 1)
 
@@ -20,8 +20,10 @@ REG = 0.001 ** 2                                                    # experiment
 
 
 class BlockFilter:
-    def __init__(self, m, n, x0=None, method=GMCKF, kernel_bw=10.0, annealing=False, k_max=300, fpi_threshold=0.1, fpi_epoch_max=1000):
+    def __init__(self, m, n, x0=None, method=GMCKF, kernel_bw=10.0, annealing=False, k_max=300, fpi_threshold=0.1, fpi_epoch_max=1000,
+                 reg=REG, anneal_span=100.0):
         self.m, self.n, self.method = m, n, method
+        self.reg, self.anneal_span = reg, anneal_span
         self.kernel_bw, self.annealing, self.k_max = kernel_bw, annealing, k_max
         self.fpi_threshold, self.fpi_epoch_max = fpi_threshold, fpi_epoch_max
         self.fpi_iterations = 0
@@ -51,7 +53,7 @@ class BlockFilter:
         elif self.method == GMCKF:
             self.sigma = self._sigma(k)
             kappa = np.exp(-0.5 * nu ** 2 / self.sigma ** 2)
-            gain_scale, r = np.ones(m), 1.0 / (kappa + REG)
+            gain_scale, r = np.ones(m), 1.0 / (kappa + self.reg)
         else:
             raise ValueError(self.method)
         s = gain_scale * a + r
@@ -106,7 +108,7 @@ class BlockFilter:
         return np.ones(m)
 
     def _sigma(self, k):
-        return self.kernel_bw + 100 * (1 - k / self.k_max) if self.annealing else self.kernel_bw
+        return self.kernel_bw + self.anneal_span * (1 - k / self.k_max) if self.annealing else self.kernel_bw
 
 
 def control_law(X, err, kappa, gain):
@@ -115,10 +117,10 @@ def control_law(X, err, kappa, gain):
 
 
 def run_replay(f_seq, dq_seq, x0, desired_f, gain, method=GMCKF, kernel_bw=10.0, annealing=False, k_max=300, fpi_threshold=0.1,
-               fpi_epoch_max=1000):
+               fpi_epoch_max=1000, reg=REG, anneal_span=100.0):
     f_seq, dq_seq = np.asarray(f_seq, float), np.asarray(dq_seq, float)
     K, m, n = len(dq_seq), f_seq.shape[1], dq_seq.shape[1]
-    filt = BlockFilter(m, n, x0, method, kernel_bw, annealing, k_max, fpi_threshold, fpi_epoch_max)
+    filt = BlockFilter(m, n, x0, method, kernel_bw, annealing, k_max, fpi_threshold, fpi_epoch_max, reg, anneal_span)
     Xs, errs, kaps, cmds, its = [], [], [], [], []
     for k in range(K):
         kappa = filt.step(f_seq[k + 1] - f_seq[k], dq_seq[k], k)
@@ -129,7 +131,7 @@ def run_replay(f_seq, dq_seq, x0, desired_f, gain, method=GMCKF, kernel_bw=10.0,
 
 
 def run_closed_loop(plant, q_start, desired_f, noise_seq, t_s, t_max, gain, x0, method=GMCKF,
-                    kernel_bw=10.0, annealing=False, initial_guess=True, fpi_threshold=0.1, fpi_epoch_max=1000):
+                    kernel_bw=10.0, annealing=False, initial_guess=True, fpi_threshold=0.1, fpi_epoch_max=1000, reg=REG, anneal_span=100.0):
     """Closed loop on a functional plant: ``plant(q) -> f`` (noise-free features at joints q).
     ``noise_seq`` (K, m) or None.  ``initial_guess`` selects what the first ``f_old`` is: the noise-free features seen while
     forming the analytic X0 (experiment.py:90) or zeros when X0 is supplied (experiment.py:56).
@@ -137,7 +139,7 @@ def run_closed_loop(plant, q_start, desired_f, noise_seq, t_s, t_max, gain, x0, 
     desired_f = np.asarray(desired_f, float)
     m, n = len(desired_f), len(q_start)
     k_max = int(t_max / t_s)
-    filt = BlockFilter(m, n, x0, method, kernel_bw, annealing, k_max, fpi_threshold, fpi_epoch_max)
+    filt = BlockFilter(m, n, x0, method, kernel_bw, annealing, k_max, fpi_threshold, fpi_epoch_max, reg, anneal_span)
     q = np.array(q_start, float)
     f = plant(q) if initial_guess else np.zeros(m)
     dq = np.zeros(n)

@@ -15,6 +15,7 @@ import numpy as np
 
 KF, MCKF, IMCCKF, GMCKF = 'KF', 'MCKF', 'IMCCKF', 'GMCKF'
 SUCCESS, FAIL = 0, 1
+REG = 0.001 ** 2                                                    # experiment.py:280
 
 
 def gaussian_kernel(e, bw):
@@ -35,17 +36,18 @@ def analytic_initial_guess(robot, f, m, n=6):
     return Jf.reshape((m * n, 1))
 
 
-def bandwidth(kernel_bw, annealing, k, k_max):
+def bandwidth(kernel_bw, annealing, k, k_max, anneal_span=100.0):
     """sigma_k (experiment.py:267-271)."""
-    return kernel_bw + 100 * (1 - k / k_max) if annealing else kernel_bw
+    return kernel_bw + anneal_span * (1 - k / k_max) if annealing else kernel_bw
 
 
 class DenseFilter:
     """State (X, P) of one estimator and its per-step update (experiment.py:70-76, 164-298)."""
 
     def __init__(self, m, n, method=GMCKF, kernel_bw=10.0, annealing=False, k_max=300,
-                 fpi_threshold=0.1, fpi_epoch_max=1000, x0=None):
+                 fpi_threshold=0.1, fpi_epoch_max=1000, x0=None, reg=REG, anneal_span=100.0):
         self.m, self.n, self.method = m, n, method
+        self.reg, self.anneal_span = reg, anneal_span
         self.kernel_bw, self.annealing, self.k_max = kernel_bw, annealing, k_max
         self.fpi_threshold, self.fpi_epoch_max = fpi_threshold, fpi_epoch_max
         mn = m * n
@@ -79,7 +81,7 @@ class DenseFilter:
             K = P @ H.T @ np.linalg.inv(H @ P @ H.T + R)
             X = X + K @ (Z - H @ X)
         elif self.method == MCKF:                                          # :194-250
-            bw = self.sigma = bandwidth(self.kernel_bw, self.annealing, k, self.k_max)
+            bw = self.sigma = bandwidth(self.kernel_bw, self.annealing, k, self.k_max, self.anneal_span)
             Bp = np.linalg.cholesky(P)
             Br = np.linalg.cholesky(R)
             B = np.block([[Bp, np.zeros((mn, m))], [np.zeros((m, mn)), Br]])
@@ -108,7 +110,7 @@ class DenseFilter:
             if not skip:
                 X = Xc
         elif self.method == IMCCKF:                                        # :251-265
-            bw = self.sigma = bandwidth(self.kernel_bw, self.annealing, k, self.k_max)
+            bw = self.sigma = bandwidth(self.kernel_bw, self.annealing, k, self.k_max, self.anneal_span)
             innov = Z - H @ X
             nrm = np.sqrt(innov.T @ np.linalg.inv(R) @ innov)
             Cy = gaussian_kernel(nrm, bw)
@@ -116,11 +118,11 @@ class DenseFilter:
             K = Cy * P @ H.T @ np.linalg.inv(R_e)
             X = X + K @ innov
         elif self.method == GMCKF:                                         # :266-294
-            bw = self.sigma = bandwidth(self.kernel_bw, self.annealing, k, self.k_max)
+            bw = self.sigma = bandwidth(self.kernel_bw, self.annealing, k, self.k_max, self.anneal_span)
             e = self.Br_inv @ Z - self.Br_inv @ H @ X
             Cy = np.diag([gaussian_kernel(e[i, 0], bw) for i in range(m)])
             try:
-                Cy_inv = np.linalg.inv(Cy + 0.001 ** 2 * np.eye(m))
+                Cy_inv = np.linalg.inv(Cy + self.reg * np.eye(m))
                 R_hat = self.Br @ Cy_inv @ self.Br.T
                 S = H @ P @ H.T + R_hat
                 K = P @ H.T @ np.linalg.inv(S)
@@ -145,7 +147,7 @@ def control_law(X, m, n, err, kappa, gain):
 
 def run_closed_loop(robot, q_start, desired_f, noise_next, t_s, t_max, gain, method=GMCKF,
                     initial_guess=True, kernel_bw=10.0, annealing=False, fpi_threshold=0.1,
-                    fpi_epoch_max=1000, x0=None, capture=False):
+                    fpi_epoch_max=1000, x0=None, capture=False, reg=REG, anneal_span=100.0):
     """One servo trial (experiment.py:48-359).  ``noise_next()`` returns the next (m,) noise sample
     (or ``None`` for a noise-free run).  Returns a dict of the reference's logs plus, when
     ``capture``, the per-step X / block-diagonal of P / commanded dq."""
@@ -160,7 +162,7 @@ def run_closed_loop(robot, q_start, desired_f, noise_next, t_s, t_max, gain, met
         x0 = analytic_initial_guess(robot, f, m, n)
     elif x0 is None:
         raise ValueError('x0 required when initial_guess is False (reference draws it unseeded, experiment.py:117)')
-    filt = DenseFilter(m, n, method, kernel_bw, annealing, k_max, fpi_threshold, fpi_epoch_max, x0)
+    filt = DenseFilter(m, n, method, kernel_bw, annealing, k_max, fpi_threshold, fpi_epoch_max, x0, reg, anneal_span)
     dq = np.zeros((n, 1))
     logs = {key: [] for key in ('t', 'err', 'q', 'f', 'noise', 'cam', 'X', 'Pblk', 'dq', 'sigma', 'kappa', 'fpi_iterations', 'fpi_skipped')}
     status, k = SUCCESS, 0
@@ -196,13 +198,13 @@ def run_closed_loop(robot, q_start, desired_f, noise_next, t_s, t_max, gain, met
 
 
 def run_replay(f_seq, dq_seq, x0, desired_f, gain, method=GMCKF, kernel_bw=10.0, annealing=False,
-               k_max=300, fpi_threshold=0.1, fpi_epoch_max=1000):
+               k_max=300, fpi_threshold=0.1, fpi_epoch_max=1000, reg=REG, anneal_span=100.0):
     """Open-loop replay: f_seq (K+1, m) observed features (row 0 = f_old of the first step), dq_seq (K, n)
     the regressor used at each step (row 0 is ignored: H = 0 on the first iteration, experiment.py:183).
     Returns per-step X (K, mn), err (K, m), kappa (K, m), commanded dq (K, n)."""
     f_seq, dq_seq = np.asarray(f_seq, float), np.asarray(dq_seq, float)
     K, m, n = len(dq_seq), f_seq.shape[1], dq_seq.shape[1]
-    filt = DenseFilter(m, n, method, kernel_bw, annealing, k_max, fpi_threshold, fpi_epoch_max, x0)
+    filt = DenseFilter(m, n, method, kernel_bw, annealing, k_max, fpi_threshold, fpi_epoch_max, x0, reg, anneal_span)
     Xs, errs, kaps, cmds = [], [], [], []
     for k in range(K):
         kappa = filt.step(f_seq[k + 1] - f_seq[k], dq_seq[k], k)

@@ -26,7 +26,10 @@ METHODS = ('GMCKF', 'KF', 'IMCCKF', 'MCKF')
 # name -> (m, n, plant kind, analytic initial guess)
 CASES = {'dh66': (6, 6, 'dh', True), 'dh66_x0': (6, 6, 'dh', False), 'dh26': (2, 6, 'dh', True),
          'lin86': (8, 6, 'linear', False), 'lin66': (6, 6, 'linear', False)}
-SEEDS = {'dh66': 6601, 'dh66_x0': 6602, 'dh26': 2601, 'lin86': 8601, 'lin66': 6603}
+SEEDS = {'dh66': 6601, 'dh66_x0': 6602, 'dh26': 2601, 'lin86': 8601, 'lin66': 6603, 'dh86': 8602}
+# Further inputs of the same recipe that are no parity case of their own (not part of configurations()): tests/estimator_params_common.py
+# runs them, and the cases above, at other values of reg and anneal_span.
+PARAM_CASES = {'dh86': (8, 6, 'dh', True)}
 # (case, method, annealing) -> the sampled trials left out of the parity comparison: every one on which oracle/c and oracle/rmckf_block were
 # measured more than 1e-12 apart -- a decade under AGREE_TOL, so that another libm or BLAS does not carry a kept trial past the gate (the
 # kept ones: <= 8.9e-13, most <= 1e-13).  Measured: dh66 RMCKF 28: 1.7, 30: 8.3e-12, 63: 1.0e-10; dh66_x0 RMCKF 17: 1.3, 30: 0.99 (annealed
@@ -58,7 +61,7 @@ def inputs(case):
     """dict(m, n, kind, guess, desired, q0 (T, n), noise (T, K, m), x0 (T, m n) -- what the estimator starts from on either route --,
     features: q -> noise-free f, discs | (J, f0, lin_q0)).  Read-only: shared by every test of a session."""
     from oracle import plant_ref, rmckf_dense
-    m, n, kind, guess = CASES[case]
+    m, n, kind, guess = CASES[case] if case in CASES else PARAM_CASES[case]
     rng = np.random.default_rng(SEEDS[case])
     d = dict(m=m, n=n, kind=kind, guess=guess)
     if kind == 'dh':

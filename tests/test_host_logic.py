@@ -74,6 +74,37 @@ def test_step_entry_point_refuses_before_it_launches(uvs):
     assert not any(bufs['status']) and not any(bufs['dq_out'])
 
 
+def test_other_reg_and_anneal_span_pass_the_argument_checks_unchanged(uvs):
+    """No entry point judges uvs_filter_params.reg or .anneal_span: with other values the host-side queries answer what they answer for the
+    defaults, a refusal is the same refusal, and the block is handed back as it was given."""
+    lib = uvs.lib()
+    plant = uvs.SyntheticPlant.ur10().to_struct()
+    V = uvs._lib.NULL_VIEW
+
+    def answers(fp):
+        ref = ctypes.byref(fp)
+        out = []
+        for T in (70, 40000, 65536):
+            out += [int(lib.uvs_rmckf_closed_loop_lanes(ref, ctypes.byref(plant), T)), int(lib.uvs_rmckf_closed_loop_segments(ref, ctypes.byref(plant), T)),
+                    int(lib.uvs_rmckf_closed_loop_workspace_bytes(ref, ctypes.byref(plant), T)), int(lib.uvs_rmckf_closed_loop_fallback_offset(ref, ctypes.byref(plant), T))]
+        out.append((lib.uvs_rmckf_step_f64(ref, 0, None, None, None, None, None, 1, 0, None, None, None, None, None), lib.uvs_last_error()))
+        out.append((lib.uvs_rmckf_replay_f64(ref, 0, V, V, V, V, V, V, V, None, None, V, V, None), lib.uvs_last_error()))
+        out.append((lib.uvs_rmckf_closed_loop_f64(ref, ctypes.byref(plant), 0, V, V, V, V, V, V, V, V, None, None, None, V, V, None), lib.uvs_last_error()))
+        return out
+
+    for method in ('GMCKF', 'MCKF', 'IMCCKF', 'KF'):
+        for lanes in (0, 2, -2):
+            mk = lambda: uvs.engine.make_params(8, 6, method, annealing=True, desired=np.zeros(8), lanes=lanes)     # noqa: E731
+            default = answers(mk())
+            assert all(rc < 0 for rc, text in default[-3:])
+            for reg, span in ((0.25, 25.0), (1e-3, 400.0), (0.0, 0.0), (1e-12, 100.0)):
+                fp = mk()
+                assert (fp.reg, fp.anneal_span) == (1e-6, 100.0)
+                fp.reg, fp.anneal_span = reg, span
+                assert answers(fp) == default, (method, lanes, reg, span)
+                assert (fp.reg, fp.anneal_span) == (reg, span)
+
+
 def test_workspace_query_is_host_logic(uvs):
     """uvs_rmckf_closed_loop_workspace_bytes: which launches the library would cut into segments (MCKF on the tuned two-lane kernel, DH plant,
     more than one round of wavefronts) and how much caller-owned scratch that takes -- no GPU involved."""
