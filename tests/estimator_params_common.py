@@ -1,23 +1,21 @@
-"""Parameter sets, inputs and CPU references shared by tests/test_oracle_c.py and tests/test_gpu_estimator_params.py: the closed loops of
-tests/closed_shapes_common.py (plus 'dh86', the (8,6) DH plant from the analytic guess, and the (32,7) linear plant of
+"""Parameter sets shared by tests/test_oracle_c.py and tests/test_gpu_estimator_params.py: the closed loops of tests/closed_shapes_common.py
+(its cases plus 'dh86', the (8,6) DH plant from the analytic guess, and 'wide', the (32,7) linear plant of
 test_gpu_parity.py::test_closed_loop_stress_plant) with uvs_filter_params.reg and .anneal_span moved off the one value every other test
 leaves them at (engine.REG = 1e-6, engine.ANNEAL_SPAN = 100).
 
     R3    RMCKF, annealing off, reg 1e-3        A25   annealing on, anneal_span 25  (RMCKF: reg 0.25; IMCC-KF, MCKF: reg ignored)
     R25   RMCKF, annealing off, reg 0.25        A400  annealing on, anneal_span 400 (likewise)
 
-The references are the two CPU oracles run with these values (oracle/c on every trial, oracle/rmckf_block on cs.sampled(case));
+The references are the two CPU oracles run with these values (cs.c_reference on every trial, cs.block_reference on cs.sampled(case));
 test_oracle_c.py holds them to cs.AGREE_TOL of each other on the kept trials, the list EXCLUDED to the 10 % cap, and -- the teeth -- the
 oracle run with the DEFAULT reg and anneal_span at least 100 gates away from the one with the set's values on the worst kept trial, so that
 a kernel that read a literal instead of the field could not pass.  R25 sits at the cap on the (6,6) DH cases and is not run there."""
-import functools
-
 import numpy as np
 
 import closed_shapes_common as cs
 
-REG, ANNEAL_SPAN = 0.001 ** 2, 100.0                             # the defaults (engine.make_params, experiment.py:280 and :271)
-GATE = 1e-8                                                      # the closed loop's GPU gate (test_gpu_closed_shapes.TOL)
+REG, ANNEAL_SPAN = cs.REG, cs.ANNEAL_SPAN                        # the defaults (engine.make_params, experiment.py:280 and :271)
+GATE = 1e-8                                                      # the closed loop's GPU gate (gpu_harness.TOL)
 TEETH = 100.0                                                    # the default-valued oracle misses GATE by at least this factor
 SETS = {'R3': (False, 1e-3, ANNEAL_SPAN), 'R25': (False, 0.25, ANNEAL_SPAN), 'A25': (True, 0.25, 25.0), 'A400': (True, 0.25, 400.0)}
 SET_METHODS = {'R3': ('GMCKF',), 'R25': ('GMCKF',), 'A25': ('GMCKF', 'IMCCKF', 'MCKF'), 'A400': ('GMCKF', 'IMCCKF', 'MCKF')}
@@ -41,53 +39,14 @@ def configurations():
     return [(case, name, method) for case, names in CASE_SETS.items() for name in names for method in SET_METHODS[name]]
 
 
-@functools.lru_cache(maxsize=None)
-def c_reference(case, name, method, default=False):
-    """oracle/c on every trial at the set's values -- or, default=True, the same estimator with reg and anneal_span left at the defaults."""
-    from oracle import c_oracle
-    inp = cs.inputs(case)
+WIDE_CONFIGS = [('R25', 'GMCKF'), ('A25', 'GMCKF'), ('A25', 'IMCCKF'), ('A400', 'GMCKF'), ('A400', 'IMCCKF')]     # case 'wide': no MCKF on the wide kernel
+
+
+def run(name, method, default=False):
+    """The estimator of set `name` as keywords of cs.c_reference, cs.block_reference and cs.oracle_agreement -- or, default=True, the same
+    estimator with reg and anneal_span left at the defaults."""
     anneal, reg, span = estimator(name, method)
-    if default:
-        reg, span = REG, ANNEAL_SPAN
-    return c_oracle.closed_loop_batch(inp['q0'], inp['noise'], inp['desired'], method=method, kernel_bw=cs.BW, annealing=anneal, dt=cs.DT,
-                                      t_max=cs.T_MAX, gain=cs.GAIN, steps=cs.K, want_x=True, plant=cs.c_plant(inp),
-                                      fpi_threshold=cs.FPI_THRESHOLD, x0=None if inp['guess'] else inp['x0'], reg=reg, anneal_span=span)
-
-
-@functools.lru_cache(maxsize=None)
-def block_reference(case, name, method, t):
-    """oracle/rmckf_block on trial t at the set's values: run_closed_loop's dict plus stats (3,) and f (K, m)."""
-    from oracle import rmckf_block, rmckf_dense
-    inp = cs.inputs(case)
-    anneal, reg, span = estimator(name, method)
-    ref = rmckf_block.run_closed_loop(inp['features'], inp['q0'][t], inp['desired'], inp['noise'][t], cs.DT, cs.T_MAX, cs.GAIN, inp['x0'][t],
-                                      method=method, kernel_bw=cs.BW, annealing=anneal, initial_guess=inp['guess'],
-                                      fpi_threshold=cs.FPI_THRESHOLD, reg=reg, anneal_span=span)
-    ref['stats'] = rmckf_dense.trial_stats(ref['err'], ref['t'])
-    ref['f'] = ref['err'] + inp['desired']
-    return ref
-
-
-def _agreement(c, block_of, trials):
-    out = {}
-    for t in trials:
-        b = block_of(t)
-        if b['status'] != c['status'][t] or b['k_done'] != c['k_done'][t]:
-            out[t] = np.inf
-            continue
-        k = b['k_done']
-        out[t] = max(cs.rel(c['X'][t, :k], b['X']), cs.rel(c['q'][t, :k], b['q']), cs.rel(c['err'][t, :k], b['err'])) if k else 0.0
-    return out
-
-
-def oracle_agreement(case, name, method):
-    """{sampled trial: worst relative difference of X, q and err between the two oracles (inf when status or k_done differ)}."""
-    return _agreement(c_reference(case, name, method), lambda t: block_reference(case, name, method, t), cs.sampled(case))
-
-
-def kept_trials(case, name, method):
-    gone = set(EXCLUDED.get((case, name, method), ()))
-    return [t for t in range(cs.T) if t not in gone]
+    return dict(method=method, anneal=anneal, reg=REG if default else reg, anneal_span=ANNEAL_SPAN if default else span)
 
 
 def _distance(a, b, kept):
@@ -105,61 +64,8 @@ def _distance(a, b, kept):
 
 def teeth(case, name, method):
     """How far the default-valued oracle run is from the set's on the worst kept trial, relative -- in units of nothing; compare with GATE."""
-    return _distance(c_reference(case, name, method), c_reference(case, name, method, True), kept_trials(case, name, method))
-
-
-# ---------------------------------------------------------------------------------------------- the (32,7) linear plant
-WIDE_T, WIDE_K = 4, 80
-WIDE_T_MAX = cs.DT * (WIDE_K + 0.5)                              # k_max = K on both sides, as in cs
-WIDE_BW = 10.0
-WIDE_CONFIGS = [('R25', 'GMCKF'), ('A25', 'GMCKF'), ('A25', 'IMCCKF'), ('A400', 'GMCKF'), ('A400', 'IMCCKF')]     # no MCKF on the wide kernel
-
-
-@functools.lru_cache(maxsize=None)
-def wide_inputs():
-    """The inputs of test_gpu_parity.py::test_closed_loop_stress_plant at T = 4, K = 80 (its generator, restated)."""
-    J, f0, lin_q0 = cs.linear_plant_arrays(32, 7, 2)
-    rng = np.random.default_rng(5)
-    q_goal = lin_q0 + rng.uniform(-0.3, 0.3, 7)
-    desired = f0 + J @ (q_goal - lin_q0)
-    q0 = q_goal + rng.uniform(-0.15, 0.15, (WIDE_T, 7))
-    noise = rng.standard_t(3, size=(WIDE_T, WIDE_K, 32)) * 0.5
-    x0 = np.tile((J * (1 + 0.1 * rng.normal(size=J.shape))).ravel(), (WIDE_T, 1))
-    d = dict(m=32, n=7, lin=(J, f0, lin_q0), desired=desired, q0=q0, noise=noise, x0=x0, features=lambda q: f0 + J @ (np.asarray(q, float) - lin_q0))
-    for a in (desired, q0, noise, x0):
-        a.setflags(write=False)
-    return d
-
-
-@functools.lru_cache(maxsize=None)
-def wide_c_reference(name, method, default=False):
-    from oracle import c_oracle
-    inp = wide_inputs()
-    anneal, reg, span = estimator(name, method)
-    if default:
-        reg, span = REG, ANNEAL_SPAN
-    return c_oracle.closed_loop_batch(inp['q0'], inp['noise'], inp['desired'], method=method, kernel_bw=WIDE_BW, annealing=anneal, dt=cs.DT,
-                                      t_max=WIDE_T_MAX, gain=cs.GAIN, steps=WIDE_K, want_x=True, plant=c_oracle.linear_plant(*inp['lin']),
-                                      x0=inp['x0'], reg=reg, anneal_span=span)
-
-
-@functools.lru_cache(maxsize=None)
-def wide_block_reference(name, method, t):
-    from oracle import rmckf_block, rmckf_dense
-    inp = wide_inputs()
-    anneal, reg, span = estimator(name, method)
-    ref = rmckf_block.run_closed_loop(inp['features'], inp['q0'][t], inp['desired'], inp['noise'][t], cs.DT, WIDE_T_MAX, cs.GAIN, inp['x0'][t],
-                                      method=method, kernel_bw=WIDE_BW, annealing=anneal, initial_guess=False, reg=reg, anneal_span=span)
-    ref['stats'] = rmckf_dense.trial_stats(ref['err'], ref['t'])
-    return ref
-
-
-def wide_oracle_agreement(name, method):
-    return _agreement(wide_c_reference(name, method), lambda t: wide_block_reference(name, method, t), range(WIDE_T))
-
-
-def wide_teeth(name, method):
-    return _distance(wide_c_reference(name, method), wide_c_reference(name, method, True), range(WIDE_T))
+    return _distance(cs.c_reference(case, **run(name, method)), cs.c_reference(case, **run(name, method, True)),
+                     cs.kept_trials((case, name, method), EXCLUDED))
 
 
 # ---------------------------------------------------------------------------------------------- per-trial reg / fpi_threshold against oracle/c

@@ -3,30 +3,23 @@ the DH / pinhole plant, (8,6) and (6,6) on the linear plant -- every estimator, 
 two-lane kernels and their four- / one-lane relatives on the linear plant, the generic templates, the careful pass alone under
 UVS_OPT_STRICT_PINV), MCKF with a fixed-point loop that iterates.
 
-Inputs and references: tests/closed_shapes_common.py (T = 70, K = 60; oracle/c on every trial, oracle/rmckf_block -- numpy pinv -- on a
+Inputs and references: tests/closed_shapes_common.py, launches and comparisons: tests/gpu_harness.py (T = 70, K = 60; oracle/c on every trial, oracle/rmckf_block -- numpy pinv -- on a
 sample; tests/test_oracle_c.py holds the two to 1e-11 of each other and lists the few (6,6) trials that miss it, which are left out here).
 Gates (test_gpu_fuzz.py, test_closed_loop_stress_plant): status and k_done exact on every trial; err, q, x and stats <= 1e-8 relative,
 per trial.  Every batch carries one trial three times -- in the first, a middle and the last wavefront -- and its three copies must come
 back with identical bits: lane- or wavefront-dependent indexing that a tolerance would hide."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import closed_shapes_common as cs
+import gpu_harness as gh
+from gpu_harness import BLOCK_TRIALS, LATENCY, STRICT, TOL, TOL_MODES
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-8
-TOL_MODES = 1e-9                                             # strict against default mode (test_strict_pinv_agrees_with_the_fast_path_on_healthy_trials)
-STRICT, LATENCY = 1, 2                                       # UVS_OPT_STRICT_PINV, UVS_OPT_LATENCY
 ERR_ARG, ERR_SHAPE = -1, -2
-BLOCK_TRIALS = (0, 14, 28, 42, 56)                           # of cs.sampled(case): compared with the numpy oracle directly as well
 LEFT_OUT = {}                                                # (case, method, annealing, trial, family) -> err deviations on a trial the gates leave out
-WORST = {}                                                   # family -> stream -> worst relative deviation from the oracles so far
-_PLANTS, _LAUNCHES = {}, {}
-STREAMS = ('x', 'err', 'q', 'f', 'dq')                      # the closed loop's per-step outputs, in the header's order
-POISON_INT = -7
+WORST = gh.Worst()                                           # family -> stream -> worst relative deviation from the oracles so far
 
 
 @pytest.fixture(scope='module')
@@ -36,156 +29,23 @@ def uvs():
     import uvs_amd
     uvs_amd.lib()
     yield uvs_amd
-    for family, worst in WORST.items():
-        print(f'closed shapes, {family}: worst relative deviations', {k: f'{v:.1e}' for k, v in worst.items()})
+    WORST.report('closed shapes')
     print('closed shapes: trials left out of the gates (the CPU oracles disagree there):', {k: list(v) for k, v in cs.EXCLUDED.items()})
     for key, devs in LEFT_OUT.items():
         print('closed shapes: left out', key, {k: f'{v:.1e}' for k, v in devs.items()})
 
 
-def _cuda(a):
-    import torch
-    return torch.as_tensor(np.array(a, order='C'), device='cuda')     # a copy: the shared inputs are read-only arrays
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _plant(uvs, case):
-    if case not in _PLANTS:
-        inp = cs.inputs(case)
-        if inp['kind'] == 'dh':
-            plant = uvs.SyntheticPlant.ur10(inp['desired'])
-            assert np.allclose(plant.points, inp['discs'], rtol=0, atol=1e-15)
-        else:
-            plant = uvs.LinearPlant(*inp['lin'])
-        _PLANTS[case] = plant
-    return _PLANTS[case]
-
-
-def _params(uvs, case, method, anneal, lanes=0, reserved=0, steps=cs.K, guess=None, fpi_threshold=cs.FPI_THRESHOLD):
-    inp = cs.inputs(case)
-    fp = uvs.engine.make_params(inp['m'], inp['n'], method, cs.BW, anneal, cs.DT, cs.DT * (steps + 0.5), cs.GAIN, inp['desired'],
-                                inp['guess'] if guess is None else guess, lanes, steps, fpi_threshold, 1000)
-    assert fp.k_max == steps
-    fp.reserved = reserved
-    return fp
-
-
-def _launch(uvs, case, method, anneal, lanes=0, reserved=0, T=cs.T, want=('x', 'err', 'q'), layout='kct', x_layout=None, final_state=False,
-            steps=cs.K, x0=None):
-    """One closed-loop launch on the first T trials of the case; numpy arrays in [trial][step][component] order whatever the layout, plus what
-    the host-side queries say about the launch.  Launches are kept: the same one serves several tests (x0: an override, never kept)."""
-    key = (case, method, anneal, lanes, reserved, T, want, layout, x_layout, final_state, steps)
-    if x0 is None and key in _LAUNCHES:
-        return _LAUNCHES[key]
-    import torch
-    inp = cs.inputs(case)
-    m, n = inp['m'], inp['n']
-    fp = _params(uvs, case, method, anneal, lanes, reserved, steps)
-    ps = _plant(uvs, case).to_struct()
-    noise = inp['noise'][:T, :steps]
-    noise = _cuda(noise.transpose(1, 2, 0) if layout == 'kct' else noise.transpose(1, 0, 2))
-    q0 = _cuda(inp['q0'][:T])
-    start = None if inp['guess'] else _cuda((inp['x0'] if x0 is None else x0)[:T])
-    # Every output is a buffer of this test's, filled with NaN (-7 for the integers) before the launch: what the kernel does not store shows.
-    layouts = {k: (x_layout or layout) if k == 'x' else layout for k in STREAMS}
-    comps = {'x': m * n, 'err': m, 'q': n, 'f': m, 'dq': n}
-    dev = {k: _poisoned(T, steps, comps[k], layouts[k]) if k in want else None for k in STREAMS}
-    dev.update(stats=torch.full((T, 3), float('nan'), dtype=torch.float64, device='cuda'),
-               status=torch.full((T,), POISON_INT, dtype=torch.int32, device='cuda'), k_done=torch.full((T,), POISON_INT, dtype=torch.int32, device='cuda'),
-               x_final=torch.full((T, m * n), float('nan'), dtype=torch.float64, device='cuda') if final_state else None,
-               p_final=torch.full((T, m * n * n), float('nan'), dtype=torch.float64, device='cuda') if final_state else None)
-    flat = lambda t: uvs._lib.NULL_VIEW if t is None else uvs._lib.View(t.data_ptr(), t.stride(0), 0, t.stride(1))      # noqa: E731
-    rc = uvs.engine.launch_closed_loop(fp, ps, T, flat(q0), uvs.engine.stream_view(noise, layout), flat(start),
-                                       *(uvs.engine.stream_view(dev[k], layouts[k]) for k in STREAMS),
-                                       dev['stats'].data_ptr(), dev['status'].data_ptr(), dev['k_done'].data_ptr(), flat(dev['x_final']), flat(dev['p_final']))
-    uvs._lib.check(rc)
-    torch.cuda.synchronize()
-    out = {'lanes': int(uvs.lib().uvs_rmckf_closed_loop_lanes(C.byref(fp), C.byref(ps), T)),
-           'segments': int(uvs.lib().uvs_rmckf_closed_loop_segments(C.byref(fp), C.byref(ps), T)),
-           'workspace': int(uvs.lib().uvs_rmckf_closed_loop_workspace_bytes(C.byref(fp), C.byref(ps), T)),
-           'fallbacks': uvs.engine.hand_over_fallbacks(fp, ps, T)}
-    for k in STREAMS:
-        out[k] = None if dev[k] is None else np.ascontiguousarray(uvs.engine.as_tkc(dev[k], layouts[k]).cpu().numpy())
-    for k in ('stats', 'status', 'k_done', 'x_final', 'p_final'):
-        out[k] = None if dev[k] is None else dev[k].cpu().numpy()
-    _assert_everything_was_stored(out, (case, method, anneal, lanes, reserved, T, want, layout, x_layout))
-    if x0 is None:
-        _LAUNCHES[key] = out
-    return out
-
-
-def _poisoned(T, K, comp, layout):
-    """A [trial][step][component] stream in the physical layout `layout`, every double NaN."""
-    import torch
-    shape = {'kct': (K, comp, T), 'ktc': (K, T, comp), 'tkc': (T, K, comp)}[layout]
-    return torch.full(shape, float('nan'), dtype=torch.float64, device='cuda')
-
-
-def _assert_everything_was_stored(out, tag):
-    """No poison is left in a status, a k_done, a live row of a stream, or the statistics and final state of a trial that succeeded."""
-    assert set(out['status'].tolist()) <= {0, 1} and out['k_done'].min() >= 0, tag
-    ok = out['status'] == 0
-    for key in STREAMS:
-        if out.get(key) is not None:
-            assert not np.isnan(_live(out, key)).any(), (key,) + tuple(tag)
-    for key in ('stats', 'x_final', 'p_final'):
-        if out.get(key) is not None:
-            assert not np.isnan(out[key][ok]).any(), (key,) + tuple(tag)
-
-
-def _live(out, key):
-    """The stream with the rows at and after k_done (unspecified) zeroed."""
-    a = out[key]
-    return np.where(np.arange(a.shape[1])[None, :, None] < out['k_done'][:, None, None], a, 0.0)
-
-
-def _per_trial_rel(a, b):
-    T = len(a)
-    return np.abs(a - b).reshape(T, -1).max(axis=1) / np.maximum(np.abs(b).reshape(T, -1).max(axis=1), 1e-300)
-
-
-def _assert_matches_c(out, case, method, anneal, family, tol=TOL):
+def _matches_c(out, case, method, anneal, family):
     """status and k_done on every trial, the streams the launch wrote and the statistics on the kept ones, against oracle/c."""
-    ref = cs.c_reference(case, method, anneal)
-    T = len(out['status'])
-    tag = (case, method, anneal, family, T)
-    assert np.array_equal(out['status'], ref['status'][:T]) and np.array_equal(out['k_done'], ref['k_done'][:T]), tag
-    kept = [t for t in cs.kept_trials(case, method, anneal) if t < T]
-    live = np.arange(cs.K)[None, :, None] < ref['k_done'][:T, None, None]
-    worst = WORST.setdefault(family, {})
-    for key, rk in (('err', 'err'), ('q', 'q'), ('x', 'X')):
-        if out.get(key) is None:
-            continue
-        d = _per_trial_rel(_live(out, key), np.where(live, ref[rk][:T], 0.0))[kept]
-        worst[key] = max(worst.get(key, 0.0), float(d.max()))
-        assert d.max() <= tol, (key, float(d.max()), kept[int(d.argmax())]) + tag
-    ok = [t for t in kept if ref['status'][t] == 0]
-    d = _per_trial_rel(out['stats'][ok], ref['stats'][ok])
-    worst['stats'] = max(worst.get('stats', 0.0), float(d.max()))
-    assert d.max() <= tol, ('stats', float(d.max())) + tag
+    key = (case, method, anneal)
+    gh.assert_matches_c(out, cs.c_reference(*key), cs.kept_trials(key), WORST, family, key)
 
 
-def _assert_matches_block(out, case, method, anneal, family, trials=BLOCK_TRIALS, tol=TOL):
-    """The same against oracle/rmckf_block (numpy pinv) on a few kept trials; f and p_final too where the launch wrote them."""
-    worst = WORST.setdefault(family, {})
-    for t in trials:
-        if t >= len(out['status']) or t not in cs.kept_trials(case, method, anneal):
-            continue
-        ref = cs.block_reference(case, method, anneal, t)
-        k = ref['k_done']
-        assert out['status'][t] == ref['status'] and out['k_done'][t] == k, (case, method, anneal, family, t)
-        for key, rk in (('err', 'err'), ('q', 'q'), ('x', 'X'), ('f', 'f')):
-            if out.get(key) is None or k == 0:
-                continue
-            d = cs.rel(out[key][t, :k], ref[rk])
-            worst[key + ' (numpy)'] = max(worst.get(key + ' (numpy)', 0.0), d)
-            assert d <= tol, (key, d, case, method, anneal, family, t)
-        if ref['status'] == 0:
-            assert cs.rel(out['stats'][t], ref['stats']) <= tol, (case, method, anneal, family, t)
+def _matches_block(out, case, method, anneal, family, trials=BLOCK_TRIALS):
+    """The same against oracle/rmckf_block (numpy pinv) on a few kept trials; f too where the launch wrote it."""
+    key = (case, method, anneal)
+    trials = [t for t in trials if t < len(out['status']) and t in cs.kept_trials(key)]
+    gh.assert_matches_block(out, lambda t: cs.block_reference(*key, t), trials, WORST, family, key)
 
 
 def _report_left_out(out, case, method, anneal, family):
@@ -197,28 +57,6 @@ def _report_left_out(out, case, method, anneal, family):
         k = blk['k_done']
         LEFT_OUT[(case, method, anneal, t, family)] = {'kernel - oracle/c': cs.rel(out['err'][t, :k], ref['err'][t, :k]), 'kernel - numpy': cs.rel(out['err'][t, :k], blk['err']),
                                                        'oracle/c - numpy': cs.rel(ref['err'][t, :k], blk['err'])}
-
-
-def _assert_twins(out, tag, twins=cs.TWINS):
-    """One trial in the first, a middle and the last wavefront: identical bits in everything the launch wrote."""
-    first = twins[0]
-    for t in twins[1:]:
-        for key in ('x', 'err', 'q', 'f', 'dq'):
-            if out.get(key) is not None:
-                assert _same_bits(_live(out, key)[t], _live(out, key)[first]), (key, t) + tuple(tag)
-        for key in ('stats', 'status', 'k_done', 'x_final', 'p_final'):
-            if out.get(key) is not None:
-                assert _same_bits(out[key][t], out[key][first]), (key, t) + tuple(tag)
-
-
-def _assert_same_launch(a, b, tag, keys=('x', 'err', 'q', 'f', 'dq', 'stats', 'status', 'k_done', 'x_final', 'p_final'), trials=None):
-    """Two launches wrote the same bits (of the first len(b) trials, or of `trials`)."""
-    sel = slice(0, len(b['status'])) if trials is None else trials
-    for key in keys:
-        if a.get(key) is None or b.get(key) is None:
-            continue
-        x, y = (_live(o, key) if key in ('x', 'err', 'q', 'f', 'dq') else o[key] for o in (a, b))
-        assert _same_bits(x[sel], y[sel]), (key,) + tuple(tag)
 
 
 ESTIMATORS = [(method, anneal) for method in cs.METHODS for anneal in (False, True)]
@@ -234,17 +72,17 @@ def test_dh66_every_lane_mapping_matches_the_oracles(uvs, case, method, anneal):
     outs = {}
     for lanes in (0, 2, 1, -1, -2):
         family = f'(6,6) DH {"tuned" if lanes in (0, 2) else "generic L" + str(abs(lanes))}'
-        out = outs[lanes] = _launch(uvs, case, method, anneal, lanes)
+        out = outs[lanes] = gh.launch(uvs, case, method, anneal, lanes)
         assert out['lanes'] == (abs(lanes) or 2) and out['segments'] == 1
-        _assert_matches_c(out, case, method, anneal, family)
-        _assert_twins(out, (case, method, anneal, lanes))
+        _matches_c(out, case, method, anneal, family)
+        gh.assert_twins(out, (case, method, anneal, lanes))
         if lanes in (0, -1, -2):
             _report_left_out(out, case, method, anneal, family)
-    _assert_matches_block(outs[0], case, method, anneal, '(6,6) DH tuned')
-    _assert_matches_block(outs[-1], case, method, anneal, '(6,6) DH generic L1')
-    _assert_matches_block(outs[-2], case, method, anneal, '(6,6) DH generic L2')
-    _assert_same_launch(outs[0], outs[2], (case, method, anneal, '0 = 2'))
-    _assert_same_launch(outs[1], outs[-1], (case, method, anneal, '1 = -1'))
+    _matches_block(outs[0], case, method, anneal, '(6,6) DH tuned')
+    _matches_block(outs[-1], case, method, anneal, '(6,6) DH generic L1')
+    _matches_block(outs[-2], case, method, anneal, '(6,6) DH generic L2')
+    gh.assert_same_launch(outs[0], outs[2], (case, method, anneal, '0 = 2'))
+    gh.assert_same_launch(outs[1], outs[-1], (case, method, anneal, '1 = -1'))
 
 
 @pytest.mark.parametrize('method', cs.METHODS)
@@ -253,23 +91,23 @@ def test_dh66_batches_of_1_and_33_are_slices_of_the_batch_of_70(uvs, method):
     kernel, the two generic templates and the careful pass alone.  A trial does not depend on its batch: the bits of the first T trials of the
     T = 70 launch (which the oracles hold)."""
     for lanes, reserved in ((0, 0), (-1, 0), (-2, 0), (0, STRICT)):
-        whole = _launch(uvs, 'dh66', method, True, lanes, reserved)
+        whole = gh.launch(uvs, 'dh66', method, True, lanes, reserved)
         for T in (1, 33):
-            part = _launch(uvs, 'dh66', method, True, lanes, reserved, T=T)
+            part = gh.launch(uvs, 'dh66', method, True, lanes, reserved, T=T)
             assert not np.isnan(part['stats']).any()
-            _assert_same_launch(whole, part, (method, lanes, reserved, T))
-            _assert_matches_c(part, 'dh66', method, True, f'(6,6) DH T = {T}')
+            gh.assert_same_launch(whole, part, (method, lanes, reserved, T))
+            _matches_c(part, 'dh66', method, True, f'(6,6) DH T = {T}')
 
 
 @pytest.mark.parametrize('method', cs.METHODS)
 def test_dh66_without_the_x_stream(uvs, method):
     """want without 'x': the XOUT = false instantiations.  err, q and the statistics inside the gates, and the bits of the launch that logs X."""
     for lanes in (0, -2):
-        out = _launch(uvs, 'dh66', method, True, lanes, want=('err', 'q'))
+        out = gh.launch(uvs, 'dh66', method, True, lanes, want=('err', 'q'))
         assert out['x'] is None
-        _assert_matches_c(out, 'dh66', method, True, '(6,6) DH no X stream')
-        _assert_twins(out, (method, lanes))
-        _assert_same_launch(_launch(uvs, 'dh66', method, True, lanes), out, (method, lanes, 'XOUT'))
+        _matches_c(out, 'dh66', method, True, '(6,6) DH no X stream')
+        gh.assert_twins(out, (method, lanes))
+        gh.assert_same_launch(gh.launch(uvs, 'dh66', method, True, lanes), out, (method, lanes, 'XOUT'))
 
 
 @pytest.mark.parametrize('method', cs.METHODS)
@@ -279,26 +117,26 @@ def test_dh66_all_five_streams_and_the_final_state(uvs, method, lanes):
     numpy oracle's P (1e-10, the gate of test_replay_other_shapes_match_block_oracle)."""
     case, anneal = 'dh66', True
     inp = cs.inputs(case)
-    out = _launch(uvs, case, method, anneal, lanes, want=('x', 'err', 'q', 'f', 'dq'), final_state=True)
+    out = gh.launch(uvs, case, method, anneal, lanes, want=('x', 'err', 'q', 'f', 'dq'), final_state=True)
     family = '(6,6) DH five streams'
-    _assert_matches_c(out, case, method, anneal, family)
-    _assert_twins(out, (method, lanes))
-    _assert_same_launch(_launch(uvs, case, method, anneal, lanes), out, (method, lanes, 'three streams = five'), keys=('x', 'err', 'q', 'stats', 'status', 'k_done'))
+    _matches_c(out, case, method, anneal, family)
+    gh.assert_twins(out, (method, lanes))
+    gh.assert_same_launch(gh.launch(uvs, case, method, anneal, lanes), out, (method, lanes, 'three streams = five'), keys=('x', 'err', 'q', 'stats', 'status', 'k_done'))
     trials = cs.sampled(case)[::7]
-    _assert_matches_block(out, case, method, anneal, family, trials)
+    _matches_block(out, case, method, anneal, family, trials)
     assert not out['status'].any()
-    assert _same_bits(out['f'] - inp['desired'], out['err'])                               # one subtraction
+    assert gh.same_bits(out['f'] - inp['desired'], out['err'])                               # one subtraction
     # q[k + 1] = q[k] + dq[k] dt: the difference quotient returns dq[k] up to the cancellation, 2 eps max|q| / dt = 2e-14 absolute
     quotient = (out['q'][:, 1:] - out['q'][:, :-1]) / cs.DT
-    d = float((_per_trial_rel(out['dq'][:, :-1], quotient)).max())
-    WORST[family]['dq (difference of q)'] = max(WORST[family].get('dq (difference of q)', 0.0), d)
+    d = float((gh.per_trial_rel(out['dq'][:, :-1], quotient)).max())
+    WORST.note(family, 'dq (difference of q)', d)
     assert d <= TOL and np.abs(out['dq']).max() > 1e-3
-    assert _same_bits(out['x_final'], out['x'][:, -1])
+    assert gh.same_bits(out['x_final'], out['x'][:, -1])
     P = out['p_final'].reshape(cs.T, inp['m'], inp['n'], inp['n'])
     assert np.abs(P - P.transpose(0, 1, 3, 2)).max() <= 1e-14 * np.abs(P).max()
     for t in trials:
         d = cs.rel(P[t], cs.block_reference(case, method, anneal, t)['P_final'])
-        WORST[family]['p_final (numpy)'] = max(WORST[family].get('p_final (numpy)', 0.0), d)
+        WORST.note(family, 'p_final (numpy)', d)
         assert d <= 1e-10, (d, t)
 
 
@@ -306,9 +144,9 @@ def test_dh66_all_five_streams_and_the_final_state(uvs, method, lanes):
 def test_dh66_record_layouts_give_the_same_bits(uvs, method):
     """Streams as [step][trial][component] (noise too) and X as per-trial records: other strides, the same bits as the trial-fastest default."""
     for lanes in (0, -1):
-        ref = _launch(uvs, 'dh66', method, True, lanes)
-        _assert_same_launch(ref, _launch(uvs, 'dh66', method, True, lanes, layout='ktc'), (method, lanes, 'ktc'))
-        _assert_same_launch(ref, _launch(uvs, 'dh66', method, True, lanes, x_layout='tkc'), (method, lanes, 'x tkc'))
+        ref = gh.launch(uvs, 'dh66', method, True, lanes)
+        gh.assert_same_launch(ref, gh.launch(uvs, 'dh66', method, True, lanes, layout='ktc'), (method, lanes, 'ktc'))
+        gh.assert_same_launch(ref, gh.launch(uvs, 'dh66', method, True, lanes, x_layout='tkc'), (method, lanes, 'x tkc'))
 
 
 @pytest.mark.parametrize('anneal', [False, True])
@@ -316,47 +154,47 @@ def test_dh66_mckf_in_four_segments_is_bit_identical_to_whole_trials(uvs, anneal
     """fp.reserved = 4 << 8 with K = 60 >= 32: the two-lane MCKF kernel runs every trial as four work items whose state crosses through the
     workspace.  The same bits as whole trials, and no work item fell back to recomputing its trial."""
     for case in ('dh66', 'dh66_x0'):
-        whole = _launch(uvs, case, 'MCKF', anneal, 0, want=('x', 'err', 'q', 'f', 'dq'), final_state=True)
+        whole = gh.launch(uvs, case, 'MCKF', anneal, 0, want=('x', 'err', 'q', 'f', 'dq'), final_state=True)
         assert whole['segments'] == 1 and whole['workspace'] == 0 and whole['fallbacks'] is None
         for lanes in (0, 2):
-            cut = _launch(uvs, case, 'MCKF', anneal, lanes, reserved=4 << 8, want=('x', 'err', 'q', 'f', 'dq'), final_state=True)
+            cut = gh.launch(uvs, case, 'MCKF', anneal, lanes, reserved=4 << 8, want=('x', 'err', 'q', 'f', 'dq'), final_state=True)
             assert cut['segments'] == 4 and cut['workspace'] > 0 and cut['fallbacks'] == 0
             ok = np.flatnonzero(whole['status'] == 0)
-            _assert_same_launch(whole, cut, (case, anneal, lanes, 'segments'), keys=('x', 'err', 'q', 'f', 'dq', 'status', 'k_done'))
-            _assert_same_launch(whole, cut, (case, anneal, lanes, 'segments, final'), keys=('stats', 'x_final', 'p_final'), trials=ok)
-            _assert_matches_c(cut, case, 'MCKF', anneal, '(6,6) DH MCKF in 4 segments')
+            gh.assert_same_launch(whole, cut, (case, anneal, lanes, 'segments'), keys=('x', 'err', 'q', 'f', 'dq', 'status', 'k_done'))
+            gh.assert_same_launch(whole, cut, (case, anneal, lanes, 'segments, final'), keys=('stats', 'x_final', 'p_final'), trials=ok)
+            _matches_c(cut, case, 'MCKF', anneal, '(6,6) DH MCKF in 4 segments')
         for T in (1, 33):                                                                   # one chunk; one full chunk and one of a single trial
-            part = _launch(uvs, case, 'MCKF', anneal, 0, reserved=4 << 8, T=T)
+            part = gh.launch(uvs, case, 'MCKF', anneal, 0, reserved=4 << 8, T=T)
             assert part['segments'] == 4 and part['fallbacks'] == 0
-            _assert_same_launch(_launch(uvs, case, 'MCKF', anneal, 0), part, (case, anneal, T, 'segments, slice'))
+            gh.assert_same_launch(gh.launch(uvs, case, 'MCKF', anneal, 0), part, (case, anneal, T, 'segments, slice'))
 
 
 def _assert_strict(uvs, case, method, anneal, family, lanes=0):
     """UVS_OPT_STRICT_PINV at `lanes` (RMCKF on a tuned kernel: certified first pass; otherwise the careful kernel alone): inside the oracle
     gates, within 1e-9 of the default mode on the kept trials, and -- where the careful kernel is the only pass -- the bits of the same
     request through the generic lane mapping, which plans the same careful kernel."""
-    fast, strict = _launch(uvs, case, method, anneal, lanes), _launch(uvs, case, method, anneal, lanes, STRICT)
+    fast, strict = gh.launch(uvs, case, method, anneal, lanes), gh.launch(uvs, case, method, anneal, lanes, STRICT)
     assert strict['lanes'] == fast['lanes'] and strict['segments'] == 1
-    _assert_matches_c(strict, case, method, anneal, family)
-    _assert_matches_block(strict, case, method, anneal, family)
-    _assert_twins(strict, (case, method, anneal, 'strict'))
+    _matches_c(strict, case, method, anneal, family)
+    _matches_block(strict, case, method, anneal, family)
+    gh.assert_twins(strict, (case, method, anneal, 'strict'))
     assert np.array_equal(strict['status'], fast['status']) and np.array_equal(strict['k_done'], fast['k_done'])
-    kept = cs.kept_trials(case, method, anneal)
+    kept = cs.kept_trials((case, method, anneal))
     for key in ('err', 'q'):
-        assert cs.rel(_live(strict, key)[kept], _live(fast, key)[kept]) <= TOL_MODES, (key, case, method, anneal)
+        assert cs.rel(gh.live(strict, key)[kept], gh.live(fast, key)[kept]) <= TOL_MODES, (key, case, method, anneal)
     m, n = cs.inputs(case)['m'], cs.inputs(case)['n']
     generic = -max(abs(lanes), {(6, 6): 2, (2, 6): 1, (8, 6): 2}[(m, n)])
-    careful = _launch(uvs, case, method, anneal, generic, STRICT)
+    careful = gh.launch(uvs, case, method, anneal, generic, STRICT)
     if method == 'GMCKF' and (m, n) != (2, 6):
         # The certified first pass is the default mode's arithmetic plus a certificate: on trials it does not mark it writes the default
         # mode's bits (test_strict_pinv_audit_at_full_size), which the careful kernel alone -- another solve -- does not.  So equal bits on the
         # kept trials say that the plan did take the certified tuned pass and not kCarefulOnly.
-        _assert_same_launch(fast, strict, (case, method, anneal, lanes, 'certified pass = default bits'), trials=kept)
-        assert not _same_bits(_live(careful, 'x')[kept], _live(strict, 'x')[kept]), (case, anneal, lanes, 'the careful pass alone would have other bits')
+        gh.assert_same_launch(fast, strict, (case, method, anneal, lanes, 'certified pass = default bits'), trials=kept)
+        assert not gh.same_bits(gh.live(careful, 'x')[kept], gh.live(strict, 'x')[kept]), (case, anneal, lanes, 'the careful pass alone would have other bits')
         for key in ('err', 'q'):
-            assert cs.rel(_live(strict, key)[kept], _live(careful, key)[kept]) <= TOL_MODES, (key, case, method, anneal)
+            assert cs.rel(gh.live(strict, key)[kept], gh.live(careful, key)[kept]) <= TOL_MODES, (key, case, method, anneal)
     else:
-        _assert_same_launch(careful, strict, (case, method, anneal, 'careful alone'))
+        gh.assert_same_launch(careful, strict, (case, method, anneal, 'careful alone'))
 
 
 @pytest.mark.parametrize('method,anneal', ESTIMATORS)
@@ -373,19 +211,19 @@ def test_dh26_matches_the_oracles(uvs, method, anneal):
     case = 'dh26'
     outs = {}
     for lanes in (0, 1, -1):
-        out = outs[lanes] = _launch(uvs, case, method, anneal, lanes)
+        out = outs[lanes] = gh.launch(uvs, case, method, anneal, lanes)
         assert out['lanes'] == 1 and out['segments'] == 1
-        _assert_matches_c(out, case, method, anneal, '(2,6) DH generic')
-        _assert_twins(out, (case, method, anneal, lanes))
-    _assert_matches_block(outs[0], case, method, anneal, '(2,6) DH generic')
-    _assert_same_launch(outs[0], outs[1], (method, anneal, '0 = 1'))
-    _assert_same_launch(outs[0], outs[-1], (method, anneal, '0 = -1'))
+        _matches_c(out, case, method, anneal, '(2,6) DH generic')
+        gh.assert_twins(out, (case, method, anneal, lanes))
+    _matches_block(outs[0], case, method, anneal, '(2,6) DH generic')
+    gh.assert_same_launch(outs[0], outs[1], (method, anneal, '0 = 1'))
+    gh.assert_same_launch(outs[0], outs[-1], (method, anneal, '0 = -1'))
     _assert_strict(uvs, case, method, anneal, '(2,6) DH strict pinv')
     if anneal:
         for reserved in (0, STRICT):
             for T in (1, 33):
-                part = _launch(uvs, case, method, anneal, 0, reserved, T=T)
-                _assert_same_launch(_launch(uvs, case, method, anneal, 0, reserved), part, (method, reserved, T))
+                part = gh.launch(uvs, case, method, anneal, 0, reserved, T=T)
+                gh.assert_same_launch(gh.launch(uvs, case, method, anneal, 0, reserved), part, (method, reserved, T))
 
 
 # ---------------------------------------------------------------------------------------------- c. the linear plant at (8,6) and (6,6)
@@ -402,37 +240,37 @@ def test_linear_plant_every_lane_mapping_matches_the_oracles(uvs, case, method, 
     for lanes in LINEAR_LANES[case]:
         tuned = lanes >= 0 and (method != 'MCKF' or lanes in (0, 2))
         family = f'{"(8,6)" if case == "lin86" else "(6,6)"} linear {"tuned" if tuned else "generic"} L{abs(lanes) or 2}'
-        out = outs[lanes] = _launch(uvs, case, method, anneal, lanes)
+        out = outs[lanes] = gh.launch(uvs, case, method, anneal, lanes)
         assert out['lanes'] == (abs(lanes) or 2) and out['segments'] == 1 and out['workspace'] == 0
-        _assert_matches_c(out, case, method, anneal, family)
-        _assert_twins(out, (case, method, anneal, lanes))
+        _matches_c(out, case, method, anneal, family)
+        gh.assert_twins(out, (case, method, anneal, lanes))
         if lanes in (0, 1, 4, -2):
-            _assert_matches_block(out, case, method, anneal, family)
-    _assert_same_launch(outs[0], outs[2], (case, method, anneal, '0 = 2'))
+            _matches_block(out, case, method, anneal, family)
+    gh.assert_same_launch(outs[0], outs[2], (case, method, anneal, '0 = 2'))
 
 
 @pytest.mark.parametrize('method', cs.METHODS)
 def test_linear_plant_batches_of_1_and_33_are_slices_of_the_batch_of_70(uvs, method):
     for case, lanes in (('lin86', 0), ('lin86', 1), ('lin86', 4), ('lin86', -4), ('lin66', 0), ('lin66', -2)):
-        whole = _launch(uvs, case, method, True, lanes)
+        whole = gh.launch(uvs, case, method, True, lanes)
         for T in (1, 33):
-            part = _launch(uvs, case, method, True, lanes, T=T)
-            _assert_same_launch(whole, part, (case, method, lanes, T))
-            _assert_matches_c(part, case, method, True, f'linear T = {T}')
+            part = gh.launch(uvs, case, method, True, lanes, T=T)
+            gh.assert_same_launch(whole, part, (case, method, lanes, T))
+            _matches_c(part, case, method, True, f'linear T = {T}')
 
 
 @pytest.mark.parametrize('method,anneal', ESTIMATORS)
 def test_linear_plant_latency_option(uvs, method, anneal):
     """UVS_OPT_LATENCY at lanes_per_filter 0: the four-lane linear kernel for KF, IMCC-KF and RMCKF -- the bits of lanes_per_filter 4 --, MCKF
     stays on two lanes.  At (6,6) the option selects nothing."""
-    out = _launch(uvs, 'lin86', method, anneal, 0, LATENCY)
+    out = gh.launch(uvs, 'lin86', method, anneal, 0, LATENCY)
     assert out['lanes'] == (2 if method == 'MCKF' else 4)
-    _assert_matches_c(out, 'lin86', method, anneal, '(8,6) linear UVS_OPT_LATENCY')
-    _assert_twins(out, (method, anneal, 'latency'))
-    _assert_same_launch(_launch(uvs, 'lin86', method, anneal, 2 if method == 'MCKF' else 4), out, (method, anneal, 'latency = forced lanes'))
-    small = _launch(uvs, 'lin66', method, anneal, 0, LATENCY)
+    _matches_c(out, 'lin86', method, anneal, '(8,6) linear UVS_OPT_LATENCY')
+    gh.assert_twins(out, (method, anneal, 'latency'))
+    gh.assert_same_launch(gh.launch(uvs, 'lin86', method, anneal, 2 if method == 'MCKF' else 4), out, (method, anneal, 'latency = forced lanes'))
+    small = gh.launch(uvs, 'lin66', method, anneal, 0, LATENCY)
     assert small['lanes'] == 2
-    _assert_same_launch(_launch(uvs, 'lin66', method, anneal, 0), small, (method, anneal, 'latency at (6,6)'))
+    gh.assert_same_launch(gh.launch(uvs, 'lin66', method, anneal, 0), small, (method, anneal, 'latency at (6,6)'))
 
 
 @pytest.mark.parametrize('method,anneal', ESTIMATORS)
@@ -448,9 +286,9 @@ def test_linear_plant_strict_pinv(uvs, case, method, anneal):
 @pytest.mark.parametrize('case', ['lin86', 'lin66'])
 def test_linear_plant_refuses_the_analytic_initial_guess(uvs, case):
     inp = cs.inputs(case)
-    fp = _params(uvs, case, 'GMCKF', False, guess=True)
+    fp = gh.params(uvs, case, 'GMCKF', False, guess=True)
     with pytest.raises(uvs._lib.UvsError) as exc:
-        uvs.engine.closed_loop(fp, _plant(uvs, case).to_struct(), _cuda(inp['q0']), _cuda(inp['noise'].transpose(1, 2, 0)), _cuda(inp['x0']))
+        uvs.engine.closed_loop(fp, gh.plant(uvs, case).to_struct(), gh.cuda(inp['q0']), gh.cuda(inp['noise'].transpose(1, 2, 0)), gh.cuda(inp['x0']))
     assert exc.value.code == ERR_ARG and len(uvs.lib().uvs_last_error()) > 0
 
 
@@ -460,10 +298,10 @@ def test_linear_plant_mckf_ignores_a_forced_segment_count(uvs, case, anneal):
     """The linear-plant instantiations compile the hand-over code out (SEG), so a forced segment count must not reach them: the query says
     whole trials, no workspace is asked for, the launch runs whole trials on the two-lane kernel -- the bits of the unforced launch."""
     for lanes in (0, 2):
-        cut = _launch(uvs, case, 'MCKF', anneal, lanes, reserved=4 << 8)
+        cut = gh.launch(uvs, case, 'MCKF', anneal, lanes, reserved=4 << 8)
         assert cut['segments'] == 1 and cut['workspace'] == 0 and cut['fallbacks'] is None and cut['lanes'] == 2
-        _assert_matches_c(cut, case, 'MCKF', anneal, 'linear MCKF, segments forced')
-        _assert_same_launch(_launch(uvs, case, 'MCKF', anneal, 2), cut, (case, anneal, lanes, 'forced segments'))
+        _matches_c(cut, case, 'MCKF', anneal, 'linear MCKF, segments forced')
+        gh.assert_same_launch(gh.launch(uvs, case, 'MCKF', anneal, 2), cut, (case, anneal, lanes, 'forced segments'))
 
 
 # ---------------------------------------------------------------------------------------------- d. a rank-deficient Jacobian among healthy neighbours
@@ -487,13 +325,12 @@ def test_a_rank_deficient_x0_among_healthy_neighbours(uvs, case, lanes):
     sv = np.linalg.svd(x, compute_uv=False)
     assert sv[-1] <= 1e-16 * sv[0] and sv[-2] > 1e-4 * sv[0], 'the input: rank n - 1, a decade under the cutoff'
     want = ('x', 'err', 'q', 'dq')
-    mixed = _launch(uvs, case, 'GMCKF', True, lanes, want=want, steps=RANKDEF_K, x0=x0)
-    healthy = _launch(uvs, case, 'GMCKF', True, lanes, want=want, steps=RANKDEF_K)
+    mixed = gh.launch(uvs, case, 'GMCKF', True, lanes, want=want, steps=RANKDEF_K, x0=x0)
+    healthy = gh.launch(uvs, case, 'GMCKF', True, lanes, want=want, steps=RANKDEF_K)
     assert not mixed['status'].any() and np.all(mixed['k_done'] == RANKDEF_K)
     others = [t for t in range(cs.T) if t != SICK]
-    _assert_same_launch(healthy, mixed, (case, lanes, 'neighbours'), trials=others)
-    _assert_twins(mixed, (case, lanes, 'rank-deficient batch'))
-    worst = WORST.setdefault('rank-deficient X0', {})
+    gh.assert_same_launch(healthy, mixed, (case, lanes, 'neighbours'), trials=others)
+    gh.assert_twins(mixed, (case, lanes, 'rank-deficient batch'))
     for t in (0, SICK - 1, SICK, SICK + 1, 47, cs.T - 1):
         ref = rmckf_block.run_closed_loop(inp['features'], inp['q0'][t], inp['desired'], inp['noise'][t, :RANKDEF_K], cs.DT, cs.DT * (RANKDEF_K + 0.5),
                                           cs.GAIN, x0[t], method='GMCKF', kernel_bw=cs.BW, annealing=True, initial_guess=False)
@@ -501,13 +338,12 @@ def test_a_rank_deficient_x0_among_healthy_neighbours(uvs, case, lanes):
         tol = 1e-6 if t == SICK else TOL
         for key, rk in (('err', 'err'), ('q', 'q'), ('x', 'X')):
             d = cs.rel(mixed[key][t], ref[rk])
-            name = key + (' (sick)' if t == SICK else ' (healthy)')
-            worst[name] = max(worst.get(name, 0.0), d)
+            WORST.note('rank-deficient X0', key + (' (sick)' if t == SICK else ' (healthy)'), d)
             assert d <= tol, (key, d, t, case, lanes)
     filt = rmckf_block.BlockFilter(m, n, x0[SICK], 'GMCKF', cs.BW, True, RANKDEF_K)
     f_first = inp['features'](inp['q0'][SICK]) + inp['noise'][SICK, 0]
     kappa = filt.step(f_first, np.zeros(n), 0)                                              # a supplied X0: the first f_old is 0
-    assert _same_bits(filt.X, x)
+    assert gh.same_bits(filt.X, x)
     first = rmckf_block.control_law(filt.X, f_first - inp['desired'], kappa, cs.GAIN)
     assert np.abs(first).max() > 1e-3                                                       # a command of a size the gate means something for
     assert np.abs(mixed['dq'][SICK, 0] - first).max() <= 1e-8 * max(1e-3, np.abs(first).max())
@@ -519,18 +355,9 @@ _REPLAY = {}
 
 
 def _replay_case():
-    """The streams of test_replay_other_shapes_match_block_oracle at (6,6), K = 40, T = 35 (its generator, restated), trial 1 in three places."""
+    """The streams of test_replay_other_shapes_match_block_oracle at (6,6), K = 40, T = 35, trial 1 in three places."""
     if 'case' not in _REPLAY:
-        m, n, K, T = 6, 6, REPLAY_K, REPLAY_T
-        rng = np.random.default_rng(1000 + m)
-        J = rng.normal(size=(T, m, n)) * 20
-        dq = rng.normal(size=(T, K, n)) * 0.3
-        f = np.zeros((T, K + 1, m))
-        f[:, 0] = rng.uniform(60, 200, (T, m))
-        for k in range(K):
-            f[:, k + 1] = f[:, k] + np.einsum('tmn,tn->tm', J, dq[:, k]) * 0.05 + rng.standard_t(2, size=(T, m))
-        x0 = (J + rng.normal(size=J.shape)).reshape(T, m * n)
-        des = rng.uniform(80, 180, m)
+        f, dq, x0, des = gh.random_replay_case(6, 6, REPLAY_K, REPLAY_T, 1006)
         for a in (f, dq, x0):
             a[list(REPLAY_TWINS[1:])] = a[REPLAY_TWINS[0]]
         _REPLAY['case'] = (f, dq, x0, des)
@@ -545,33 +372,11 @@ def _replay_reference(method, t, fpi_threshold=cs.FPI_THRESHOLD):
     return _REPLAY[(method, t, fpi_threshold)]
 
 
-def _replay(uvs, method, lanes, want, layout='kct', T=REPLAY_T, fpi_threshold=cs.FPI_THRESHOLD):
-    """uvs_rmckf_replay_f64 on the first T trials, into buffers of this test's that are filled with NaN (-7 for the integers) before the launch:
-    a store the kernel leaves out shows.  numpy arrays in [trial][step][component] order."""
-    import torch
+def _tuned_replay(uvs, method, lanes, want, layout='kct', T=REPLAY_T, fpi_threshold=cs.FPI_THRESHOLD):
+    """gh.replay on the first T trials; numpy arrays in [trial][step][component] order."""
     f, dq, x0, des = _replay_case()
-    m, n, K = 6, 6, REPLAY_K
-    fp = uvs.engine.make_params(m, n, method, 7.5, True, 0.05, 15, 0.2, des, False, lanes, K, fpi_threshold, 1000)
-    order = (1, 2, 0) if layout == 'kct' else (1, 0, 2)
-    f_dev, dq_dev, x0_dev = _cuda(f[:T].transpose(order)), _cuda(dq[:T].transpose(order)), _cuda(x0[:T])
-    comps = {'x': m * n, 'err': m, 'kappa': m, 'dqcmd': n}
-    dev = {k: _poisoned(T, K, comps[k], layout) if k in want else None for k in comps}
-    dev.update(status=torch.full((T,), POISON_INT, dtype=torch.int32, device='cuda'), k_done=torch.full((T,), POISON_INT, dtype=torch.int32, device='cuda'),
-               x_final=torch.full((T, m * n), float('nan'), dtype=torch.float64, device='cuda'),
-               p_final=torch.full((T, m * n * n), float('nan'), dtype=torch.float64, device='cuda'))
-    flat = lambda t: uvs._lib.View(t.data_ptr(), t.stride(0), 0, t.stride(1))                # noqa: E731
-    view = uvs.engine.stream_view
-    rc = uvs.lib().uvs_rmckf_replay_f64(C.byref(fp), T, view(f_dev, layout), view(dq_dev, layout), flat(x0_dev), *(view(dev[k], layout) for k in comps),
-                                        dev['status'].data_ptr(), dev['k_done'].data_ptr(), flat(dev['x_final']), flat(dev['p_final']),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    uvs._lib.check(rc)
-    torch.cuda.synchronize()
-    out = {k: None if dev[k] is None else np.ascontiguousarray(uvs.engine.as_tkc(dev[k], layout).cpu().numpy()) for k in comps}
-    out.update({k: dev[k].cpu().numpy() for k in ('status', 'k_done', 'x_final', 'p_final')})
-    for k, v in out.items():
-        if v is not None:
-            assert not (np.isnan(v).any() if v.dtype.kind == 'f' else (v == POISON_INT).any()), (k, 'not stored', method, lanes, want, layout, T)
-    return out
+    fp = uvs.engine.make_params(6, 6, method, 7.5, True, 0.05, 15, 0.2, des, False, lanes, REPLAY_K, fpi_threshold, 1000)
+    return gh.replay(uvs, fp, f[:T], dq[:T], x0[:T], want, layout)
 
 
 REPLAY_KEYS = ('x', 'err', 'kappa', 'dqcmd', 'status', 'k_done', 'x_final', 'p_final')
@@ -588,47 +393,38 @@ def test_tuned_replay_at_66_matches_the_block_oracle(uvs, method):
     refs = [_replay_reference(method, t) for t in range(REPLAY_T)]
     if method == 'MCKF':
         assert max(r['fpi_iterations'].max() for r in refs) >= 3
-    worst = WORST.setdefault('(6,6) tuned replay', {})
     full, alone = ('x', 'err', 'kappa', 'dqcmd'), ('x', 'err', 'kappa')
     outs = {}
     for lanes in (0, 2, -2):
         for want in (full, alone, ('err',)):
-            out = outs[(lanes, want)] = _replay(uvs, method, lanes, want)
+            out = outs[(lanes, want)] = _tuned_replay(uvs, method, lanes, want)
             tag = (method, lanes, want)
             assert not out['status'].any() and np.all(out['k_done'] == REPLAY_K), tag
             assert [k for k in full if out[k] is not None] == list(want), tag
-            assert _same_bits(out['err'], f[:, 1:] - des), tag
+            assert gh.same_bits(out['err'], f[:, 1:] - des), tag
             for key in REPLAY_KEYS:
                 if out[key] is not None:
                     for t in REPLAY_TWINS[1:]:
-                        assert _same_bits(out[key][t], out[key][REPLAY_TWINS[0]]), (key, t) + tag
-            for t, ref in enumerate(refs):
-                checks = [('p_final', out['p_final'][t].reshape(6, 6, 6), ref['P_final'], 1e-10), ('x_final', out['x_final'][t], ref['X'][-1], 1e-10)]
-                if 'x' in want:
-                    checks += [('x', out['x'][t], ref['X'], 1e-10), ('kappa', out['kappa'][t], ref['kappa'], 1e-9)]
-                    assert _same_bits(out['x_final'][t], out['x'][t, -1]), (t,) + tag
-                if 'dqcmd' in want:
-                    checks.append(('dqcmd', out['dqcmd'][t], ref['dq_cmd'], 1e-8))
-                for key, a, b, tol in checks:
-                    d = cs.rel(a, b)
-                    worst[key] = max(worst.get(key, 0.0), d)
-                    assert d <= tol, (key, d, t) + tag
+                        assert gh.same_bits(out[key][t], out[key][REPLAY_TWINS[0]]), (key, t) + tag
+            gh.assert_replay(out, refs, WORST, '(6,6) tuned replay', tag)
+            if 'x' in want:
+                assert gh.same_bits(out['x_final'], out['x'][:, -1]), tag
     for want in (full, alone, ('err',)):
         for key in REPLAY_KEYS:
             if outs[(0, want)][key] is not None:
-                assert _same_bits(outs[(0, want)][key], outs[(2, want)][key]), (key, method, want, '0 = 2')
+                assert gh.same_bits(outs[(0, want)][key], outs[(2, want)][key]), (key, method, want, '0 = 2')
     for lanes in (0, 2):
         for want in (full, alone):
-            records = _replay(uvs, method, lanes, want, layout='ktc')
+            records = _tuned_replay(uvs, method, lanes, want, layout='ktc')
             for key in REPLAY_KEYS:
                 if records[key] is not None:
-                    assert _same_bits(records[key], outs[(lanes, want)][key]), (key, method, lanes, want, 'ktc')
+                    assert gh.same_bits(records[key], outs[(lanes, want)][key]), (key, method, lanes, want, 'ktc')
     for want in (full, alone):                                                              # T = 1 and T = 33: slices of the batch of 35
         for T in (1, 33):
-            part = _replay(uvs, method, 0, want, T=T)
+            part = _tuned_replay(uvs, method, 0, want, T=T)
             for key in REPLAY_KEYS:
                 if part[key] is not None:
-                    assert _same_bits(part[key], outs[(0, want)][key][:T]), (key, method, want, T)
+                    assert gh.same_bits(part[key], outs[(0, want)][key][:T]), (key, method, want, T)
     if method == 'MCKF':
         # With fpi_threshold 1e-4 every trial needs more than the first fixed-point pass, so the careful second pass re-runs it and what the
         # tuned kernel stored is overwritten.  At the reference's 0.1 the first pass is the whole story (the oracle: two iterations, the second
@@ -637,13 +433,6 @@ def test_tuned_replay_at_66_matches_the_block_oracle(uvs, method):
         assert max(r['fpi_iterations'].max() for r in loose) == 2
         for lanes in (0, 2):
             for want in (full, alone):
-                out = _replay(uvs, method, lanes, want, fpi_threshold=0.1)
+                out = _tuned_replay(uvs, method, lanes, want, fpi_threshold=0.1)
                 assert not out['status'].any() and np.all(out['k_done'] == REPLAY_K)
-                for t, ref in enumerate(loose):
-                    checks = [('x', out['x'][t], ref['X'], 1e-10), ('kappa', out['kappa'][t], ref['kappa'], 1e-9), ('p_final', out['p_final'][t].reshape(6, 6, 6), ref['P_final'], 1e-10)]
-                    if 'dqcmd' in want:
-                        checks.append(('dqcmd', out['dqcmd'][t], ref['dq_cmd'], 1e-8))
-                    for key, a, b, tol in checks:
-                        d = cs.rel(a, b)
-                        worst[key] = max(worst.get(key, 0.0), d)
-                        assert d <= tol, (key, d, t, method, lanes, want, 'fpi_threshold 0.1')
+                gh.assert_replay(out, loose, WORST, '(6,6) tuned replay', (method, lanes, want, 'fpi_threshold 0.1'), skip=('x_final',))

@@ -4,6 +4,8 @@ comparison, so the gates are tight."""
 import numpy as np
 import pytest
 
+from conftest import rel_err
+
 pytestmark = pytest.mark.gpu
 
 
@@ -14,10 +16,6 @@ def uvs():
     import uvs_amd
     uvs_amd.lib()
     return uvs_amd
-
-
-def rel_err(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(np.asarray(b)).max(), 1e-300))
 
 
 def test_random_configurations_match_c_oracle(uvs):

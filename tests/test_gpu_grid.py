@@ -4,18 +4,17 @@ depend on its neighbours in the batch.  Every comparison here is np.array_equal 
 lean on the uniform kernels."""
 import ctypes as C
 import json
-import os
 
 import numpy as np
 import pytest
 
+import gpu_harness as gh
 from conftest import load_golden, scene_desired, rel_err
+from gpu_harness import STREAMS
 from sweep_common import STATS_TOL
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 METHODS = ('GMCKF', 'MCKF', 'KF', 'IMCCKF')
-STREAMS = ('x', 'err', 'q', 'f', 'dq')
 BWS, GAINS = (2.0, 5.0, 10.0, 20.0), (0.1, 0.2, 0.4)
 
 
@@ -27,85 +26,35 @@ def uvs():
     return uvs_amd
 
 
-def _cuda(a):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), device='cuda')
-
-
-def _config(method, annealing=False):
-    cfg = json.load(open(os.path.join(ROOT, 'examples', 'config.json')))         # the reference's configuration
-    cfg['estimator']['method'] = method
-    cfg['estimator']['estimator_params']['annealing'] = annealing
-    return cfg
-
-
-def _setup(uvs, method, E, annealing=False, alpha=1.5):
-    """Config, plan, start poses and noise (device, [K][m][E]) of E trials of the alpha cell, plant, and a parameter-block factory."""
-    cfg = uvs.batch.load_config(_config(method, annealing))
-    plan = uvs.batch.plan_trials(cfg, [alpha], E)
-    ex, p = cfg['experiments'], cfg['estimator']['estimator_params']
-    K = len(uvs.engine.loop_clock(ex['dt'], ex['t_max']))
-    noise = uvs.batch.device_noise(cfg, plan, 0, E, K).contiguous()
-    plant = uvs.SyntheticPlant.ur10(ex['desired_f']).to_struct()
-
-    def fp(lanes=0, kernel_bw=p['kernel_bw'], gain=ex['ibvs_gain'], desired=ex['desired_f'], segments=0, fpi_threshold=p['fpi_threshold']):
-        f = uvs.engine.make_params(8, 6, method, kernel_bw, annealing, ex['dt'], ex['t_max'], gain, desired, True, lanes, None, fpi_threshold, p['fpi_epoch_max'])
-        f.reserved = segments << 8
-        return f
-    return cfg, plan, _cuda(plan.q_start), noise, plant, fp
-
-
-def _host(out, keys=STREAMS):
-    return {k: out[k].cpu().numpy() for k in keys + ('stats', 'status', 'k_done') if out.get(k) is not None}
-
-
-def _assert_same_bits(got, lo, ref, what):
-    """Trials [lo, lo + E) of the grid launch ``got`` against the uniform launch ``ref`` of E trials: status, k_done, stats and every stream up to k_done
-    (rows at and after k_done are unspecified)."""
-    E = len(ref['status'])
-    assert np.array_equal(got['status'][lo:lo + E], ref['status']), what
-    assert np.array_equal(got['k_done'][lo:lo + E], ref['k_done']), what
-    assert set(ref['status'].tolist()) <= {0, 1}, what                              # no mark left behind
-    ok = ref['status'] == 0
-    assert np.array_equal(got['stats'][lo:lo + E][ok], ref['stats'][ok]), what      # (a FAILed trial's statistics are discarded)
-    K = ref['err'].shape[0] if 'err' in ref else 0
-    logged = np.arange(K)[:, None] < ref['k_done'][None, :]                         # (K, E)
-    for key in STREAMS:
-        if key in ref:
-            a, b = got[key][:, :, lo:lo + E], ref[key]
-            same = (a == b) | (np.isnan(a) & np.isnan(b))
-            assert same[np.broadcast_to(logged[:, None, :], same.shape)].all(), (what, key)
-
-
 def _grid_vs_uniform(uvs, method, lanes, annealing=False, segments=0, desired_pair=None, E=100, bws=BWS, gains=GAINS, want=STREAMS):
     import torch
-    cfg, plan, q0, noise, plant, fp = _setup(uvs, method, E, annealing)
+    cfg, plan, q0, noise, plant, fp = gh.setup(uvs, method, E, annealing)
     cells = [(b, g) for b in bws for g in gains]
     H = len(cells)
-    tp = dict(kernel_bw=_cuda(np.repeat([c[0] for c in cells], E)), gain=_cuda(np.repeat([c[1] for c in cells], E)),
-              source=_cuda((np.arange(H * E) % E).astype(np.int32)))
+    tp = dict(kernel_bw=gh.cuda(np.repeat([c[0] for c in cells], E)), gain=gh.cuda(np.repeat([c[1] for c in cells], E)),
+              source=gh.cuda((np.arange(H * E) % E).astype(np.int32)))
     des_of = None
     if desired_pair is not None:                                                    # two targets inside the same scene, alternating from trial to trial
         des_of = np.stack([desired_pair[(t + t // E) % 2] for t in range(H * E)])
-        tp['desired'] = _cuda(des_of)
+        tp['desired'] = gh.cuda(des_of)
     fp_grid = fp(lanes, segments=segments)
     out = uvs.engine.closed_loop(fp_grid, plant, q0, noise, want=want, trial_params=tp)
     torch.cuda.synchronize()
     if segments:
         assert int(uvs.lib().uvs_rmckf_closed_loop_segments(C.byref(fp_grid), C.byref(plant), H * E)) == segments
         assert uvs.engine.hand_over_fallbacks(fp_grid, plant, H * E) == 0
-    got = _host(out, want)
+    got = gh.host(out, want)
     assert got['status'].shape == (H * E,)
     for h, (b, g) in enumerate(cells):
         if des_of is None:
             ref = uvs.engine.closed_loop(fp(lanes, b, g, segments=segments), plant, q0, noise, want=want)
-            _assert_same_bits(got, h * E, _host(ref, want), (method, lanes, b, g))
+            gh.assert_same_bits(got, h * E, gh.host(ref, want), (method, lanes, b, g))
         else:                                                                       # a uniform launch per target, over the trials that have it
             for which in (0, 1):
                 sel = np.nonzero((np.arange(E) + h) % 2 == which)[0]
-                ref = _host(uvs.engine.closed_loop(fp(lanes, b, g, desired_pair[which], segments=segments), plant, q0[sel], noise[:, :, sel].contiguous(), want=want), want)
+                ref = gh.host(uvs.engine.closed_loop(fp(lanes, b, g, desired_pair[which], segments=segments), plant, q0[sel], noise[:, :, sel].contiguous(), want=want), want)
                 sub = {k: (v[h * E + sel] if k in ('stats', 'status', 'k_done') else v[:, :, h * E + sel]) for k, v in got.items()}
-                _assert_same_bits(sub, 0, ref, (method, lanes, b, g, which))
+                gh.assert_same_bits(sub, 0, ref, (method, lanes, b, g, which))
     return got
 
 
@@ -127,7 +76,7 @@ def test_grid_launch_with_annealing(uvs, method):
 @pytest.mark.parametrize('method', METHODS)
 def test_grid_launch_with_per_trial_targets(uvs, method):
     g = load_golden('closed_gmckf_target_shift')
-    cfg = _config(method)
+    cfg = gh.config(method)
     assert np.array_equal(scene_desired(g), cfg['experiments']['desired_f'])       # the fixture's scene is the reference config's
     _grid_vs_uniform(uvs, method, 2, desired_pair=(np.asarray(cfg['experiments']['desired_f'], float), g['desired']), bws=(5.0, 20.0), gains=(0.1, 0.4),
                      want=('x', 'err', 'q'))
@@ -145,21 +94,21 @@ def test_grid_launch_at_full_size(uvs, method):
     a sample of cells."""
     import torch
     E, H = 128, 512
-    cfg, plan, q0, noise, plant, fp = _setup(uvs, method, E)
+    cfg, plan, q0, noise, plant, fp = gh.setup(uvs, method, E)
     bw = np.linspace(2.0, 33.0, 32)
     gain = np.linspace(0.05, 0.425, 16)
     cells = [(b, g) for b in bw for g in gain]
-    tp = dict(kernel_bw=_cuda(np.repeat([c[0] for c in cells], E)), gain=_cuda(np.repeat([c[1] for c in cells], E)),
-              source=_cuda((np.arange(H * E) % E).astype(np.int32)))
+    tp = dict(kernel_bw=gh.cuda(np.repeat([c[0] for c in cells], E)), gain=gh.cuda(np.repeat([c[1] for c in cells], E)),
+              source=gh.cuda((np.arange(H * E) % E).astype(np.int32)))
     want = ('err', 'q')
-    got = _host(uvs.engine.closed_loop(fp(0), plant, q0, noise, want=want, trial_params=tp), want)
+    got = gh.host(uvs.engine.closed_loop(fp(0), plant, q0, noise, want=want, trial_params=tp), want)
     torch.cuda.synchronize()
     if method == 'MCKF':
         f = fp(0)
         assert int(uvs.lib().uvs_rmckf_closed_loop_segments(C.byref(f), C.byref(plant), H * E)) > 1 and uvs.engine.hand_over_fallbacks(f, plant, H * E) == 0
     for h in (0, 1, 15, 16, 100, 255, 256, 300, 495, 511):
-        ref = _host(uvs.engine.closed_loop(fp(2, *cells[h]), plant, q0, noise, want=want), want)
-        _assert_same_bits(got, h * E, ref, (method, h, cells[h]))
+        ref = gh.host(uvs.engine.closed_loop(fp(2, *cells[h]), plant, q0, noise, want=want), want)
+        gh.assert_same_bits(got, h * E, ref, (method, h, cells[h]))
 
 
 @pytest.mark.parametrize('lanes', (0, 2))
@@ -167,10 +116,10 @@ def test_grid_launch_at_full_size(uvs, method):
 def test_null_trial_params_equal_the_uniform_call(uvs, method, lanes):
     """A uvs_trial_params whose members are all NULL runs, and equals uvs_rmckf_closed_loop_ws_f64 bit for bit."""
     E = 100
-    cfg, plan, q0, noise, plant, fp = _setup(uvs, method, E)
-    got = _host(uvs.engine.closed_loop(fp(lanes), plant, q0, noise, want=STREAMS, trial_params={}))
-    ref = _host(uvs.engine.closed_loop(fp(lanes), plant, q0, noise, want=STREAMS))
-    _assert_same_bits(got, 0, ref, (method, lanes))
+    cfg, plan, q0, noise, plant, fp = gh.setup(uvs, method, E)
+    got = gh.host(uvs.engine.closed_loop(fp(lanes), plant, q0, noise, want=STREAMS, trial_params={}))
+    ref = gh.host(uvs.engine.closed_loop(fp(lanes), plant, q0, noise, want=STREAMS))
+    gh.assert_same_bits(got, 0, ref, (method, lanes))
     final = uvs.engine.closed_loop(fp(lanes), plant, q0, noise, want=(), final_state=True, trial_params={'gain': None})
     final_ref = uvs.engine.closed_loop(fp(lanes), plant, q0, noise, want=(), final_state=True)
     ok = ref['status'] == 0
@@ -187,14 +136,14 @@ def test_careful_pass_reads_the_per_trial_values(uvs):
     plant = uvs.SyntheticPlant.ur10(scene_desired(g)).to_struct()
     mk = lambda gain: uvs.engine.make_params(8, 6, meta['method'], p['kernel_bw'], p['annealing'], meta['dt'], meta['t_max'], gain, g['desired'], False)   # noqa: E731
     T = 3
-    q0, noise, x0 = _cuda(np.tile(g['q_start'], (T, 1))), _cuda(np.repeat(g['noise'][:, :, None], T, axis=2)), _cuda(np.tile(g['X'][0], (T, 1)))
+    q0, noise, x0 = gh.cuda(np.tile(g['q_start'], (T, 1))), gh.cuda(np.repeat(g['noise'][:, :, None], T, axis=2)), gh.cuda(np.tile(g['X'][0], (T, 1)))
     want = ('x', 'err', 'q', 'dq')
-    got = _host(uvs.engine.closed_loop(mk(0.3), plant, q0, noise, x0, want=want, trial_params={'gain': _cuda(np.asarray(gains))}), want)
+    got = gh.host(uvs.engine.closed_loop(mk(0.3), plant, q0, noise, x0, want=want, trial_params={'gain': gh.cuda(np.asarray(gains))}), want)
     assert got['status'].tolist() == [0, 0, 0]
     for i, gain in enumerate(gains):
-        ref = _host(uvs.engine.closed_loop(mk(gain), plant, q0, noise, x0, want=want), want)
+        ref = gh.host(uvs.engine.closed_loop(mk(gain), plant, q0, noise, x0, want=want), want)
         sub = {k: (v[[i] * T] if k in ('stats', 'status', 'k_done') else v[:, :, [i] * T]) for k, v in got.items()}
-        _assert_same_bits(sub, 0, ref, gain)
+        gh.assert_same_bits(sub, 0, ref, gain)
     K = len(g['t'])
     assert rel_err(got['err'][:, :, 1], g['err']) <= 1e-7 and rel_err(got['q'][:, :, 1], g['q']) <= 1e-7 and rel_err(got['x'][g['X_steps'], :, 1], g['X']) <= 1e-7
     assert rel_err(got['dq'][:K - 1, :, 1], g['dq_prev'][1:]) <= 1e-6
@@ -221,12 +170,12 @@ def test_careful_pass_in_a_mixed_grid(uvs):
     meta, p = g['meta'], g['meta']['params']
     mk = lambda gain: uvs.engine.make_params(8, 6, meta['method'], p['kernel_bw'], p['annealing'], meta['dt'], meta['t_max'], gain, g['desired'], False, 0, K)   # noqa: E731
     gains = (meta['gain'], 0.35)
-    tp = dict(gain=_cuda(np.repeat(gains, E)), source=_cuda((np.arange(2 * E) % E).astype(np.int32)))
+    tp = dict(gain=gh.cuda(np.repeat(gains, E)), source=gh.cuda((np.arange(2 * E) % E).astype(np.int32)))
     want = ('x', 'err', 'q')
-    got = _host(uvs.engine.closed_loop(mk(0.0), plant, _cuda(q0), _cuda(noise), _cuda(x0), want=want, trial_params=tp), want)
+    got = gh.host(uvs.engine.closed_loop(mk(0.0), plant, gh.cuda(q0), gh.cuda(noise), gh.cuda(x0), want=want, trial_params=tp), want)
     assert not got['status'].any()
     for i, gain in enumerate(gains):
-        ref = _host(uvs.engine.closed_loop(mk(gain), plant, _cuda(q0), _cuda(noise), _cuda(x0), want=want), want)
+        ref = gh.host(uvs.engine.closed_loop(mk(gain), plant, gh.cuda(q0), gh.cuda(noise), gh.cuda(x0), want=want), want)
         assert not ref['status'].any() and np.array_equal(got['k_done'][i * E:(i + 1) * E], ref['k_done'])
         for key in want:
             assert rel_err(got[key][:, :, i * E:(i + 1) * E], ref[key]) <= 1e-11, (gain, key)
@@ -248,12 +197,12 @@ def test_grid_against_the_oracle(uvs, method):
     for each estimator)."""
     from oracle import c_oracle
     E, bws, gains = 32, (5.0, 10.0, 20.0), (0.1, 0.2)
-    cfg, plan, q0, noise, plant, fp = _setup(uvs, method, E)
+    cfg, plan, q0, noise, plant, fp = gh.setup(uvs, method, E)
     cells = [(b, g) for b in bws for g in gains]
     H = len(cells)
-    tp = dict(kernel_bw=_cuda(np.repeat([c[0] for c in cells], E)), gain=_cuda(np.repeat([c[1] for c in cells], E)),
-              source=_cuda((np.arange(H * E) % E).astype(np.int32)))
-    got = _host(uvs.engine.closed_loop(fp(0), plant, q0, noise, want=(), trial_params=tp), ())
+    tp = dict(kernel_bw=gh.cuda(np.repeat([c[0] for c in cells], E)), gain=gh.cuda(np.repeat([c[1] for c in cells], E)),
+              source=gh.cuda((np.arange(H * E) % E).astype(np.int32)))
+    got = gh.host(uvs.engine.closed_loop(fp(0), plant, q0, noise, want=(), trial_params=tp), ())
     host_noise = np.ascontiguousarray(noise.cpu().numpy().transpose(2, 0, 1))       # (E, K, m)
     ex, p = cfg['experiments'], cfg['estimator']['estimator_params']
     calm_total = 0
@@ -278,23 +227,23 @@ def test_grid_against_the_oracle(uvs, method):
 def test_source_equals_physical_copies(uvs, method):
     """`source` repeating E trials H times against the launch fed H physical copies of q_start / noise."""
     E, H = 100, 6
-    cfg, plan, q0, noise, plant, fp = _setup(uvs, method, E)
+    cfg, plan, q0, noise, plant, fp = gh.setup(uvs, method, E)
     cells = [(b, g) for b in (5.0, 20.0) for g in GAINS]
-    tp = dict(kernel_bw=_cuda(np.repeat([c[0] for c in cells], E)), gain=_cuda(np.repeat([c[1] for c in cells], E)))
+    tp = dict(kernel_bw=gh.cuda(np.repeat([c[0] for c in cells], E)), gain=gh.cuda(np.repeat([c[1] for c in cells], E)))
     want = ('x', 'err', 'q')
-    ref = _host(uvs.engine.closed_loop(fp(2), plant, q0.repeat(H, 1), noise.repeat(1, 1, H), want=want, trial_params=tp), want)
-    got = _host(uvs.engine.closed_loop(fp(2), plant, q0, noise, want=want, trial_params=dict(tp, source=_cuda((np.arange(H * E) % E).astype(np.int32)))), want)
-    _assert_same_bits(got, 0, ref, method)
+    ref = gh.host(uvs.engine.closed_loop(fp(2), plant, q0.repeat(H, 1), noise.repeat(1, 1, H), want=want, trial_params=tp), want)
+    got = gh.host(uvs.engine.closed_loop(fp(2), plant, q0, noise, want=want, trial_params=dict(tp, source=gh.cuda((np.arange(H * E) % E).astype(np.int32)))), want)
+    gh.assert_same_bits(got, 0, ref, method)
     # ... and a permutation: trial t reads the inputs of trial E - 1 - t, writes at t
     rev = np.arange(E)[::-1].copy()
-    flipped = _host(uvs.engine.closed_loop(fp(2), plant, q0, noise, want=want, trial_params={'source': _cuda(rev.astype(np.int32))}), want)
-    plain = _host(uvs.engine.closed_loop(fp(2), plant, q0[_cuda(rev)], noise[:, :, _cuda(rev)].contiguous(), want=want), want)
-    _assert_same_bits(flipped, 0, plain, (method, 'reversed'))
+    flipped = gh.host(uvs.engine.closed_loop(fp(2), plant, q0, noise, want=want, trial_params={'source': gh.cuda(rev.astype(np.int32))}), want)
+    plain = gh.host(uvs.engine.closed_loop(fp(2), plant, q0[gh.cuda(rev)], noise[:, :, gh.cuda(rev)].contiguous(), want=want), want)
+    gh.assert_same_bits(flipped, 0, plain, (method, 'reversed'))
 
 
 @pytest.mark.parametrize('method', ('GMCKF', 'MCKF'))
 def test_run_grid_equals_run_sweep_per_grid_cell(uvs, method):
-    cfg = _config(method)
+    cfg = gh.config(method)
     grid = {'kernel_bw': [5, 20], 'ibvs_gain': [0.1, 0.2, 0.4]}
     cells, E = [1.2, 1.5], 100
     res = uvs.batch.run_grid(cfg, grid, cells=cells, epoch=E)
@@ -326,10 +275,10 @@ def test_grid_entry_point_is_graph_capturable(uvs, method, segments):
     import torch
     E, H = 48, 2
     T = E * H
-    cfg, plan, q0, noise, plant, fp_of = _setup(uvs, method, E)
+    cfg, plan, q0, noise, plant, fp_of = gh.setup(uvs, method, E)
     K = noise.shape[0]
     fp = fp_of(2, segments=segments)
-    tp = dict(kernel_bw=_cuda(np.repeat([5.0, 20.0], E)), gain=_cuda(np.repeat([0.1, 0.3], E)), source=_cuda((np.arange(T) % E).astype(np.int32)))
+    tp = dict(kernel_bw=gh.cuda(np.repeat([5.0, 20.0], E)), gain=gh.cuda(np.repeat([0.1, 0.3], E)), source=gh.cuda((np.arange(T) % E).astype(np.int32)))
     eager = uvs.engine.closed_loop(fp, plant, q0, noise, want=('x', 'err', 'q'), trial_params=tp)
     torch.cuda.synchronize()
     q_in, nz_in = torch.empty_like(q0), torch.empty_like(noise)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_names, load_golden, rel_err, scene_desired
+from gpu_harness import random_replay_case
 
 pytestmark = pytest.mark.gpu
 
@@ -407,25 +408,13 @@ def test_baseline_config_1_batch(uvs):
 
 
 # ---------------------------------------------------------------------------------------------- other shapes
-def _random_replay_case(m, n, K, T, seed):
-    rng = np.random.default_rng(seed)
-    J = rng.normal(size=(T, m, n)) * 20
-    dq = rng.normal(size=(T, K, n)) * 0.3
-    f = np.zeros((T, K + 1, m))
-    f[:, 0] = rng.uniform(60, 200, (T, m))
-    for k in range(K):
-        f[:, k + 1] = f[:, k] + np.einsum('tmn,tn->tm', J, dq[:, k]) * 0.05 + rng.standard_t(2, size=(T, m))
-    x0 = (J + rng.normal(size=J.shape)).reshape(T, m * n)
-    return f, dq, x0, rng.uniform(80, 180, m)
-
-
 @pytest.mark.parametrize('method', ['GMCKF', 'KF', 'IMCCKF'])
 @pytest.mark.parametrize('m,n,lanes', [(2, 6, 1), (6, 6, 1), (8, 6, 1), (8, 6, 4), (32, 7, 8), (32, 7, 16), (32, 7, 32)])
 def test_replay_other_shapes_match_block_oracle(uvs, m, n, lanes, method):
     """Shapes the reference cannot run (experiment.py hard-wires m = 8, n = 6): oracle = per-row restatement."""
     from oracle import rmckf_block
     K, T = 40, 5
-    f, dq, x0, des = _random_replay_case(m, n, K, T, 1000 + m)
+    f, dq, x0, des = random_replay_case(m, n, K, T, 1000 + m)
     fp = uvs.engine.make_params(m, n, method, 7.5, True, 0.05, 15, 0.2, des, False, lanes, steps=K)
     out = uvs.engine.replay(fp, _cuda(f.transpose(1, 2, 0)), _cuda(dq.transpose(1, 2, 0)), _cuda(x0), final_state=True)
     for t in range(T):

@@ -14,18 +14,16 @@ import zlib
 import numpy as np
 import pytest
 
-from conftest import load_golden
+import gpu_harness as gh
+from conftest import load_golden, rel_err as rel
+from gpu_harness import DEFAULT_LANES, K_MAX, SHAPES, TOL_DQ, TOL_KAPPA, TOL_P, TOL_X
 
 pytestmark = pytest.mark.gpu
 
-TOL_X, TOL_P, TOL_DQ, TOL_KAPPA = 1e-10, 1e-9, 1e-7, 1e-9
-K_MAX = 300                                                  # make_params(t_s = 0.05, t_max = 15)
-SHAPES = [(8, 6, 1), (8, 6, 2), (8, 6, 4), (8, 6, 8), (6, 6, 1), (6, 6, 2), (2, 6, 1), (32, 7, 8), (32, 7, 16), (32, 7, 32)]   # UVS_SHAPES
-DEFAULT_LANES = {(8, 6): 4, (6, 6): 2, (2, 6): 1, (32, 7): 16}          # what lanes_per_filter = 0 resolves to on this route
 LANE_CASES = SHAPES + [(m, n, 0) for m, n in DEFAULT_LANES] + [(8, 6, -8), (6, 6, -1), (2, 6, -1), (32, 7, -32)]
 METHODS = ['GMCKF', 'KF', 'IMCCKF', 'MCKF']
 RANKDEF = 'rankdef_gmckf_zero_and_scaled_col'
-WORST = {}                                                   # worst deviation per key over the per-step parity cases run so far
+WORST = gh.Worst()                                           # 'module': worst deviation per key over the per-step parity cases run so far
 
 
 @pytest.fixture(scope='module')
@@ -37,26 +35,8 @@ def uvs():
     return uvs_amd
 
 
-def _cuda(a):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), device='cuda')
-
-
 def _np(t):
     return t.cpu().numpy().copy()
-
-
-def rel(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _lanes(m, n, lanes):
-    return abs(lanes) or DEFAULT_LANES[(m, n)]
 
 
 def _seed(*key):
@@ -64,52 +44,18 @@ def _seed(*key):
 
 
 # ---------------------------------------------------------------------------------------------- 1. per-step parity
-def _parity_run(uvs, rng, m, n, lanes, method, k0, scale, thr, cap, steps=6):
-    """One bank of T = 64 // L + 3 filters (two blocks, the second ragged) stepped `steps` times from k0; every step compared with the
-    oracle started from the same state, then both sides continue from the ORACLE's state and command.  Returns the worst deviations."""
-    from oracle import rmckf_block
-    L = _lanes(m, n, lanes)
-    T = 64 // L + 3
-    bw, gain = float(rng.choice([1.0, 10.0, 50.0])), float(rng.uniform(0.05, 0.6))
-    desired = 128 + 10 * rng.standard_normal(m)
-    fp = uvs.engine.make_params(m, n, method, bw, True, 0.05, 15.0, gain, desired, False, lanes, 0, thr, cap)
+def _parity_run(uvs, rng, m, n, lanes, method, k0, scale, thr, cap, route, steps=6):
+    """One bank of T = 64 // L + 3 filters (two blocks, the second ragged) stepped `steps` times from k0 (gh.step_recipe at a kernel_bw drawn
+    from {1, 10, 50}, annealed); every step compared with the oracle started from the same state, then both sides continue from the ORACLE's
+    state and command.  The deviations go to WORST[route] and WORST['module']; returns how many filters FAILed, on both sides."""
+    bw = float(rng.choice([1.0, 10.0, 50.0]))
+    head, *recipe = gh.step_recipe(rng, m, n, lanes, method, k0, scale, bw, True, steps, fpi_threshold=thr, fpi_epoch_max=cap)
+    fp = uvs.engine.make_params(m, n, method, bw, True, 0.05, 15.0, head['gain'], head['desired'], False, lanes, 0, thr, cap)
     assert fp.k_max == K_MAX
-    J = rng.standard_normal((T, m, n)) * 50
-    x0 = J.reshape(T, m * n)
-    bank = uvs.engine.FilterBank(fp, T, x0)
-    fresh = lambda t: rmckf_block.BlockFilter(m, n, x0[t], method, bw, True, K_MAX, thr, cap)     # noqa: E731
-    filt = [fresh(t) for t in range(T)]
-    f_old, dq = 128 + 20 * rng.standard_normal((T, m)), np.zeros((T, n))
-    worst, fails = {'X': 0.0, 'P': 0.0, 'dq': 0.0, 'kappa': 0.0}, 0
-    for s in range(steps):
-        k = k0 + s
-        f = f_old + np.einsum('tmn,tn->tm', J, dq) * 0.05 + scale * rng.standard_t(2.0, size=(T, m))
-        out = bank.step(_cuda(f), _cuda(f_old), _cuda(dq), k)
-        cmd, err, kap, status = (_np(o) for o in out)
-        Xg, Pg = _np(bank.X), _np(bank.P).reshape(T, m, n, n)
-        assert _same_bits(err, f - desired), ('err', m, n, lanes, method, k)              # one subtraction: the same bits
-        new_dq = np.zeros((T, n))
-        for t in range(T):
-            tag = (m, n, lanes, method, T, k, t, bw, thr, cap, scale)
-            with np.errstate(all='ignore'):
-                kappa = filt[t].step(f[t] - f_old[t], dq[t], k)
-                finite = bool(np.all(np.isfinite(filt[t].X)))
-            assert (status[t] == 0) == finite, ('status', int(status[t]), finite) + tag
-            if not finite:                                                                  # restart this filter on both sides (the copy-back below)
-                filt[t] = fresh(t)
-                filt[t].first = False
-                fails += 1
-                continue
-            ref_cmd = rmckf_block.control_law(filt[t].X, f[t] - desired, kappa, gain)
-            d = {'X': rel(Xg[t], filt[t].X.ravel()), 'P': rel(Pg[t], filt[t].P), 'dq': rel(cmd[t], ref_cmd), 'kappa': rel(kap[t], kappa)}
-            for key, tol in (('X', TOL_X), ('P', TOL_P), ('dq', TOL_DQ), ('kappa', TOL_KAPPA)):
-                worst[key] = max(worst[key], d[key])
-                assert d[key] <= tol, (key, d[key]) + tag
-            new_dq[t] = ref_cmd
-        bank.X.copy_(_cuda(np.stack([fl.X.ravel() for fl in filt])))
-        bank.P.copy_(_cuda(np.stack([fl.P for fl in filt])).reshape(bank.P.shape))
-        f_old, dq = f, np.clip(new_dq, -5, 5)
-    return worst, fails
+    bank = uvs.engine.FilterBank(fp, head['T'], head['x0'])
+    for s, st in enumerate(recipe):
+        gh.assert_step(bank, st, head['desired'], WORST, (route, 'module'), (m, n, lanes, method, head['T'], bw, thr, cap, scale), fresh=s == 0)
+    return sum(int((~st['finite']).sum()) for st in recipe)
 
 
 @pytest.mark.parametrize('method', METHODS)
@@ -118,33 +64,15 @@ def test_every_step_matches_the_block_oracle(uvs, m, n, lanes, method):
     """Annealed bandwidth (kernel_bw from {1, 10, 50}) at k = 0.. and k = 290.. of 300, noise scales 1, 30 and 400 (zero and subnormal
     correntropy weights; at the narrow bandwidths of k = 290), MCKF at (threshold, cap) = (0.1, 1000) and (1e-2, 3)."""
     rng = np.random.default_rng(_seed(m, n, lanes, method))
-    worst, fails = {}, 0
+    route, fails = (m, n, lanes, method), 0
     for thr, cap in ([(0.1, 1000), (1e-2, 3)] if method == 'MCKF' else [(0.1, 1000)]):
         for k0, scale in ((0, 1.0), (290, 1.0), (0, 30.0), (290, 30.0), (290, 400.0)):
-            w, nf = _parity_run(uvs, rng, m, n, lanes, method, k0, scale, thr, cap)
-            fails += nf
-            for key, v in w.items():
-                worst[key] = max(worst.get(key, 0.0), v)
-    for key, v in worst.items():
-        WORST[key] = max(WORST.get(key, 0.0), v)
+            fails += _parity_run(uvs, rng, m, n, lanes, method, k0, scale, thr, cap, route)
     fmt = lambda w: {k: f'{v:.1e}' for k, v in w.items()}                                   # noqa: E731
-    print(f'step parity ({m},{n}) lanes {lanes} {method}: worst relative deviations {fmt(worst)}, {fails} FAILs on both sides; module so far {fmt(WORST)}')
+    print(f'step parity ({m},{n}) lanes {lanes} {method}: worst relative deviations {fmt(WORST[route])}, {fails} FAILs on both sides; module so far {fmt(WORST["module"])}')
 
 
 # ---------------------------------------------------------------------------------------------- 2. chained run, no resynchronisation
-def _random_replay_case(m, n, K, T, seed):
-    """The streams of test_gpu_parity._random_replay_case, restated."""
-    rng = np.random.default_rng(seed)
-    J = rng.normal(size=(T, m, n)) * 20
-    dq = rng.normal(size=(T, K, n)) * 0.3
-    f = np.zeros((T, K + 1, m))
-    f[:, 0] = rng.uniform(60, 200, (T, m))
-    for k in range(K):
-        f[:, k + 1] = f[:, k] + np.einsum('tmn,tn->tm', J, dq[:, k]) * 0.05 + rng.standard_t(2, size=(T, m))
-    x0 = (J + rng.normal(size=J.shape)).reshape(T, m * n)
-    return f, dq, x0, rng.uniform(80, 180, m)
-
-
 @pytest.mark.parametrize('method', ['GMCKF', 'KF', 'IMCCKF'])
 @pytest.mark.parametrize('m,n,lanes', [(8, 6, 4), (6, 6, 2), (2, 6, 1), (32, 7, 16)])
 def test_forty_chained_steps_match_run_replay(uvs, m, n, lanes, method):
@@ -152,12 +80,12 @@ def test_forty_chained_steps_match_run_replay(uvs, m, n, lanes, method):
     test_replay_other_shapes_match_block_oracle on the streams of its generator."""
     from oracle import rmckf_block
     K, T = 40, 5
-    f, dq, x0, des = _random_replay_case(m, n, K, T, 1000 + m)
+    f, dq, x0, des = gh.random_replay_case(m, n, K, T, 1000 + m)
     fp = uvs.engine.make_params(m, n, method, 7.5, True, 0.05, 15, 0.2, des, False, lanes, 0)
     bank = uvs.engine.FilterBank(fp, T, x0)
     X, cmd, kap = [], [], []
     for k in range(K):
-        out = bank.step(_cuda(f[:, k + 1]), _cuda(f[:, k]), _cuda(dq[:, k]), k)
+        out = bank.step(gh.cuda(f[:, k + 1]), gh.cuda(f[:, k]), gh.cuda(dq[:, k]), k)
         assert not _np(out[3]).any()
         X.append(_np(bank.X)); cmd.append(_np(out[0])); kap.append(_np(out[2]))
     X, cmd, kap, P = np.array(X), np.array(cmd), np.array(kap), _np(bank.P).reshape(T, m, n, n)
@@ -194,7 +122,7 @@ def _run(uvs, fp, inp, sel=None, k0=0):
     keys = ('X', 'P', 'dq', 'err', 'kappa', 'status')
     rec = {key: [] for key in keys}
     for s in range(len(inp['f'])):
-        out = bank.step(_cuda(inp['f'][s][sel]), _cuda(inp['f_old'][s][sel]), _cuda(inp['dq'][s][sel]), k0 + s)
+        out = bank.step(gh.cuda(inp['f'][s][sel]), gh.cuda(inp['f_old'][s][sel]), gh.cuda(inp['dq'][s][sel]), k0 + s)
         for key, v in zip(keys, (bank.X, bank.P) + tuple(out)):
             rec[key].append(_np(v))
     return {key: np.array(v) for key, v in rec.items()}                                     # [step][filter]...
@@ -204,7 +132,7 @@ def _assert_singletons_equal(uvs, fp, inp, batch, T):
     for t in range(T):
         one = _run(uvs, fp, inp, [t])
         for key in batch:
-            assert _same_bits(batch[key][:, t], one[key][:, 0]), (key, t)
+            assert gh.same_bits(batch[key][:, t], one[key][:, 0]), (key, t)
 
 
 def _oracle_chain(fp_args, inp, t, method='GMCKF'):
@@ -282,7 +210,7 @@ def test_a_filter_does_not_depend_on_its_neighbours(uvs, shape):
     _assert_singletons_equal(uvs, fp, healthy, out_h, T)                                   # (a)
     _assert_singletons_equal(uvs, fp, mixed, out_m, T)
     for key in out_m:                                                                       # (b)
-        assert _same_bits(out_m[key][:, keep], out_h[key][:, keep]), key
+        assert gh.same_bits(out_m[key][:, keep], out_h[key][:, keep]), key
     _assert_sick_commands(out_m, sick, ref_cmd)
     oracle = {t: _oracle_chain(args, healthy, t) for t in range(T)}
     worst = {'default': 0.0, 'strict': 0.0}
@@ -290,7 +218,7 @@ def test_a_filter_does_not_depend_on_its_neighbours(uvs, shape):
     for inp, out, who in ((healthy, out_h, range(T)), (mixed, out_m, keep)):               # (c)
         out_s = _run(uvs, strict, inp)
         for key in ('X', 'P', 'err', 'kappa', 'status'):
-            assert _same_bits(out_s[key], out[key]), key
+            assert gh.same_bits(out_s[key], out[key]), key
         for t in who:
             for s, (X, P, cmd, kappa) in enumerate(oracle[t]):
                 assert rel(out['X'][s, t], X.ravel()) <= TOL_X and rel(out['P'][s, t].reshape(P.shape), P) <= TOL_P, (s, t)
@@ -335,8 +263,8 @@ def test_a_nan_sample_fails_its_filter_alone(uvs, lanes, method):
     assert b['status'][1].tolist() == [int(t == hit) for t in range(T)]
     others = [t for t in range(T) if t != hit]
     for key in a:
-        assert _same_bits(a[key][:, others], b[key][:, others]), key
-        assert _same_bits(a[key][0], b[key][0]), key
+        assert gh.same_bits(a[key][:, others], b[key][:, others]), key
+        assert gh.same_bits(a[key][0], b[key][0]), key
 
 
 @pytest.mark.parametrize('lanes', [4, 8])
@@ -351,8 +279,8 @@ def test_an_infinite_sample_skips_the_mckf_correction(uvs, lanes):
     fp = uvs.engine.make_params(m, n, 'MCKF', 10.0, True, 0.05, 15.0, 0.2, desired, False, lanes, 0)
     out = _run(uvs, fp, inp)
     assert not out['status'].any()
-    assert _same_bits(out['X'][1, hit], out['X'][0, hit])                                   # skipped: the state of the step before
-    assert _same_bits(out['P'][1, hit], out['P'][0, hit] + np.tile(np.eye(n), (m, 1, 1)).reshape(out['P'][0, hit].shape))
+    assert gh.same_bits(out['X'][1, hit], out['X'][0, hit])                                   # skipped: the state of the step before
+    assert gh.same_bits(out['P'][1, hit], out['P'][0, hit] + np.tile(np.eye(n), (m, 1, 1)).reshape(out['P'][0, hit].shape))
     for t in range(T):
         ref = _oracle_chain((m, n, 10.0, True, 0.2, desired), inp, t, 'MCKF')
         for s, (X, P, cmd, kappa) in enumerate(ref):
@@ -378,19 +306,19 @@ def test_step_host_is_the_same_kernel_on_pinned_operands(uvs, T, method):
     held = None
     for k in range(S):
         f, f_old = inp['f'][k], inp['f_old'][k]
-        ref = [_np(o) for o in dev.step(_cuda(f), _cuda(f_old), _cuda(prev), k)]
+        ref = [_np(o) for o in dev.step(gh.cuda(f), gh.cuda(f_old), gh.cuda(prev), k)]
         views_e = explicit.step_host(f, f_old, k, dq_prev=prev)
         views_c = chained.step_host(f, f_old, k)
         for name, r, e, c in zip(('dq', 'err', 'kappa', 'status'), ref, views_e, views_c):
-            assert _same_bits(r, e) and _same_bits(r, c), (name, k)
+            assert gh.same_bits(r, e) and gh.same_bits(r, c), (name, k)
         if held is not None:                                                                # call k - 1's views after call k
             for views in held[:2]:
                 for name, view, then in zip(('dq', 'err', 'kappa', 'status'), views, held[2]):
-                    assert _same_bits(view, then), (name, k)
+                    assert gh.same_bits(view, then), (name, k)
         held = (views_e, views_c, ref)
         prev = ref[0]                                                                       # the explicit regressor is the previous return
     for bank in (explicit, chained):
-        assert _same_bits(_np(bank.X), _np(dev.X)) and _same_bits(_np(bank.P), _np(dev.P))
+        assert gh.same_bits(_np(bank.X), _np(dev.X)) and gh.same_bits(_np(bank.P), _np(dev.P))
     assert not ref[3].any()
 
 
@@ -398,9 +326,9 @@ def test_step_host_is_the_same_kernel_on_pinned_operands(uvs, T, method):
 def test_a_lane_count_that_is_not_instantiated_is_refused(uvs):
     fp = uvs.engine.make_params(8, 6, 'GMCKF', desired=np.zeros(8), lanes=16, steps=0)
     bank = uvs.engine.FilterBank(fp, 3, np.ones((3, 48)))
-    z = _cuda(np.zeros((3, 8)))
+    z = gh.cuda(np.zeros((3, 8)))
     with pytest.raises(uvs._lib.UvsError) as exc:
-        bank.step(z, z, _cuda(np.zeros((3, 6))), 0)
+        bank.step(z, z, gh.cuda(np.zeros((3, 6))), 0)
     assert exc.value.code == -2                                                             # UVS_ERR_SHAPE
     assert len(uvs.lib().uvs_last_error()) > 0
-    assert _same_bits(_np(bank.X), np.ones((3, 48)))                                        # nothing ran
+    assert gh.same_bits(_np(bank.X), np.ones((3, 48)))                                        # nothing ran

@@ -90,7 +90,7 @@ def test_c_oracle_agrees_with_the_block_oracle_at_the_other_shapes(case, method,
     if method == 'MCKF':
         assert ref['fpi'].max() >= 3                                    # the fixed-point loop does iterate
     if shapes.CASES[case][2] == 'linear':
-        assert not ref['status'].any() and np.all(ref['k_done'] == shapes.K)
+        assert not ref['status'].any() and np.all(ref['k_done'] == shapes.inputs(case)['K'])
 
 
 # ---------------------------------------------------------------------------------------------- reg and anneal_span off their defaults
@@ -102,7 +102,7 @@ def test_oracles_agree_at_other_reg_and_anneal_span(case, name, method):
     that used a literal 1e-6 or 100 in place of the field cannot pass tests/test_gpu_estimator_params.py."""
     anneal, reg, span = params.estimator(name, method)
     assert (reg, span) != (params.REG, params.ANNEAL_SPAN) and (anneal or span == params.ANNEAL_SPAN)
-    agreement = params.oracle_agreement(case, name, method)
+    agreement = shapes.oracle_agreement(case, **params.run(name, method))
     apart = tuple(sorted(t for t, d in agreement.items() if not d <= shapes.AGREE_TOL))
     listed = tuple(params.EXCLUDED.get((case, name, method), ()))
     close = [d for t, d in agreement.items() if t not in apart]
@@ -112,8 +112,8 @@ def test_oracles_agree_at_other_reg_and_anneal_span(case, name, method):
     assert set(apart) <= set(listed), {t: agreement[t] for t in apart if t not in listed}
     assert len(listed) <= shapes.MAX_EXCLUDED_FRACTION * len(agreement)
     assert not set(listed) & set(shapes.TWINS)
-    ref = params.c_reference(case, name, method)
-    assert not ref['status'].any() and np.all(ref['k_done'] == shapes.K)
+    ref = shapes.c_reference(case, **params.run(name, method))
+    assert not ref['status'].any() and np.all(ref['k_done'] == shapes.inputs(case)['K'])
     if method == 'MCKF':
         assert ref['fpi'].max() >= 2                                    # the fixed-point loop iterates at these bandwidths too
     assert bite >= params.TEETH * params.GATE, bite
@@ -122,12 +122,12 @@ def test_oracles_agree_at_other_reg_and_anneal_span(case, name, method):
 @pytest.mark.parametrize('name,method', params.WIDE_CONFIGS)
 def test_oracles_agree_at_other_reg_and_anneal_span_on_the_wide_shape(name, method):
     """(32,7) on the linear plant (the inputs of test_closed_loop_stress_plant, T = 4, K = 80): every trial at AGREE_TOL, and the teeth."""
-    agreement = params.wide_oracle_agreement(name, method)
-    bite = params.wide_teeth(name, method)
+    agreement = shapes.oracle_agreement('wide', **params.run(name, method))
+    bite = params.teeth('wide', name, method)
     print(f'(32,7) {name} {method}: agree to {max(agreement.values()):.1e}; the default-valued run is {bite:.1e} away')
     assert max(agreement.values()) <= shapes.AGREE_TOL, agreement
-    ref = params.wide_c_reference(name, method)
-    assert not ref['status'].any() and np.all(ref['k_done'] == params.WIDE_K)
+    ref = shapes.c_reference('wide', **params.run(name, method))
+    assert not ref['status'].any() and np.all(ref['k_done'] == shapes.inputs('wide')['K'])
     assert bite >= params.TEETH * params.GATE, bite
 
 
@@ -141,10 +141,10 @@ def test_dense_oracle_agrees_with_the_block_oracle_at_other_reg_and_anneal_span(
     inp = shapes.inputs('dh86')
     anneal, reg, span = params.estimator(name, method)
     for t in (0, 28, 56):
-        run = params.block_reference('dh86', name, method, t)
+        run = shapes.block_reference('dh86', t=t, **params.run(name, method))
         f_seq = np.vstack([inp['features'](inp['q0'][t])[None], run['f']])
         dq_seq = np.vstack([np.zeros((1, 6)), np.diff(run['q'], axis=0) / shapes.DT])
-        kw = dict(method=method, kernel_bw=shapes.BW, annealing=anneal, k_max=shapes.K, fpi_threshold=shapes.FPI_THRESHOLD, reg=reg, anneal_span=span)
+        kw = dict(method=method, kernel_bw=inp['bw'], annealing=anneal, k_max=inp['K'], fpi_threshold=shapes.FPI_THRESHOLD, reg=reg, anneal_span=span)
         a = rmckf_dense.run_replay(f_seq, dq_seq, inp['x0'][t], inp['desired'], shapes.GAIN, **kw)
         b = rmckf_block.run_replay(f_seq, dq_seq, inp['x0'][t], inp['desired'], shapes.GAIN, **kw)
         tol_x, tol_cmd = (1e-10, 1e-8) if method == 'MCKF' else (1e-11, 1e-9)
