@@ -1,0 +1,65 @@
+"""ctypes binding of libuvs_vision.so (include/uvs_vision.h): the circle detectors of the live route on the device.
+
+Like ``_lib``: no CPU fallback.  If the HIP library is missing or fails to load, ``lib()`` raises ``UvsLibraryError`` -- the device route
+never substitutes the numpy detectors of ``utils``.
+"""
+import ctypes as C
+import os
+import subprocess
+
+from ._lib import UvsError, UvsLibraryError
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, 'libuvs_vision.so')
+CSRC = os.path.join(HERE, 'csrc_vision')
+
+SIDE = 256                                                          # UVS_VISION_SIDE
+N_COLOURS = (1, 3, 4)                                               # green | red, green, blue | red, green, blue, pink
+
+# name -> (restype, argtypes); every symbol include/uvs_vision.h declares
+_VP, _I64, _I32 = C.c_void_p, C.c_int64, C.c_int32
+SYMBOLS = {
+    'uvs_vision_version': (C.c_char_p, []),
+    'uvs_vision_last_error': (C.c_char_p, []),
+    'uvs_detect_circles_u8': (C.c_int, [_I64, _VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+}
+
+_lib = None
+
+
+def build(force=False):
+    """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
+    if force and os.path.exists(LIB_PATH):
+        os.remove(LIB_PATH)
+    subprocess.run(['make', '-C', CSRC], check=True)
+    return LIB_PATH
+
+
+def lib():
+    """The loaded library with typed entry points; raises UvsLibraryError when it cannot be loaded."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise UvsLibraryError(f'{LIB_PATH} is missing: run `make -C {CSRC}` (or __graft_entry__.build()); '
+                                  'there is no CPU fallback for the device detectors')
+        try:
+            import torch  # noqa: F401  (first, so that one HIP runtime serves torch and this library: see _lib.lib)
+            handle = C.CDLL(LIB_PATH)
+        except OSError as exc:
+            raise UvsLibraryError(f'cannot load {LIB_PATH}: {exc}') from exc
+        for name, (res, args) in SYMBOLS.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = res, args
+        _lib = handle
+    return _lib
+
+
+class UvsVisionError(UvsError):
+    def __init__(self, code, text):
+        RuntimeError.__init__(self, f'libuvs_vision error {code}: {text}')
+        self.code = code
+
+
+def check(code):
+    if code != 0:
+        raise UvsVisionError(code, lib().uvs_vision_last_error().decode())

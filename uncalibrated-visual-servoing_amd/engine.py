@@ -294,6 +294,53 @@ def replay_f32(fp, f, dq, x0, want=('x', 'err'), layout='kct'):
     return out
 
 
+def _frames_arg(frames):
+    """(tensor, T) of a uint8 frame batch the detector kernel can read in place: on the device or in pinned host memory, (T, H, W, 3) or one
+    (H, W, 3) frame, rows and pixels dense.  The frame stride is free (a padded batch is a view of a wider buffer)."""
+    torch = _torch()
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise ValueError('frames: a torch uint8 tensor (T, 256, 256, 3) or (256, 256, 3)')
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f'frames: (T, 256, 256, 3) RGB, got {tuple(frames.shape)}')
+    if not (frames.is_cuda or frames.is_pinned()):
+        raise ValueError('frames must be on the device or in pinned host memory: the kernel reads them in place (no hidden copy)')
+    if frames.shape[0] and tuple(frames.stride()[1:]) != (frames.shape[2] * 3, 3, 1):
+        raise ValueError('frames: rows and pixels must be dense (only the frame stride is free)')
+    return frames, frames.shape[0]
+
+
+def detect_circles(frames, n_colours=4, noise=None, out=None, pixels=None):
+    """Centre-of-mass circle detectors (utils.py:11-166: n_colours 1 = detectGreenCircle, 3 = detectRGBCircles, 4 = detect4Circles) of a
+    batch of camera frames in one launch on the current stream.  ``frames``: torch uint8 (T, 256, 256, 3) or one (256, 256, 3) frame,
+    unflipped as the sensor hands them over, on the device or pinned.  ``noise`` (T, 2 n_colours) fp64 is added to the features in the same
+    launch (experiment.py:135); ``pixels`` (T, n_colours) int32 receives the mask sizes.  Returns ``out``: (T, 2 n_colours) fp64 on the
+    device unless the caller passes its own (device or pinned) tensor.  A colour that is not in a frame gives NaN, like the reference."""
+    from . import _vision
+    torch = _torch()
+    frames, T = _frames_arg(frames)
+    m = 2 * int(n_colours)
+
+    def operand(t, name, dtype, cols):
+        if t is None:
+            return None
+        if t.dtype != dtype or tuple(t.shape) != (T, cols) or not t.is_contiguous() or not (t.is_cuda or t.is_pinned()):
+            raise ValueError(f'{name}: contiguous {dtype} tensor ({T}, {cols}) on the device or pinned')
+        return t.data_ptr()
+
+    if out is None:
+        out = torch.empty((T, m), dtype=torch.float64, device=frames.device if frames.is_cuda else current_device())
+    if T == 0:
+        return out
+    rc = _vision.lib().uvs_detect_circles_u8(T, frames.data_ptr(), frames.stride(0) if T > 1 else frames.shape[1] * frames.shape[2] * 3,
+                                             frames.shape[1], frames.shape[2], int(n_colours), operand(noise, 'noise', torch.float64, m),
+                                             operand(out, 'out', torch.float64, m), operand(pixels, 'pixels', torch.int32, int(n_colours)),
+                                             _stream())
+    _vision.check(rc)
+    return out
+
+
 class FilterBank:
     """T estimators whose state (X, P) stays in HBM between ``step`` calls: the drop-in used when the robot is external."""
 
@@ -311,6 +358,7 @@ class FilterBank:
         self.status = torch.zeros(T, dtype=torch.int32, device=device)
         self.first = True
         self._host = None
+        self._image, self._f_last = None, None                      # step_image's own records; the features its next call takes as f_old
 
     def _host_io(self):
         """Pinned host records the step kernel reads and writes in place (zero-copy: hipHostMalloc memory is mapped into the device's address
@@ -352,6 +400,76 @@ class FilterBank:
         h['calls'] += 1
         stream.synchronize()
         return views['dq'][i], views['err'][i], views['kappa'][i], views['status'][i]
+
+    def set_features(self, f0):
+        """The features in hand before the first ``step_image`` call -- the reference's ``f`` ahead of its loop: zeros, or the initial-guess
+        detection (experiment.py:76, :89).  The first call's f_old (experiment.py:128)."""
+        self._f_last = np.broadcast_to(np.asarray(f0, float), (self.T, self.fp.m)).copy()
+
+    def _image_io(self):
+        """What ``step_image`` adds to the pinned records of ``_host_io``: a frame buffer for callers that hand over numpy arrays, two noise
+        records, and the detector call of each parity with everything that does not change from step to step."""
+        from . import _vision
+        torch = _torch()
+        m, T = self.fp.m, self.T
+        if m // 2 not in _vision.N_COLOURS or m % 2:
+            raise ValueError(f'step_image: m = {m} features are not those of a circle detector (2, 6 or 8)')
+        h = self._host
+        noise = torch.zeros((2, T, m), dtype=torch.float64).pin_memory()
+        fn = _vision.lib().uvs_detect_circles_u8
+        img = dict(frames=None, shape=(T, _vision.SIDE, _vision.SIDE, 3), stride=_vision.SIDE * _vision.SIDE * 3,
+                   noise=noise, noise_np=noise.numpy(), noise_ptr=[noise[i].data_ptr() for i in (0, 1)])
+        img['call'] = [lambda src, stride, noise_ptr, stream, i=i: fn(T, src, stride, _vision.SIDE, _vision.SIDE, m // 2, noise_ptr,
+                                                                      h['ptr']['f'][i], None, stream) for i in (0, 1)]
+        img['check'] = _vision.check
+        if self._f_last is None:
+            self.set_features(np.zeros(m))
+        return img
+
+    def step_image(self, frames, k, noise=None, dq_prev=None):
+        """The fused live step: detector and estimator of one loop iteration (experiment.py:127-312) as two launches on one stream and one
+        synchronisation.  ``frames``: (T, 256, 256, 3) uint8 -- a numpy array (copied into a pinned buffer this bank owns) or a torch tensor
+        that is pinned or on the device (read in place); one (256, 256, 3) frame when T = 1.  ``noise`` (T, m) array-like or None is added to
+        the detection on the device.  The detector writes f into this call's pinned input record; f_old is the f of the previous
+        ``step_image`` call, noise included (experiment.py:128), and on the first call what ``set_features`` was given (default zeros).
+        Returns numpy views (dq, err, kappa, status, f) with the lifetime of ``step_host``'s."""
+        h = self._host
+        if h is None:
+            h = self._host = self._host_io()
+        img = self._image
+        if img is None:
+            img = self._image = self._image_io()
+        i = h['calls'] & 1
+        views = h['np']
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8:
+                raise ValueError('step_image: frames must be uint8')
+            if img['frames'] is None:                                # allocated once, on the first numpy frame
+                img['frames'] = _torch().zeros(img['shape'], dtype=_torch().uint8).pin_memory()
+                img['frames_np'] = img['frames'].numpy()
+            img['frames_np'][...] = frames.reshape(img['shape'])
+            src, stride = img['frames'].data_ptr(), img['stride']
+        else:
+            frames, T = _frames_arg(frames)
+            if tuple(frames.shape) != img['shape']:
+                raise ValueError(f'step_image: frames {tuple(frames.shape)} for a bank of {self.T} filters, expected {img["shape"]}')
+            src, stride = frames.data_ptr(), (frames.stride(0) if T > 1 else img['stride'])
+        noise_ptr = None
+        if noise is not None:
+            img['noise_np'][i][...] = noise
+            noise_ptr = img['noise_ptr'][i]
+        views['f_old'][i][...] = self._f_last
+        if dq_prev is not None:
+            views['dq'][1 - i][...] = dq_prev
+        stream = _torch().cuda.current_stream()
+        handle = C.c_void_p(stream.cuda_stream)
+        img['check'](img['call'][i](src, stride, noise_ptr, handle))
+        _lib.check(h['call'][i](int(self.first), int(k), h['ptr']['dq'][1 - i], handle))
+        self.first = False
+        h['calls'] += 1
+        stream.synchronize()
+        self._f_last = views['f'][i]
+        return views['dq'][i], views['err'][i], views['kappa'][i], views['status'][i], views['f'][i]
 
     def step(self, f, f_old, dq_prev, k):
         """f, f_old: (T, m), dq_prev: (T, n) cuda fp64 tensors.  Updates X, P in place; returns (dq, err, kappa, status)."""

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import engine
 from .plant import SyntheticRobot, camera_pose
-from .utils import gaussianKernel  # noqa: F401  (re-exported like the reference module namespace)
+from .utils import detect4Circles_device, gaussianKernel  # noqa: F401  (gaussianKernel re-exported like the reference module namespace)
 
 
 class Method(Enum):
@@ -43,7 +43,12 @@ def detect4Circles(image):
     return _detect(image)
 
 
+def _is_frame(image):
+    return isinstance(image, np.ndarray) and image.dtype == np.uint8
+
+
 _GPU_METHODS = (Method.KF, Method.MCKF, Method.IMCCKF, Method.GMCKF)
+PERCEPTION = ('host', 'device')
 
 
 def bandwidth_log(method, k, kernel_bw, annealing, t_s, t_max):
@@ -72,6 +77,11 @@ class Experiment:
                 self.annealing = method_params['annealing']
         self.lanes = int(method_params.get('lanes_per_filter', 0))
         self.x0 = method_params.get('x0')            # explicit initial state when initial_guess is False (reference: unseeded random)
+        # where camera frames of an external robot are turned into features: 'host' = utils.detect4Circles (numpy), 'device' = the HIP
+        # detector fused into the estimator step (FilterBank.step_image); feature carriers of synthetic robots keep the host hook
+        self.perception = method_params.get('perception', 'host')
+        if self.perception not in PERCEPTION:
+            raise ValueError(f"perception must be one of {PERCEPTION}, got {self.perception!r}")
         self.logger = logging.getLogger(__name__)
         if logger is not None:
             self.logger.setLevel(logger.level)
@@ -140,10 +150,14 @@ class Experiment:
         f = np.zeros(m)
         noise = np.zeros(m)
         x0 = None
+        on_device = self.perception == 'device'
         if self.initial_guess:
             image, resolution = robot.getCameraImage()
             try:
-                f = np.array(detect4Circles(image), float)
+                if on_device and _is_frame(image):
+                    f = np.array(detect4Circles_device(image), float)
+                else:
+                    f = np.array(detect4Circles(image), float)
             except Exception as exc:                                 # reference: log and continue (experiment.py:91-92)
                 self.logger.error(exc)
             x0 = self._analytic_guess(robot, f, resolution, m, n)
@@ -153,20 +167,35 @@ class Experiment:
             x0 = np.random.default_rng().random(m * n)               # experiment.py:117
         dev = torch.device('cuda')
         bank = engine.FilterBank(self._params(m, n, steps=0), 1, x0, dev)
+        bank.set_features(f)
         dq = np.zeros(n)
         status, k = ExperimentStatus.SUCCESS, 0
         while (t := robot.sim.getSimulationTime()) < self.t_max:
             image, resolution = robot.getCameraImage()
             f_old = f.copy()
-            try:
-                f = np.array(detect4Circles(image), float)
-                if self.noise_prof is not None:
-                    noise = self.noise_prof.getNoise()
-                    f += noise
-            except Exception as exc:
-                self.logger.error(exc)
+            fused = on_device and _is_frame(image)                   # detection, noise and step in one stream submission below
+            if not fused:
+                try:
+                    f = np.array(detect4Circles(image), float)
+                    if self.noise_prof is not None:
+                        noise = self.noise_prof.getNoise()
+                        f += noise
+                except Exception as exc:
+                    self.logger.error(exc)
             robot.computePose(recalculate_fkine=True)
-            dq_h, err_h, _, st = bank.step_host(f, f_old, k, dq)    # zero-copy: inputs and outputs in pinned host memory, one launch
+            out = None
+            if fused:
+                try:
+                    if self.noise_prof is not None:
+                        noise = self.noise_prof.getNoise()
+                    out = bank.step_image(image, k, noise if self.noise_prof is not None else None, dq)
+                except Exception as exc:                             # a frame the detector refuses: log, keep the old f, step on it
+                    self.logger.error(exc)
+            if out is None:
+                dq_h, err_h, _, st = bank.step_host(f, f_old, k, dq)    # zero-copy: inputs and outputs in pinned host memory, one launch
+            else:
+                dq_h, err_h, _, st, f_h = out
+                f = f_h[0].copy()
             if st[0] != 0:                                           # non-finite X: pinv would raise (experiment.py:313-316)
                 status = ExperimentStatus.FAIL
                 self.logger.error('Experiment failed')

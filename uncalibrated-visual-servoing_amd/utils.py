@@ -14,8 +14,10 @@ def gaussianKernel(e, bw):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Perception front-end of the live-simulator route: colour-threshold + centre-of-mass circle
-# detectors with the reference's names and return conventions (utils.py:11-166).  Host-side numpy: one 256x256 image per
-# step at batch size 1 is not device work.  The Hough variant needs OpenCV, which this image does not have.
+# detectors with the reference's names and return conventions (utils.py:11-166).  Two routes: host-side numpy (these functions, the
+# bit-exact restatement the fixtures hold), and the ``*_device`` functions below, one HIP launch for a batch of frames (libuvs_vision).
+# With the estimator step at 25 us per iteration the host detector is what a live loop pays for, so Experiment can fuse the device
+# detector into that step (method_params['perception'] = 'device').  The Hough variant needs OpenCV, which this image does not have.
 CENTER_OF_MASS = 0
 HOUGH_CIRCLES = 1
 
@@ -65,6 +67,32 @@ def detectRGBCircles(image, method=CENTER_OF_MASS):
 def detect4Circles(image, method=CENTER_OF_MASS):
     """utils.py:126-166: red, green, blue and pink circles, f in R^8."""
     return _detect(image, ('red', 'green', 'blue', 'pink'), method)
+
+
+def _detect_device(frames, n_colours):
+    """numpy (2 n_colours,) of one frame or (T, 2 n_colours) of a batch; frames: uint8 numpy array (copied to the device) or a torch tensor
+    on the device or pinned (read in place).  No numpy fallback: without the HIP library or a GPU this raises."""
+    from . import engine
+    torch = engine._torch()
+    if not torch.is_tensor(frames):
+        frames = torch.from_numpy(np.ascontiguousarray(frames)).to(engine.current_device())
+    f = engine.detect_circles(frames, n_colours).cpu().numpy()
+    return f[0] if frames.dim() == 3 else f
+
+
+def detectGreenCircle_device(frames):
+    """utils.py:11-51 (CENTER_OF_MASS) on the device."""
+    return _detect_device(frames, 1)
+
+
+def detectRGBCircles_device(frames):
+    """utils.py:53-124 (CENTER_OF_MASS) on the device."""
+    return _detect_device(frames, 3)
+
+
+def detect4Circles_device(frames):
+    """utils.py:126-166 (CENTER_OF_MASS) on the device."""
+    return _detect_device(frames, 4)
 
 
 def quat2euler(h):
