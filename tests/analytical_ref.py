@@ -1,7 +1,7 @@
 """Vectorised numpy restatement of the calibrated IBVS baseline (Method.ANALYTICAL, experiment.py:145-162 and :300-320) over a batch of
-trials, on the plant of oracle/plant_ref.py: the checker of uvs_analytical_closed_loop_f64.  Per step: f = project(q) + noise; J_image from
-the noisy raw-pixel u, v and the Euclidean camera-disc distance; J_feature = J_image kron(I2, R^T) J_robot; pinv raises on a non-finite
-J_feature (FAIL, k_done = k); dq = -gain pinv(J_feature) (f - desired); q += dq dt.  np.linalg.pinv on stacks follows numpy's cutoff."""
+trials, on the plant of oracle/plant_ref.py or on any DH / pinhole plant handed over (``plant=``): the checker of
+uvs_analytical_closed_loop_f64.  Per step: f = project(q) + noise; J_image from the noisy raw-pixel u, v and the
+Euclidean camera-disc distance; J_feature = J_image kron(I2, R^T) J_robot; pinv raises on a non-finite J_feature (FAIL, k_done = k); dq = -gain pinv(J_feature) (f - desired); q += dq dt.  np.linalg.pinv on stacks follows numpy's cutoff."""
 import numpy as np
 
 from oracle import plant_ref
@@ -19,10 +19,31 @@ def _dh_batch(theta, d, a, alpha):
     return rz @ rx
 
 
-def fkine_all_batch(q):
-    """plant_ref.fkine_all for (B, 6) joints: list of six (B, 4, 4) cumulative transforms."""
+PLANT_KEYS = ('theta_offset', 'd', 'a', 'alpha', 'focal', 'center', 'points')
+
+
+def plant_values(plant=None):
+    """dict of PLANT_KEYS from a plant description -- a uvs_amd.SyntheticPlant or a dict with any of those keys; what is missing (None:
+    everything) is the UR10 / pinhole plant of oracle/plant_ref.py with its discs."""
+    table = np.array(plant_ref.DH_TABLE)
+    out = dict(theta_offset=table[:, 0], d=table[:, 1], a=table[:, 2], alpha=table[:, 3], focal=plant_ref.FOCAL, center=plant_ref.CENTER, points=None)
+    if plant is not None:
+        unknown = set(plant) - set(PLANT_KEYS) if isinstance(plant, dict) else ()
+        assert not unknown, unknown
+        for key in PLANT_KEYS:
+            value = plant.get(key) if isinstance(plant, dict) else getattr(plant, key)
+            if value is not None:
+                out[key] = value
+    if out['points'] is None:
+        out['points'] = plant_ref.place_discs()
+    return {k: float(v) if k in ('focal', 'center') else np.array(v, float) for k, v in out.items()}
+
+
+def fkine_all_batch(q, plant=None):
+    """plant_ref.fkine_all for (B, 6) joints, on the DH table of ``plant`` (plant_values): list of six (B, 4, 4) cumulative transforms."""
+    pv = plant_values(plant)
     out, T = [], None
-    for i, (off, d, a, alpha) in enumerate(plant_ref.DH_TABLE):
+    for i, (off, d, a, alpha) in enumerate(zip(pv['theta_offset'], pv['d'], pv['a'], pv['alpha'])):
         link = _dh_batch(q[:, i] + off, d, a, alpha)
         T = link if i == 0 else T @ link
         out.append(T)
@@ -43,13 +64,15 @@ def geometric_jacobian_batch(Ts):
 
 
 def run(q_start, noise=None, desired=plant_ref.DESIRED_F, dt=0.05, t_max=15.0, gain=0.2, points=None, steps=None,
-        logs=('err', 'q', 'f', 'dq', 'j')):
-    """q_start (B, 6); noise (B, K, 8) or None.  Returns dict of the per-step streams named in ``logs`` (B, K, .) -- rows at and after
+        logs=('err', 'q', 'f', 'dq', 'j'), plant=None):
+    """q_start (B, 6); noise (B, K, 8) or None; ``plant``: a plant description (plant_values; None: oracle/plant_ref.py's), whose discs
+    ``points`` replaces when given.  Returns dict of the per-step streams named in ``logs`` (B, K, .) -- rows at and after
     k_done are zero -- plus status (B,), k_done (B,), stats (B, 3) = ||ISE||, ||IAE||, ||ITAE|| over the features, and t (K,).
     ``logs=()`` keeps only the statistics (full-size batches: the J stream of 65 536 trials is 7.5 GB)."""
     q = np.array(q_start, float).reshape(-1, 6).copy()
     B = q.shape[0]
-    discs = plant_ref.place_discs() if points is None else np.asarray(points, float)
+    pv = plant_values(plant)
+    discs = pv['points'] if points is None else np.asarray(points, float)
     P = len(discs)
     m = 2 * P
     desired = np.asarray(desired, float)
@@ -63,16 +86,16 @@ def run(q_start, noise=None, desired=plant_ref.DESIRED_F, dt=0.05, t_max=15.0, g
     acc = np.zeros((B, 3, m))                                    # per-feature sums of e^2, |e|, t |e| over the logged steps
     status, k_done = np.zeros(B, np.int32), np.full(B, K, np.int32)
     alive = np.ones(B, bool)
-    F = plant_ref.FOCAL
+    F, center = pv['focal'], pv['center']
     for k in range(K):
-        Ts = fkine_all_batch(q)
+        Ts = fkine_all_batch(q, pv)
         R, pos = Ts[5][:, :3, :3], Ts[5][:, :3, 3]
         f = np.zeros((B, m))
         Z = np.zeros((B, P))
         for i, d in enumerate(discs):
             pc = np.einsum('bji,bj->bi', R, d - pos)             # R^T (d - t)
-            f[:, 2 * i] = plant_ref.CENTER + F * pc[:, 0] / pc[:, 2]
-            f[:, 2 * i + 1] = plant_ref.CENTER + F * pc[:, 1] / pc[:, 2]
+            f[:, 2 * i] = center + F * pc[:, 0] / pc[:, 2]
+            f[:, 2 * i + 1] = center + F * pc[:, 1] / pc[:, 2]
             Z[:, i] = np.linalg.norm(pos - d, axis=1)
         if noise is not None:
             f = f + noise[:, k, :m]

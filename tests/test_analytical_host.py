@@ -105,6 +105,112 @@ def test_mix_hold_gate_is_the_trajectory_sensitivity():
     assert spread('analytical_a1p5') <= 1e-11
 
 
+# ---------------------------------------------------------------------------------------------- off the fixture path (tests/analytical_common.py)
+# The preconditions that give tests/test_gpu_analytical.py its teeth, on the restatement alone.
+def test_restatement_on_ur10_values_gives_the_default_bits(uvs):
+    import analytical_common as ac
+    default = ac.reference('base')
+    for plant in (uvs.SyntheticPlant.ur10(), ac.ur10_values(), {'focal': uvs.SyntheticPlant.ur10().focal}):
+        out = ac.restate(plant)
+        for key, ref in default.items():
+            assert out[key].tobytes() == ref.tobytes(), key
+
+
+@pytest.mark.parametrize('case, f_range, cond_max', [('tilted', (85.0, 290.0), 80.0), ('tilted_placed', (30.0, 225.0), 70.0)])
+def test_tilted_plant_is_healthy_and_calm(case, f_range, cond_max):
+    """Every trial SUCCESS, the features and cond(J) of every step in a calm range (measured: default discs [90.5, 282.3] and 74.6; discs placed
+    for the tilted plant [34.9, 219.9] and 64.0), and a 1e-14 shift of q0 moves q by 1.8e-14: the 1e-8 / 1e-10 gates are the kernel's to meet."""
+    import analytical_common as ac
+    ref = ac.reference(case)
+    assert not ref['status'].any() and np.all(ref['k_done'] == ac.K)
+    assert f_range[0] <= ref['f'].min() and ref['f'].max() <= f_range[1], (ref['f'].min(), ref['f'].max())
+    cond = np.linalg.cond(ref['j'].reshape(ac.T, ac.K, 8, 6))
+    assert cond.max() <= cond_max, cond.max()
+    assert ac.rdiag_spread(ref['j'].reshape(ac.T, ac.K, 8, 6)).max() <= 2.0 ** 10        # nowhere near the first pass's watch
+    moved = ac.restate(ac.plant_of(case), q0=ac.base_inputs()['q0'] + 1e-14, logs=('q',))
+    assert np.abs(moved['q'] - ref['q']).max() <= 1e-12
+
+
+@pytest.mark.parametrize('case', ['tilted', 'tilted_placed'])
+@pytest.mark.parametrize('group', ['alpha', 'd', 'a', 'theta_offset', 'focal', 'center'])
+def test_every_plant_parameter_group_moves_the_jacobian(case, group):
+    """With one group alone put back to its UR10 values the J stream of EVERY trial differs by >= 1e-6 relative: a kernel that ignores any one
+    group cannot pass the 1e-10 gate on any trial."""
+    import analytical_common as ac
+    assert group in ac.PLANT_GROUPS and len(ac.PLANT_GROUPS) == 6
+    ref = ac.reference(case)['j']
+    plant = dict(ac.plant_of(case))
+    plant[group] = ac.ur10_values()[group]
+    assert not np.array_equal(plant[group], ac.plant_of(case)[group])
+    other = ac.restate(plant, logs=('j',))['j']
+    d = np.abs(other - ref).reshape(ac.T, -1).max(axis=1) / np.abs(ref).reshape(ac.T, -1).max(axis=1)
+    assert d.min() >= 1e-6, d.min()
+
+
+def test_generalised_kinematics_against_finite_differences():
+    """kron(I2, R^T) J_robot of the restatement on the tilted plant against central differences (h = 1e-6) of its own forward kinematics: the
+    position columns from d pos, the angular ones from dR R^T.  Gate 1e-8 relative: truncation ~ h^2 = 1e-12, rounding ~ eps / h = 2e-10."""
+    import analytical_common as ac
+    import analytical_ref
+    plant, q, h = ac.tilted_values(), ac.base_inputs()['q0'], 1e-6
+    Ts = analytical_ref.fkine_all_batch(q, plant)
+    R = Ts[5][:, :3, :3]
+    Rt = np.transpose(R, (0, 2, 1))
+    Jg = analytical_ref.geometric_jacobian_batch(Ts)
+    Jc = np.concatenate([Rt @ Jg[:, :3], Rt @ Jg[:, 3:]], axis=1)                      # kron(I2, R^T) J_robot, (T, 6, 6)
+    fd = np.zeros_like(Jc)
+    for i in range(6):
+        step = np.zeros(6)
+        step[i] = h
+        hi, lo = (analytical_ref.fkine_all_batch(q + s, plant)[5] for s in (step, -step))
+        fd[:, :3, i] = np.einsum('bji,bj->bi', R, (hi[:, :3, 3] - lo[:, :3, 3]) / (2 * h))
+        W = (hi[:, :3, :3] - lo[:, :3, :3]) / (2 * h) @ Rt                             # dR R^T = [omega]x in the world frame
+        assert np.abs(W + np.transpose(W, (0, 2, 1))).max() <= 1e-8
+        omega = np.stack([W[:, 2, 1], W[:, 0, 2], W[:, 1, 0]], axis=1)
+        fd[:, 3:, i] = np.einsum('bji,bj->bi', R, omega)
+    for rows in (slice(0, 3), slice(3, 6)):
+        d = np.abs(Jc[:, rows] - fd[:, rows]).max() / np.abs(Jc[:, rows]).max()
+        assert d <= 1e-8, (rows, d)
+
+
+def test_mixed_wavefront_preconditions():
+    """What the outliers of the mixed case do, on the restatement: at the hit steps the |R_cc| spread of qr(J) is far beyond the first pass's
+    watch (measured 4e20 - 8e20 against 2^34), J has numerical rank 2 with sigma_3 / sigma_1 ~ 1e-22 - 3e-17 under numpy's 1e-15 cutoff and
+    sigma_2 / sigma_1 ~ 1e-11 above it, and a plain QR solve is nowhere near numpy's truncated command (~1e-12 against ~0.05: relative
+    difference 1.0); everywhere else spread <= 10.3 and cond <= 67; the hit trials' q moves by 1.8e-14 under a 1e-14 shift of q0; and the
+    three extra trials FAIL at steps 9, 23 and 30."""
+    import analytical_common as ac
+    ref = ac.reference('mixed')
+    J = ref['j'].reshape(ac.T, ac.K, 8, 6)
+    hits = [(t, ac.HIT_STEP) for t in ac.HIT] + [(64, 5)]
+    for t, k in hits:
+        assert k < ref['k_done'][t]
+        assert ac.rdiag_spread(J[t, k]) >= 1e6 * ac.WATCH
+        sv = np.linalg.svd(J[t, k], compute_uv=False)
+        assert np.linalg.matrix_rank(J[t, k]) == 2
+        assert sv[2] / sv[0] <= 1e-15 / 20 and sv[1] / sv[0] >= 1e-15 * 1e3, sv / sv[0]   # margins to numpy's cutoff on either side
+        cmd = ref['dq'][t, k]
+        plain = -ac.GAIN * ac.plain_qr_solve(J[t, k], ref['err'][t, k])
+        assert np.abs(cmd).max() <= 1e-10 and np.abs(plain).max() >= 1e-3
+        assert np.abs(plain - cmd).max() / np.abs(plain).max() >= 0.5
+    calm = np.arange(ac.K)[None, :] < ref['k_done'][:, None]
+    for t, k in hits:
+        calm[t, k] = False
+    assert ac.rdiag_spread(J[calm]).max() <= 16.0 and np.linalg.cond(J[calm]).max() <= 80.0
+    moved = ac.restate(None, ac.mixed_noise(), q0=ac.base_inputs()['q0'] + 1e-14, logs=('q',))
+    for t in ac.HIT:
+        assert np.abs(moved['q'][t] - ref['q'][t]).max() <= 1e-12
+    expect_status, expect_k = np.zeros(ac.T, np.int32), np.full(ac.T, ac.K, np.int32)
+    for t, k in ac.FAIL_AT.items():
+        expect_status[t], expect_k[t] = 1, k
+    assert ac.FAIL_AT == {20: 9, 41: 23, 64: 30}
+    assert np.array_equal(ref['status'], expect_status) and np.array_equal(ref['k_done'], expect_k)
+    base = ac.reference('base')                                             # the outliers touch no other trial of the restatement
+    for key in ('err', 'q', 'f', 'dq', 'j', 'stats'):
+        assert ref[key][list(ac.UNTOUCHED)].tobytes() == base[key][list(ac.UNTOUCHED)].tobytes(), key
+    assert len(ac.UNTOUCHED) == 63
+
+
 def test_new_kernels_have_no_scratch():
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import kernel_resources

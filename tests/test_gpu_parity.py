@@ -545,6 +545,30 @@ def test_stats_kernel_matches_matlab_definition(uvs):
         assert rel_err(got[j], trial_stats(err[j, :k_done[j]], t[:k_done[j]])) <= 1e-12
 
 
+@pytest.mark.parametrize('with_k_done', [True, False])
+@pytest.mark.parametrize('layout', ['kct', 'ktc', 'tkc'])
+@pytest.mark.parametrize('m', [2, 6, 8, 32])
+def test_stats_kernel_shapes_layouts_and_k_done(uvs, m, layout, with_k_done):
+    """The same definition at other feature counts, in the three layouts, over two blocks of which the second is one trial long (T = 257), with
+    k_done holding 0 and K, and with k_done = None (all K rows): against sums accumulated in np.longdouble, 1e-12 on every statistic."""
+    rng = np.random.default_rng(100 * m + len(layout))
+    K, T = 61, 257
+    err = rng.normal(size=(T, K, m)) * 10
+    t = uvs.engine.loop_clock(0.05, 15)[:K]
+    k_done = rng.integers(0, K + 1, T).astype(np.int32)
+    k_done[[0, 255, 256]] = 0, K, K - 1
+    k_done[[1, 254]] = K, 0
+    rows = k_done if with_k_done else np.full(T, K, np.int32)
+    e = np.where(np.arange(K)[None, :, None] < rows[:, None, None], err, 0.0).astype(np.longdouble)
+    sums = np.stack([(e * e).sum(axis=1), np.abs(e).sum(axis=1), (t.astype(np.longdouble)[None, :, None] * np.abs(e)).sum(axis=1)], axis=1)   # (T, 3, m)
+    ref = np.sqrt((sums * sums).sum(axis=2)).astype(np.float64)
+    assert np.all(ref[rows == 0] == 0) and np.all(ref[rows > 0] > 0)
+    dev = _cuda(err.transpose({'kct': (1, 2, 0), 'ktc': (1, 0, 2), 'tkc': (0, 1, 2)}[layout]))
+    got = uvs.engine.stats_reduce(dev, t, _cuda(k_done) if with_k_done else None, layout=layout).cpu().numpy()
+    assert got.shape == (T, 3)
+    assert np.all(np.abs(got - ref) <= 1e-12 * ref), float(np.abs(got / np.where(ref > 0, ref, 1) - 1).max())
+
+
 # ---------------------------------------------------------------------------------------------- bulk check against the C oracle
 def test_monte_carlo_batch_matches_c_oracle(uvs):
     """2 048 trials of BASELINE config 2 (alpha-stable alpha = 1.5, jittered starts, product noise generator) through the
