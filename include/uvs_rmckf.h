@@ -61,7 +61,13 @@ enum { UVS_STATUS_SUCCESS = 0, UVS_STATUS_FAIL = 1 };
  *   grows by 2^34 against its right-hand side (catches the Kahan-like Jacobian of tests/golden/rankdef_gmckf_kahan_c1000, whose entries give
  *   nothing away); normal-equation kernels (the (32,7) closed loop, the replay's control wavefronts): the spread of the Cholesky pivots, a
  *   factorisation that breaks down, and (round 6) a refinement step that does not converge (correction >= 2^-20 of the solution), which is how a
- *   Kahan-like Jacobian shows there -- and re-runs only the trials it marks. */
+ *   Kahan-like Jacobian shows there -- and re-runs only the trials it marks.
+ *   What the default mode promises, held over the condition range by tests/test_gpu_pinv_ladder.py against a multiprecision pinv: the plain
+ *   solve untruncated up to cond 1e13, and numpy's truncated command wherever a singular value below the cutoff shows in the factor's entries
+ *   or in the growth of the solution.  What it does NOT promise: a Kahan-like Jacobian below the cutoff whose right-hand side avoids the small
+ *   direction up to rounding (kappa o err orthogonal to u_min to 1e-16) -- the solution then grows only by what rounding puts into that
+ *   direction (1e5, not 2^34), no watch fires, and the plain command comes back: measured at (6,6), KF, off-diagonals -1000 / -3000, 6e16 to
+ *   1e19 perturbation bounds from numpy's command on the step route and the replay.  UVS_OPT_STRICT_PINV returns numpy's command there. */
 #define UVS_OPT_STRICT_PINV 1
 /* Small batches.  A closed-loop batch of the (8,6) shape that does not fill the chip (at most 16 384 trials; every estimator on the DH
  *   plant, lanes_per_filter == 0; MCKF too since round 5) runs with four lanes per filter instead of two -- half the trials per wavefront, twice the

@@ -75,14 +75,21 @@ static void features(const oracle_plant *pl, const double *Tc, double *f) {
     }
 }
 
-/* numpy.linalg.pinv(J) @ y through a one-sided Jacobi SVD of the taller of J / J^T.  Returns 0, or -1 when J is non-finite. */
+/* numpy.linalg.pinv(J) @ y through a one-sided Jacobi SVD of the taller of J / J^T.  Returns 0, or -1 when J is non-finite.
+ * The working copy is J times the power of two that brings its largest entry to [1, 2): the rotation test multiplies two squared column
+ * norms, which overflows from entries of 1e77 and underflows to 0 from 1e-77 (tests/test_pinv_ladder_host.py: Jacobians times 2^+-300 came
+ * back unrotated).  The scaling is exact, so every other result keeps its bits, and it leaves the result as out = out' * 2^-e. */
 static int pinv_apply(const double *J, int m, int n, const double *y, double *out) {
     for (int i = 0; i < m * n; ++i)
         if (!isfinite(J[i])) return -1;
     const int tall = m >= n, rows = tall ? m : n, cols = tall ? n : m;
     double A[MAXM * MAXM], V[MAXM * MAXM];                       /* A: rows x cols working copy, V: cols x cols */
+    double amax = 0;
+    for (int i = 0; i < m * n; ++i)
+        if (fabs(J[i]) > amax) amax = fabs(J[i]);
+    const int e2 = amax > 0 ? ilogb(amax) : 0;
     for (int r = 0; r < rows; ++r)
-        for (int c = 0; c < cols; ++c) A[r * cols + c] = tall ? J[r * n + c] : J[c * n + r];
+        for (int c = 0; c < cols; ++c) A[r * cols + c] = ldexp(tall ? J[r * n + c] : J[c * n + r], -e2);
     for (int i = 0; i < cols * cols; ++i) V[i] = 0;
     for (int i = 0; i < cols; ++i) V[i * cols + i] = 1;
     for (int sweep = 0; sweep < 60; ++sweep) {
@@ -138,6 +145,7 @@ static int pinv_apply(const double *J, int m, int n, const double *y, double *ou
             for (int i = 0; i < n; ++i) out[i] += A[i * cols + c] * vy;
         }
     }
+    for (int i = 0; i < n; ++i) out[i] = ldexp(out[i], -e2);
     return 0;
 }
 

@@ -512,9 +512,25 @@ struct Spread {
 // sol = pinv(Rm) c for a small square matrix through a one-sided Jacobi (Hestenes) SVD: columns of A = Rm are rotated until
 // mutually orthogonal, A = U diag(sigma), V accumulates the rotations, Rm = U diag(sigma) V^T.  numpy's cutoff: components with
 // sigma_j <= 1e-15 * sigma_max are dropped.  Only the careful kernels instantiate this (rare path; clarity over speed).
+// The rotation test multiplies two squared column norms, which overflows from entries of 1e77 on and underflows to zero below 1e-77 (a
+// Jacobian times 2^+-300 came back unrotated: tests/test_gpu_pinv_ladder.py), so the factor is first brought to a largest entry in [1, 2) by a
+// power of two.  That scaling is exact -- every rotation, singular value and projection scales with it, in the same bits -- and leaves the
+// solution as sol = sol' * 2^-e.
 template <int N>
 UVS_DEV void svd_solve(double (&A)[N][N], const double (&c)[N], double (&sol)[N]) {
     double V[N][N];
+    double amax = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j < N; ++j) amax = fmax(amax, fabs(A[i][j]));                 // (NaNs drop out of fmax and run through as before)
+    int e2 = (amax > 0.0 && amax < __builtin_inf()) ? ilogb(amax) : 0;
+    e2 = e2 > 1000 ? 1000 : (e2 < -1000 ? -1000 : e2);
+    const double down = ldexp(1.0, -e2);
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j < N; ++j) A[i][j] *= down;
 #pragma unroll
     for (int i = 0; i < N; ++i)
 #pragma unroll
@@ -572,6 +588,8 @@ UVS_DEV void svd_solve(double (&A)[N][N], const double (&c)[N], double (&sol)[N]
 #pragma unroll
         for (int i = 0; i < N; ++i) sol[i] = fma(V[i][j], w, sol[i]);
     }
+#pragma unroll
+    for (int i = 0; i < N; ++i) sol[i] *= down;
 }
 
 // ---------------------------------------------------------------- normal equations (wide-shape kernel, control-law wavefronts of the replay)
@@ -793,6 +811,13 @@ UVS_DEV bool lstsq_wide(const double (&J)[M][N], const double (&y)[M], double (&
             w[c] = (diag[c] != 0.0) ? rhs / diag[c] : 0.0;
         }
     }
+    // solution growth (Spread::grows), as in the tall solvers: the forward substitution's result against its right-hand side.  Without it
+    // the factor [[1, 0], [1e9, 1]] -- entries 1e9 apart, below the spread's 2^34, condition 1e18 -- returned the plain command, 1e18 times
+    // numpy's truncated one (tests/test_gpu_pinv_ladder.py, the hidden pair).  Changes only which solves are marked.
+    double smax = 0.0, ymax = 0.0;
+#pragma unroll
+    for (int c = 0; c < M; ++c) { smax = fmax(smax, fabs(w[c])); ymax = fmax(ymax, fabs(y[c])); }
+    const bool grows = !solved && spread.grows(smax, ymax);
 #pragma unroll
     for (int c = M - 1; c >= 0; --c) {
         double d = vp[c] * w[c];
@@ -805,7 +830,7 @@ UVS_DEV bool lstsq_wide(const double (&J)[M][N], const double (&y)[M], double (&
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) sol[j] = w[j];
-    return suspect;
+    return suspect || grows;
 }
 
 // dq = -gain * pinv(X.reshape(m, n)) @ (kappa o err)   (experiment.py:300-312); result replicated in the group
