@@ -73,6 +73,83 @@ int uvs_detect_circles_u8(int64_t T, const uint8_t *frames, int64_t frame_stride
                           const double *noise, double *f_out, int32_t *pixels_out,
                           void *stream);
 
+/*
+ * The synthetic camera: the sensor side of the same 256 x 256 frames.  A DH arm carries a pinhole camera that looks at up to four
+ * coloured discs; the entry points below project the discs, rasterise them into frames the detector above can read, and -- the loop's
+ * hot path -- return what the detector would return for those frames without ever writing them.
+ *
+ * The camera is this library's own description (nothing of uvs_rmckf.h is needed): the DH table as the uvs_plant struct of that header
+ * holds it (cos_alpha / sin_alpha computed by the host), the world points, the pinhole, and the physical disc radii in metres.
+ * Colour order of the points: red, green, blue, pink; with n_points == 1 the one disc is the green one.
+ */
+#define UVS_CAMERA_MAX_JOINTS 8
+#define UVS_CAMERA_MAX_POINTS 4
+
+typedef struct uvs_camera {
+    int32_t n_joints;                               /* 1 .. UVS_CAMERA_MAX_JOINTS */
+    int32_t n_points;                               /* 1, 3 or 4 */
+    double theta_offset[UVS_CAMERA_MAX_JOINTS];
+    double d[UVS_CAMERA_MAX_JOINTS];
+    double a[UVS_CAMERA_MAX_JOINTS];
+    double cos_alpha[UVS_CAMERA_MAX_JOINTS];
+    double sin_alpha[UVS_CAMERA_MAX_JOINTS];
+    double points[UVS_CAMERA_MAX_POINTS][3];        /* world coordinates */
+    double focal, center;                           /* pixels */
+    double radius[UVS_CAMERA_MAX_POINTS];           /* metres */
+} uvs_camera;
+
+/*
+ * Joint update and disc projection of T trials.
+ *   q_prev [T][n_joints] in; dq [T][n_joints] in or NULL.  With dq the joints are q = q_prev + dq * dt (one rounded multiply, then one
+ *     rounded add: the loop's new_q = q_now + dq * t_s), without it q = q_prev and dt is ignored.
+ *   q_out [T][n_joints] out or NULL: q.  It must not overlap q_prev.
+ *   discs_out [T][n_points][3] out: (u, v, r) in pixels of the flipped frame (u right, v down).  The camera pose is the product of the DH
+ *     links Rz(theta) Tz(d) Rx(alpha) Tx(a); per point pc = R^T (w - t), u = center + focal * pc0 / pc2, v = center + focal * pc1 / pc2,
+ *     r = focal * radius / pc2.  A point with pc2 <= 0 or a non-finite pc2 (behind the camera, NaN joints) gets r = -1: it is not drawn.
+ *     A disc renders as a circle of that radius: no perspective-correct ellipse.
+ * Errors: UVS_ERR_ARG for NULL cam / q_prev / discs_out, T < 0, n_joints outside 1 .. 8, n_points not in {1, 3, 4}, q_out overlapping
+ * q_prev.  T == 0 returns UVS_OK and launches nothing.
+ */
+int uvs_camera_project_f64(const uvs_camera *cam, int64_t T, const double *q_prev, const double *dq, double dt,
+                           double *q_out, double *discs_out, void *stream);
+
+/*
+ * Rasteriser: T frames [256][256][3] uint8 of n_colours discs, written UNFLIPPED as the sensor hands them over (flipped row i is stored
+ * at row 255 - i), frame t at frames + t * frame_stride_bytes.  Alignment and stride rules are the detector's: frames 16-byte aligned,
+ * frame_stride_bytes a multiple of 16 and at least 256 * 256 * 3; bytes beyond a frame's 196 608 are not written.
+ *   discs [T][n_colours][3] in: (u, v, r) as uvs_camera_project_f64 writes them.
+ * The pixel rule is part of the contract.  Pixel (flipped row i, column j) belongs to disc c iff r_c >= 0 and
+ *   fl(fl(dx * dx) + fl(dy * dy)) <= fl(r_c * r_c),   dx = (double)j - u_c,  dy = (double)i - v_c;
+ * a NaN anywhere gives nothing.  The painter's order is the colour order (a later disc overwrites an earlier one); the colours are
+ * (255,0,0), (0,255,0), (0,0,255), (255,0,255), with n_colours == 1 the one disc is green; every other pixel is `background` in all
+ * three channels.
+ * Errors: UVS_ERR_ARG for NULL discs / frames, T < 0, n_colours not in {1, 3, 4}, background outside 0 .. 249 (250 and above would
+ * enter a mask of the detector), a misaligned frames pointer, a stride below 256 * 256 * 3 or not a multiple of 16.  T == 0 returns
+ * UVS_OK and launches nothing.  One workgroup per frame, 16-byte stores.
+ */
+int uvs_render_discs_u8(int64_t T, const double *discs, int32_t n_colours, int32_t background, uint8_t *frames,
+                        int64_t frame_stride_bytes, void *stream);
+
+/*
+ * The frame-free detector: what uvs_detect_circles_u8 returns for the frames uvs_render_discs_u8 writes from `discs`, bit for bit
+ * (features, NaN pairs of empty masks, mask sizes, noise epilogue), without the frames.  Thread (colour c, index i) counts the rows at
+ * which c is the topmost disc in column i and the columns at which it is topmost in row i, visiting only the disc's bounding box
+ * [centre - r - 1, centre + r + 1] clipped to the frame; the sums that follow are the detector's own code.
+ *   discs [T][n_colours][3] in; noise [T][2*n_colours] in or NULL; f_out [T][2*n_colours] out; pixels_out [T][n_colours] int32 out or NULL.
+ * Errors: UVS_ERR_ARG for NULL discs / f_out, T < 0, n_colours not in {1, 3, 4}.  T == 0 returns UVS_OK and launches nothing.
+ */
+int uvs_disc_features_f64(int64_t T, const double *discs, int32_t n_colours, const double *noise, double *f_out,
+                          int32_t *pixels_out, void *stream);
+
+/*
+ * uvs_camera_project_f64 and uvs_disc_features_f64 in one launch (one workgroup per trial), bit-identical to the two calls in a row:
+ * joints in, noisy detected features out.  Arguments as above with n_colours = cam->n_points; discs_out [T][n_points][3] out or NULL.
+ * Errors: those of the two calls (f_out takes the place of discs_out as the mandatory output).
+ */
+int uvs_camera_features_f64(const uvs_camera *cam, int64_t T, const double *q_prev, const double *dq, double dt,
+                            double *q_out, const double *noise, double *f_out, int32_t *pixels_out, double *discs_out,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

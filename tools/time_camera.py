@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Time the synthetic camera on the device, in one run on one GPU box:
+  (a) engine.render_discs followed by engine.detect_circles, frames resident in HBM, at T = 1, 64 and 4 096;
+  (b) engine.disc_features on the same discs: the frame-free detector, which moves no frame;
+  (c) engine.camera_features: projection and frame-free detection in one launch, from the joints;
+  (d) engine.camera_closed_loop at T = 1 024, K = 299 (two launches per step), wall clock, and next to it engine.closed_loop on the same
+      trials as context -- ideal features, plant in the kernel: a different computation, not a gate.  The loop is timed twice: as called
+      (the analytic initial guess of every trial is host work inside the call) and with x0 handed in (the loop alone).
+(a)-(c) are HIP-event times around the launches, taken in alternating blocks so that all three see the same machine state; every figure is
+the median of 250 iterations after a warm-up, with the 10th and 90th percentile.  The acceptance condition is (b) below (a) at every T.
+Writes profiles/camera_device.txt (or the path given).  usage: tools/time_camera.py [out.txt]"""
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import uvs_amd as uvs  # noqa: E402
+import torch  # noqa: E402
+
+OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'profiles', 'camera_device.txt')
+ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
+Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
+DESIRED = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+lines = []
+
+
+def say(text=''):
+    print(text, flush=True)
+    lines.append(text)
+
+
+def stats(us):
+    us = np.asarray(us)
+    return float(np.median(us)), float(np.percentile(us, 10)), float(np.percentile(us, 90))
+
+
+def fmt(us):
+    med, lo, hi = stats(us)
+    return f'{med:10.1f} us   (p10 {lo:.1f}, p90 {hi:.1f}, n = {len(us)})'
+
+
+def alternate(fns, rounds=ROUNDS, block=BLOCK, warm=WARM):
+    """HIP-event time of every call of every function, in alternating blocks."""
+    for fn in fns.values():
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    events = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            for _ in range(block):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                events[name].append((e0, e1))
+        torch.cuda.synchronize()
+    return {name: [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev] for name, ev in events.items()}
+
+
+plant = uvs.SyntheticPlant.ur10()
+cam = plant.to_camera()                              # the uvs_camera struct, built once: the wrappers take it in place of the plant
+rng = np.random.default_rng(2025)
+say(f'# tools/time_camera.py on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+    f'{uvs.lib().uvs_version().decode()}')
+say(f'# (a)-(c): HIP events, medians of {ROUNDS} x {BLOCK} iterations in alternating blocks after {WARM} warm-up calls; discs of radius '
+    f'{uvs.plant.DISC_RADIUS} m seen from joints within 0.05 rad of the goal pose')
+say()
+ok = True
+for T in (1, 64, 4096):
+    q = torch.as_tensor(Q_GOAL + rng.uniform(-0.05, 0.05, (T, 6)), device='cuda')
+    discs = uvs.engine.camera_project(cam, q)
+    frames = torch.empty((T, 256, 256, 3), dtype=torch.uint8, device='cuda')
+    f_a, f_b, f_c = (torch.empty((T, 8), dtype=torch.float64, device='cuda') for _ in range(3))
+
+    def run_a():
+        uvs.engine.render_discs(discs, out=frames)
+        uvs.engine.detect_circles(frames, out=f_a)
+
+    us = alternate({'a': run_a, 'b': lambda: uvs.engine.disc_features(discs, out=f_b), 'c': lambda: uvs.engine.camera_features(cam, q, out=f_c)})
+    torch.cuda.synchronize()
+    same = torch.equal(f_a.view(torch.int64), f_b.view(torch.int64)) and torch.equal(f_b.view(torch.int64), f_c.view(torch.int64))
+    assert bool(torch.isfinite(f_a).all()) and same, 'the three routes disagree'
+    a, b = stats(us['a'])[0], stats(us['b'])[0]
+    ok = ok and b < a
+    say(f'T = {T}')
+    say(f'  (a) render_discs + detect_circles (frames in HBM)  {fmt(us["a"])}')
+    say(f'  (b) disc_features (no frame)                       {fmt(us["b"])}')
+    say(f'  (c) camera_features (from the joints, one launch)  {fmt(us["c"])}')
+    say(f'  (b) / (a) = {b / a:.3f}: (b) is {"BELOW" if b < a else "NOT below"} (a); features of (a), (b), (c) bit-identical')
+say()
+say(f'acceptance: (b) below (a) at every T: {"yes" if ok else "NO"}')
+
+# ---- (d) the loop through pixels, wall clock
+T, K = 1024, 299
+fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+assert fp.steps == K
+q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+q0[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+q0_d = torch.as_tensor(q0, device='cuda')
+noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+noise_kct = noise.permute(0, 2, 1).contiguous()                      # closed_loop's default layout [step][component][trial]
+
+
+def wall(fn, n=5):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return ms
+
+
+out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise)
+torch.cuda.synchronize()
+ms_pixels = wall(lambda: uvs.engine.camera_closed_loop(fp, plant, q0_d, noise))
+# the same with the initial guess handed in: what is left is the loop itself (2 K launches, their ctypes calls, the logs' allocation)
+f0 = uvs.engine.camera_features(plant, q0_d).cpu().numpy()
+robot, x0 = uvs.SyntheticRobot(plant, 0.05), np.empty((T, 48))
+for t in range(T):
+    robot.start(q0[t])
+    x0[t] = uvs.plant.analytic_guess(robot, f0[t], (256, 256), 8, 6)
+x0_d = torch.as_tensor(x0, device='cuda')
+given = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise, x0=x0_d)
+assert all(torch.equal(given[key].view(torch.int64), out[key].view(torch.int64)) for key in ('err', 'q', 'f', 'dq'))
+ms_loop = wall(lambda: uvs.engine.camera_closed_loop(fp, plant, q0_d, noise, x0=x0_d))
+ideal = uvs.engine.closed_loop(fp, plant.to_struct(), q0_d, noise_kct, want=('err', 'q'))
+ms_ideal = wall(lambda: uvs.engine.closed_loop(fp, plant.to_struct(), q0_d, noise_kct, want=('err', 'q')))
+say()
+say(f'(d) T = {T}, K = {K}, GMCKF, white noise 0.3 px; wall clock of {len(ms_pixels)} runs after one warm-up run, host work (analytic guess per trial, '
+    'allocation) included')
+say(f'  camera_closed_loop (through pixels, 2 launches per step)   median {np.median(ms_pixels):9.1f} ms   (min {min(ms_pixels):.1f}, max {max(ms_pixels):.1f})'
+    f'   = {np.median(ms_pixels) / K * 1e3:.1f} us per step')
+say(f'  the same with x0 handed in (the loop alone)                median {np.median(ms_loop):9.1f} ms   (min {min(ms_loop):.1f}, max {max(ms_loop):.1f})'
+    f'   = {np.median(ms_loop) / K * 1e3:.1f} us per step')
+say(f'  closed_loop (ideal features, plant in the kernel; context) median {np.median(ms_ideal):9.1f} ms   (min {min(ms_ideal):.1f}, max {max(ms_ideal):.1f})')
+done = out['k_done'].cpu().numpy()
+say(f'  through pixels: {int((out["status"] == 0).sum())} of {T} trials SUCCESS, smallest mask {int(out["pixels"].min())} px; '
+    f'median ISE / IAE / ITAE {np.median(out["stats"].cpu().numpy()[done == K], axis=0).round(3).tolist()}')
+say(f'  ideal features: {int((ideal["status"] == 0).sum())} of {T} trials SUCCESS; '
+    f'median ISE / IAE / ITAE {np.median(ideal["stats"].cpu().numpy(), axis=0).round(3).tolist()}')
+
+os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+open(OUT, 'w').write('\n'.join(lines) + '\n')

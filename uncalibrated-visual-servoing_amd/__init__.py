@@ -9,7 +9,7 @@ from . import _lib, _vision, utils, noise, pcg, plant, engine, noise_device, exp
 from ._lib import UvsError, UvsLibraryError, build, lib  # noqa: F401
 from .experiment import Experiment, ExperimentStatus, Method  # noqa: F401
 from .noise import NoiseProfiler, NoiseType, noise_batch  # noqa: F401
-from .plant import LinearPlant, SyntheticPlant, SyntheticRobot  # noqa: F401
+from .plant import CameraRobot, LinearPlant, SyntheticPlant, SyntheticRobot  # noqa: F401
 from .utils import gaussianKernel  # noqa: F401
 
 __version__ = "0.6.0"

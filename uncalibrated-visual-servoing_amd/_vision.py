@@ -1,4 +1,4 @@
-"""ctypes binding of libuvs_vision.so (include/uvs_vision.h): the circle detectors of the live route on the device.
+"""ctypes binding of libuvs_vision.so (include/uvs_vision.h): the circle detectors of the live route and the synthetic camera on the device.
 
 Like ``_lib``: no CPU fallback.  If the HIP library is missing or fails to load, ``lib()`` raises ``UvsLibraryError`` -- the device route
 never substitutes the numpy detectors of ``utils``.
@@ -16,12 +16,29 @@ CSRC = os.path.join(HERE, 'csrc_vision')
 SIDE = 256                                                          # UVS_VISION_SIDE
 N_COLOURS = (1, 3, 4)                                               # green | red, green, blue | red, green, blue, pink
 
+MAX_JOINTS, MAX_POINTS = 8, 4                                       # UVS_CAMERA_MAX_JOINTS, UVS_CAMERA_MAX_POINTS
+
+
+class Camera(C.Structure):
+    """uvs_camera of include/uvs_vision.h (plant.SyntheticPlant.to_camera fills it)."""
+    _fields_ = [('n_joints', C.c_int32), ('n_points', C.c_int32),
+                ('theta_offset', C.c_double * MAX_JOINTS), ('d', C.c_double * MAX_JOINTS), ('a', C.c_double * MAX_JOINTS),
+                ('cos_alpha', C.c_double * MAX_JOINTS), ('sin_alpha', C.c_double * MAX_JOINTS),
+                ('points', (C.c_double * 3) * MAX_POINTS), ('focal', C.c_double), ('center', C.c_double),
+                ('radius', C.c_double * MAX_POINTS)]
+
+
 # name -> (restype, argtypes); every symbol include/uvs_vision.h declares
-_VP, _I64, _I32 = C.c_void_p, C.c_int64, C.c_int32
+_VP, _I64, _I32, _F64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double
+_CAM = C.POINTER(Camera)
 SYMBOLS = {
     'uvs_vision_version': (C.c_char_p, []),
     'uvs_vision_last_error': (C.c_char_p, []),
     'uvs_detect_circles_u8': (C.c_int, [_I64, _VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    'uvs_camera_project_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _VP]),
+    'uvs_render_discs_u8': (C.c_int, [_I64, _VP, _I32, _I32, _VP, _I64, _VP]),
+    'uvs_disc_features_f64': (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP, _VP]),
+    'uvs_camera_features_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

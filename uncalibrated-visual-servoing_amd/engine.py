@@ -341,6 +341,186 @@ def detect_circles(frames, n_colours=4, noise=None, out=None, pixels=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- synthetic camera
+def _operand(t, name, dtype, shape, optional=False):
+    """data_ptr of a contiguous device-or-pinned tensor of the given dtype and shape (None for an optional one that is absent)."""
+    if t is None and optional:
+        return None
+    torch = _torch()
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not (t.is_cuda or t.is_pinned()):
+        raise ValueError(f'{name}: contiguous {dtype} tensor {tuple(shape)} on the device or pinned')
+    return t.data_ptr()
+
+
+def _camera(plant, radius):
+    from . import _vision
+    return plant if isinstance(plant, _vision.Camera) else plant.to_camera(radius)
+
+
+def _device_of(*tensors):
+    for t in tensors:
+        if t is not None and t.is_cuda:
+            return t.device
+    return current_device()
+
+
+def camera_project(plant, q_prev, dq=None, dt=0.0, radius=None, q_out=None, out=None):
+    """Disc projection of T trials on the current stream (uvs_camera_project_f64).  ``plant``: a ``SyntheticPlant`` (with ``radius`` in metres,
+    default plant.DISC_RADIUS) or the ``uvs_camera`` struct of ``SyntheticPlant.to_camera``.  ``q_prev`` (T, n) fp64; with ``dq`` (T, n) the joints
+    are q_prev + dq * dt, written to ``q_out`` (T, n) when given.  Returns ``out``: (T, n_points, 3) rows (u, v, r) in pixels; r = -1 for a point
+    that is not in front of the camera."""
+    from . import _vision, plant as plant_mod
+    torch = _torch()
+    cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    T, n = q_prev.shape[0], cam.n_joints
+    if out is None:
+        out = torch.empty((T, cam.n_points, 3), dtype=torch.float64, device=_device_of(q_prev))
+    rc = _vision.lib().uvs_camera_project_f64(C.byref(cam), T, _operand(q_prev, 'q_prev', torch.float64, (T, n)),
+                                              _operand(dq, 'dq', torch.float64, (T, n), True), float(dt),
+                                              _operand(q_out, 'q_out', torch.float64, (T, n), True),
+                                              _operand(out, 'out', torch.float64, (T, cam.n_points, 3)), _stream())
+    _vision.check(rc)
+    return out
+
+
+def _discs_arg(discs, n_colours):
+    torch = _torch()
+    if not torch.is_tensor(discs) or discs.dim() != 3 or tuple(discs.shape[1:]) != (int(n_colours), 3):
+        raise ValueError(f'discs: a torch fp64 tensor (T, {int(n_colours)}, 3) of rows (u, v, r)')
+    return discs.shape[0], _operand(discs, 'discs', torch.float64, discs.shape)
+
+
+def render_discs(discs, n_colours=4, background=96, out=None):
+    """Rasterise ``discs`` (T, n_colours, 3) fp64 rows (u, v, r) into camera frames on the current stream (uvs_render_discs_u8; the pixel rule
+    is ``plant.render_discs``'s, byte for byte).  Returns ``out``: uint8 (T, 256, 256, 3), unflipped as the detectors expect them, on the device
+    unless the caller passes its own device or pinned tensor -- whose frame stride is free (bytes between frames are not written)."""
+    from . import _vision
+    torch = _torch()
+    T, ptr = _discs_arg(discs, n_colours)
+    if out is None:
+        out = torch.empty((T, _vision.SIDE, _vision.SIDE, 3), dtype=torch.uint8, device=_device_of(discs))
+    frames, Tf = _frames_arg(out)
+    if Tf != T or tuple(frames.shape[1:3]) != (_vision.SIDE, _vision.SIDE):
+        raise ValueError(f'out: ({T}, 256, 256, 3) uint8, got {tuple(out.shape)}')
+    rc = _vision.lib().uvs_render_discs_u8(T, ptr, int(n_colours), int(background), frames.data_ptr(),
+                                           frames.stride(0) if T > 1 else _vision.SIDE * _vision.SIDE * 3, _stream())
+    _vision.check(rc)
+    return out
+
+
+def disc_features(discs, n_colours=4, noise=None, out=None, pixels=None):
+    """The frame-free detector (uvs_disc_features_f64): what ``detect_circles(render_discs(discs))`` returns, bit for bit, in one launch that
+    never writes a frame.  Arguments and result as ``detect_circles`` with ``discs`` (T, n_colours, 3) in place of the frames."""
+    from . import _vision
+    torch = _torch()
+    T, ptr = _discs_arg(discs, n_colours)
+    m = 2 * int(n_colours)
+    if out is None:
+        out = torch.empty((T, m), dtype=torch.float64, device=_device_of(discs))
+    rc = _vision.lib().uvs_disc_features_f64(T, ptr, int(n_colours), _operand(noise, 'noise', torch.float64, (T, m), True),
+                                             _operand(out, 'out', torch.float64, (T, m)),
+                                             _operand(pixels, 'pixels', torch.int32, (T, int(n_colours)), True), _stream())
+    _vision.check(rc)
+    return out
+
+
+def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_out=None, out=None, pixels=None, discs=None):
+    """``camera_project`` and ``disc_features`` in one launch (uvs_camera_features_f64), bit-identical to the two in a row: joints in, noisy
+    detected features (T, 2 n_points) out.  ``discs`` (T, n_points, 3) receives the projection when given."""
+    from . import _vision, plant as plant_mod
+    torch = _torch()
+    cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    T, n, npts = q_prev.shape[0], cam.n_joints, cam.n_points
+    if out is None:
+        out = torch.empty((T, 2 * npts), dtype=torch.float64, device=_device_of(q_prev))
+    rc = _vision.lib().uvs_camera_features_f64(C.byref(cam), T, _operand(q_prev, 'q_prev', torch.float64, (T, n)),
+                                               _operand(dq, 'dq', torch.float64, (T, n), True), float(dt),
+                                               _operand(q_out, 'q_out', torch.float64, (T, n), True),
+                                               _operand(noise, 'noise', torch.float64, (T, 2 * npts), True),
+                                               _operand(out, 'out', torch.float64, (T, 2 * npts)),
+                                               _operand(pixels, 'pixels', torch.int32, (T, npts), True),
+                                               _operand(discs, 'discs', torch.float64, (T, npts, 3), True), _stream())
+    _vision.check(rc)
+    return out
+
+
+def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None):
+    """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
+    plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
+    radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
+    None: with fp.initial_guess the analytic guess (plant.analytic_guess) per trial from the noise-free detection at q_start -- which is also
+    the first step's f_old (zeros without initial_guess, where x0 must be given).
+    Step k is two launches on the current stream and no synchronisation: uvs_camera_features_f64 (q_log[k-1], dq_log[k-1] -> q_log[k], f_log[k])
+    and uvs_rmckf_step_f64 (-> dq_log[k], err_log[k], kappa_log[k], status_log[k]), each on rows of the logs, which are plain (K, T, comp)
+    tensors.  A disc that leaves the frame gives NaN features, a non-finite X and FAIL at that step, as the reference's loop ends on a NaN
+    detection.  Returns a dict: 'err', 'q', 'f', 'dq', 'kappa' (K, T, comp; rows at and after k_done unspecified), 'pixels' (T, n_points) the
+    smallest mask per colour over the steps up to and including k_done, 'status', 'k_done' (T,) int32, 'stats' (T, 3)."""
+    from . import _vision, plant as plant_mod
+    torch = _torch()
+    K, m, n = fp.steps, fp.m, fp.n
+    T, dev = q_start.shape[0], q_start.device
+    if K < 1 or T < 1:
+        raise ValueError('camera_closed_loop: at least one step (fp.steps) and one trial')
+    if not q_start.is_cuda:
+        raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
+    if not isinstance(plant, plant_mod.SyntheticPlant):
+        raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
+    cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    npts = cam.n_points
+    if m != 2 * npts or n != cam.n_joints:
+        raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * npts} features of {cam.n_joints} joints')
+    q0 = _operand(q_start, 'q_start', torch.float64, (T, n))
+    noise_ptr = _operand(noise, 'noise', torch.float64, (K, T, m), True)
+    f64 = dict(dtype=torch.float64, device=dev)
+    f0 = torch.zeros((T, m), **f64)
+    if fp.initial_guess:
+        camera_features(cam, q_start, out=f0)
+        if x0 is None:
+            f_host, q_host = f0.cpu().numpy(), q_start.cpu().numpy()
+            x0 = np.empty((T, m * n))
+            robot = plant_mod.SyntheticRobot(plant, fp.dt)
+            for t in range(T):
+                robot.start(q_host[t])
+                x0[t] = plant_mod.analytic_guess(robot, f_host[t], (plant_mod.RESOLUTION, plant_mod.RESOLUTION), m, n)
+    if x0 is None:
+        raise ValueError('camera_closed_loop: x0 is needed when fp.initial_guess is 0 (the reference draws it unseeded, experiment.py:117)')
+    X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
+    P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
+    log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
+    status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
+    pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
+    dq_zero = torch.zeros((T, n), **f64)
+    features, step = _vision.lib().uvs_camera_features_f64, _lib.lib().uvs_rmckf_step_f64
+    cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
+    row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
+    at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
+    noise_row = 0 if noise is None else noise.stride(0) * 8
+    for k in range(K):
+        q_prev, dq_prev, f_old = (q0, None, f0.data_ptr()) if k == 0 else (at('q', k - 1), at('dq', k - 1), at('f', k - 1))
+        _vision.check(features(cam_ref, T, q_prev, dq_prev, fp.dt, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k),
+                               at('pixels', k), None, stream))
+        _lib.check(step(fp_ref, T, X.data_ptr(), P.data_ptr(), at('f', k), f_old, dq_zero.data_ptr() if k == 0 else dq_prev, int(k == 0), k,
+                        at('dq', k), at('err', k), at('kappa', k), at('status', k), stream))
+    failed = status_log != 0
+    steps = torch.arange(K, device=dev, dtype=torch.int32)[:, None]
+    k_done = torch.where(failed, steps, torch.full_like(steps, K)).amin(0)          # the first FAIL, else K
+    status = (k_done < K).to(torch.int32)
+    seen = steps <= k_done[None, :]                                  # the failing step's own masks count: an empty one shows as 0
+    pixels = torch.where(seen[:, :, None], pixel_log, torch.full_like(pixel_log, 2 ** 31 - 1)).amin(0)
+    out = dict(log, pixels=pixels, status=status, k_done=k_done)
+    out['stats'] = stats_reduce(log['err'], _loop_times(fp.dt, K), k_done, layout='ktc')
+    return out
+
+
+def _loop_times(t_s, K):
+    """The first K times of ``loop_clock``: t_s accumulated in floating point."""
+    ts, t = [], 0.0 + t_s
+    for _ in range(K):
+        ts.append(t)
+        t += t_s
+    return np.array(ts)
+
+
 class FilterBank:
     """T estimators whose state (X, P) stays in HBM between ``step`` calls: the drop-in used when the robot is external."""
 

@@ -16,7 +16,7 @@ from enum import Enum
 import numpy as np
 
 from . import engine
-from .plant import SyntheticRobot, camera_pose
+from .plant import SyntheticRobot, analytic_guess, camera_pose
 from .utils import detect4Circles_device, gaussianKernel  # noqa: F401  (gaussianKernel re-exported like the reference module namespace)
 
 
@@ -214,14 +214,4 @@ class Experiment:
         return (status, logs['t'][:k], logs['err'][:k], logs['q'][:k], logs['f'][:k], logs['des'][:k], logs['cam'][:k],
                 logs['noise'][:k], self._bandwidth_log(k))
 
-    @staticmethod
-    def _analytic_guess(robot, f, resolution, m, n):
-        """X0 for an external robot (experiment.py:94-114), evaluated once on the host from the robot's own kinematics."""
-        depth = robot.computeZ(m // 2)
-        focal = resolution[0] / (2 * np.tan(0.5 * np.deg2rad(robot.perspective_angle)))
-        Ji = np.zeros((m, 6))
-        for i in range(m // 2):
-            u, v = f[2 * i], f[2 * i + 1]
-            Ji[2 * i] = [-focal / depth[i], 0.0, u / depth[i], u * v / focal, -(focal ** 2 + u ** 2) / focal, v]
-            Ji[2 * i + 1] = [0.0, -focal / depth[i], v / depth[i], (focal ** 2 + v ** 2) / focal, -u * v / focal, -u]
-        return (Ji @ np.kron(np.eye(2), robot.getCameraRotation().T) @ robot.jacobian()).reshape(m * n)
+    _analytic_guess = staticmethod(analytic_guess)                   # X0 for an external robot (experiment.py:94-114); engine.camera_closed_loop's too

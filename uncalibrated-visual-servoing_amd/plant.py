@@ -15,6 +15,8 @@ from . import _lib
 
 RESOLUTION = 256
 FOV_DEG = 65.0
+DISC_RADIUS = 0.024                     # metres: 8.01 px at SyntheticPlant.ur10()'s goal pose (CameraRobot)
+DISC_COLOURS = ((255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 0, 255))       # red, green, blue, pink (utils.py:126-166)
 
 
 def focal_length(resolution=RESOLUTION, fov_deg=FOV_DEG):
@@ -33,6 +35,44 @@ def camera_pose(T):
     pose[4] = np.arcsin(np.clip(-T[2, 0], -1.0, 1.0))
     pose[5] = np.arctan2(T[1, 0], T[0, 0])
     return pose
+
+
+def render_discs(discs, n_colours=4, background=96):
+    """Camera frames of coloured discs: the numpy statement of the pixel rule uvs_render_discs_u8 (include/uvs_vision.h) is held to.
+    ``discs``: (n_colours, 3) or (T, n_colours, 3) rows (u, v, r) in pixels of the flipped frame (u right, v down), colour order red,
+    green, blue, pink (n_colours == 1: the green disc).  Pixel (flipped row i, column j) belongs to disc c iff r_c >= 0 and
+    fl(fl(dx * dx) + fl(dy * dy)) <= fl(r_c * r_c) with dx = j - u_c, dy = i - v_c; a NaN gives nothing; a later disc overwrites an earlier
+    one; everything else is ``background``.  A disc is drawn as a circle (no perspective-correct ellipse).  Returns uint8 (256, 256, 3) or
+    (T, 256, 256, 3), UNFLIPPED as the sensor hands frames over (flipped row i is row 255 - i)."""
+    discs = np.asarray(discs, float)
+    if n_colours not in (1, 3, 4) or discs.shape[-2:] != (n_colours, 3) or discs.ndim not in (2, 3):
+        raise ValueError(f'discs: (n_colours, 3) or (T, n_colours, 3) with n_colours in (1, 3, 4), got {discs.shape} for n_colours = {n_colours}')
+    if not 0 <= background < 250:
+        raise ValueError('background must be 0 .. 249: 250 and above would enter a mask of the detectors')
+    batch = discs.reshape((-1,) + discs.shape[-2:])
+    grid = np.arange(RESOLUTION, dtype=float)
+    frames = np.full((len(batch), RESOLUTION, RESOLUTION, 3), background, np.uint8)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for frame, scene in zip(frames, batch):
+            for c, (u, v, r) in enumerate(scene):
+                if not r >= 0:
+                    continue
+                dx, dy = grid[None, :] - u, grid[:, None] - v
+                frame[(dx * dx + dy * dy) <= r * r] = DISC_COLOURS[1 if n_colours == 1 else c]
+    frames = frames[:, ::-1].copy()
+    return frames[0] if discs.ndim == 2 else frames
+
+
+def analytic_guess(robot, f, resolution, m, n):
+    """X0 for an external robot (experiment.py:94-114), evaluated once on the host from the robot's own kinematics."""
+    depth = robot.computeZ(m // 2)
+    focal = resolution[0] / (2 * np.tan(0.5 * np.deg2rad(robot.perspective_angle)))
+    Ji = np.zeros((m, 6))
+    for i in range(m // 2):
+        u, v = f[2 * i], f[2 * i + 1]
+        Ji[2 * i] = [-focal / depth[i], 0.0, u / depth[i], u * v / focal, -(focal ** 2 + u ** 2) / focal, v]
+        Ji[2 * i + 1] = [0.0, -focal / depth[i], v / depth[i], (focal ** 2 + v ** 2) / focal, -u * v / focal, -u]
+    return (Ji @ np.kron(np.eye(2), robot.getCameraRotation().T) @ robot.jacobian()).reshape(m * n)
 
 
 @dataclass
@@ -133,6 +173,22 @@ class SyntheticPlant:
     def features(self, q):
         return self.project(self.fkine_all(q)[-1])
 
+    def discs(self, q, radius=DISC_RADIUS):
+        """(n_points, 3) rows (u, v, r) in pixels of the discs of physical ``radius`` (metres; a scalar or one per point) around the world
+        points, seen from the camera at joints ``q``: the numpy statement uvs_camera_project_f64 is held to.  u, v as ``project``;
+        r = focal * radius / depth along the optical axis, -1 for a point that is not in front of the camera (depth <= 0 or not finite)."""
+        T = self.fkine_all(q)[-1]
+        R, t = T[:3, :3], T[:3, 3]
+        radius = np.broadcast_to(np.asarray(radius, float), (self.n_points,))
+        out = np.empty((self.n_points, 3))
+        with np.errstate(all='ignore'):
+            for i, w in enumerate(self.points):
+                pc = R.T @ (w - t)
+                out[i, 0] = self.center + self.focal * pc[0] / pc[2]
+                out[i, 1] = self.center + self.focal * pc[1] / pc[2]
+                out[i, 2] = self.focal * radius[i] / pc[2] if pc[2] > 0 and np.isfinite(pc[2]) else -1.0
+        return out
+
     # ---------------------------------------------------------------- device description
     def to_struct(self):
         n, npts = self.n_joints, self.n_points
@@ -148,6 +204,26 @@ class SyntheticPlant:
                 s.points[i][c] = self.points[i][c]
         s.focal, s.center = self.focal, self.center
         s.kind = _lib.PLANT_DH_PINHOLE
+        return s
+
+
+    def to_camera(self, radius=DISC_RADIUS):
+        """The ``uvs_camera`` struct of include/uvs_vision.h for discs of physical ``radius`` (metres; a scalar or one per point)."""
+        from . import _vision
+        n, npts = self.n_joints, self.n_points
+        if n > _vision.MAX_JOINTS or npts not in _vision.N_COLOURS:
+            raise ValueError('camera: at most 8 joints and 1, 3 or 4 points')
+        s = _vision.Camera()
+        s.n_joints, s.n_points = n, npts
+        for i in range(n):
+            s.theta_offset[i], s.d[i], s.a[i] = self.theta_offset[i], self.d[i], self.a[i]
+            s.cos_alpha[i], s.sin_alpha[i] = np.cos(self.alpha[i]), np.sin(self.alpha[i])
+        radius = np.broadcast_to(np.asarray(radius, float), (npts,))
+        for i in range(npts):
+            for c in range(3):
+                s.points[i][c] = self.points[i][c]
+            s.radius[i] = radius[i]
+        s.focal, s.center = self.focal, self.center
         return s
 
 
@@ -256,3 +332,27 @@ class SyntheticRobot:
 
     def features(self):
         return self.plant.project(self.fkine(True))
+
+
+class CameraRobot:
+    """A robot that carries a camera: the duck-type of ``SyntheticRobot`` (to which everything but the camera is delegated) whose
+    ``getCameraImage()`` returns a real frame -- uint8 (256, 256, 3), unflipped, the plant's discs drawn by ``render_discs`` at their
+    projected centres and radii -- so that ``Experiment`` detects its features from pixels, on the host or (perception='device') on the GPU.
+    Deliberately NOT a ``SyntheticRobot``: ``Experiment.run()`` sends those down the plant-in-kernel route, and this robot has to take the
+    external-robot route.  ``radius``: physical disc radius in metres; the default 0.024 m measures 8.01 px at ``SyntheticPlant.ur10()``'s
+    goal pose (depth 0.602 m, focal 200.9 px).  A disc is drawn as a circle, not as the ellipse a tilted camera would see."""
+
+    def __init__(self, plant=None, radius=DISC_RADIUS, dt=0.05, background=96):
+        self._robot = SyntheticRobot(plant, dt)
+        self.radius, self.background = radius, background
+
+    def __getattr__(self, name):                                    # everything but the camera: the synthetic robot's
+        if name == '_robot':
+            raise AttributeError(name)
+        return getattr(self._robot, name)
+
+    def discs(self):
+        return self._robot.plant.discs(self._robot.q, self.radius)
+
+    def getCameraImage(self):
+        return render_discs(self.discs(), self._robot.plant.n_points, self.background), (RESOLUTION, RESOLUTION)
