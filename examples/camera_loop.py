@@ -3,7 +3,8 @@
 feeds the estimator the ideal projections of the discs plus noise, and through engine.camera_closed_loop, which feeds it what the centre-of-mass
 detector returns for the 256 x 256 frame of those discs (the reference's live route) plus the same noise.  Prints the median ISE / IAE / ITAE of
 both, side by side, and the smallest colour mask the detector ever saw.
-usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0]"""
+--fused runs the pixel loop as one launch with the initial guess computed on the device (engine.camera_closed_loop(fused=True, guess='device')).
+usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused]"""
 import argparse
 import os
 import sys
@@ -21,6 +22,7 @@ def main():
     ap.add_argument('--sigma', type=float, default=0.3, help='standard deviation of the white measurement noise, pixels')
     ap.add_argument('--radius', type=float, default=None, help='physical disc radius in metres (default plant.DISC_RADIUS: about 8 px at the goal)')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--fused', action='store_true', help='the pixel loop as one launch, initial guess on the device, no log returned')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
@@ -34,7 +36,10 @@ def main():
     noise = rng.standard_normal((K, T, 8)) * args.sigma
     q0_d, noise_d = torch.as_tensor(q0, device='cuda'), torch.as_tensor(noise, device='cuda')
     ideal = uvs.engine.closed_loop(fp, plant.to_struct(), q0_d, noise_d.permute(0, 2, 1).contiguous(), want=('err',))
-    pixels = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, radius=args.radius)
+    if args.fused:
+        pixels = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, radius=args.radius, fused=True, guess='device', want=())
+    else:
+        pixels = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, radius=args.radius)
     torch.cuda.synchronize()
     print(f'{args.method}, {T} trials of {K} steps, white noise {args.sigma} px; median over the trials that ran to the end')
     print(f'{"":28s}{"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"SUCCESS":>10s}')

@@ -150,6 +150,50 @@ int uvs_camera_features_f64(const uvs_camera *cam, int64_t T, const double *q_pr
                             double *q_out, const double *noise, double *f_out, int32_t *pixels_out, double *discs_out,
                             void *stream);
 
+/*
+ * The pixel closed loop in ONE launch: K steps of { joints, projection, frame-free detection, estimator, control law } for T trials, with the
+ * filter state resident in registers.  Step for step it is the loop a caller writes with the camera-features entry point above and the
+ * single-step entry point of libuvs_rmckf (state in HBM, two launches per step), and since both libraries compile with -ffp-contract=off
+ * every output has that loop's bits.  The estimator code is libuvs_rmckf's own device header, compiled into this library.
+ *   fp: the uvs_filter_params struct of uvs_rmckf.h (K = fp->steps >= 1; dt, gain, method, kernel_bw, annealing, desired, option bit
+ *     UVS_OPT_STRICT_PINV as there).  (fp->m, fp->n) must be (8, 6), (6, 6) or (2, 6) with fp->m == 2 * cam->n_points and fp->n ==
+ *     cam->n_joints, and fp->lanes_per_filter 0: the kernel runs the lane counts the single-step entry point resolves for 0 (4, 2, 1).
+ *   q_start [T][n] in.  noise [K][T][m] in or NULL.  x0 [T][m*n] in: the initial estimate.  f0 [T][m] in: the first step's f_old -- the
+ *     noise-free detection at q_start when fp->initial_guess, zeros otherwise.
+ *   q_log [K][T][n], f_log [K][T][m], dq_log [K][T][n], err_log [K][T][m], kappa_log [K][T][m] out, each or NULL (not written).
+ *   status [T], k_done [T] int32 out; stats [T][3] out: ||ISE||, ||IAE||, ||ITAE|| of the error rows k < k_done with the clock t_k = dt
+ *     accumulated in floating point, summed in the order of libuvs_rmckf's statistics kernel.  pixels [T][n_points] int32 out or NULL: the
+ *     smallest mask per colour over the steps k <= k_done.
+ * Step k: q_k = q_{k-1} + dq_{k-1} * dt (one rounded multiply, one rounded add; q_0 = q_start), f_k = detection at q_k + noise_k,
+ * z = f_k - f_{k-1}, err = f_k - desired, estimator update with regressor dq_{k-1} (zero at k = 0) and bandwidth sigma_k, then the control
+ * law: the plain least-squares solve, and the careful one (numpy's pinv) for a filter whose watch fires, or for all under UVS_OPT_STRICT_PINV.
+ * A non-finite state after the update -- a disc left the frame: NaN features -- gives status FAIL and k_done = k, and the trial stops.
+ * Rows q_log[k], f_log[k] are written for k <= k_done, rows dq_log[k], err_log[k], kappa_log[k] for k < k_done; the rest is left as it was.
+ * Estimators: GMCKF, KF and IMCC-KF at all three shapes.  MCKF at (8, 6) and (2, 6); at (6, 6) its instantiation spills to scratch memory,
+ * is not built, and is refused with UVS_ERR_METHOD (-4, as in uvs_rmckf.h), like UVS_METHOD_ANALYTICAL at every shape.
+ * Errors, all before the first HIP call: UVS_ERR_ARG for NULL fp / cam / q_start / x0 / f0 / status / k_done / stats, T < 0, fp->steps < 1,
+ * fp->k_max < 1, n_joints outside 1 .. 8, n_points not in {1, 3, 4}, MCKF with fpi_epoch_max < 1; UVS_ERR_METHOD as above; UVS_ERR_SHAPE
+ * for lanes_per_filter != 0, m != 2 * n_points, n != n_joints, or another (m, n).  T == 0 returns UVS_OK and launches nothing.
+ * One workgroup of 256 threads per trial up to 256 trials, per four trials beyond; the results do not depend on which.
+ */
+#ifndef UVS_ERR_METHOD
+#define UVS_ERR_METHOD (-4)
+#endif
+struct uvs_filter_params;
+int uvs_camera_closed_loop_f64(const struct uvs_filter_params *fp, const uvs_camera *cam, int64_t T, const double *q_start,
+                               const double *noise, const double *x0, const double *f0, double *q_log, double *f_log, double *dq_log,
+                               double *err_log, double *kappa_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels,
+                               void *stream);
+
+/*
+ * The analytic initial guess X0 of the loop (experiment.py:94-114) for T trials, one lane each: the geometric Jacobian of the DH chain in the
+ * camera frame at q_start, the depths |camera - point|, and the image-Jacobian rows at the DETECTED features f0 (raw pixels).
+ *   q_start [T][6] in; f0 [T][2*n_points] in; x0_out [T][2*n_points*6] out.
+ * The same formula as the host's numpy statement, in another order of operations: equal to about 1e-13 relative, not bit for bit.
+ * Errors: UVS_ERR_ARG for a NULL pointer, T < 0, n_points not in {1, 3, 4}; UVS_ERR_SHAPE for n_joints != 6.  T == 0 returns UVS_OK.
+ */
+int uvs_camera_guess_f64(const uvs_camera *cam, int64_t T, const double *q_start, const double *f0, double *x0_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

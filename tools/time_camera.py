@@ -5,7 +5,11 @@
   (c) engine.camera_features: projection and frame-free detection in one launch, from the joints;
   (d) engine.camera_closed_loop at T = 1 024, K = 299 (two launches per step), wall clock, and next to it engine.closed_loop on the same
       trials as context -- ideal features, plant in the kernel: a different computation, not a gate.  The loop is timed twice: as called
-      (the analytic initial guess of every trial is host work inside the call) and with x0 handed in (the loop alone).
+      (the analytic initial guess of every trial is host work inside the call) and with x0 handed in (the loop alone);
+  (e) camera_closed_loop(fused=True) -- the same loop as one launch -- with x0 handed in, against (d) "the loop alone", also at T = 64 and 4 096;
+  (f) camera_closed_loop(fused=True, guess='device') as called, against (d) as called;
+  (g) (e) with want=(): no log is allocated or written.
+      (e)-(g) and their (d) counterparts are host-clock times around synchronised calls, taken in alternating blocks in the same process.
 (a)-(c) are HIP-event times around the launches, taken in alternating blocks so that all three see the same machine state; every figure is
 the median of 250 iterations after a warm-up, with the 10th and 90th percentile.  The acceptance condition is (b) below (a) at every T.
 Writes profiles/camera_device.txt (or the path given).  usage: tools/time_camera.py [out.txt]"""
@@ -145,6 +149,56 @@ say(f'  through pixels: {int((out["status"] == 0).sum())} of {T} trials SUCCESS,
     f'median ISE / IAE / ITAE {np.median(out["stats"].cpu().numpy()[done == K], axis=0).round(3).tolist()}')
 say(f'  ideal features: {int((ideal["status"] == 0).sum())} of {T} trials SUCCESS; '
     f'median ISE / IAE / ITAE {np.median(ideal["stats"].cpu().numpy(), axis=0).round(3).tolist()}')
+
+
+# ---- (e)-(g) the same loop as one launch, against (d) in alternating blocks
+def wall_alternate(fns, rounds=5, block=4):
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            ms[name] += wall(fn, block)[:]
+    return ms
+
+
+def fmt_ms(ms):
+    med, lo, hi = stats(ms)
+    return f'median {med:9.2f} ms   (p10 {lo:.2f}, p90 {hi:.2f}, n = {len(ms)})'
+
+
+loop = uvs.engine.camera_closed_loop
+fused = loop(fp, plant, q0_d, noise, x0=x0_d, fused=True)
+torch.cuda.synchronize()
+same = all(torch.equal(fused[key].view(torch.int64), given[key].view(torch.int64)) for key in ('err', 'q', 'f', 'dq', 'kappa', 'stats'))
+same = same and all(torch.equal(fused[key], given[key]) for key in ('status', 'k_done', 'pixels'))
+assert same, 'the one-launch loop and the two-launch loop disagree'
+ms = wall_alternate({'d_loop': lambda: loop(fp, plant, q0_d, noise, x0=x0_d),
+                     'e': lambda: loop(fp, plant, q0_d, noise, x0=x0_d, fused=True),
+                     'g': lambda: loop(fp, plant, q0_d, noise, x0=x0_d, fused=True, want=()),
+                     'f': lambda: loop(fp, plant, q0_d, noise, fused=True, guess='device')})
+ms_called = wall_alternate({'d_called': lambda: loop(fp, plant, q0_d, noise)}, rounds=2, block=3)
+say()
+say(f'(e)-(g) T = {T}, K = {K}, GMCKF, white noise 0.3 px; host clock around synchronised calls, alternating blocks, allocation included')
+say(f'  (d) two launches per step, x0 handed in (the loop alone)     {fmt_ms(ms["d_loop"])}')
+say(f'  (e) fused=True, x0 handed in (one launch)                    {fmt_ms(ms["e"])}   = {np.median(ms["e"]) / K * 1e3:.1f} us per step')
+say(f'  (g) (e) with want=()                                         {fmt_ms(ms["g"])}')
+say(f'  (d) two launches per step, as called (host guess per trial)  {fmt_ms(ms_called["d_called"])}')
+say(f"  (f) fused=True, guess='device', as called (three launches)   {fmt_ms(ms['f'])}")
+e_med, d_med, f_med, dc_med = (float(np.median(v)) for v in (ms['e'], ms['d_loop'], ms['f'], ms_called['d_called']))
+say(f'  (e) / (d) the loop alone = {e_med / d_med:.3f}: (e) is {"BELOW" if e_med < d_med else "NOT below"} (d);  '
+    f'(f) / (d) as called = {f_med / dc_med:.4f}: (f) is {"BELOW" if f_med < dc_med else "NOT below"} (d)')
+say(f'  logs, stats, status, k_done and pixels of (e) and (d): bit-identical; median ISE / IAE / ITAE of (e) '
+    f'{np.median(fused["stats"].cpu().numpy()[done == K], axis=0).round(3).tolist()}, of (d) '
+    f'{np.median(given["stats"].cpu().numpy()[done == K], axis=0).round(3).tolist()}')
+for T_other in (64, 4096):
+    q_o = torch.as_tensor(q0[np.arange(T_other) % T] + rng.uniform(-0.01, 0.01, (T_other, 6)), device='cuda')
+    noise_o = torch.as_tensor(rng.standard_normal((K, T_other, 8)) * 0.3, device='cuda')
+    x0_o = uvs.engine.camera_guess(plant, q_o, uvs.engine.camera_features(plant, q_o))
+    ms_o = wall_alternate({'d_loop': lambda: loop(fp, plant, q_o, noise_o, x0=x0_o), 'e': lambda: loop(fp, plant, q_o, noise_o, x0=x0_o, fused=True)},
+                          rounds=3, block=3)
+    say(f'  T = {T_other:5d}: (d) the loop alone {fmt_ms(ms_o["d_loop"])};  (e) {fmt_ms(ms_o["e"])}')
 
 os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
 open(OUT, 'w').write('\n'.join(lines) + '\n')

@@ -39,6 +39,9 @@ SYMBOLS = {
     'uvs_render_discs_u8': (C.c_int, [_I64, _VP, _I32, _I32, _VP, _I64, _VP]),
     'uvs_disc_features_f64': (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP, _VP]),
     'uvs_camera_features_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    # fp (a pointer to _lib.FilterParams, passed with byref), cam, T, q_start, noise, x0, f0, five logs, status, k_done, stats, pixels, stream
+    'uvs_camera_closed_loop_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 14),
+    'uvs_camera_guess_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -10,73 +10,26 @@
 #include <cstdio>
 
 #include "uvs_vision.h"
+#include "vision_device.hpp"
 
 namespace uvs_vision {
 
-constexpr int kSide = UVS_VISION_SIDE;          // rows = columns = grid points (utils.py:7-9)
 constexpr int kRowBytes = kSide * 3;            // 768 B = 16 lanes x 48 B = 16 lanes x 16 whole pixels
-constexpr int kThreads = 1024;                  // 16 column groups x 64 row groups
+static_assert(kThreads == 16 * 64, "16 column groups x 64 row groups");
 constexpr int kPasses = kSide / 64;             // rows per thread
 constexpr int kThreshold = 250;                 // utils.py:15
 // LDS pitches in dwords, chosen so that the 16-byte reads of phase 2 spread over all banks: column-count records of 64 row groups (+4),
 // row records of 16 column groups (+4).
 constexpr int kColPitch = 68, kRowPitch = 20;
-constexpr int kColours = 4;                     // red, green, blue, pink (utils.py:126-166)
 
 __device__ __forceinline__ uint32_t byte_of(const uint32_t (&d)[12], int k) { return (d[k >> 2] >> (8 * (k & 3))) & 0xffu; }
 
-// p[i] = fl(g[i] * 255.0) with g = np.linspace(0, 1, 256): g[i] = fl(i * fl(1/255)), g[255] = 1.0 (the endpoint is assigned, not computed)
-__device__ __forceinline__ double grid_product(int i) {
-    const double step = 1.0 / 255.0;
-    const double g = i < kSide - 1 ? static_cast<double>(i) * step : 1.0;
-    return g * 255.0;
-}
-
-// Phase 2 of every detector here, from the integer counts on: thread (colour tid >> 8, grid index tid & 255) brings the number of mask pixels
-// of its colour in column i (cc) and in flipped row i (rc).  The bits of the result depend on the order below, so the frame detector and the
-// frame-free ones share this one function.  Called by all kThreads threads of the workgroup (it synchronises).
-__device__ __forceinline__ void centre_of_mass(int cc, int rc, int n_colours, const double *__restrict__ noise, double *__restrict__ f_out,
-                                               int32_t *__restrict__ pixels_out) {
-    __shared__ double part_u[kThreads / 64], part_v[kThreads / 64];
-    __shared__ int part_n[kThreads / 64];
-    const int tid = threadIdx.x;
-    const int i = tid & 255;
-    const double p = grid_product(i);
-    double su = static_cast<double>(cc) * p, sv = static_cast<double>(rc) * p;   // X * mask, Y * mask (utils.py:25-27), summed by count
-    int n = cc;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {                     // a wavefront holds one colour: 64 consecutive grid indices
-        su += __shfl_down(su, off, 64);
-        sv += __shfl_down(sv, off, 64);
-        n += __shfl_down(n, off, 64);
-    }
-    if ((tid & 63) == 0) {
-        part_u[tid >> 6] = su;
-        part_v[tid >> 6] = sv;
-        part_n[tid >> 6] = n;
-    }
-    __syncthreads();
-
-    if (tid < n_colours) {
-        const int colour = n_colours == 1 ? 1 : tid;             // detectGreenCircle: green alone
-        double s_u = 0.0, s_v = 0.0;
-        int count = 0;
-        for (int k = 0; k < 4; ++k) {
-            s_u += part_u[4 * colour + k];
-            s_v += part_v[4 * colour + k];
-            count += part_n[4 * colour + k];
-        }
-        const double total = static_cast<double>(255 * count);   // np.sum of the uint8 mask of 255s (utils.py:26)
-        double u = (255.0 * s_u) / total, v = (255.0 * s_v) / total;   // 0.0 / 0.0 = NaN for an empty mask, like the reference
-        const int64_t o = static_cast<int64_t>(blockIdx.x) * (2 * n_colours) + 2 * tid;
-        if (noise != nullptr) {                                  // f += noise (experiment.py:135)
-            u += noise[o];
-            v += noise[o + 1];
-        }
-        f_out[o] = u;
-        f_out[o + 1] = v;
-        if (pixels_out != nullptr) pixels_out[static_cast<int64_t>(blockIdx.x) * n_colours + tid] = count;
-    }
+// centre_of_mass (vision_device.hpp) for the kernels of this unit, whose trial is the workgroup: [T][2 n_colours] noise and features, [T][n_colours] masks
+__device__ __forceinline__ void centre_of_mass_of_block(int cc, int rc, int n_colours, const double *__restrict__ noise, double *__restrict__ f_out,
+                                                        int32_t *__restrict__ pixels_out) {
+    const int64_t o = static_cast<int64_t>(blockIdx.x) * (2 * n_colours);
+    centre_of_mass(cc, rc, n_colours, noise != nullptr ? noise + o : nullptr, f_out + o,
+                   pixels_out != nullptr ? pixels_out + static_cast<int64_t>(blockIdx.x) * n_colours : nullptr);
 }
 
 __global__ __launch_bounds__(kThreads) void detect_circles_kernel(const uint8_t *__restrict__ frames, int64_t frame_stride, int n_colours,
@@ -151,32 +104,10 @@ __global__ __launch_bounds__(kThreads) void detect_circles_kernel(const uint8_t 
             rc += static_cast<int>(((v.x >> rs) & 255u) + ((v.y >> rs) & 255u) + ((v.z >> rs) & 255u) + ((v.w >> rs) & 255u));
         }
     }
-    centre_of_mass(cc, rc, n_colours, noise, f_out, pixels_out);
+    centre_of_mass_of_block(cc, rc, n_colours, noise, f_out, pixels_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- synthetic camera
-// A disc as the kernels hold it: centre, and r2 = fl(r * r) -- or -1 for a disc that draws nothing (r < 0, NaN r, or no such disc), which no
-// squared distance is below.  The pixel rule of the header is `dx2 + dy2 <= r2` with each square rounded once (-ffp-contract=off).
-struct Disc {
-    double u, v, r, r2;
-};
-
-__device__ __forceinline__ Disc load_disc(const double *d, bool present) {
-    Disc o;
-    o.u = present ? d[0] : 0.0;
-    o.v = present ? d[1] : 0.0;
-    o.r = present ? d[2] : -1.0;
-    o.r2 = o.r >= 0.0 ? o.r * o.r : -1.0;
-    return o;
-}
-
-// Inclusive pixel range [lo, hi] of [centre - r - 1, centre + r + 1] clipped to the frame: conservative against the exact rule by a whole
-// pixel.  fmax / fmin drop a NaN operand, so a bound that is NaN (inf - inf) becomes the frame edge, never an unconverted NaN.
-__device__ __forceinline__ void pixel_range(double centre, double r, int &lo, int &hi) {
-    lo = static_cast<int>(fmin(fmax(ceil(centre - r - 1.0), 0.0), static_cast<double>(kSide)));
-    hi = static_cast<int>(fmax(fmin(floor(centre + r + 1.0), static_cast<double>(kSide - 1)), -1.0));
-}
-
 // colour word (R in the low byte) of disc k of n: red, green, blue, pink; the one disc of n == 1 is green
 __device__ __forceinline__ uint32_t colour_word(int k, int n) {
     const int slot = n == 1 ? 1 : k;
@@ -239,110 +170,11 @@ __global__ __launch_bounds__(kThreads) void render_discs_kernel(const double *__
     }
 }
 
-// Counts of thread (colour c = tid >> 8, index i = tid & 255) for the frame the rasteriser above would write from the n_colours discs at
-// `discs` (global memory or LDS): cc = rows at which c's disc is the topmost one in column i, rc = columns at which it is in flipped row i.
-__device__ __forceinline__ void disc_counts(const double *discs, int n_colours, int &cc, int &rc) {
-    const int c = threadIdx.x >> 8, i = threadIdx.x & 255;
-    const int own = n_colours == 1 ? (c == 1 ? 0 : -1) : (c < n_colours ? c : -1);   // wavefront-uniform
-    cc = 0;
-    rc = 0;
-    if (own < 0) return;
-    const Disc me = load_disc(discs + 3 * own, true);
-    if (!(me.r2 >= 0.0)) return;
-    Disc over[kColours - 1];                                     // the discs painted after mine; absent ones never cover a pixel
-#pragma unroll
-    for (int k = 0; k < kColours - 1; ++k) {
-        const int other = own + 1 + k;
-        over[k] = load_disc(discs + 3 * (other < n_colours ? other : own), other < n_colours);
-    }
-    int x0, x1, y0, y1;
-    pixel_range(me.u, me.r, x0, x1);
-    pixel_range(me.v, me.r, y0, y1);
-    const double fi = static_cast<double>(i);
-    if (i >= x0 && i <= x1) {                                    // column i: walk the rows of the box
-        const double dx = fi - me.u, dx2 = dx * dx;
-        double ox2[kColours - 1];
-#pragma unroll
-        for (int k = 0; k < kColours - 1; ++k) {
-            const double o = fi - over[k].u;
-            ox2[k] = o * o;
-        }
-        for (int y = y0; y <= y1; ++y) {
-            const double fy = static_cast<double>(y), dy = fy - me.v;
-            bool top = dx2 + dy * dy <= me.r2;
-#pragma unroll
-            for (int k = 0; k < kColours - 1; ++k) {
-                const double o = fy - over[k].v;
-                top = top && !(ox2[k] + o * o <= over[k].r2);
-            }
-            cc += top ? 1 : 0;
-        }
-    }
-    if (i >= y0 && i <= y1) {                                    // flipped row i: walk the columns of the box
-        const double dy = fi - me.v, dy2 = dy * dy;
-        double oy2[kColours - 1];
-#pragma unroll
-        for (int k = 0; k < kColours - 1; ++k) {
-            const double o = fi - over[k].v;
-            oy2[k] = o * o;
-        }
-        for (int x = x0; x <= x1; ++x) {
-            const double fx = static_cast<double>(x), dx = fx - me.u;
-            bool top = dx * dx + dy2 <= me.r2;
-#pragma unroll
-            for (int k = 0; k < kColours - 1; ++k) {
-                const double o = fx - over[k].u;
-                top = top && !(o * o + oy2[k] <= over[k].r2);
-            }
-            rc += top ? 1 : 0;
-        }
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void disc_features_kernel(const double *__restrict__ discs, int n_colours, const double *__restrict__ noise,
                                                                  double *__restrict__ f_out, int32_t *__restrict__ pixels_out) {
     int cc, rc;
     disc_counts(discs + static_cast<int64_t>(blockIdx.x) * (3 * n_colours), n_colours, cc, rc);
-    centre_of_mass(cc, rc, n_colours, noise, f_out, pixels_out);
-}
-
-// Joint i of trial t -- q = q_prev + dq * dt when dq is given, written to q_out when that is given -- and the sine and cosine of its DH angle.
-__device__ __forceinline__ void joint_sincos(const uvs_camera &cam, int64_t t, int i, const double *__restrict__ q_prev,
-                                             const double *__restrict__ dq, double dt, double *__restrict__ q_out, double &s, double &c) {
-    const int n = cam.n_joints;
-    double q = q_prev[t * n + i];
-    if (dq != nullptr) {
-        const double step = dq[t * n + i] * dt;                  // one rounded multiply, then one rounded add
-        q = q + step;
-    }
-    if (q_out != nullptr) q_out[t * n + i] = q;
-    sincos(q + cam.theta_offset[i], &s, &c);
-}
-
-// One more link of the chain: T <- T * Rz(theta) Tz(d) Rx(alpha) Tx(a), summed left to right as a plain matrix product.
-__device__ __forceinline__ void chain_link(const uvs_camera &cam, int i, double s, double c, double (&T)[3][4]) {
-    const double ca = cam.cos_alpha[i], sa = cam.sin_alpha[i], aa = cam.a[i], dd = cam.d[i];
-    const double l01 = -s * ca, l02 = s * sa, l03 = aa * c;
-    const double l11 = c * ca, l12 = -c * sa, l13 = aa * s;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double t0 = T[r][0], t1 = T[r][1], t2 = T[r][2], t3 = T[r][3];
-        T[r][0] = t0 * c + t1 * s;
-        T[r][1] = t0 * l01 + t1 * l11 + t2 * sa;
-        T[r][2] = t0 * l02 + t1 * l12 + t2 * ca;
-        T[r][3] = t0 * l03 + t1 * l13 + t2 * dd + t3;
-    }
-}
-
-// (u, v, r) of world point p seen from the camera pose T = [R | t]: pc = R^T (w - t); r = -1 for a point that is not in front of the camera
-__device__ __forceinline__ void project_disc(const uvs_camera &cam, int p, const double (&T)[3][4], double *out) {
-    const double dx = cam.points[p][0] - T[0][3], dy = cam.points[p][1] - T[1][3], dz = cam.points[p][2] - T[2][3];
-    const double xc = T[0][0] * dx + T[1][0] * dy + T[2][0] * dz;
-    const double yc = T[0][1] * dx + T[1][1] * dy + T[2][1] * dz;
-    const double zc = T[0][2] * dx + T[1][2] * dy + T[2][2] * dz;
-    out[0] = cam.center + cam.focal * xc / zc;
-    out[1] = cam.center + cam.focal * yc / zc;
-    out[2] = (zc > 0.0 && isfinite(zc)) ? cam.focal * cam.radius[p] / zc : -1.0;
+    centre_of_mass_of_block(cc, rc, n_colours, noise, f_out, pixels_out);
 }
 
 constexpr int kProjectThreads = 64;
@@ -387,12 +219,12 @@ __global__ __launch_bounds__(kThreads) void camera_features_kernel(const uvs_cam
     __syncthreads();
     int cc, rc;
     disc_counts(sdisc, cam.n_points, cc, rc);
-    centre_of_mass(cc, rc, cam.n_points, noise, f_out, pixels_out);
+    centre_of_mass_of_block(cc, rc, cam.n_points, noise, f_out, pixels_out);
 }
 
 thread_local char g_err[256] = "";
 
-int fail(int code, const char *fmt, const char *detail = "") {
+int fail(int code, const char *fmt, const char *detail) {
     std::snprintf(g_err, sizeof g_err, fmt, detail);
     return code;
 }

@@ -1,0 +1,260 @@
+// Device code shared by the translation units of libuvs_vision.so (uvs_vision.hip, uvs_camera_loop.hip): the detector's phase 2 in the two
+// forms its callers need, the disc geometry of the synthetic camera, and the DH chain.  The summation order of the phase 2 is a contract
+// (see centre_of_mass): every unit that sums mask pixels goes through wave_partial and ColourSum, so they all give the same bits.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "uvs_vision.h"
+
+namespace uvs_vision {
+
+constexpr int kSide = UVS_VISION_SIDE;          // rows = columns = grid points (utils.py:7-9)
+constexpr int kThreads = 1024;                  // one workgroup per frame: 4 colours x 256 grid indices
+constexpr int kColours = 4;                     // red, green, blue, pink (utils.py:126-166)
+
+// p[i] = fl(g[i] * 255.0) with g = np.linspace(0, 1, 256): g[i] = fl(i * fl(1/255)), g[255] = 1.0 (the endpoint is assigned, not computed)
+__device__ __forceinline__ double grid_product(int i) {
+    const double step = 1.0 / 255.0;
+    const double g = i < kSide - 1 ? static_cast<double>(i) * step : 1.0;
+    return g * 255.0;
+}
+
+// First stage of the phase 2: the 64 lanes of a wavefront hold 64 consecutive grid indices of one colour, lane l the index i = 64 k + l with
+// cc mask pixels in column i and rc in flipped row i.  Lane 0 receives the wavefront's sums of cc * p[i], rc * p[i] and cc through the
+// __shfl_down tree (32, 16, .., 1); the other lanes receive partial trees nobody reads.  All 64 lanes must call it.
+__device__ __forceinline__ void wave_partial(int cc, int rc, int i, double &su, double &sv, int &n) {
+    const double p = grid_product(i);
+    su = static_cast<double>(cc) * p;                            // X * mask, Y * mask (utils.py:25-27), summed by count
+    sv = static_cast<double>(rc) * p;
+    n = cc;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        su += __shfl_down(su, off, 64);
+        sv += __shfl_down(sv, off, 64);
+        n += __shfl_down(n, off, 64);
+    }
+}
+
+// Second stage: the four partials of one colour are added in index order, starting from 0.0, then (255 S) / (255 count).  0.0 / 0.0 = NaN
+// for an empty mask, like the reference.  A wavefront whose 64 indices hold no mask pixel has the partial (+0.0, +0.0, 0): adding it is exact.
+struct ColourSum {
+    double s_u = 0.0, s_v = 0.0;
+    int count = 0;
+    __device__ __forceinline__ void add(double su, double sv, int n) {
+        s_u += su;
+        s_v += sv;
+        count += n;
+    }
+    __device__ __forceinline__ void centre(double &u, double &v) const {
+        const double total = static_cast<double>(255 * count);   // np.sum of the uint8 mask of 255s (utils.py:26)
+        u = (255.0 * s_u) / total;
+        v = (255.0 * s_v) / total;
+    }
+};
+
+// Phase 2 of every one-workgroup-per-frame detector, from the integer counts on: thread (colour tid >> 8, grid index tid & 255) brings the
+// number of mask pixels of its colour in column i (cc) and in flipped row i (rc).  noise, f_out and pixels_out are THE TRIAL'S OWN rows
+// (2 n_colours doubles, 2 n_colours doubles, n_colours ints; noise and pixels_out may be NULL).  The bits of the result depend on the order:
+// wave_partial per 64 consecutive indices, ColourSum per colour, then the noise add.  Called by all kThreads threads (it synchronises).
+__device__ __forceinline__ void centre_of_mass(int cc, int rc, int n_colours, const double *__restrict__ noise, double *__restrict__ f_out,
+                                               int32_t *__restrict__ pixels_out) {
+    __shared__ double part_u[kThreads / 64], part_v[kThreads / 64];
+    __shared__ int part_n[kThreads / 64];
+    const int tid = threadIdx.x;
+    double su, sv;
+    int n;
+    wave_partial(cc, rc, tid & 255, su, sv, n);                  // a wavefront holds one colour: 64 consecutive grid indices
+    if ((tid & 63) == 0) {
+        part_u[tid >> 6] = su;
+        part_v[tid >> 6] = sv;
+        part_n[tid >> 6] = n;
+    }
+    __syncthreads();
+
+    if (tid < n_colours) {
+        const int colour = n_colours == 1 ? 1 : tid;             // detectGreenCircle: green alone
+        ColourSum sum;
+        for (int k = 0; k < 4; ++k) sum.add(part_u[4 * colour + k], part_v[4 * colour + k], part_n[4 * colour + k]);
+        double u, v;
+        sum.centre(u, v);
+        const int count = sum.count;
+        if (noise != nullptr) {                                  // f += noise (experiment.py:135)
+            u += noise[2 * tid];
+            v += noise[2 * tid + 1];
+        }
+        f_out[2 * tid] = u;
+        f_out[2 * tid + 1] = v;
+        if (pixels_out != nullptr) pixels_out[tid] = count;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- synthetic camera
+// A disc as the kernels hold it: centre, and r2 = fl(r * r) -- or -1 for a disc that draws nothing (r < 0, NaN r, or no such disc), which no
+// squared distance is below.  The pixel rule of the header is `dx2 + dy2 <= r2` with each square rounded once (-ffp-contract=off).
+struct Disc {
+    double u, v, r, r2;
+};
+
+__device__ __forceinline__ Disc load_disc(const double *d, bool present) {
+    Disc o;
+    o.u = present ? d[0] : 0.0;
+    o.v = present ? d[1] : 0.0;
+    o.r = present ? d[2] : -1.0;
+    o.r2 = o.r >= 0.0 ? o.r * o.r : -1.0;
+    return o;
+}
+
+// Inclusive pixel range [lo, hi] of [centre - r - 1, centre + r + 1] clipped to the frame: conservative against the exact rule by a whole
+// pixel.  fmax / fmin drop a NaN operand, so a bound that is NaN (inf - inf) becomes the frame edge, never an unconverted NaN.
+__device__ __forceinline__ void pixel_range(double centre, double r, int &lo, int &hi) {
+    lo = static_cast<int>(fmin(fmax(ceil(centre - r - 1.0), 0.0), static_cast<double>(kSide)));
+    hi = static_cast<int>(fmax(fmin(floor(centre + r + 1.0), static_cast<double>(kSide - 1)), -1.0));
+}
+
+// The disc of the n_colours at `discs` that colour slot c (red, green, blue, pink) shows, or -1: the one disc of n_colours == 1 is the green one
+__device__ __forceinline__ int disc_of_colour(int c, int n_colours) { return n_colours == 1 ? (c == 1 ? 0 : -1) : (c < n_colours ? c : -1); }
+
+// Could disc o cover a pixel of the box [x0, x1] x [y0, y1]?  No, when it draws nothing or when its own pixel ranges miss the box: for a disc
+// of ordinary size (centre and radius below 1e9 in magnitude: no overflow, rounding far below the range's whole pixel of slack) every pixel
+// the rule gives it lies inside its ranges.  Anything else -- a NaN centre, a huge disc -- counts as "could".
+__device__ __forceinline__ bool may_cover(const Disc &o, int x0, int x1, int y0, int y1) {
+    if (!(o.r2 >= 0.0)) return false;
+    if (!(fabs(o.u) < 1e9 && fabs(o.v) < 1e9 && o.r < 1e9)) return true;
+    int ox0, ox1, oy0, oy1;
+    pixel_range(o.u, o.r, ox0, ox1);
+    pixel_range(o.v, o.r, oy0, oy1);
+    return ox0 <= x1 && ox1 >= x0 && oy0 <= y1 && oy1 >= y0;
+}
+
+// The two walks of disc_counts_at over the box of `me`; OVER = false leaves the tests against the discs painted later out (none can cover a
+// pixel of the box), which is three of the four distance tests of every pixel.
+template <bool OVER>
+__device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kColours - 1], int x0, int x1, int y0, int y1, int i, int &cc, int &rc) {
+    const double fi = static_cast<double>(i);
+    if (i >= x0 && i <= x1) {                                    // column i: walk the rows of the box
+        const double dx = fi - me.u, dx2 = dx * dx;
+        double ox2[kColours - 1];
+        if constexpr (OVER) {
+#pragma unroll
+            for (int k = 0; k < kColours - 1; ++k) {
+                const double o = fi - over[k].u;
+                ox2[k] = o * o;
+            }
+        }
+        for (int y = y0; y <= y1; ++y) {
+            const double fy = static_cast<double>(y), dy = fy - me.v;
+            bool top = dx2 + dy * dy <= me.r2;
+            if constexpr (OVER) {
+#pragma unroll
+                for (int k = 0; k < kColours - 1; ++k) {
+                    const double o = fy - over[k].v;
+                    top = top && !(ox2[k] + o * o <= over[k].r2);
+                }
+            }
+            cc += top ? 1 : 0;
+        }
+    }
+    if (i >= y0 && i <= y1) {                                    // flipped row i: walk the columns of the box
+        const double dy = fi - me.v, dy2 = dy * dy;
+        double oy2[kColours - 1];
+        if constexpr (OVER) {
+#pragma unroll
+            for (int k = 0; k < kColours - 1; ++k) {
+                const double o = fi - over[k].v;
+                oy2[k] = o * o;
+            }
+        }
+        for (int x = x0; x <= x1; ++x) {
+            const double fx = static_cast<double>(x), dx = fx - me.u;
+            bool top = dx * dx + dy2 <= me.r2;
+            if constexpr (OVER) {
+#pragma unroll
+                for (int k = 0; k < kColours - 1; ++k) {
+                    const double o = fx - over[k].u;
+                    top = top && !(o * o + oy2[k] <= over[k].r2);
+                }
+            }
+            rc += top ? 1 : 0;
+        }
+    }
+}
+
+// Counts of (colour c, index i) for the frame the rasteriser would write from the n_colours discs at `discs` (global memory or LDS):
+// cc = rows at which c's disc is the topmost one in column i, rc = columns at which it is in flipped row i.  c and the discs are the same
+// in all lanes of a wavefront (every caller's are), so which of the two walks runs is a scalar branch.
+__device__ __forceinline__ void disc_counts_at(const double *discs, int n_colours, int c, int i, int &cc, int &rc) {
+    const int own = disc_of_colour(c, n_colours);
+    cc = 0;
+    rc = 0;
+    if (own < 0) return;
+    const Disc me = load_disc(discs + 3 * own, true);
+    if (!(me.r2 >= 0.0)) return;
+    int x0, x1, y0, y1;
+    pixel_range(me.u, me.r, x0, x1);
+    pixel_range(me.v, me.r, y0, y1);
+    Disc over[kColours - 1];                                     // the discs painted after mine; absent ones never cover a pixel
+    bool covered = false;
+#pragma unroll
+    for (int k = 0; k < kColours - 1; ++k) {
+        const int other = own + 1 + k;
+        over[k] = load_disc(discs + 3 * (other < n_colours ? other : own), other < n_colours);
+        covered = covered || may_cover(over[k], x0, x1, y0, y1);
+    }
+    if (__builtin_amdgcn_readfirstlane(static_cast<int>(covered)))
+        box_counts<true>(me, over, x0, x1, y0, y1, i, cc, rc);
+    else
+        box_counts<false>(me, over, x0, x1, y0, y1, i, cc, rc);
+}
+
+// The same for thread (colour c = tid >> 8, index i = tid & 255) of a one-workgroup-per-frame kernel; c is wavefront-uniform there.
+__device__ __forceinline__ void disc_counts(const double *discs, int n_colours, int &cc, int &rc) {
+    disc_counts_at(discs, n_colours, threadIdx.x >> 8, threadIdx.x & 255, cc, rc);
+}
+
+// Joint i of trial t -- q = q_prev + dq * dt when dq is given, written to q_out when that is given -- and the sine and cosine of its DH angle.
+__device__ __forceinline__ void joint_sincos(const uvs_camera &cam, int64_t t, int i, const double *__restrict__ q_prev,
+                                             const double *__restrict__ dq, double dt, double *__restrict__ q_out, double &s, double &c) {
+    const int n = cam.n_joints;
+    double q = q_prev[t * n + i];
+    if (dq != nullptr) {
+        const double step = dq[t * n + i] * dt;                  // one rounded multiply, then one rounded add
+        q = q + step;
+    }
+    if (q_out != nullptr) q_out[t * n + i] = q;
+    sincos(q + cam.theta_offset[i], &s, &c);
+}
+
+// One more link of the chain: T <- T * Rz(theta) Tz(d) Rx(alpha) Tx(a), summed left to right as a plain matrix product.
+__device__ __forceinline__ void chain_link(const uvs_camera &cam, int i, double s, double c, double (&T)[3][4]) {
+    const double ca = cam.cos_alpha[i], sa = cam.sin_alpha[i], aa = cam.a[i], dd = cam.d[i];
+    const double l01 = -s * ca, l02 = s * sa, l03 = aa * c;
+    const double l11 = c * ca, l12 = -c * sa, l13 = aa * s;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double t0 = T[r][0], t1 = T[r][1], t2 = T[r][2], t3 = T[r][3];
+        T[r][0] = t0 * c + t1 * s;
+        T[r][1] = t0 * l01 + t1 * l11 + t2 * sa;
+        T[r][2] = t0 * l02 + t1 * l12 + t2 * ca;
+        T[r][3] = t0 * l03 + t1 * l13 + t2 * dd + t3;
+    }
+}
+
+// (u, v, r) of world point p seen from the camera pose T = [R | t]: pc = R^T (w - t); r = -1 for a point that is not in front of the camera
+__device__ __forceinline__ void project_disc(const uvs_camera &cam, int p, const double (&T)[3][4], double *out) {
+    const double dx = cam.points[p][0] - T[0][3], dy = cam.points[p][1] - T[1][3], dz = cam.points[p][2] - T[2][3];
+    const double xc = T[0][0] * dx + T[1][0] * dy + T[2][0] * dz;
+    const double yc = T[0][1] * dx + T[1][1] * dy + T[2][1] * dz;
+    const double zc = T[0][2] * dx + T[1][2] * dy + T[2][2] * dz;
+    out[0] = cam.center + cam.focal * xc / zc;
+    out[1] = cam.center + cam.focal * yc / zc;
+    out[2] = (zc > 0.0 && isfinite(zc)) ? cam.focal * cam.radius[p] / zc : -1.0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side, shared
+// The calling thread's error text and the two ways an entry point ends (defined in uvs_vision.hip).
+extern thread_local char g_err[256];
+int fail(int code, const char *fmt, const char *detail = "");
+int launched(const char *what);
+bool colours_ok(int32_t n);
+
+}  // namespace uvs_vision

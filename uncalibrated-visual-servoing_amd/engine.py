@@ -444,7 +444,56 @@ def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_o
     return out
 
 
-def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None):
+def camera_guess(plant, q_start, f0, radius=None, out=None):
+    """The analytic initial guess of T trials on the device (uvs_camera_guess_f64): what ``plant.analytic_guess`` returns per trial for the
+    joints ``q_start`` (T, 6) and the detected features ``f0`` (T, 2 n_points), both cuda fp64, to about 1e-13 relative (another order of
+    operations, not the same bits).  Returns ``out``: (T, 2 n_points * 6)."""
+    from . import _vision, plant as plant_mod
+    torch = _torch()
+    cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    T, n, m = q_start.shape[0], cam.n_joints, 2 * cam.n_points
+    if out is None:
+        out = torch.empty((T, m * n), dtype=torch.float64, device=_device_of(q_start, f0))
+    rc = _vision.lib().uvs_camera_guess_f64(C.byref(cam), T, _operand(q_start, 'q_start', torch.float64, (T, n)),
+                                            _operand(f0, 'f0', torch.float64, (T, m)), _operand(out, 'out', torch.float64, (T, m * n)), _stream())
+    _vision.check(rc)
+    return out
+
+
+CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
+
+
+def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want):
+    """camera_closed_loop(fused=True): at most three launches and no host loop."""
+    from . import _vision
+    torch = _torch()
+    K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
+    T, dev = q_start.shape[0], q_start.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    q0 = _operand(q_start, 'q_start', torch.float64, (T, n))
+    noise_ptr = _operand(noise, 'noise', torch.float64, (K, T, m), True)
+    f0 = torch.zeros((T, m), **f64)
+    if fp.initial_guess:
+        camera_features(cam, q_start, out=f0)
+        if x0 is None and guess == 'device':
+            x0 = camera_guess(cam, q_start, f0)
+    if x0 is None:
+        raise ValueError("camera_closed_loop: fused=True takes x0, or guess='device' with fp.initial_guess")
+    X0 = torch.as_tensor(x0, **f64).reshape(T, m * n).contiguous()
+    comps = dict(err=m, q=n, f=m, dq=n, kappa=m)
+    log = {key: torch.empty((K, T, comps[key]), **f64) for key in CAMERA_LOGS if key in want}
+    ptr = lambda key: log[key].data_ptr() if key in log else None   # noqa: E731
+    status, k_done = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2))
+    stats = torch.empty((T, 3), **f64)
+    pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
+    rc = _vision.lib().uvs_camera_closed_loop_f64(C.byref(fp), C.byref(cam), T, q0, noise_ptr, X0.data_ptr(), f0.data_ptr(), ptr('q'), ptr('f'),
+                                                  ptr('dq'), ptr('err'), ptr('kappa'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(),
+                                                  pixels.data_ptr(), _stream())
+    _vision.check(rc)
+    return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
+
+
+def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -454,8 +503,16 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None):
     and uvs_rmckf_step_f64 (-> dq_log[k], err_log[k], kappa_log[k], status_log[k]), each on rows of the logs, which are plain (K, T, comp)
     tensors.  A disc that leaves the frame gives NaN features, a non-finite X and FAIL at that step, as the reference's loop ends on a NaN
     detection.  Returns a dict: 'err', 'q', 'f', 'dq', 'kappa' (K, T, comp; rows at and after k_done unspecified), 'pixels' (T, n_points) the
-    smallest mask per colour over the steps up to and including k_done, 'status', 'k_done' (T,) int32, 'stats' (T, 3)."""
+    smallest mask per colour over the steps up to and including k_done, 'status', 'k_done' (T,) int32, 'stats' (T, 3).
+    ``fused=True`` runs the same loop as ONE launch (uvs_camera_closed_loop_f64: the filter state stays in registers over the K steps) and
+    returns the same bits; ``want`` names the logs to return (the others are neither allocated nor written).  ``guess='device'`` computes the
+    initial guess with ``camera_guess`` instead of the per-trial host loop, under either value of ``fused``: equal to the host's to about
+    1e-13, not in the last bits.  With fused=True a ``Camera`` struct is accepted for ``plant`` when x0 is given or guess='device'."""
     from . import _vision, plant as plant_mod
+    if guess not in ('host', 'device'):
+        raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
+    if fused and not getattr(q_start, 'is_cuda', False):
+        raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     torch = _torch()
     K, m, n = fp.steps, fp.m, fp.n
     T, dev = q_start.shape[0], q_start.device
@@ -463,6 +520,11 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None):
         raise ValueError('camera_closed_loop: at least one step (fp.steps) and one trial')
     if not q_start.is_cuda:
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
+    if fused and (x0 is not None or guess == 'device' or not fp.initial_guess):
+        cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+        if m != 2 * cam.n_points or n != cam.n_joints:
+            raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want))
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -475,6 +537,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None):
     f0 = torch.zeros((T, m), **f64)
     if fp.initial_guess:
         camera_features(cam, q_start, out=f0)
+        if x0 is None and guess == 'device':
+            x0 = camera_guess(cam, q_start, f0)
         if x0 is None:
             f_host, q_host = f0.cpu().numpy(), q_start.cpu().numpy()
             x0 = np.empty((T, m * n))
@@ -485,6 +549,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None):
     if x0 is None:
         raise ValueError('camera_closed_loop: x0 is needed when fp.initial_guess is 0 (the reference draws it unseeded, experiment.py:117)')
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
+    if fused:                                                        # the host guess is in hand: the rest is the one launch
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want))
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
@@ -507,7 +573,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None):
     status = (k_done < K).to(torch.int32)
     seen = steps <= k_done[None, :]                                  # the failing step's own masks count: an empty one shows as 0
     pixels = torch.where(seen[:, :, None], pixel_log, torch.full_like(pixel_log, 2 ** 31 - 1)).amin(0)
-    out = dict(log, pixels=pixels, status=status, k_done=k_done)
+    out = dict({key: t for key, t in log.items() if key in want}, pixels=pixels, status=status, k_done=k_done)
     out['stats'] = stats_reduce(log['err'], _loop_times(fp.dt, K), k_done, layout='ktc')
     return out
 
