@@ -170,7 +170,8 @@ int uvs_camera_features_f64(const uvs_camera *cam, int64_t T, const double *q_pr
  * A non-finite state after the update -- a disc left the frame: NaN features -- gives status FAIL and k_done = k, and the trial stops.
  * Rows q_log[k], f_log[k] are written for k <= k_done, rows dq_log[k], err_log[k], kappa_log[k] for k < k_done; the rest is left as it was.
  * Estimators: GMCKF, KF and IMCC-KF at all three shapes.  MCKF at (8, 6) and (2, 6); at (6, 6) its instantiation spills to scratch memory,
- * is not built, and is refused with UVS_ERR_METHOD (-4, as in uvs_rmckf.h), like UVS_METHOD_ANALYTICAL at every shape.
+ * is not built, and is refused with UVS_ERR_METHOD (-4, as in uvs_rmckf.h), like UVS_METHOD_ANALYTICAL at every shape
+ * (the calibrated baseline has its own pixel loop, uvs_camera_analytical_loop_f64 below).
  * Errors, all before the first HIP call: UVS_ERR_ARG for NULL fp / cam / q_start / x0 / f0 / status / k_done / stats, T < 0, fp->steps < 1,
  * fp->k_max < 1, n_joints outside 1 .. 8, n_points not in {1, 3, 4}, MCKF with fpi_epoch_max < 1; UVS_ERR_METHOD as above; UVS_ERR_SHAPE
  * for lanes_per_filter != 0, m != 2 * n_points, n != n_joints, or another (m, n).  T == 0 returns UVS_OK and launches nothing.
@@ -193,6 +194,53 @@ int uvs_camera_closed_loop_f64(const struct uvs_filter_params *fp, const uvs_cam
  * Errors: UVS_ERR_ARG for a NULL pointer, T < 0, n_points not in {1, 3, 4}; UVS_ERR_SHAPE for n_joints != 6.  T == 0 returns UVS_OK.
  */
 int uvs_camera_guess_f64(const uvs_camera *cam, int64_t T, const double *q_start, const double *f0, double *x0_out, void *stream);
+
+/*
+ * The calibrated IBVS baseline (Method.ANALYTICAL, experiment.py:145-162 and :300-320) through pixels: the control law whose interaction
+ * matrix is evaluated from the model at every step instead of estimated -- what the estimators of the loop above are compared against.
+ * The two entry points below are that loop's single step and its one launch.  The step, defined once for both:
+ *   (rot, pos, Jc) = the camera pose and the geometric Jacobian of the DH chain in the camera frame at the joints q;
+ *   depth_p = |pos - points[p]|, the true camera-disc distance (computeZ(recalculate_fkine=True));
+ *   rows 2p, 2p+1 of J = the image-Jacobian rows at the NOISY DETECTED u = f[2p], v = f[2p+1] (raw pixels) and depth_p, times Jc;
+ *   err = f - desired; kappa = 1;
+ *   status FAIL when an entry of J is not finite (numpy's pinv raises there, :313-316): a disc left the frame (NaN pair) or the noise
+ *     row holds a NaN;
+ *   dq = -gain * pinv(J) err by the solver sequence of the loop above: the plain least-squares solve with its watches, and the careful
+ *     one (numpy's pinv) for a solve whose watch fires, or for every solve under UVS_OPT_STRICT_PINV.
+ * Both kernels form every value through the same device functions (libuvs_rmckf's device header, compiled into this library with
+ * -ffp-contract=off) in the same order: K x (uvs_camera_features_f64, uvs_camera_analytical_step_f64) on rows of the logs and the one
+ * launch give the same bits.
+ * Both entry points, before the first HIP call: fp->method must be UVS_METHOD_ANALYTICAL (else UVS_ERR_METHOD); fp->lanes_per_filter 0,
+ * (fp->m, fp->n) one of (8, 6), (6, 6), (2, 6) with fp->m == 2 * cam->n_points and fp->n == cam->n_joints == 6 (else UVS_ERR_SHAPE; the
+ * kernels run 4, 2, 1 lanes per trial); fp->reserved 0 or UVS_OPT_STRICT_PINV (else UVS_ERR_ARG); m, n, gain, desired, reserved -- and
+ * for the loop steps and dt -- are read, the estimator fields are ignored.  UVS_ERR_ARG for a NULL mandatory pointer, T < 0, n_joints
+ * outside 1 .. 8, n_points not in {1, 3, 4}.  T == 0 returns UVS_OK and launches nothing.  All three shapes are built, in every form,
+ * with 0 B of scratch memory.
+ *
+ * uvs_camera_analytical_step_f64: one step for T trials.
+ *   q [T][n] in; f [T][m] in: detected features, noise already added.
+ *   dq_out [T][n] out; err_out [T][m] out; j_out [T][m*n] out or NULL: J, row-major; status [T] int32 out: UVS_STATUS_SUCCESS or _FAIL.
+ *   On FAIL the trial's dq_out row is unspecified; err_out and j_out are still written.
+ * 64 / lanes trials per wavefront.
+ */
+int uvs_camera_analytical_step_f64(const struct uvs_filter_params *fp, const uvs_camera *cam, int64_t T, const double *q, const double *f,
+                                   double *dq_out, double *err_out, double *j_out, int32_t *status, void *stream);
+
+/*
+ * uvs_camera_analytical_loop_f64: the pixel closed loop of the calibrated law in ONE launch, K = fp->steps >= 1 (else UVS_ERR_ARG).
+ *   q_start [T][n] in.  noise [K][T][m] in or NULL.
+ *   q_log [K][T][n], f_log [K][T][m], dq_log [K][T][n], err_log [K][T][m] out, each or NULL (not written).
+ *   status [T], k_done [T] int32 out; stats [T][3] out; pixels [T][n_points] int32 out or NULL: as uvs_camera_closed_loop_f64 writes them.
+ * Step k: q_k = q_{k-1} + dq_{k-1} * dt (one rounded multiply, one rounded add; q_0 = q_start), f_k = the frame-free detection at q_k
+ * + noise_k, then the step above.  The rules are those of uvs_camera_closed_loop_f64: rows q_log[k], f_log[k] are written for
+ * k <= k_done, rows dq_log[k], err_log[k] for k < k_done, the rest is left as it was; the clock t_k = dt accumulated in floating point
+ * and the order of the statistics' sums; pixels = the smallest mask per colour over k <= k_done; a FAILed trial (k_done = the failing
+ * step) stops alone.  There is no x0, f0 or kappa_log.
+ * One workgroup of 256 threads per trial up to 256 trials, per four trials beyond; the results do not depend on which.
+ */
+int uvs_camera_analytical_loop_f64(const struct uvs_filter_params *fp, const uvs_camera *cam, int64_t T, const double *q_start,
+                                   const double *noise, double *q_log, double *f_log, double *dq_log, double *err_log, int32_t *status,
+                                   int32_t *k_done, double *stats, int32_t *pixels, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,15 @@
       (e)-(g) and their (d) counterparts are host-clock times around synchronised calls, taken in alternating blocks in the same process.
 (a)-(c) are HIP-event times around the launches, taken in alternating blocks so that all three see the same machine state; every figure is
 the median of 250 iterations after a warm-up, with the 10th and 90th percentile.  The acceptance condition is (b) below (a) at every T.
-Writes profiles/camera_device.txt (or the path given).  usage: tools/time_camera.py [out.txt]"""
+Writes profiles/camera_device.txt (or the path given).  usage: tools/time_camera.py [out.txt]
+With --analytical only the calibrated baseline's pixel loop is timed, into profiles/camera_analytical.txt (or the path given):
+  (h) camera_closed_loop with fp.method == ANALYTICAL, fused=False: K x (camera features, analytical step);
+  (i) the same with fused=True: one launch;
+  (e) the fused GMCKF loop with x0 handed in, as context;
+      at T = 1 024, K = 299, white noise 0.3 px, host clock around synchronised calls in alternating blocks of one process; (h) and (i) at
+      T = 64 as well.  The acceptance condition is (i) below (h) at both sizes; (i) against (e) is reported, not gated.  Also the paired
+      ISE / IAE / ITAE medians of ANALYTICAL and GMCKF through pixels on the same starts and noise.
+usage: tools/time_camera.py --analytical [out.txt]"""
 import os
 import sys
 import time
@@ -24,7 +32,9 @@ sys.path.insert(0, ROOT)
 import uvs_amd as uvs  # noqa: E402
 import torch  # noqa: E402
 
-OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'profiles', 'camera_device.txt')
+ANALYTICAL = '--analytical' in sys.argv[1:]
+ARGV = [a for a in sys.argv[1:] if a != '--analytical']
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
 DESIRED = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
@@ -64,6 +74,90 @@ def alternate(fns, rounds=ROUNDS, block=BLOCK, warm=WARM):
         torch.cuda.synchronize()
     return {name: [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev] for name, ev in events.items()}
 
+
+def wall(fn, n=5):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return ms
+
+
+def wall_alternate(fns, rounds=5, block=4):
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            ms[name] += wall(fn, block)[:]
+    return ms
+
+
+def fmt_ms(ms):
+    med, lo, hi = stats(ms)
+    return f'median {med:9.2f} ms   (p10 {lo:.2f}, p90 {hi:.2f}, n = {len(ms)})'
+
+
+def analytical_section():
+    """(h), (i), (e): see the module docstring."""
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K = 299
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    fp_cal = uvs.engine.make_params(8, 6, 'ANALYTICAL', 10.0, False, 0.05, 15.0, 0.2, DESIRED)
+    assert fp.steps == K and fp_cal.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --analytical on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# K = {K}, white noise 0.3 px; host clock around synchronised calls, alternating blocks in one process, allocation of the logs included')
+    ok = True
+    for T, rounds, block in ((1024, 5, 4), (64, 5, 4)):
+        q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+        q0[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+        q0_d = torch.as_tensor(q0, device='cuda')
+        noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+        x0_d = uvs.engine.camera_guess(plant, q0_d, uvs.engine.camera_features(plant, q0_d))
+        stepwise, fused = loop(fp_cal, plant, q0_d, noise), loop(fp_cal, plant, q0_d, noise, fused=True)
+        gmckf = loop(fp, plant, q0_d, noise, x0=x0_d, fused=True)
+        torch.cuda.synchronize()
+        same = all(torch.equal(fused[key].view(torch.int64), stepwise[key].view(torch.int64)) for key in ('err', 'q', 'f', 'dq', 'stats'))
+        same = same and all(torch.equal(fused[key], stepwise[key]) for key in ('status', 'k_done', 'pixels'))
+        assert same, 'the one launch and the stepwise loop of the calibrated law disagree'
+        fns = {'h': lambda: loop(fp_cal, plant, q0_d, noise), 'i': lambda: loop(fp_cal, plant, q0_d, noise, fused=True)}
+        if T == 1024:
+            fns['e'] = lambda: loop(fp, plant, q0_d, noise, x0=x0_d, fused=True)
+        ms = wall_alternate(fns, rounds=rounds, block=block)
+        h_med, i_med = float(np.median(ms['h'])), float(np.median(ms['i']))
+        ok = ok and i_med < h_med
+        say()
+        say(f'T = {T}')
+        say(f'  (h) ANALYTICAL, stepwise: K x (camera features, analytical step)   {fmt_ms(ms["h"])}   = {h_med / K * 1e3:.1f} us per step')
+        say(f'  (i) ANALYTICAL, fused=True: one launch                             {fmt_ms(ms["i"])}   = {i_med / K * 1e3:.1f} us per step')
+        say(f'  (i) / (h) = {i_med / h_med:.4f}: (i) is {"BELOW" if i_med < h_med else "NOT below"} (h); logs, stats, status, k_done, pixels bit-identical')
+        if 'e' in ms:
+            e_med = float(np.median(ms['e']))
+            say(f'  (e) GMCKF, fused=True, x0 handed in (context)                      {fmt_ms(ms["e"])}   = {e_med / K * 1e3:.1f} us per step')
+            say(f'  (i) / (e) = {i_med / e_med:.4f} (reported, not gated)')
+        ok_cal, ok_est = (fused['status'] == 0).cpu().numpy(), (gmckf['status'] == 0).cpu().numpy()
+        both = ok_cal & ok_est
+        med_cal, med_est = (np.median(out['stats'].cpu().numpy()[both], axis=0).round(3).tolist() for out in (fused, gmckf))
+        say(f'  through pixels, paired over the {int(both.sum())} of {T} trials both ran to the end (FAIL: ANALYTICAL {int((~ok_cal).sum())}, '
+            f'GMCKF {int((~ok_est).sum())}); smallest mask {int(fused["pixels"].min())} px')
+        say(f'    median ISE / IAE / ITAE   ANALYTICAL {med_cal}   GMCKF {med_est}')
+    say()
+    say(f'acceptance: (i) below (h) at both sizes: {"yes" if ok else "NO"}')
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if ANALYTICAL:
+    analytical_section()
+    sys.exit(0)
 
 plant = uvs.SyntheticPlant.ur10()
 cam = plant.to_camera()                              # the uvs_camera struct, built once: the wrappers take it in place of the plant
@@ -109,18 +203,6 @@ noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
 noise_kct = noise.permute(0, 2, 1).contiguous()                      # closed_loop's default layout [step][component][trial]
 
 
-def wall(fn, n=5):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(n):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return ms
-
-
 out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise)
 torch.cuda.synchronize()
 ms_pixels = wall(lambda: uvs.engine.camera_closed_loop(fp, plant, q0_d, noise))
@@ -152,22 +234,6 @@ say(f'  ideal features: {int((ideal["status"] == 0).sum())} of {T} trials SUCCES
 
 
 # ---- (e)-(g) the same loop as one launch, against (d) in alternating blocks
-def wall_alternate(fns, rounds=5, block=4):
-    for fn in fns.values():
-        fn()
-    torch.cuda.synchronize()
-    ms = {name: [] for name in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            ms[name] += wall(fn, block)[:]
-    return ms
-
-
-def fmt_ms(ms):
-    med, lo, hi = stats(ms)
-    return f'median {med:9.2f} ms   (p10 {lo:.2f}, p90 {hi:.2f}, n = {len(ms)})'
-
-
 loop = uvs.engine.camera_closed_loop
 fused = loop(fp, plant, q0_d, noise, x0=x0_d, fused=True)
 torch.cuda.synchronize()

@@ -42,6 +42,10 @@ SYMBOLS = {
     # fp (a pointer to _lib.FilterParams, passed with byref), cam, T, q_start, noise, x0, f0, five logs, status, k_done, stats, pixels, stream
     'uvs_camera_closed_loop_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 14),
     'uvs_camera_guess_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _VP, _VP]),
+    # fp, cam, T, q, f, dq_out, err_out, j_out, status, stream
+    'uvs_camera_analytical_step_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 7),
+    # fp, cam, T, q_start, noise, four logs, status, k_done, stats, pixels, stream
+    'uvs_camera_analytical_loop_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 11),
 }
 
 _lib = None

@@ -460,7 +460,85 @@ def camera_guess(plant, q_start, f0, radius=None, out=None):
     return out
 
 
+def camera_analytical_step(plant, q, f, fp, radius=None, dq=None, err=None, j=None, status=None):
+    """One step of the calibrated IBVS baseline for T trials on the current stream (uvs_camera_analytical_step_f64): the interaction matrix
+    from the model at the joints ``q`` (T, 6) and the DETECTED features ``f`` (T, 2 n_points) -- raw pixels, noise already added -- then
+    dq = -gain pinv(J) (f - desired).  ``plant``: a SyntheticPlant or a ``Camera`` struct; ``fp.method`` must be ANALYTICAL.  Returns
+    (dq (T, 6), err (T, m), status (T,) int32), written into the tensors given or into new ones; ``j`` (T, m * 6), when given, receives J.
+    A trial whose J is not finite has status FAIL and an unspecified dq row."""
+    from . import _vision, plant as plant_mod
+    torch = _torch()
+    cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    T, n, m = q.shape[0], cam.n_joints, 2 * cam.n_points
+    dev = _device_of(q, f)
+    if dq is None:
+        dq = torch.empty((T, n), dtype=torch.float64, device=dev)
+    if err is None:
+        err = torch.empty((T, m), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty(T, dtype=torch.int32, device=dev)
+    rc = _vision.lib().uvs_camera_analytical_step_f64(C.byref(fp), C.byref(cam), T, _operand(q, 'q', torch.float64, (T, n)),
+                                                      _operand(f, 'f', torch.float64, (T, m)), _operand(dq, 'dq', torch.float64, (T, n)),
+                                                      _operand(err, 'err', torch.float64, (T, m)),
+                                                      _operand(j, 'j', torch.float64, (T, m * n), True),
+                                                      _operand(status, 'status', torch.int32, (T,)), _stream())
+    _vision.check(rc)
+    return dq, err, status
+
+
 CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
+ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
+
+
+def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want):
+    """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs."""
+    from . import _vision
+    torch = _torch()
+    K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
+    T, dev = q_start.shape[0], q_start.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    q0 = _operand(q_start, 'q_start', torch.float64, (T, n))
+    noise_ptr = _operand(noise, 'noise', torch.float64, (K, T, m), True)
+    comps = dict(err=m, q=n, f=m, dq=n)
+    if fused:
+        log = {key: torch.empty((K, T, comps[key]), **f64) for key in ANALYTICAL_CAMERA_LOGS if key in want}
+        ptr = lambda key: log[key].data_ptr() if key in log else None   # noqa: E731
+        status, k_done = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2))
+        stats = torch.empty((T, 3), **f64)
+        pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
+        rc = _vision.lib().uvs_camera_analytical_loop_f64(C.byref(fp), C.byref(cam), T, q0, noise_ptr, ptr('q'), ptr('f'), ptr('dq'), ptr('err'),
+                                                          status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
+        _vision.check(rc)
+        return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
+    log = {key: torch.empty((K, T, comp), **f64) for key, comp in comps.items()}
+    status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
+    pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
+    features, step = _vision.lib().uvs_camera_features_f64, _vision.lib().uvs_camera_analytical_step_f64
+    cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
+    row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
+    at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
+    noise_row = 0 if noise is None else noise.stride(0) * 8
+    for k in range(K):
+        q_prev, dq_prev = (q0, None) if k == 0 else (at('q', k - 1), at('dq', k - 1))
+        _vision.check(features(cam_ref, T, q_prev, dq_prev, fp.dt, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k),
+                               at('pixels', k), None, stream))
+        _vision.check(step(fp_ref, cam_ref, T, at('q', k), at('f', k), at('dq', k), at('err', k), None, at('status', k), stream))
+    return _reduce_camera_logs(fp, log, status_log, pixel_log, want)
+
+
+def _reduce_camera_logs(fp, log, status_log, pixel_log, want):
+    """k_done, status, pixels and stats of a stepwise pixel loop from its per-step status words and mask sizes."""
+    torch = _torch()
+    K, dev = status_log.shape[0], status_log.device
+    failed = status_log != 0
+    steps = torch.arange(K, device=dev, dtype=torch.int32)[:, None]
+    k_done = torch.where(failed, steps, torch.full_like(steps, K)).amin(0)          # the first FAIL, else K
+    status = (k_done < K).to(torch.int32)
+    seen = steps <= k_done[None, :]                                  # the failing step's own masks count: an empty one shows as 0
+    pixels = torch.where(seen[:, :, None], pixel_log, torch.full_like(pixel_log, 2 ** 31 - 1)).amin(0)
+    out = dict({key: t for key, t in log.items() if key in want}, pixels=pixels, status=status, k_done=k_done)
+    out['stats'] = stats_reduce(log['err'], _loop_times(fp.dt, K), k_done, layout='ktc')
+    return out
 
 
 def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want):
@@ -507,10 +585,22 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     ``fused=True`` runs the same loop as ONE launch (uvs_camera_closed_loop_f64: the filter state stays in registers over the K steps) and
     returns the same bits; ``want`` names the logs to return (the others are neither allocated nor written).  ``guess='device'`` computes the
     initial guess with ``camera_guess`` instead of the per-trial host loop, under either value of ``fused``: equal to the host's to about
-    1e-13, not in the last bits.  With fused=True a ``Camera`` struct is accepted for ``plant`` when x0 is given or guess='device'."""
+    1e-13, not in the last bits.  With fused=True a ``Camera`` struct is accepted for ``plant`` when x0 is given or guess='device'.
+    ``fp.method == ANALYTICAL`` runs the calibrated IBVS baseline through the same pixels instead of an estimator: fused=True is one launch
+    (uvs_camera_analytical_loop_f64), fused=False K x (uvs_camera_features_f64, uvs_camera_analytical_step_f64) with the same reduction, and
+    the two return the same bits.  It takes no ``x0`` and no ``guess`` (ValueError), ``want`` is a subset of ('err', 'q', 'f', 'dq') --
+    there is no 'kappa' -- and ``plant`` may be a ``Camera`` struct."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
+    analytical = fp.method == _lib.METHOD_ANALYTICAL
+    if analytical:                                                   # refused on the arguments alone, before anything is looked at
+        if x0 is not None or guess != 'host':
+            raise ValueError('camera_closed_loop: the calibrated baseline estimates nothing: it takes no x0 and no guess')
+        want = ANALYTICAL_CAMERA_LOGS if want is CAMERA_LOGS else tuple(want)
+        unknown = [key for key in want if key not in ANALYTICAL_CAMERA_LOGS]
+        if unknown:
+            raise ValueError(f'camera_closed_loop: the calibrated baseline logs {ANALYTICAL_CAMERA_LOGS}, it has no {unknown}')
     if fused and not getattr(q_start, 'is_cuda', False):
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     torch = _torch()
@@ -520,6 +610,11 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         raise ValueError('camera_closed_loop: at least one step (fp.steps) and one trial')
     if not q_start.is_cuda:
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
+    if analytical:
+        cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+        if m != 2 * cam.n_points or n != cam.n_joints:
+            raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
+        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want)
     if fused and (x0 is not None or guess == 'device' or not fp.initial_guess):
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -567,15 +662,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
                                at('pixels', k), None, stream))
         _lib.check(step(fp_ref, T, X.data_ptr(), P.data_ptr(), at('f', k), f_old, dq_zero.data_ptr() if k == 0 else dq_prev, int(k == 0), k,
                         at('dq', k), at('err', k), at('kappa', k), at('status', k), stream))
-    failed = status_log != 0
-    steps = torch.arange(K, device=dev, dtype=torch.int32)[:, None]
-    k_done = torch.where(failed, steps, torch.full_like(steps, K)).amin(0)          # the first FAIL, else K
-    status = (k_done < K).to(torch.int32)
-    seen = steps <= k_done[None, :]                                  # the failing step's own masks count: an empty one shows as 0
-    pixels = torch.where(seen[:, :, None], pixel_log, torch.full_like(pixel_log, 2 ** 31 - 1)).amin(0)
-    out = dict({key: t for key, t in log.items() if key in want}, pixels=pixels, status=status, k_done=k_done)
-    out['stats'] = stats_reduce(log['err'], _loop_times(fp.dt, K), k_done, layout='ktc')
-    return out
+    return _reduce_camera_logs(fp, log, status_log, pixel_log, want)
 
 
 def _loop_times(t_s, K):
