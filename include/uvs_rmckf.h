@@ -250,6 +250,7 @@ int uvs_analytical_closed_loop_f64(const uvs_filter_params *fp, const uvs_plant 
  * (experiment.py:166-312 without the plant): the parity workhorse.
  *   f        [T][K+1][m]  in   observed features; row 0 is f_old of the first step (:128)
  *   dq       [T][K][n]    in   regressor of step k (previous command, :188); row 0 ignored (H = 0, :183)
+ *                              (held by tests/test_gpu_parity.py::test_replay_ignores_row_0_of_dq: NaN there changes no bit of any output)
  *   x0       [T][1][m*n]  in
  *   x_out    [T][K][m*n], err_out [T][K][m], kappa_out [T][K][m], dqcmd_out [T][K][n]  out (NULL to skip)
  *   status   [T] int32, k_done [T] int32  out   (status is REQUIRED when dqcmd_out is requested: same two-pass scheme as the closed loop)
@@ -265,8 +266,10 @@ int uvs_rmckf_replay_f64(const uvs_filter_params *fp, int64_t T, uvs_view f, uvs
 /*
  * Single-precision estimator-only replay (SURVEY.md 8d "fp32 variant: report measured error"): the estimator of experiment.py:166-297 over
  * recorded streams with fp32 streams AND fp32 state, (8,6), KF / IMCC-KF / GMCKF.  A MEASURED LOWER-PRECISION VARIANT, not a drop-in: per-step
- * X deviates from the reference's fp64 runs by ~1e-6 relative (bounded at 1e-5 by tests/test_gpu_replay_f32.py), and no control law is
- * solved.  Views as in uvs_rmckf_replay_f64 with float elements (strides in floats); f has K + 1 rows, dq K rows, x0 one row.
+ * X deviates from the reference's fp64 runs by ~1e-6 relative (bounded at 1e-5 by tests/test_gpu_replay_f32.py, which also holds it to
+ * within twice the error of a plain float32 restatement of the estimators, oracle/rmckf_block_f32.py, on every estimator, stream
+ * selection, view and FAIL placement), and no control law is solved.  Views as in uvs_rmckf_replay_f64 with float elements (strides in
+ * floats); f has K + 1 rows, dq K rows (row 0 ignored), x0 one row.
  *   x_out [T][K][m*n], err_out [T][K][m] out (base NULL to skip); status / k_done [T] int32 out (NULL to skip; FAIL = non-finite X)
  */
 typedef struct uvs_view_f32 {

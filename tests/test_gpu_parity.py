@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_names, load_golden, rel_err, scene_desired
+import gpu_harness as gh
 from gpu_harness import random_replay_case
 
 pytestmark = pytest.mark.gpu
@@ -423,6 +424,53 @@ def test_replay_other_shapes_match_block_oracle(uvs, m, n, lanes, method):
         assert rel_err(out['dqcmd'].cpu().numpy()[:, :, t], ref['dq_cmd']) <= 1e-8
         assert rel_err(out['kappa'].cpu().numpy()[:, :, t], ref['kappa']) <= 1e-9
         assert rel_err(out['p_final'].cpu().numpy()[t].reshape(m, n, n), ref['P_final']) <= 1e-10
+
+
+# (m, n), lanes_per_filter, with the commanded dq, fp.reserved, estimators: every family of replay kernels uvs_rmckf_replay_f64 chooses between
+_THREE = ('GMCKF', 'KF', 'IMCCKF')
+ROW0_ROUTES = [((8, 6), 0, False, 0, _THREE), ((8, 6), 4, False, 0, _THREE),                 # the estimator-only row kernels
+               ((8, 6), 0, True, 0, _THREE + ('MCKF',)),                                     # the same + control wavefronts; MCKF once
+               ((8, 6), 2, True, 0, _THREE), ((8, 6), -2, True, 0, _THREE),                  # tuned kernel, generic template
+               ((8, 6), 0, True, gh.STRICT, _THREE),                                         # UVS_OPT_STRICT_PINV: the careful pass alone
+               ((6, 6), 2, True, 0, _THREE), ((2, 6), 1, True, 0, _THREE), ((32, 7), 8, True, 0, _THREE)]
+
+
+def _route_id(route):
+    (m, n), lanes, cmd, reserved, _ = route
+    return f'{m}x{n}-lanes{lanes}-{"cmd" if cmd else "alone"}{"-strict" if reserved else ""}'
+
+
+@pytest.mark.parametrize('route', ROW0_ROUTES, ids=_route_id)
+def test_replay_ignores_row_0_of_dq(uvs, route):
+    """"dq row 0 ignored (H = 0)", include/uvs_rmckf.h: the first step has no regressor (experiment.py:183-185), so what row 0 of dq holds --
+    zeros, as in every recorded stream, other finite values, or NaN -- must not reach a single bit of any output, and no trial may FAIL.
+    T = 35 trials (gh.step_recipe at two lanes per filter: 32 + 3) over K = 6 steps of the single-step suite's oracle-driven inputs."""
+    import zlib
+    shape, lanes, cmd, reserved, methods = route
+    (m, n), K = shape, 6
+    for method in methods:
+        rng = np.random.default_rng(zlib.crc32(repr((m, n, method, 'row 0')).encode()))
+        head, *steps = gh.step_recipe(rng, m, n, 2, method, 0, 1.0, 7.5, True, K)
+        T = head['T']
+        assert T == 35 and all(st['finite'].all() for st in steps)
+        f = np.stack([steps[0]['f_old']] + [st['f'] for st in steps], axis=1)                 # (T, K + 1, m)
+        dq = np.stack([st['dq'] for st in steps], axis=1)                                     # (T, K, n)
+        assert not dq[:, 0].any() and np.abs(dq[:, 1]).min() > 0
+        fp = uvs.engine.make_params(m, n, method, 7.5, True, 0.05, 15.0, head['gain'], head['desired'], False, lanes, K)
+        fp.reserved = reserved
+        want = ('x', 'err', 'kappa', 'dqcmd') if cmd else ('x', 'err', 'kappa')
+        outs = []
+        for row0 in (0.0, 0.3 * rng.standard_normal((T, n)), np.nan):
+            dq_in = dq.copy()
+            dq_in[:, 0] = row0
+            outs.append(gh.replay(uvs, fp, f, dq_in, head['x0'], want))
+        tag = (shape, lanes, cmd, reserved, method)
+        for out in outs:
+            assert not out['status'].any() and np.all(out['k_done'] == K), tag
+            for key in ('x', 'err', 'kappa', 'dqcmd', 'status', 'k_done', 'x_final', 'p_final'):
+                assert (out[key] is None and outs[0][key] is None) or gh.same_bits(out[key], outs[0][key]), (key,) + tag
+        for t in range(T):                                                                    # and X is the oracle's, which sees H = 0 first, then row k at step k
+            assert rel_err(outs[0]['x'][t], np.stack([st['X'][t] for st in steps])) <= gh.REPLAY_GATES['x'][1], (t,) + tag
 
 
 @pytest.mark.parametrize('method', ['GMCKF', 'KF', 'IMCCKF'])

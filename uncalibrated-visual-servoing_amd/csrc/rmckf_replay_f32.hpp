@@ -1,7 +1,10 @@
 // Estimator-only replay in single precision -- the "measured variant" of SURVEY.md sections 0 (fact 5), 7 (step 2) and 8d: the same
 // row-form estimator as experiment.py:166-297 over recorded feature / joint-delta streams, fp32 streams AND fp32 state.  It is never the
-// headline and carries no parity gate beyond a measured bound (tests/test_gpu_replay_f32.py prints the per-fixture error against the
-// reference's fp64 runs): its purpose is to show what the streaming design does once VALU issue stops binding.  fp64 arithmetic issues one
+// headline and no parity path.  tests/test_gpu_replay_f32.py prints the per-fixture error against the reference's fp64 runs (~1e-6, bounded
+// at 1e-5) and holds the kernel to a plain float32 restatement of the same formulas (oracle/rmckf_block_f32.py, test infrastructure: Joseph
+// form, no FMA): its error against fp64 at most twice the restatement's, on all twelve instantiations, any strides, NULL status / k_done,
+// dq row 0 never read, and a FAILed trial leaving its earlier rows and its neighbours alone.  Its purpose is to show what the streaming
+// design does once VALU issue stops binding.  fp64 arithmetic issues one
 // wave64 FMA per 4 cycles and binds every fp64 kernel of this library; here two rows of a filter ride in one register pair and every
 // multiply-add is a v_pk_fma_f32 (two fp32 FMAs per lane and instruction, same issue cost), so the arithmetic of a step shrinks 4x per
 // trial and the kernel is left with its streams: read f (m) + dq (n), write X (mn) + err (m) = 4 (2m + n + mn) = 280 B per update at (8,6).
