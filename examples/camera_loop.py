@@ -7,7 +7,12 @@ both, side by side, and the smallest colour mask the detector ever saw.
 --baseline answers the question the reference's experiment asks -- what does not knowing the Jacobian cost? -- through pixels: the chosen
 estimator and the calibrated control law (Method.ANALYTICAL, fp.method == ANALYTICAL) on the same starts and the same noise, paired trial by
 trial over the trials both ran to the end, with the FAIL count of each.
-usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline]"""
+--miscalibration asks what each side loses when the model is WRONG -- the experiment that motivates uncalibrated visual servoing.  A ladder
+of miscalibration levels (LEVELS below: the signed fraction of a focal length 20 % long, discs believed 5 cm aside and 20 cm lower, encoder
+zeros off by up to 0.1 rad, links 3 % short; a negative level errs the other way) times the trials is ONE launch per side: the calibrated law on every trial's believed model
+(engine.camera_closed_loop(believed=..., believed_index=...)), and the estimator started from the analytic guess of that same wrong model, on the
+same starts and the same noise at every level.  Prints the median ISE / IAE / ITAE per level over the trials neither side FAILed.
+usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]"""
 import argparse
 import os
 import sys
@@ -16,6 +21,49 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+LEVELS = (-1.0, -0.5, 0.0, 0.5, 1.0)                                  # fraction of the full miscalibration below, either way; 0 is the true model
+JOINT_OFFSETS = np.array([0.03, -0.02, 0.04, -0.03, 0.02, 0.1])      # radians; the last one is a camera roll
+
+
+def believed_plant(uvs, plant, level):
+    """The model believed at miscalibration ``level``: every knob of plant.miscalibrated moved by that fraction of its full value."""
+    return uvs.plant.miscalibrated(plant, focal_scale=1.0 + 0.2 * level, point_offset=level * np.array([0.05, -0.05, -0.2]),
+                                   joint_offset=level * JOINT_OFFSETS, link_scale=1.0 - 0.03 * level)
+
+
+def miscalibration_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed=0, levels=LEVELS):
+    """The robustness table as a list of lines: levels x trials in one launch per side."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    fp = uvs.engine.make_params(8, 6, method, 10.0, False, 0.05, 15.0, 0.2, desired, True)
+    fp_cal = uvs.engine.make_params(8, 6, 'ANALYTICAL', 10.0, False, 0.05, 15.0, 0.2, desired)
+    n, K = len(levels), fp.steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    noise = rng.standard_normal((K, trials, 8)) * sigma
+    q0_d = torch.as_tensor(np.tile(q0, (n, 1)), device='cuda')       # the same starts and the same noise at every level
+    noise_d = torch.as_tensor(np.tile(noise, (1, n, 1)), device='cuda')
+    believed = uvs.engine.believed_models([believed_plant(uvs, plant, level) for level in levels], radius)
+    index = np.repeat(np.arange(n, dtype=np.int32), trials)
+    kw = dict(radius=radius, fused=True, want=(), believed=believed, believed_index=index)
+    calibrated = uvs.engine.camera_closed_loop(fp_cal, plant, q0_d, noise_d, **kw)
+    estimator = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, guess='device', **kw)
+    torch.cuda.synchronize()
+    lines = [f'miscalibration ladder, {n} levels x {trials} trials of {K} steps in one launch per side, white noise {sigma} px; '
+             'median over the trials neither side FAILed',
+             f'{"level":>6s}{"focal":>7s}{"paired":>8s}   {"ANALYTICAL on the wrong model":^36s}{"FAIL":>6s}   {method + " started from it":^36s}{"FAIL":>6s}',
+             f'{"":21s}   {"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"":6s}   {"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}']
+    for i, level in enumerate(levels):
+        rows = slice(i * trials, (i + 1) * trials)
+        ok_cal, ok_est = ((out['status'][rows] == 0).cpu().numpy() for out in (calibrated, estimator))
+        both = ok_cal & ok_est
+        med = [np.median(out['stats'][rows].cpu().numpy()[both], axis=0) if both.any() else np.full(3, np.nan) for out in (calibrated, estimator)]
+        lines.append(f'{level:6.2f}{1.0 + 0.2 * level:7.2f}{int(both.sum()):>8d}   {med[0][0]:12.3f}{med[0][1]:12.3f}{med[0][2]:12.3f}{int((~ok_cal).sum()):>6d}'
+                     f'   {med[1][0]:12.3f}{med[1][1]:12.3f}{med[1][2]:12.3f}{int((~ok_est).sum()):>6d}')
+    return lines
 
 
 def main():
@@ -27,9 +75,13 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--fused', action='store_true', help='the pixel loop as one launch, initial guess on the device, no log returned')
     ap.add_argument('--baseline', action='store_true', help='pair the estimator with the calibrated law (ANALYTICAL) through the same pixels')
+    ap.add_argument('--miscalibration', action='store_true', help='a ladder of wrong models x trials in one launch per side, and nothing else')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
+    if args.miscalibration:
+        print('\n'.join(miscalibration_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
+        return
     desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])                   # config.json:9
     plant = uvs.SyntheticPlant.ur10(desired)
     fp = uvs.engine.make_params(8, 6, args.method, 10.0, False, 0.05, 15.0, 0.2, desired, True)

@@ -242,6 +242,44 @@ int uvs_camera_analytical_loop_f64(const struct uvs_filter_params *fp, const uvs
                                    const double *noise, double *q_log, double *f_log, double *dq_log, double *err_log, int32_t *status,
                                    int32_t *k_done, double *stats, int32_t *pixels, void *stream);
 
+/*
+ * The calibrated law on a WRONG model, per trial.  The loop above hands its control side the camera that renders the frames; the entry
+ * points below take the control side's model as a second operand, so that the baseline can be miscalibrated, differently in every trial:
+ *   believed [n_believed] in: uvs_camera structs IN DEVICE (or pinned host) MEMORY, unlike `cam`, which stays a host struct passed by value
+ *     into the launch.  A wrong model is a uvs_camera with other numbers in it -- focal: the intrinsics; points: the depth assumption;
+ *     theta_offset: encoder zeros (joint 6: camera roll); d, a, cos_alpha, sin_alpha: link and hand-eye geometry.  n_joints and n_points
+ *     of a believed struct are ignored (the shape is fp's, and cam's where there is one), and so are center and radius, which the law
+ *     does not read.
+ *   believed_index [T] int32 in (device or pinned) or NULL.  With an index trial t uses believed[believed_index[t]].  Without one
+ *     n_believed must be 1 (every trial uses believed[0]) or T (trial t uses believed[t]), else UVS_ERR_ARG.
+ *   An index outside [0, n_believed) never becomes an address.  That trial reads no model and FAILs: the step writes its status FAIL and
+ *     nothing else; the loop writes status FAIL and k_done = 0 and nothing else (no log row, no stats, no pixels); the guess writes
+ *     nothing.  Its neighbours are untouched.
+ * The step is the one of uvs_camera_analytical_step_f64, the same device function on the same operands: with believed == the true camera
+ * every entry point here gives the bits of its calibrated counterpart, and K x (uvs_camera_features_f64 on the true camera,
+ * uvs_camera_believed_step_f64) on rows of the logs gives the bits of uvs_camera_believed_loop_f64.
+ * Refusals, before the first HIP call: those of the calibrated entry points (method, reserved, lanes_per_filter, shape, NULL mandatory
+ * pointers, T, and for the loop steps), UVS_ERR_ARG for NULL believed, n_believed < 1, or n_believed not in {1, T} without an index.
+ * T == 0 (with n_believed == 1 or an index) returns UVS_OK and launches nothing.  All three shapes are built, in every form, with 0 B of
+ * scratch memory: the kernels stage their trials' models through LDS (472 B per trial) instead of holding them in registers.
+ *
+ * uvs_camera_believed_step_f64: uvs_camera_analytical_step_f64 without `cam` (n_points = fp->m / 2, n_joints = fp->n), 64 / lanes trials
+ * per wavefront.
+ * uvs_camera_believed_loop_f64: uvs_camera_analytical_loop_f64; the sensor side (projection, detection) uses `cam`, the law `believed`.
+ * uvs_camera_believed_guess_f64: uvs_camera_guess_f64 on the trial's believed model, so that an estimator can start from the same wrong
+ *   model the baseline is stuck with.  There is no true camera among its operands, so the number of points is an argument of its own;
+ *   six joints.  f0 are the features detected on the true camera.  UVS_ERR_ARG for a NULL pointer, T < 0, n_points not in {1, 3, 4}.
+ */
+int uvs_camera_believed_step_f64(const struct uvs_filter_params *fp, int64_t T, const uvs_camera *believed, int64_t n_believed,
+                                 const int32_t *believed_index, const double *q, const double *f, double *dq_out, double *err_out,
+                                 double *j_out, int32_t *status, void *stream);
+int uvs_camera_believed_loop_f64(const struct uvs_filter_params *fp, const uvs_camera *cam, int64_t T, const uvs_camera *believed,
+                                 int64_t n_believed, const int32_t *believed_index, const double *q_start, const double *noise,
+                                 double *q_log, double *f_log, double *dq_log, double *err_log, int32_t *status, int32_t *k_done,
+                                 double *stats, int32_t *pixels, void *stream);
+int uvs_camera_believed_guess_f64(int64_t T, int32_t n_points, const uvs_camera *believed, int64_t n_believed,
+                                  const int32_t *believed_index, const double *q_start, const double *f0, double *x0_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,15 @@ With --analytical only the calibrated baseline's pixel loop is timed, into profi
       at T = 1 024, K = 299, white noise 0.3 px, host clock around synchronised calls in alternating blocks of one process; (h) and (i) at
       T = 64 as well.  The acceptance condition is (i) below (h) at both sizes; (i) against (e) is reported, not gated.  Also the paired
       ISE / IAE / ITAE medians of ANALYTICAL and GMCKF through pixels on the same starts and noise.
-usage: tools/time_camera.py --analytical [out.txt]"""
+usage: tools/time_camera.py --analytical [out.txt]
+With --believed only the calibrated baseline on a per-trial believed model is timed, into profiles/camera_believed.txt (or the path given):
+  (j) camera_closed_loop with fp.method == ANALYTICAL and believed models mixed over the trials through an index, fused=False:
+      K x (camera features on the true camera, believed step);
+  (k) the same with fused=True: one launch;
+  (i) the calibrated one launch of --analytical, in the same run;
+      method and sizes as --analytical.  The acceptance condition is (k) below (j) at both sizes; (k) against (i) -- what reading the model
+      from LDS per trial costs -- is reported, not gated.  Then the robustness table of examples/camera_loop.py --miscalibration.
+usage: tools/time_camera.py --believed [out.txt]"""
 import os
 import sys
 import time
@@ -32,9 +40,9 @@ sys.path.insert(0, ROOT)
 import uvs_amd as uvs  # noqa: E402
 import torch  # noqa: E402
 
-ANALYTICAL = '--analytical' in sys.argv[1:]
-ARGV = [a for a in sys.argv[1:] if a != '--analytical']
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
+ANALYTICAL, BELIEVED = '--analytical' in sys.argv[1:], '--believed' in sys.argv[1:]
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_believed.txt' if BELIEVED else 'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
 DESIRED = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
@@ -155,6 +163,64 @@ def analytical_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def believed_section():
+    """(j), (k), (i): see the module docstring."""
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K = 299
+    fp_cal = uvs.engine.make_params(8, 6, 'ANALYTICAL', 10.0, False, 0.05, 15.0, 0.2, DESIRED)
+    assert fp_cal.steps == K
+    loop = uvs.engine.camera_closed_loop
+    believed = uvs.engine.believed_models([example.believed_plant(uvs, plant, level) for level in example.LEVELS])
+    say(f'# tools/time_camera.py --believed on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# K = {K}, white noise 0.3 px; host clock around synchronised calls, alternating blocks in one process, allocation of the logs included')
+    say(f'# believed models: the {len(example.LEVELS)} levels of examples/camera_loop.py --miscalibration, mixed over the trials through a device index')
+    ok = True
+    for T, rounds, block in ((1024, 5, 4), (64, 5, 4)):
+        q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+        q0[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+        q0_d = torch.as_tensor(q0, device='cuda')
+        noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+        index = torch.as_tensor((np.arange(T) % believed.shape[0]).astype(np.int32), device='cuda')
+        kw = dict(believed=believed, believed_index=index)
+        stepwise, fused = loop(fp_cal, plant, q0_d, noise, **kw), loop(fp_cal, plant, q0_d, noise, fused=True, **kw)
+        torch.cuda.synchronize()
+        k_done = fused['k_done'].cpu().numpy()
+        same = all(torch.equal(fused[key], stepwise[key]) for key in ('status', 'k_done', 'pixels')) \
+            and torch.equal(fused['stats'].view(torch.int64), stepwise['stats'].view(torch.int64))
+        for key in ('err', 'q', 'f', 'dq'):                          # the specified rows: q, f up to and including k_done, dq, err before it
+            rows = torch.arange(K, device='cuda')[:, None] < (fused['k_done'][None, :] + (1 if key in ('q', 'f') else 0))
+            a, b = (out[key].view(torch.int64)[rows] for out in (fused, stepwise))
+            same = same and torch.equal(a, b)
+        assert same, 'the one launch and the stepwise loop on the believed models disagree'
+        ms = wall_alternate({'j': lambda: loop(fp_cal, plant, q0_d, noise, **kw), 'k': lambda: loop(fp_cal, plant, q0_d, noise, fused=True, **kw),
+                             'i': lambda: loop(fp_cal, plant, q0_d, noise, fused=True)}, rounds=rounds, block=block)
+        j_med, k_med, i_med = (float(np.median(ms[key])) for key in 'jki')
+        ok = ok and k_med < j_med
+        say()
+        say(f'T = {T}   ({int((k_done == K).sum())} of {T} trials ran to the end on their believed models)')
+        say(f'  (j) believed, stepwise: K x (camera features, believed step)   {fmt_ms(ms["j"])}   = {j_med / K * 1e3:.1f} us per step')
+        say(f'  (k) believed, fused=True: one launch                           {fmt_ms(ms["k"])}   = {k_med / K * 1e3:.1f} us per step')
+        say(f'  (i) calibrated, fused=True: one launch (row (i) of --analytical) {fmt_ms(ms["i"])}   = {i_med / K * 1e3:.1f} us per step')
+        say(f'  (k) / (j) = {k_med / j_med:.4f}: (k) is {"BELOW" if k_med < j_med else "NOT below"} (j); specified log rows, stats, status, k_done, pixels '
+            'bit-identical')
+        say(f'  (k) / (i) = {k_med / i_med:.4f} (reported, not gated: the model per trial from LDS against the model in scalar registers)')
+    say()
+    say(f'acceptance: (k) below (j) at both sizes: {"yes" if ok else "NO"}')
+    say()
+    say('# examples/camera_loop.py --miscalibration (its defaults)')
+    for line in example.miscalibration_table(uvs):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if BELIEVED:
+    believed_section()
+    sys.exit(0)
 if ANALYTICAL:
     analytical_section()
     sys.exit(0)

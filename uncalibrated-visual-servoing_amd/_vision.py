@@ -46,6 +46,13 @@ SYMBOLS = {
     'uvs_camera_analytical_step_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 7),
     # fp, cam, T, q_start, noise, four logs, status, k_done, stats, pixels, stream
     'uvs_camera_analytical_loop_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 11),
+    # the believed operand is (believed: device array of Camera, n_believed, believed_index: device int32 [T] or None)
+    # fp, T, believed operand, q, f, dq_out, err_out, j_out, status, stream
+    'uvs_camera_believed_step_f64': (C.c_int, [_VP, _I64, _VP, _I64, _VP] + [_VP] * 7),
+    # fp, cam, T, believed operand, q_start, noise, four logs, status, k_done, stats, pixels, stream
+    'uvs_camera_believed_loop_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _I64, _VP] + [_VP] * 11),
+    # T, n_points, believed operand, q_start, f0, x0_out, stream
+    'uvs_camera_believed_guess_f64': (C.c_int, [_I64, _I32, _VP, _I64, _VP] + [_VP] * 4),
 }
 
 _lib = None

@@ -444,28 +444,112 @@ def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_o
     return out
 
 
-def camera_guess(plant, q_start, f0, radius=None, out=None):
+def believed_models(models, radius=None, device=None):
+    """The believed-model operand of the calibrated baseline on a wrong model: ``models`` -- a ``SyntheticPlant``, a ``Camera`` struct, or a
+    sequence of either (``plant.miscalibrated`` makes wrong plants) -- packed as the device array of ``uvs_camera`` structs that
+    uvs_camera_believed_step_f64 / _loop_f64 / _guess_f64 read: a uint8 tensor (n_believed, sizeof(uvs_camera)).  Pack once and pass the
+    tensor as ``believed=`` to as many calls as needed.  ``radius`` as ``SyntheticPlant.to_camera`` (the law does not read it)."""
+    from . import _vision, plant as plant_mod
+    torch = _torch()
+    if isinstance(models, (_vision.Camera, plant_mod.SyntheticPlant)):
+        models = [models]
+    models = list(models)
+    if not models:
+        raise ValueError('believed_models: at least one model')
+    size = C.sizeof(_vision.Camera)
+    host = np.empty((len(models), size), np.uint8)
+    for i, model in enumerate(models):
+        if not isinstance(model, (_vision.Camera, plant_mod.SyntheticPlant)):
+            raise ValueError('believed_models: a SyntheticPlant, a Camera struct, or a sequence of them')
+        cam = _camera(model, plant_mod.DISC_RADIUS if radius is None else radius)
+        host[i] = np.frombuffer(C.string_at(C.addressof(cam), size), np.uint8)
+    return torch.from_numpy(host).to(current_device(device))
+
+
+def _check_believed(believed, believed_index, T, who):
+    """What can be said of a ``believed=`` / ``believed_index=`` pair for T trials on the host alone, before anything is packed or uploaded:
+    ValueError, or (n_believed, the index as a host int32 array | the caller's device tensor | None)."""
+    import torch                                                     # not _torch(): these refusals need no GPU
+    from . import _vision, plant as plant_mod
+    if believed is None:
+        raise ValueError(f'{who}: believed_index without believed')
+    size = C.sizeof(_vision.Camera)
+    if torch.is_tensor(believed):
+        if believed.dtype != torch.uint8 or believed.dim() != 2 or believed.shape[1] != size or not believed.is_contiguous():
+            raise ValueError(f'{who}: believed is what believed_models returns: a contiguous uint8 tensor (n_believed, {size}) on the device')
+        n = believed.shape[0]
+    else:
+        n = 1 if isinstance(believed, (_vision.Camera, plant_mod.SyntheticPlant)) else len(believed)
+    if n < 1:
+        raise ValueError(f'{who}: at least one believed model')
+    if believed_index is None:
+        if n not in (1, T):
+            raise ValueError(f'{who}: {n} believed models for {T} trials: one, or one per trial, or pass believed_index')
+        return n, None
+    if torch.is_tensor(believed_index) and believed_index.is_cuda:   # the kernels FAIL a trial whose index names no model
+        return n, believed_index
+    host = np.asarray(believed_index.numpy() if torch.is_tensor(believed_index) else believed_index)
+    if host.shape != (T,) or host.dtype.kind not in 'iu':
+        raise ValueError(f'{who}: believed_index is {T} integers, one per trial')
+    if host.size and (host.min() < 0 or host.max() >= n):
+        raise ValueError(f'{who}: believed_index must lie in [0, {n}), got {int(host.min())} .. {int(host.max())}')
+    return n, np.ascontiguousarray(host, np.int32)
+
+
+def _believed_operand(believed, believed_index, T, radius, dev, who):
+    """(pointer, n_believed, index pointer or None, tensors to keep alive) of a ``believed=`` / ``believed_index=`` pair for T trials; a
+    host-side index is checked before it is uploaded."""
+    torch = _torch()
+    n, index = _check_believed(believed, believed_index, T, who)
+    if not torch.is_tensor(believed):
+        believed = believed_models(believed, radius, dev)
+    if not (believed.is_cuda or believed.is_pinned()):
+        raise ValueError(f'{who}: believed is what believed_models returns: a tensor on the device (or pinned)')
+    if index is None:
+        return believed.data_ptr(), n, None, (believed,)
+    if not torch.is_tensor(index):
+        index = torch.from_numpy(index).to(dev)
+    return believed.data_ptr(), n, _operand(index, 'believed_index', torch.int32, (T,)), (believed, index)
+
+
+def camera_guess(plant, q_start, f0, radius=None, out=None, believed=None, believed_index=None):
     """The analytic initial guess of T trials on the device (uvs_camera_guess_f64): what ``plant.analytic_guess`` returns per trial for the
     joints ``q_start`` (T, 6) and the detected features ``f0`` (T, 2 n_points), both cuda fp64, to about 1e-13 relative (another order of
-    operations, not the same bits).  Returns ``out``: (T, 2 n_points * 6)."""
+    operations, not the same bits).  Returns ``out``: (T, 2 n_points * 6).
+    ``believed`` (what ``believed_models`` returns or takes) and ``believed_index`` ((T,) integers, host or device): the guess of trial t from
+    its own believed model instead (uvs_camera_believed_guess_f64; ``plant`` then only says how many points there are) -- with an index
+    ``believed[believed_index[t]]``, without one the one model there is, or ``believed[t]`` of T.  ``f0`` stays what the true camera detects."""
+    if believed is None and believed_index is not None:
+        raise ValueError('camera_guess: believed_index without believed')
     from . import _vision, plant as plant_mod
     torch = _torch()
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
     T, n, m = q_start.shape[0], cam.n_joints, 2 * cam.n_points
     if out is None:
         out = torch.empty((T, m * n), dtype=torch.float64, device=_device_of(q_start, f0))
+    if believed is not None:
+        models, n_believed, index, _keep = _believed_operand(believed, believed_index, T, radius, _device_of(q_start, f0), 'camera_guess')
+        rc = _vision.lib().uvs_camera_believed_guess_f64(T, cam.n_points, models, n_believed, index, _operand(q_start, 'q_start', torch.float64, (T, n)),
+                                                         _operand(f0, 'f0', torch.float64, (T, m)), _operand(out, 'out', torch.float64, (T, m * n)),
+                                                         _stream())
+        _vision.check(rc)
+        return out
     rc = _vision.lib().uvs_camera_guess_f64(C.byref(cam), T, _operand(q_start, 'q_start', torch.float64, (T, n)),
                                             _operand(f0, 'f0', torch.float64, (T, m)), _operand(out, 'out', torch.float64, (T, m * n)), _stream())
     _vision.check(rc)
     return out
 
 
-def camera_analytical_step(plant, q, f, fp, radius=None, dq=None, err=None, j=None, status=None):
+def camera_analytical_step(plant, q, f, fp, radius=None, dq=None, err=None, j=None, status=None, believed=None, believed_index=None):
     """One step of the calibrated IBVS baseline for T trials on the current stream (uvs_camera_analytical_step_f64): the interaction matrix
     from the model at the joints ``q`` (T, 6) and the DETECTED features ``f`` (T, 2 n_points) -- raw pixels, noise already added -- then
     dq = -gain pinv(J) (f - desired).  ``plant``: a SyntheticPlant or a ``Camera`` struct; ``fp.method`` must be ANALYTICAL.  Returns
     (dq (T, 6), err (T, m), status (T,) int32), written into the tensors given or into new ones; ``j`` (T, m * 6), when given, receives J.
-    A trial whose J is not finite has status FAIL and an unspecified dq row."""
+    A trial whose J is not finite has status FAIL and an unspecified dq row.
+    ``believed`` / ``believed_index`` (as ``camera_guess`` takes them): the step of trial t on its own believed model
+    (uvs_camera_believed_step_f64); ``plant`` then only gives the shape.  With the true model as ``believed`` the bits are the same."""
+    if believed is None and believed_index is not None:
+        raise ValueError('camera_analytical_step: believed_index without believed')
     from . import _vision, plant as plant_mod
     torch = _torch()
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -477,11 +561,16 @@ def camera_analytical_step(plant, q, f, fp, radius=None, dq=None, err=None, j=No
         err = torch.empty((T, m), dtype=torch.float64, device=dev)
     if status is None:
         status = torch.empty(T, dtype=torch.int32, device=dev)
-    rc = _vision.lib().uvs_camera_analytical_step_f64(C.byref(fp), C.byref(cam), T, _operand(q, 'q', torch.float64, (T, n)),
-                                                      _operand(f, 'f', torch.float64, (T, m)), _operand(dq, 'dq', torch.float64, (T, n)),
-                                                      _operand(err, 'err', torch.float64, (T, m)),
-                                                      _operand(j, 'j', torch.float64, (T, m * n), True),
-                                                      _operand(status, 'status', torch.int32, (T,)), _stream())
+    operands = (_operand(q, 'q', torch.float64, (T, n)), _operand(f, 'f', torch.float64, (T, m)), _operand(dq, 'dq', torch.float64, (T, n)),
+                _operand(err, 'err', torch.float64, (T, m)), _operand(j, 'j', torch.float64, (T, m * n), True),
+                _operand(status, 'status', torch.int32, (T,)), _stream())
+    if believed is not None:
+        if fp.m != m or fp.n != n:
+            raise ValueError(f'camera_analytical_step: fp is ({fp.m}, {fp.n}) but the camera gives {m} features of {n} joints')
+        models, n_believed, index, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_analytical_step')
+        rc = _vision.lib().uvs_camera_believed_step_f64(C.byref(fp), T, models, n_believed, index, *operands)
+    else:
+        rc = _vision.lib().uvs_camera_analytical_step_f64(C.byref(fp), C.byref(cam), T, *operands)
     _vision.check(rc)
     return dq, err, status
 
@@ -490,8 +579,9 @@ CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
 ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
 
 
-def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want):
-    """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs."""
+def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None):
+    """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
+    ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -506,15 +596,21 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want):
         status, k_done = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2))
         stats = torch.empty((T, 3), **f64)
         pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
-        rc = _vision.lib().uvs_camera_analytical_loop_f64(C.byref(fp), C.byref(cam), T, q0, noise_ptr, ptr('q'), ptr('f'), ptr('dq'), ptr('err'),
-                                                          status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
+        outputs = (ptr('q'), ptr('f'), ptr('dq'), ptr('err'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
+        if believed is None:
+            rc = _vision.lib().uvs_camera_analytical_loop_f64(C.byref(fp), C.byref(cam), T, q0, noise_ptr, *outputs)
+        else:
+            rc = _vision.lib().uvs_camera_believed_loop_f64(C.byref(fp), C.byref(cam), T, *believed, q0, noise_ptr, *outputs)
         _vision.check(rc)
         return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in comps.items()}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
-    features, step = _vision.lib().uvs_camera_features_f64, _vision.lib().uvs_camera_analytical_step_f64
-    cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
+    features, cam_ref, fp_ref, stream = _vision.lib().uvs_camera_features_f64, C.byref(cam), C.byref(fp), _stream()
+    if believed is None:
+        step = lambda *rows: _vision.lib().uvs_camera_analytical_step_f64(fp_ref, cam_ref, T, *rows)          # noqa: E731
+    else:
+        step = lambda *rows: _vision.lib().uvs_camera_believed_step_f64(fp_ref, T, *believed, *rows)          # noqa: E731
     row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
     at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
     noise_row = 0 if noise is None else noise.stride(0) * 8
@@ -522,7 +618,7 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want):
         q_prev, dq_prev = (q0, None) if k == 0 else (at('q', k - 1), at('dq', k - 1))
         _vision.check(features(cam_ref, T, q_prev, dq_prev, fp.dt, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k),
                                at('pixels', k), None, stream))
-        _vision.check(step(fp_ref, cam_ref, T, at('q', k), at('f', k), at('dq', k), at('err', k), None, at('status', k), stream))
+        _vision.check(step(at('q', k), at('f', k), at('dq', k), at('err', k), None, at('status', k), stream))
     return _reduce_camera_logs(fp, log, status_log, pixel_log, want)
 
 
@@ -571,7 +667,8 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want):
     return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
 
 
-def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS):
+def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
+                       believed_index=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -589,11 +686,29 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     ``fp.method == ANALYTICAL`` runs the calibrated IBVS baseline through the same pixels instead of an estimator: fused=True is one launch
     (uvs_camera_analytical_loop_f64), fused=False K x (uvs_camera_features_f64, uvs_camera_analytical_step_f64) with the same reduction, and
     the two return the same bits.  It takes no ``x0`` and no ``guess`` (ValueError), ``want`` is a subset of ('err', 'q', 'f', 'dq') --
-    there is no 'kappa' -- and ``plant`` may be a ``Camera`` struct."""
+    there is no 'kappa' -- and ``plant`` may be a ``Camera`` struct.
+    ``believed`` (what ``believed_models`` returns or takes) and ``believed_index`` ((T,) integers, host or device) separate the camera that
+    renders the frames -- always ``plant`` -- from the model the control side believes in, per trial: with an index trial t believes in
+    ``believed[believed_index[t]]``, without one in the one model there is, or in ``believed[t]`` of T.  With ANALYTICAL the law runs on the
+    believed model at every step (fused=True: uvs_camera_believed_loop_f64, one launch; fused=False: K x (uvs_camera_features_f64 on the true
+    camera, uvs_camera_believed_step_f64); the same bits, and with the true model as ``believed`` the bits of the call without it).  With an
+    estimator the believed models feed the initial guess alone (``camera_guess(believed=...)``) and the estimator's loop is untouched; that
+    needs guess='device', and guess='host' or an explicit ``x0`` next to ``believed`` is a ValueError, like ``believed_index`` without
+    ``believed`` and a host-side index out of range."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
     analytical = fp.method == _lib.METHOD_ANALYTICAL
+    if believed is None and believed_index is not None:
+        raise ValueError('camera_closed_loop: believed_index without believed')
+    if believed is not None and not analytical:
+        if x0 is not None or guess != 'device':
+            raise ValueError("camera_closed_loop: with an estimator the believed models feed the device's initial guess alone: "
+                             "guess='device' and no x0")
+        if not fp.initial_guess:
+            raise ValueError('camera_closed_loop: believed models need fp.initial_guess (they feed the analytic initial guess)')
+    if believed is not None:                                         # a host-side index out of range is refused here, before any device work
+        _check_believed(believed, believed_index, q_start.shape[0], 'camera_closed_loop')
     if analytical:                                                   # refused on the arguments alone, before anything is looked at
         if x0 is not None or guess != 'host':
             raise ValueError('camera_closed_loop: the calibrated baseline estimates nothing: it takes no x0 and no guess')
@@ -614,7 +729,15 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want)
+        if believed is None:
+            return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want)
+        *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
+        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand))
+    if believed is not None:                                         # an estimator that starts from the wrong model; the rest is the x0= path
+        cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+        if m != 2 * cam.n_points or n != cam.n_joints:
+            raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
+        x0 = camera_guess(cam, q_start, camera_features(cam, q_start), radius=radius, believed=believed, believed_index=believed_index)
     if fused and (x0 is not None or guess == 'device' or not fp.initial_guess):
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:

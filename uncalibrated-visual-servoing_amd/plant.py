@@ -227,6 +227,23 @@ class SyntheticPlant:
         return s
 
 
+def miscalibrated(plant, focal_scale=1.0, point_offset=(0.0, 0.0, 0.0), joint_offset=0.0, link_scale=1.0):
+    """A new ``SyntheticPlant``: what a controller BELIEVES about ``plant`` when its calibration is off.  ``focal_scale`` multiplies the focal
+    length (the intrinsics); ``point_offset`` -- (3,) or (n_points, 3) metres -- moves the world points (the depth assumption);
+    ``joint_offset`` -- a scalar or one value per joint, radians -- is added to the encoder zeros ``theta_offset`` (the last joint's is a
+    camera roll); ``link_scale`` multiplies ``d`` and ``a`` (link and hand-eye lengths).  ``fov_deg`` follows the new focal length, because
+    ``analytic_guess`` derives its focal length from the robot's ``perspective_angle``; with ``focal_scale == 1`` it is kept as it is, and with
+    all defaults the result equals ``plant`` field for field.  The result is an ordinary plant: hand it to ``engine.believed_models``, or
+    to a ``SyntheticRobot`` for the numpy side."""
+    focal = plant.focal * focal_scale
+    fov_deg = plant.fov_deg if focal_scale == 1.0 else float(np.rad2deg(2.0 * np.arctan(plant.center / focal)))
+    return SyntheticPlant(theta_offset=np.asarray(plant.theta_offset, float) + np.asarray(joint_offset, float),
+                          d=np.asarray(plant.d, float) * link_scale, a=np.asarray(plant.a, float) * link_scale,
+                          alpha=np.array(plant.alpha, float),
+                          points=np.asarray(plant.points, float) + np.asarray(point_offset, float),
+                          focal=focal, center=plant.center, fov_deg=fov_deg)
+
+
 class LinearPlant:
     """Consistent linearised camera f = f0 + J (q - q0) for shapes without a DH model (BASELINE config 5: m = 32, n = 7;
     a 7-joint arm would be redundant for a 6-DoF camera pose and leave the feature Jacobian rank 6).  J, f0, q0 are uploaded
