@@ -123,6 +123,10 @@ int uvs_camera_project_f64(const uvs_camera *cam, int64_t T, const double *q_pre
  * a NaN anywhere gives nothing.  The painter's order is the colour order (a later disc overwrites an earlier one); the colours are
  * (255,0,0), (0,255,0), (0,0,255), (255,0,255), with n_colours == 1 the one disc is green; every other pixel is `background` in all
  * three channels.
+ * The rule holds for every disc, whatever its size: u, v and r may be huge or infinite (a point that grazes the camera's focal plane
+ * projects to some 1e7 px and beyond), and the frames are those of the rule evaluated at all 65 536 pixels.  The kernels here and
+ * below visit a disc's bounding box only, [centre - r - 1, centre + r + 1] clipped to the frame, while |u|, |v| and r are all below
+ * 1e9; any other disc -- from 2^54 on the rule's rounded dx reaches past that box -- is given the whole frame as its box.
  * Errors: UVS_ERR_ARG for NULL discs / frames, T < 0, n_colours not in {1, 3, 4}, background outside 0 .. 249 (250 and above would
  * enter a mask of the detector), a misaligned frames pointer, a stride below 256 * 256 * 3 or not a multiple of 16.  T == 0 returns
  * UVS_OK and launches nothing.  One workgroup per frame, 16-byte stores.
@@ -134,7 +138,8 @@ int uvs_render_discs_u8(int64_t T, const double *discs, int32_t n_colours, int32
  * The frame-free detector: what uvs_detect_circles_u8 returns for the frames uvs_render_discs_u8 writes from `discs`, bit for bit
  * (features, NaN pairs of empty masks, mask sizes, noise epilogue), without the frames.  Thread (colour c, index i) counts the rows at
  * which c is the topmost disc in column i and the columns at which it is topmost in row i, visiting only the disc's bounding box
- * [centre - r - 1, centre + r + 1] clipped to the frame; the sums that follow are the detector's own code.
+ * [centre - r - 1, centre + r + 1] clipped to the frame (the whole frame for a disc with |u|, |v| or r not below 1e9, see the pixel
+ * rule above); the sums that follow are the detector's own code.
  *   discs [T][n_colours][3] in; noise [T][2*n_colours] in or NULL; f_out [T][2*n_colours] out; pixels_out [T][n_colours] int32 out or NULL.
  * Errors: UVS_ERR_ARG for NULL discs / f_out, T < 0, n_colours not in {1, 3, 4}.  T == 0 returns UVS_OK and launches nothing.
  */

@@ -206,6 +206,92 @@ def test_detection_is_within_half_a_pixel_of_the_centre_on_the_host(uvs):
     assert worst < 0.5
 
 
+HUGE_COUNTS = {
+    'huge_1e12': [65536, 0, 0, 0], 'huge_off_centre': [65536, 0, 0, 0], 'inf_radius': [65536, 0, 0, 0], 'inf_all': [65536, 0, 0, 0],
+    'inf_radius_minus_inf_u': [65536, 0, 0, 0], 'inf_u_small_radius': [0, 0, 0, 0],
+    'below_1e9': [39689, 0, 0, 0], 'below_1e9_over_red': [177, 39689, 0, 0],
+    'above_1e9': [65325, 0, 0, 0], 'above_1e9_over_red': [0, 65325, 0, 0],
+    'above_1e9_rim': [39725, 0, 0, 0], 'above_1e9_rim_over_red': [177, 39725, 0, 0],
+    'rim_2_54_right': [14848, 0, 0, 0], 'rim_2_54_right_green_alone': [0, 14848, 0, 0],           # columns 198 .. 255
+    'rim_2_54_right_under_green': [14654, 284, 0, 0], 'rim_2_54_right_pink_over_three': [156, 248, 136, 14848],
+    'rim_2_54_left': [25856, 0, 0, 0], 'rim_2_54_left_green_alone': [0, 25856, 0, 0],             # columns 0 .. 100
+    'rim_2_54_left_under_green': [25856, 284, 0, 0], 'rim_2_54_left_pink_over_three': [0, 248, 136, 25856],
+    'rim_2_54_below': [41984, 0, 0, 0], 'rim_2_54_below_green_alone': [0, 41984, 0, 0],           # rows 92 .. 255
+    'rim_2_54_below_under_green': [41984, 284, 0, 0], 'rim_2_54_below_pink_over_three': [156, 248, 0, 41984],
+}
+
+
+def test_huge_and_non_finite_discs_on_the_host(uvs):
+    """The masks plant.render_discs gives the discs of camera_common.huge_scenes, pinned: what the kernels are held to byte for byte in
+    tests/test_gpu_camera.py.  Beyond 2^54 the rule quantises: x - 2^55 is a multiple of 8, so whole columns fall on the rim together."""
+    scenes = cc.huge_scenes()
+    assert set(scenes) == set(HUGE_COUNTS)
+    for name, (n, disc) in scenes.items():
+        assert cc.host_counts(uvs.plant.render_discs(disc, n)).tolist() == HUGE_COUNTS[name], name
+    flipped = uvs.plant.render_discs(scenes['rim_2_54_right'][1])[::-1]
+    assert np.all(flipped[:, 198:, 0] == 255) and np.all(flipped[:, :198, 0] == 96)
+
+
+def test_box_mirror_keeps_every_pixel_of_the_rule():
+    """pixel_range as the kernels have it (camera_common.pixel_range mirrors vision_device.hpp) against the rule, over discs far from the
+    frame whose rim crosses it: |centre| = 2^e (1 + rand) along one axis, either sign, e = 20 .. 60.  With the whole-frame rule for
+    operands not below 1e9 no disc loses a pixel.  Without it -- the box [centre - r - 1, centre + r + 1] alone -- nothing is lost up to
+    2^53 and most discs lose pixels from 2^54 on, where doubles near the centre are 4 apart and the one pixel of slack no longer covers
+    the rounding of dx: the reason the rule is there."""
+    rng = np.random.default_rng(54)
+    lost = {}
+    for e in range(20, 61):
+        lost[e] = 0
+        for _ in range(48):
+            far = rng.choice([-1.0, 1.0]) * 2.0 ** e * (1.0 + rng.random())
+            near, target = rng.uniform(0, 255), rng.uniform(20, 235, 2)
+            u, v = (far, near) if rng.random() < 0.5 else (near, far)
+            disc = (u, v, float(np.hypot(u - target[0], v - target[1])))
+            assert 0 < cc.rule_mask(disc).sum() < 65536 or e >= 54, disc        # up to 2^53 the rim does cross the frame
+            assert cc.pixels_outside_box(disc) == 0, disc
+            lost[e] += cc.pixels_outside_box(disc, guarded=False) > 0
+    print('discs of 48 that lose pixels to the unguarded box, by exponent:', {e: n for e, n in lost.items() if n})
+    assert all(lost[e] == 0 for e in range(20, 54)) and all(lost[e] > 0 for e in (54, 55, 56)), lost
+    assert cc.pixel_range(2.0 ** 55, 2.0 ** 55 - 200.0) == (199, 255)                       # the rule gives column 198 as well
+    assert cc.pixels_outside_box(cc.RIM_BEYOND_2_54['right'], guarded=False) == 256
+    assert cc.disc_box(cc.RIM_BEYOND_2_54['right']) == ((0, 255), (0, 255))
+    # an infinite slack is the whole axis whatever the operands are (NaN bounds become frame edges); a slack of one with non-finite operands
+    for centre, r in ((np.inf, np.inf), (-np.inf, np.inf), (np.nan, 5.0), (100.0, np.inf), (np.inf, 5.0), (-np.inf, 5.0), (3e300, 1e300)):
+        assert cc.pixel_range(centre, r, np.inf) == (0, 255), (centre, r)
+    assert cc.pixel_range(np.inf, np.inf) == (0, 255) and cc.pixel_range(np.nan, 5.0) == (0, 255) and cc.pixel_range(np.inf, 5.0) == (256, 255)
+    assert cc.disc_box((np.inf, 100.0, 5.0)) == ((0, 255), (0, 255)) and cc.disc_box((np.inf, 100.0, 5.0), guarded=False) == ((256, 255), (94, 106))
+    assert cc.disc_box((-2.5, 100.3, 7.0)) == ((0, 5), (93, 108)) and cc.disc_box((254.2, 300.0, 8.0)) == ((246, 255), (256, 255))
+    assert cc.disc_box((1e9, 128.0, 5.0)) == ((0, 255), (0, 255)) and cc.disc_box((9.9e8, 128.0, 5.0)) == ((256, 255), (122, 134))
+
+
+# ------------------------------------------------------------------------------------------------------------- scenes through a camera
+@pytest.mark.parametrize('name', cc.camera_scene_names())
+def test_jitter_varies_the_masks_and_keeps_the_scenes(uvs, name):
+    """camera_common.scene_plant returns the scene at Q_GOAL, and JITTER = 2 mrad is an amplitude at which the 259 start poses of
+    tests/test_gpu_camera_scenes.py give at least three different rows of mask sizes (discs move by a pixel or two: clipped and
+    overlapping masks change) while a colour that has no pixel in the scene has none in any trial (covered stays covered, outside stays
+    outside), so that every trial of such a scene FAILs at step 0."""
+    n, plant, radius = cc.camera_scene(uvs, name)
+    q = cc.scene_joints(259, name)
+    assert np.array_equal(q[0], cc.Q_GOAL) and 0 < np.abs(q[1:] - cc.Q_GOAL).max() <= cc.JITTER
+    discs = np.stack([plant.discs(x, radius) for x in q])
+    if name == 'grazing':
+        assert 1e6 < discs[0, 0, 2] < 1e8 and np.all(discs[0, 1:, 2] < 10.0)
+    else:
+        want = cc.edge_scenes()[name][1]
+        drawn = want[:, 2] >= 0
+        assert np.all(discs[0, ~drawn, 2] == -1.0)
+        assert not drawn.any() or np.abs(discs[0, drawn] - want[drawn]).max() <= 2e-13
+    counts = cc.host_counts(uvs.plant.render_discs(discs, n))
+    counts = {4: counts, 3: counts[:, :3], 1: counts[:, 1:2]}[n]
+    if name not in cc.CONSTANT_COUNTS and name != 'point_on_lattice':
+        assert len({tuple(row) for row in counts.tolist()}) >= 3
+    if name in cc.EMPTY_MASK:
+        assert np.all((counts == 0).any(axis=1)) and np.array_equal(counts == 0, np.broadcast_to(counts[0] == 0, counts.shape))
+    elif name != 'point_on_lattice':
+        assert np.all(counts[0] > 0)
+
+
 # ------------------------------------------------------------------------------------------------------------- projection on the host
 def test_discs_of_the_plant(uvs):
     plant = uvs.SyntheticPlant.ur10()

@@ -22,7 +22,7 @@ DT = 0.05
 Q_HOST_ROUTE = np.array([[0.00236432, 0.09009274, 1.89232733, 0.08972989, -1.60843004, -0.01533471],
                          [-0.05930895, -0.04753733, 2.01356834, -0.04391825, -1.57375814, 0.09614744]])
 Q_LEAVES = np.array([-0.47915568, -0.55367504, 2.20583478, -0.05228325, -1.09351535, 0.40221985])     # all four discs out of view at step 6
-LOGS = ('err', 'q', 'f', 'dq', 'kappa')
+LOGS = cc.LOGS
 # The loop kernel has two forms: up to SMALL trials one trial per workgroup (four wavefronts share its colours), beyond that G trials per
 # workgroup (one wavefront each).  Both forms must give the two-launch loop's bits, so the cases below come at batch sizes on both sides.
 G, SMALL = 4, 256
@@ -45,10 +45,7 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def bits(t):
-    """int64 view of an fp64 tensor / array on the host: equality of bits, NaN payloads included."""
-    a = t.cpu().numpy() if hasattr(t, 'cpu') else np.asarray(t)
-    return np.ascontiguousarray(a).view(np.int64)
+bits = cc.bits
 
 
 def params(uvs, method, K, initial_guess=True, m=8, annealing=False):
@@ -68,25 +65,7 @@ def device_x0(uvs, plant, q0):
     return uvs.engine.camera_guess(plant, q0, uvs.engine.camera_features(plant, q0))
 
 
-def assert_same_bits(got, want, K, where, trials=None, want_trials=None):
-    """Every specified value of ``got`` equals that of ``want`` bit for bit; ``trials`` / ``want_trials`` pair up the trials to compare."""
-    import torch
-    T = got['status'].shape[0]
-    trials = list(range(T)) if trials is None else trials
-    want_trials = trials if want_trials is None else want_trials
-    k_done = got['k_done'].cpu().numpy()
-    assert np.array_equal(k_done[trials], want['k_done'].cpu().numpy()[want_trials]), (where, 'k_done')
-    assert torch.equal(got['status'].cpu()[trials], want['status'].cpu()[want_trials]), (where, 'status')
-    assert torch.equal(got['pixels'].cpu()[trials], want['pixels'].cpu()[want_trials]), (where, 'pixels')
-    assert np.array_equal(bits(got['stats'])[trials], bits(want['stats'])[want_trials]), (where, 'stats')
-    for key in LOGS:
-        if key not in got:
-            continue
-        a, b = bits(got[key]), bits(want[key])
-        assert a.shape[0] == K and a.shape[2] == b.shape[2], (where, key)
-        for t, tw in zip(trials, want_trials):
-            rows = min(K, k_done[t] + 1) if key in ('q', 'f') else k_done[t]
-            assert np.array_equal(a[:rows, t], b[:rows, tw]), (where, key, t)
+assert_same_bits = cc.assert_same_bits                            # shared with tests/test_gpu_camera_scenes.py
 
 
 def both_routes(uvs, fp, plant, q0, noise, x0):

@@ -134,14 +134,12 @@ __global__ __launch_bounds__(kLoopThreads) void camera_loop_kernel(const LoopArg
             project_disc(cam, lane, pose, &s_disc[w][3 * lane]);
         }
         __syncthreads();
-        // ---- frame-free detection: feature pair j is colour c's centre of mass
+        // ---- frame-free detection: feature pair j is the centre of mass of disc j's colour
 #pragma unroll 1
         for (int j = j_first; j < npts; j += j_step) {
-            const int c = npts == 1 ? 1 : j;
-            const Disc me = load_disc(&s_disc[w][3 * j], true);  // disc_of_colour(c, npts) == j
+            const Disc me = load_disc(&s_disc[w][3 * j], true);  // disc j shows colour j (npts == 1: green)
             int x0, x1, y0, y1;
-            pixel_range(me.u, me.r, x0, x1);
-            pixel_range(me.v, me.r, y0, y1);
+            disc_box(me, x0, x1, y0, y1);
             ColourSum sum;
 #pragma unroll 1
             for (int b = 0; b < 4; ++b) {                        // the colour's four wavefronts of centre_of_mass, in index order
@@ -152,7 +150,7 @@ __global__ __launch_bounds__(kLoopThreads) void camera_loop_kernel(const LoopArg
                 int n = 0;
                 if (__builtin_amdgcn_readfirstlane(static_cast<int>(touched))) {   // the same discs in every lane: wavefront-uniform
                     int cc, rc;
-                    disc_counts_at(s_disc[w], npts, c, lo + lane, cc, rc);
+                    disc_counts_in_box(s_disc[w], npts, j, me, x0, x1, y0, y1, lo + lane, cc, rc);
                     wave_partial(cc, rc, lo + lane, su, sv, n);
                 }
                 sum.add(su, sv, n);

@@ -125,8 +125,7 @@ __global__ __launch_bounds__(kThreads) void render_discs_kernel(const double *__
 #pragma unroll
     for (int k = 0; k < kColours; ++k) {
         d[k] = load_disc(mine + 3 * (k < n_colours ? k : 0), k < n_colours);
-        pixel_range(d[k].u, d[k].r, x0[k], x1[k]);
-        pixel_range(d[k].v, d[k].r, y0[k], y1[k]);
+        disc_box(d[k], x0[k], x1[k], y0[k], y1[k]);
     }
     const uint32_t bg = background * 0x010101u;
 #pragma unroll

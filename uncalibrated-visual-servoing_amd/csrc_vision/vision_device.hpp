@@ -104,25 +104,39 @@ __device__ __forceinline__ Disc load_disc(const double *d, bool present) {
     return o;
 }
 
-// Inclusive pixel range [lo, hi] of [centre - r - 1, centre + r + 1] clipped to the frame: conservative against the exact rule by a whole
-// pixel.  fmax / fmin drop a NaN operand, so a bound that is NaN (inf - inf) becomes the frame edge, never an unconverted NaN.
-__device__ __forceinline__ void pixel_range(double centre, double r, int &lo, int &hi) {
-    lo = static_cast<int>(fmin(fmax(ceil(centre - r - 1.0), 0.0), static_cast<double>(kSide)));
-    hi = static_cast<int>(fmax(fmin(floor(centre + r + 1.0), static_cast<double>(kSide - 1)), -1.0));
+// Inclusive pixel range [lo, hi] of [centre - r - slack, centre + r + slack] clipped to the frame.  fmax / fmin drop a NaN operand, so a
+// bound that is NaN (inf - inf) becomes the frame edge, never an unconverted NaN: with slack = inf the range is the whole axis, whatever
+// centre and r are.
+__device__ __forceinline__ void pixel_range(double centre, double r, double slack, int &lo, int &hi) {
+    lo = static_cast<int>(fmin(fmax(ceil(centre - r - slack), 0.0), static_cast<double>(kSide)));
+    hi = static_cast<int>(fmax(fmin(floor(centre + r + slack), static_cast<double>(kSide - 1)), -1.0));
+}
+
+// A disc of ordinary size: centre and radius below 1e9 in magnitude (false for a NaN or an infinite operand)
+__device__ __forceinline__ bool ordinary(const Disc &d) { return fabs(d.u) < 1e9 && fabs(d.v) < 1e9 && d.r < 1e9; }
+
+// The box [x0, x1] x [y0, y1] that holds every pixel the rule gives the disc.  For a disc of ordinary size one pixel of slack around
+// centre -+ r: doubles of that size are at most 2^-22 apart, so the slack covers every rounding of the rule's dx and of the bounds.  It
+// does not from 2^54 on, where dx = x - centre itself rounds to multiples of 4 and more and the rule's pixels reach past
+// centre -+ r -+ 1 (tests/test_camera_host.py: test_box_mirror_keeps_every_pixel_of_the_rule): any other disc gets the whole frame.
+__device__ __forceinline__ void disc_box(const Disc &d, int &x0, int &x1, int &y0, int &y1) {
+    const double slack = ordinary(d) ? 1.0 : HUGE_VAL;
+    pixel_range(d.u, d.r, slack, x0, x1);
+    pixel_range(d.v, d.r, slack, y0, y1);
 }
 
 // The disc of the n_colours at `discs` that colour slot c (red, green, blue, pink) shows, or -1: the one disc of n_colours == 1 is the green one
 __device__ __forceinline__ int disc_of_colour(int c, int n_colours) { return n_colours == 1 ? (c == 1 ? 0 : -1) : (c < n_colours ? c : -1); }
 
 // Could disc o cover a pixel of the box [x0, x1] x [y0, y1]?  No, when it draws nothing or when its own pixel ranges miss the box: for a disc
-// of ordinary size (centre and radius below 1e9 in magnitude: no overflow, rounding far below the range's whole pixel of slack) every pixel
-// the rule gives it lies inside its ranges.  Anything else -- a NaN centre, a huge disc -- counts as "could".
+// of ordinary size every pixel the rule gives it lies inside its ranges (disc_box).  Anything else -- a NaN centre, a huge disc -- counts
+// as "could".
 __device__ __forceinline__ bool may_cover(const Disc &o, int x0, int x1, int y0, int y1) {
     if (!(o.r2 >= 0.0)) return false;
-    if (!(fabs(o.u) < 1e9 && fabs(o.v) < 1e9 && o.r < 1e9)) return true;
+    if (!ordinary(o)) return true;
     int ox0, ox1, oy0, oy1;
-    pixel_range(o.u, o.r, ox0, ox1);
-    pixel_range(o.v, o.r, oy0, oy1);
+    pixel_range(o.u, o.r, 1.0, ox0, ox1);
+    pixel_range(o.v, o.r, 1.0, oy0, oy1);
     return ox0 <= x1 && ox1 >= x0 && oy0 <= y1 && oy1 >= y0;
 }
 
@@ -179,19 +193,15 @@ __device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kC
     }
 }
 
-// Counts of (colour c, index i) for the frame the rasteriser would write from the n_colours discs at `discs` (global memory or LDS):
-// cc = rows at which c's disc is the topmost one in column i, rc = columns at which it is in flipped row i.  c and the discs are the same
-// in all lanes of a wavefront (every caller's are), so which of the two walks runs is a scalar branch.
-__device__ __forceinline__ void disc_counts_at(const double *discs, int n_colours, int c, int i, int &cc, int &rc) {
-    const int own = disc_of_colour(c, n_colours);
+// Counts of index i for disc `own` of the n_colours at `discs` (global memory or LDS) in the frame the rasteriser would write: cc = rows at
+// which it is the topmost one in column i, rc = columns at which it is in flipped row i.  `me` is that disc, loaded (me.r2 >= 0), and
+// [x0, x1] x [y0, y1] its disc_box: a caller that has both in hand -- the closed loops, which skip whole blocks of indices by the box --
+// passes them on instead of having them formed again.  The discs are the same in all lanes of a wavefront (every caller's are), so which
+// of the two walks runs is a scalar branch.
+__device__ __forceinline__ void disc_counts_in_box(const double *discs, int n_colours, int own, const Disc &me, int x0, int x1, int y0, int y1, int i,
+                                                   int &cc, int &rc) {
     cc = 0;
     rc = 0;
-    if (own < 0) return;
-    const Disc me = load_disc(discs + 3 * own, true);
-    if (!(me.r2 >= 0.0)) return;
-    int x0, x1, y0, y1;
-    pixel_range(me.u, me.r, x0, x1);
-    pixel_range(me.v, me.r, y0, y1);
     Disc over[kColours - 1];                                     // the discs painted after mine; absent ones never cover a pixel
     bool covered = false;
 #pragma unroll
@@ -204,6 +214,19 @@ __device__ __forceinline__ void disc_counts_at(const double *discs, int n_colour
         box_counts<true>(me, over, x0, x1, y0, y1, i, cc, rc);
     else
         box_counts<false>(me, over, x0, x1, y0, y1, i, cc, rc);
+}
+
+// Counts of (colour c, index i) from the discs alone; c is the same in all lanes of a wavefront.
+__device__ __forceinline__ void disc_counts_at(const double *discs, int n_colours, int c, int i, int &cc, int &rc) {
+    const int own = disc_of_colour(c, n_colours);
+    cc = 0;
+    rc = 0;
+    if (own < 0) return;
+    const Disc me = load_disc(discs + 3 * own, true);
+    if (!(me.r2 >= 0.0)) return;
+    int x0, x1, y0, y1;
+    disc_box(me, x0, x1, y0, y1);
+    disc_counts_in_box(discs, n_colours, own, me, x0, x1, y0, y1, i, cc, rc);
 }
 
 // The same for thread (colour c = tid >> 8, index i = tid & 255) of a one-workgroup-per-frame kernel; c is wavefront-uniform there.
