@@ -12,7 +12,11 @@ of miscalibration levels (LEVELS below: the signed fraction of a focal length 20
 zeros off by up to 0.1 rad, links 3 % short; a negative level errs the other way) times the trials is ONE launch per side: the calibrated law on every trial's believed model
 (engine.camera_closed_loop(believed=..., believed_index=...)), and the estimator started from the analytic guess of that same wrong model, on the
 same starts and the same noise at every level.  Prints the median ISE / IAE / ITAE per level over the trials neither side FAILed.
-usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]"""
+--grid asks which kernel bandwidth and which gain survive pixel quantisation: kernel_bw x gain (GRID_BANDWIDTHS x GRID_GAINS below) over the SAME
+starts and the same noise is ONE launch (engine.camera_closed_loop(fused=True, trial_params=...) with a 'source' index, so the inputs are
+uploaded once, not once per cell).  Prints the median ISE / IAE / ITAE per cell over the trials that ran to the end, and the FAIL count.
+usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
+       [--grid]"""
 import argparse
 import os
 import sys
@@ -66,6 +70,44 @@ def miscalibration_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None,
     return lines
 
 
+GRID_BANDWIDTHS = (1.0, 2.0, 3.5, 5.0, 7.5, 10.0, 15.0, 20.0)         # sigma_0, pixels
+GRID_GAINS = (0.05, 0.1, 0.15, 0.2, 0.25, 0.3, 0.4, 0.5)
+
+
+def grid_table(uvs, method='GMCKF', trials=16, sigma=0.3, radius=None, seed=0, bandwidths=GRID_BANDWIDTHS, gains=GRID_GAINS):
+    """The kernel_bw x gain table through pixels as a list of lines: cells x trials in one launch."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    fp = uvs.engine.make_params(8, 6, method, 10.0, False, 0.05, 15.0, 0.2, desired, True)
+    K = fp.steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    noise = rng.standard_normal((K, trials, 8)) * sigma
+    cells = [(bw, gain) for bw in bandwidths for gain in gains]
+    T = len(cells) * trials
+    tp = {'kernel_bw': torch.as_tensor(np.repeat([c[0] for c in cells], trials), device='cuda'),
+          'gain': torch.as_tensor(np.repeat([c[1] for c in cells], trials), device='cuda'),
+          'source': np.arange(T) % trials}                            # cell c is the output trials [c trials, (c + 1) trials), all reading the same inputs
+    out = uvs.engine.camera_closed_loop(fp, plant, torch.as_tensor(q0, device='cuda'), torch.as_tensor(noise, device='cuda'), radius=radius,
+                                        fused=True, guess='device', want=(), trial_params=tp)
+    torch.cuda.synchronize()
+    status, stats = out['status'].cpu().numpy().reshape(len(cells), trials), out['stats'].cpu().numpy().reshape(len(cells), trials, 3)
+    lines = [f'{method} through pixels, kernel_bw x gain: {len(cells)} cells x {trials} trials of {K} steps in one launch, white noise {sigma} px, '
+             'the same starts and noise in every cell; median over the trials that ran to the end',
+             f'{"kernel_bw":>10s}{"gain":>7s}{"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"FAIL":>6s}']
+    for c, (bw, gain) in enumerate(cells):
+        ok = status[c] == 0
+        med = np.median(stats[c][ok], axis=0) if ok.any() else np.full(3, np.nan)
+        lines.append(f'{bw:10.2f}{gain:7.2f}{med[0]:12.3f}{med[1]:12.3f}{med[2]:12.3f}{int((~ok).sum()):>6d}')
+    medians = np.array([np.median(stats[c][status[c] == 0], axis=0) if (status[c] == 0).any() else np.full(3, np.inf) for c in range(len(cells))])
+    for i, name in enumerate(('ISE', 'IAE', 'ITAE')):
+        best = int(np.argmin(medians[:, i]))
+        lines.append(f'smallest median {name}: kernel_bw {cells[best][0]:g}, gain {cells[best][1]:g}')
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -76,9 +118,13 @@ def main():
     ap.add_argument('--fused', action='store_true', help='the pixel loop as one launch, initial guess on the device, no log returned')
     ap.add_argument('--baseline', action='store_true', help='pair the estimator with the calibrated law (ANALYTICAL) through the same pixels')
     ap.add_argument('--miscalibration', action='store_true', help='a ladder of wrong models x trials in one launch per side, and nothing else')
+    ap.add_argument('--grid', action='store_true', help='kernel_bw x gain over the same starts and noise in one launch, and nothing else')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
+    if args.grid:
+        print('\n'.join(grid_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
+        return
     if args.miscalibration:
         print('\n'.join(miscalibration_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
         return

@@ -192,6 +192,38 @@ int uvs_camera_closed_loop_f64(const struct uvs_filter_params *fp, const uvs_cam
                                void *stream);
 
 /*
+ * The same loop with PER-TRIAL estimator parameters: a hyperparameter grid over the same starts and noise in one launch, as
+ * uvs_rmckf_closed_loop_grid_f64 of uvs_rmckf.h runs one on ideal features.  The block is this library's own struct:
+ *   kernel_bw, gain, reg, fpi_threshold [T] in: trial t runs with its own sigma_0, gain, regulariser and fixed-point threshold.
+ *   desired [T][m] in: trial t's desired features.
+ *   A NULL member means fp's value for every trial.  The arrays are device (or pinned host) memory.  fp->annealing, anneal_span, dt,
+ *     steps, k_max, fpi_epoch_max, initial_guess, method and UVS_OPT_STRICT_PINV stay launch-wide.
+ *   source [T] int32 in or NULL: trial t reads q_start[source[t]], the noise rows noise[k][source[t]] -- noise is then [K][n_in][m], its
+ *     row stride n_in * m, not T * m -- x0[source[t]] and f0[source[t]]: those four hold n_in trials.  NULL: trial t reads trial t, the
+ *     four hold T trials, and n_in is not read.  Every output of trial t is written at t; the logs are [K][T][comp].
+ *   An index outside [0, n_in) never becomes an address (the rule of believed_index below).  That trial writes status FAIL and
+ *     k_done = 0 and nothing else -- no log row, no stats, no pixels -- and its neighbours keep their bits.
+ * Every value is used exactly where uvs_camera_closed_loop_f64 uses fp's, by the same operations in the same order (the two kernels are
+ * one text): trial t's results are bit-identical to those of that call with t's values, and a block whose members are all NULL is that
+ * call.  The other arguments are that call's.
+ * Built: GMCKF, KF and IMCC-KF at (8, 6), (6, 6) and (2, 6), MCKF at (8, 6) and (2, 6), each in both workgroup forms (chosen by T, the
+ * number of output trials) with 0 B of scratch memory.  MCKF at (6, 6) would spill here as it does there: it is not built and is refused
+ * with UVS_ERR_METHOD.  No other flavour is missing.
+ * Errors, all before the first HIP call: those of uvs_camera_closed_loop_f64, in its order, then UVS_ERR_ARG for a NULL tp or for source
+ * with n_in < 1.  T == 0 returns UVS_OK and launches nothing.
+ */
+typedef struct uvs_camera_trial_params {
+    const double *kernel_bw, *gain, *reg, *fpi_threshold;  /* [T] device or pinned; NULL = fp's value for every trial */
+    const double *desired;                                 /* [T][m]; NULL = fp->desired */
+    const int32_t *source;                                 /* [T]; NULL = t */
+    int64_t n_in;                                          /* trials that q_start / noise / x0 / f0 hold; read only with source */
+} uvs_camera_trial_params;
+int uvs_camera_closed_loop_grid_f64(const struct uvs_filter_params *fp, const uvs_camera *cam, int64_t T,
+                                    const uvs_camera_trial_params *tp, const double *q_start, const double *noise, const double *x0,
+                                    const double *f0, double *q_log, double *f_log, double *dq_log, double *err_log, double *kappa_log,
+                                    int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, void *stream);
+
+/*
  * The analytic initial guess X0 of the loop (experiment.py:94-114) for T trials, one lane each: the geometric Jacobian of the DH chain in the
  * camera frame at q_start, the depths |camera - point|, and the image-Jacobian rows at the DETECTED features f0 (raw pixels).
  *   q_start [T][6] in; f0 [T][2*n_points] in; x0_out [T][2*n_points*6] out.

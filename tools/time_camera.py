@@ -28,7 +28,19 @@ With --believed only the calibrated baseline on a per-trial believed model is ti
   (i) the calibrated one launch of --analytical, in the same run;
       method and sizes as --analytical.  The acceptance condition is (k) below (j) at both sizes; (k) against (i) -- what reading the model
       from LDS per trial costs -- is reported, not gated.  Then the robustness table of examples/camera_loop.py --miscalibration.
-usage: tools/time_camera.py --believed [out.txt]"""
+usage: tools/time_camera.py --believed [out.txt]
+With --grid only the per-trial pixel loop is timed, into profiles/camera_grid.txt (or the path given): GMCKF, K = 299, white noise 0.3 px,
+64 cells (8 bandwidths x 8 gains) x 16 trials = 1 024 output trials over the same 16 starts and noise rows;
+  (j) the grid as 64 uniform fused launches of 16 trials, one per cell, synchronised once at the end;
+  (k) the grid as ONE launch: camera_closed_loop(fused=True, trial_params=...) with 'source';
+  (e) the uniform fused launch of 1 024 trials, x0 handed in -- with this library and, given --parent-lib=PATH (a libuvs_vision.so built
+      from the parent commit, loaded next to this one), with that one in turn;
+  (l) (e)'s trials through the per-trial kernel, every trial with fp's own kernel_bw and gain: what the kernel flavour costs, apart from
+      what the grid's other bandwidths and gains make the estimator do;
+      host clock around synchronised calls, alternating blocks of one process.  The acceptance condition is (k) below (j); (e) new against
+      (e) parent and (k) / (e) are reported next to the parent's own spread.  Every cell of (k) is checked against its launch of (j), bit
+      for bit, before anything is timed.  Then the table of examples/camera_loop.py --grid.
+usage: tools/time_camera.py --grid [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -40,9 +52,11 @@ sys.path.insert(0, ROOT)
 import uvs_amd as uvs  # noqa: E402
 import torch  # noqa: E402
 
-ANALYTICAL, BELIEVED = '--analytical' in sys.argv[1:], '--believed' in sys.argv[1:]
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_believed.txt' if BELIEVED else 'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
+ANALYTICAL, BELIEVED, GRID = '--analytical' in sys.argv[1:], '--believed' in sys.argv[1:], '--grid' in sys.argv[1:]
+PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+                                        'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
 DESIRED = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
@@ -218,6 +232,125 @@ def believed_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def grid_section():
+    """(j), (k), (e): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, E = 299, 16
+    bandwidths, gains = example.GRID_BANDWIDTHS, example.GRID_GAINS
+    cells = [(bw, gain) for bw in bandwidths for gain in gains]
+    T = len(cells) * E
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    assert fp.steps == K and T == 1024
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --grid on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, K = {K}, white noise 0.3 px; {len(cells)} cells (kernel_bw {list(bandwidths)} x gain {list(gains)}) x {E} trials = {T} output '
+        'trials over the same starts and noise')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included')
+
+    def starts(n):
+        q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (n, 1))
+        q[:, :2] += rng.uniform(-0.1, 0.0, (n, 2))
+        q_d = torch.as_tensor(q, device='cuda')
+        return q_d, torch.as_tensor(rng.standard_normal((K, n, 8)) * 0.3, device='cuda'), \
+            uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+
+    q_in, noise_in, x0_in = starts(E)
+    q_all, noise_all, x0_all = starts(T)
+    tp = {'kernel_bw': torch.as_tensor(np.repeat([c[0] for c in cells], E), device='cuda'),
+          'gain': torch.as_tensor(np.repeat([c[1] for c in cells], E), device='cuda'),
+          'source': torch.as_tensor((np.arange(T) % E).astype(np.int32), device='cuda')}
+    fps = []
+    for bw, gain in cells:
+        one = type(fp).from_buffer_copy(fp)
+        one.kernel_bw, one.gain = bw, gain
+        fps.append(one)
+
+    def run_j():
+        return [loop(one, plant, q_in, noise_in, x0=x0_in, fused=True) for one in fps]
+
+    def run_k():
+        return loop(fp, plant, q_in, noise_in, x0=x0_in, fused=True, trial_params=tp)
+
+    def run_e():
+        return loop(fp, plant, q_all, noise_all, x0=x0_all, fused=True)
+
+    tp_same = {'kernel_bw': torch.full((T,), fp.kernel_bw, dtype=torch.float64, device='cuda'),
+               'gain': torch.full((T,), fp.gain, dtype=torch.float64, device='cuda'),
+               'source': torch.arange(T, dtype=torch.int32, device='cuda')}
+
+    def run_l():
+        return loop(fp, plant, q_all, noise_all, x0=x0_all, fused=True, trial_params=tp_same)
+
+    per_cell, one_launch = run_j(), run_k()
+    torch.cuda.synchronize()
+    for c, want in enumerate(per_cell):
+        rows = slice(c * E, (c + 1) * E)
+        done = want['k_done']
+        same = all(torch.equal(one_launch[key][rows], want[key]) for key in ('status', 'k_done', 'pixels')) \
+            and torch.equal(one_launch['stats'][rows].view(torch.int64), want['stats'].view(torch.int64))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):                 # the specified rows: q, f up to and including k_done, the others before it
+            spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+            same = same and torch.equal(one_launch[key][:, rows].view(torch.int64)[spec], want[key].view(torch.int64)[spec])
+        assert same, f'cell {cells[c]} of the one launch and its uniform launch disagree'
+    uniform_all, same_all = run_e(), run_l()
+    torch.cuda.synchronize()
+    assert all(torch.equal(same_all[key].view(torch.int64), uniform_all[key].view(torch.int64)) for key in ('err', 'q', 'f', 'dq', 'kappa', 'stats'))
+    fns = {'j': run_j, 'k': run_k, 'e': run_e, 'l': run_l}
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_grid_f64'), 'the parent library has no per-trial entry point'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def run_e_parent():
+            mine, uvs._vision._lib = uvs._vision._lib, parent
+            try:
+                return run_e()
+            finally:
+                uvs._vision._lib = mine
+
+        new, old = run_e(), run_e_parent()
+        torch.cuda.synchronize()
+        assert all(torch.equal(new[key].view(torch.int64), old[key].view(torch.int64)) for key in ('err', 'q', 'f', 'dq', 'kappa', 'stats'))
+        fns['e_parent'] = run_e_parent
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    spread = lambda v: (np.percentile(v, 90) - np.percentile(v, 10)) / np.median(v)   # noqa: E731
+    say()
+    say(f'  (j) {len(cells)} uniform fused launches of {E} trials, one per cell   {fmt_ms(ms["j"])}   = {med["j"] / len(cells):.2f} ms per cell')
+    say(f'  (k) the grid in ONE launch (trial_params with source)       {fmt_ms(ms["k"])}')
+    say(f'  (e) uniform fused launch of {T} trials, this library        {fmt_ms(ms["e"])}')
+    if 'e_parent' in ms:
+        say(f'  (e) the same with the parent\'s library                      {fmt_ms(ms["e_parent"])}')
+        say(f'  (e) new / (e) parent = {med["e"] / med["e_parent"]:.4f}; the parent\'s own p10-p90 spread is {spread(ms["e_parent"]) * 100:.2f} % of its median, '
+            f'this library\'s {spread(ms["e"]) * 100:.2f} %; the outputs of the two are bit-identical')
+    say(f'  (k) / (j) = {med["k"] / med["j"]:.4f}: (k) is {"BELOW" if med["k"] < med["j"] else "NOT below"} (j); every cell of (k) has the bits of '
+        'its launch of (j)')
+    say(f'  (l) (e)\'s trials through the per-trial kernel, fp\'s values    {fmt_ms(ms["l"])}')
+    say(f'  (k) / (e) = {med["k"] / med["e"]:.4f} (reported, not gated);  (l) / (e) = {med["l"] / med["e"]:.4f}: the kernel flavour alone, same trials, same bits')
+    careful = lambda out: int((out['k_done'] < K).sum())             # noqa: E731
+    say(f'  trials that FAILed: (k) {careful(one_launch)}, (e) {careful(uniform_all)}')
+    say()
+    say(f'acceptance: (k) below (j): {"yes" if med["k"] < med["j"] else "NO"}')
+    say()
+    say('# examples/camera_loop.py --grid (its defaults)')
+    for line in example.grid_table(uvs):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if GRID:
+    grid_section()
+    sys.exit(0)
 if BELIEVED:
     believed_section()
     sys.exit(0)

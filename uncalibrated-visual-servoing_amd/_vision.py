@@ -28,6 +28,12 @@ class Camera(C.Structure):
                 ('radius', C.c_double * MAX_POINTS)]
 
 
+class CameraTrialParams(C.Structure):
+    """uvs_camera_trial_params of include/uvs_vision.h: device pointers (None = fp's value, or trial t for 'source') and n_in."""
+    _fields_ = [('kernel_bw', C.c_void_p), ('gain', C.c_void_p), ('reg', C.c_void_p), ('fpi_threshold', C.c_void_p),
+                ('desired', C.c_void_p), ('source', C.c_void_p), ('n_in', C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/uvs_vision.h declares
 _VP, _I64, _I32, _F64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double
 _CAM = C.POINTER(Camera)
@@ -41,6 +47,8 @@ SYMBOLS = {
     'uvs_camera_features_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _VP, _VP, _VP]),
     # fp (a pointer to _lib.FilterParams, passed with byref), cam, T, q_start, noise, x0, f0, five logs, status, k_done, stats, pixels, stream
     'uvs_camera_closed_loop_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 14),
+    # the same with tp (a pointer to CameraTrialParams, passed with byref) after T
+    'uvs_camera_closed_loop_grid_f64': (C.c_int, [_VP, _CAM, _I64, _VP] + [_VP] * 14),
     'uvs_camera_guess_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _VP, _VP]),
     # fp, cam, T, q, f, dq_out, err_out, j_out, status, stream
     'uvs_camera_analytical_step_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 7),
@@ -62,7 +70,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-C', CSRC], check=True)
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 5)), '-C', CSRC], check=True)         # five translation units, one rule each
     return LIB_PATH
 
 

@@ -1,0 +1,409 @@
+// The pixel closed loop as ONE launch per batch: the one kernel text of uvs_camera_loop.hip (camera_loop_kernel, one uvs_filter_params for the
+// batch) and of uvs_camera_grid.hip (camera_grid_kernel, per-trial estimator parameters and a source index: a hyperparameter grid in one launch).
+// One text, two flavours, chosen per TRANSLATION UNIT as ../csrc does for closed_loop_grid_kernel: a unit that defines UVS_CAMERA_PER_TRIAL
+// before it includes this header sees the kernel as camera_grid_kernel(GridLoopArgs) with the switch PTP on; every other unit sees the uniform
+// kernel it always was -- same name, same argument block, same registers, LDS and time per instantiation.  (A shared
+// __device__ body behind two __global__ wrappers moved the register allocation there; nothing here is shared at run time.)
+// The estimator is the one of libuvs_rmckf.so, read from its device header (Rows::update, control_law, bandwidth, bandwidth_of); the sensor
+// side is vision_device.hpp.  Both libraries compile with -ffp-contract=off, so every value a kernel here forms has the bits the two-launch
+// loop (uvs_camera_features_f64, then uvs_rmckf_step_f64, K times) forms.
+//
+// Mapping.  A workgroup of 256 threads = four wavefronts is alone on its compute unit (one wavefront per SIMD, so the kernel may take the
+// whole register file: the estimator state alone is 108 dwords per lane at (8,6,4)).  It carries G trials:
+//   G = 4, batches of more than 256 trials: wavefront w owns trial w of the workgroup on the sensor side;
+//   G = 1, batches of up to 256 trials (one per compute unit of an MI355X): the four wavefronts share one trial, each repeats the short
+//     projection for itself and detects every fourth feature pair (one colour each), so a step's detection takes a quarter of the time.
+//   sensor side, every step: lane i < n advances joint i and takes its sine and cosine, lane p < n_points multiplies the links and projects
+//     its disc into LDS, then the 64 lanes walk the (colour, 64-index block) pairs of centre_of_mass in its order -- only the blocks the disc's
+//     clipped bounding box touches; every other one has the exact partial +0.0 -- and lane 0 finishes the colour: the features go to LDS and
+//     to the log.
+//   estimator side, every step: wavefront 0 alone.  Lanes L slot + sub, sub < L, are the L lanes of the workgroup's trial `slot`; the lanes
+//     from G L on shadow those (same slot modulo G) so that every cross-lane move has a full wavefront, and store nothing.  State (X, P),
+//     previous features, previous command and the error sums stay in registers over all K steps.
+// Barriers hand the sines, the discs, the features and the command over.  Every barrier is reached by all 256 threads the same number of
+// times: no thread leaves the step loop on its own -- a FAILed trial or a padding trial (which shadows trial T - 1) goes on computing and
+// stores nothing -- and the one early exit, "every trial of this workgroup has failed", is read by every thread from the same G LDS words
+// after the last barrier of the step, before anything rewrites them.
+//
+// PTP.  Trial t reads q_start, the noise rows, x0 and f0 of input trial source[t] (n_in of them; the noise row stride is n_in * M) and writes
+// every output at t.  On the estimator side lane L slot + sub holds ITS trial's sigma_0, gain, regulariser and fixed-point threshold -- the
+// four trials of wavefront 0 belong to different grid cells, so these are per-lane values, never wavefront-uniform -- parked in LDS (G x 4
+// doubles a lane reads once per step: MCKF at (8,6,4) has no four register pairs to spare over the step) and its own desired features in
+// the register array that held fp's.  A source index outside [0, n_in) never becomes an address: the trial is `void`, computes on input
+// trial 0 so that every barrier is still reached, counts as failed for the early exit, and stores status FAIL, k_done = 0 and nothing else.
+#ifndef UVS_CAMERA_LOOP_DEVICE_HPP
+#define UVS_CAMERA_LOOP_DEVICE_HPP
+
+#include "../csrc/rmckf_device.hpp"
+
+#include <climits>
+
+#include "uvs_vision.h"
+#include "vision_device.hpp"
+
+namespace uvs_vision {
+
+constexpr int kLoopTrials = 4;                                   // trials per workgroup of a large batch = wavefronts per workgroup
+constexpr int kLoopThreads = 64 * kLoopTrials;
+constexpr long long kSmallBatch = 256;                           // up to one trial per compute unit of an MI355X: one trial per workgroup
+constexpr int kJoints = 6;                                       // the DH arms of this project (camera_jacobian<6>)
+
+struct LoopArgs {
+    uvs_filter_params fp;
+    uvs_camera cam;
+    long long T;
+    const double *q_start, *noise, *x0, *f0;
+    double *q_log, *f_log, *dq_log, *err_log, *kappa_log;        // [K][T][comp], each or NULL
+    int32_t *status, *k_done;
+    double *stats;
+    int32_t *pixels;
+};
+// uvs_camera_closed_loop_grid_f64: the per-trial block rides in a derived argument block that only camera_grid_kernel takes
+struct GridLoopArgs : LoopArgs {
+    uvs_camera_trial_params tp;
+};
+
+#ifdef UVS_CAMERA_PER_TRIAL
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = GridLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL camera_grid_kernel
+#else
+constexpr bool kCameraPerTrial = false;
+using CameraLoopKernelArgs = LoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL camera_loop_kernel
+#endif
+__device__ __forceinline__ const uvs_camera_trial_params *trial_params_of(const LoopArgs &) { return nullptr; }
+__device__ __forceinline__ const uvs_camera_trial_params *trial_params_of(const GridLoopArgs &a) { return &a.tp; }
+
+template <int M, int N, int L, int METHOD_T, int G>
+__global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
+    constexpr bool PTP = kCameraPerTrial;
+    constexpr int R = M / L, W = kLoopThreads / 64;
+    static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
+    __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
+    __shared__ double s_disc[W][kColours * 3];
+    __shared__ double s_f[G][M];                                 // this step's features, sensor side -> estimator side
+    __shared__ double s_dq[G][N];                                // this step's command, estimator side -> sensor side
+    __shared__ int s_alive[G];                                   // trial has not FAILed, as of the end of this step
+    __shared__ int s_pix[G][kColours];                           // smallest mask so far
+    __shared__ double s_sum[G][3][M];                            // per-feature ISE, IAE, ITAE after the loop
+    // Three rows per lane, (6,6,2): X, P and the careful solve's two n x n matrices do not fit 512 registers together.  The control law reads X
+    // alone, so wavefront 0 parks P in LDS around it (plane [entry][lane]: consecutive lanes, consecutive banks).
+    constexpr bool PARK = R * uvs::Sym<N>::NP > 42;
+    __shared__ double s_park[PARK ? R * uvs::Sym<N>::NP : 1][PARK ? 64 : 1];
+    __shared__ double s_tp[PTP ? G : 1][4];                      // PTP: the trial's kernel_bw, gain, reg, fpi_threshold
+
+    const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const uvs_filter_params &fp = A.fp;
+    const uvs_camera &cam = A.cam;
+    const long long T = A.T;
+    const int K = fp.steps, npts = cam.n_points;
+
+    // sensor side: this wavefront's trial, and the feature pairs it detects: all of its own trial's, or every fourth of the workgroup's one trial
+    const int ws = G == 1 ? 0 : w;
+    const bool writer = G == W || w == 0;                        // G = 1: the four wavefronts hold the same joints; the first one logs them
+    const int j_first = G == 1 ? w : 0, j_step = G == 1 ? W : 1;
+    long long trial = static_cast<long long>(blockIdx.x) * G + ws;
+    bool valid = trial < T;
+    if (!valid) trial = T - 1;                                   // a padding wavefront shadows the last trial and stores nothing
+    long long src = trial;                                       // the input trial: q_start and the noise rows come from there
+    long long in_rows = T;                                       // trials per noise row
+    if constexpr (PTP) {
+        const uvs_camera_trial_params &tp = *trial_params_of(A);
+        if (tp.source != nullptr) {
+            src = tp.source[trial];
+            in_rows = tp.n_in;
+            if (src < 0 || src >= in_rows) {                     // names no input trial: void.  Never an address; nothing of it is stored
+                src = 0;
+                valid = false;
+            }
+        }
+    }
+    double q = lane < N ? A.q_start[src * N + lane] : 0.0;
+    // Row k of a [K][T][comp] log is step_rows * comp doubles past row k - 1.  The cursors below are this lane's own addresses in row 0 (NULL for
+    // a log that is not wanted, or where this lane has nothing to store), kept in vector registers: fifteen pointers as scalars did not fit.
+    const long long step_rows = T;
+    double *q_at = (valid && writer && lane < N && A.q_log != nullptr) ? A.q_log + trial * N + lane : nullptr;
+    double *f_at = (valid && lane == 0 && A.f_log != nullptr) ? A.f_log + trial * M : nullptr;
+    const double *noise_at = A.noise != nullptr ? A.noise + src * M : nullptr;
+    bool seen = true;                                            // this trial has not FAILed before this step: its rows q[k], f[k] are due
+    if (lane < kColours) s_pix[ws][lane] = INT_MAX;
+
+    // estimator side (wavefront 0): this lane's trial and rows
+    const int slot = (lane / L) & (G - 1), sub = lane % L;
+    long long etrial = static_cast<long long>(blockIdx.x) * G + slot;
+    const bool owner = lane < G * L;                             // the lanes beyond shadow these
+    bool evalid = owner && etrial < T;
+    if (etrial >= T) etrial = T - 1;
+    long long esrc = etrial;                                     // the input trial: x0 and f0 come from there
+    bool evoid = false;
+    if constexpr (PTP) {
+        const uvs_camera_trial_params &tp = *trial_params_of(A);
+        if (tp.source != nullptr) {
+            esrc = tp.source[etrial];
+            if (esrc < 0 || esrc >= tp.n_in) {
+                esrc = 0;
+                evoid = true;
+            }
+        }
+        if (w == 0 && owner && sub == 0) {                       // read back by this lane and its trial's other lanes after the first barrier
+            s_tp[slot][0] = tp.kernel_bw != nullptr ? tp.kernel_bw[etrial] : fp.kernel_bw;
+            s_tp[slot][1] = tp.gain != nullptr ? tp.gain[etrial] : fp.gain;
+            s_tp[slot][2] = tp.reg != nullptr ? tp.reg[etrial] : fp.reg;
+            s_tp[slot][3] = tp.fpi_threshold != nullptr ? tp.fpi_threshold[etrial] : fp.fpi_threshold;
+        }
+    }
+    const bool estore = evalid && !evoid;                        // this lane's trial has rows to log
+    double *err_at = (estore && A.err_log != nullptr) ? A.err_log + etrial * M + sub * R : nullptr;
+    double *kappa_at = (estore && A.kappa_log != nullptr) ? A.kappa_log + etrial * M + sub * R : nullptr;
+    double *dq_at = (estore && sub == 0 && A.dq_log != nullptr) ? A.dq_log + etrial * N : nullptr;
+    uvs::Rows<M, N, L> st;
+    st.init_cov();
+    double f_prev[R], des[R], dq[N], ise[R], iae[R], itae[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int row = sub * R + r;
+        des[r] = fp.desired[row];
+        if constexpr (PTP) {
+            const double *tp_des = trial_params_of(A)->desired;
+            if (tp_des != nullptr) des[r] = tp_des[etrial * M + row];
+        }
+        f_prev[r] = A.f0[esrc * M + row];
+        ise[r] = iae[r] = itae[r] = 0.0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) st.x[r][j] = A.x0[(esrc * M + row) * N + j];
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) dq[j] = 0.0;                     // first step: H = 0 (experiment.py:183)
+    double t = 0.0 + fp.dt;                                      // engine._loop_times: t_s accumulated in floating point
+    int status = UVS_STATUS_SUCCESS, k_done = K;
+    bool alive = true;
+    const bool strict = (fp.reserved & UVS_OPT_STRICT_PINV) != 0;
+    uvs_filter_params fp_trial;                                  // PTP: the launch's block with the trial's own reg and fpi_threshold, per lane
+    if constexpr (PTP) fp_trial = A.fp;
+    const uvs_filter_params &fpe = PTP ? fp_trial : A.fp;        // what the estimator update reads
+
+    for (int k = 0; k < K; ++k) {
+        // ---- joints: q_k = q_{k-1} + dq_{k-1} * dt, one rounded multiply and one rounded add (joint_sincos)
+        if (lane < N) {
+            if (k > 0) {
+                const double step = s_dq[ws][lane] * fp.dt;
+                q = q + step;
+            }
+            if (seen && q_at != nullptr) *q_at = q;
+            double s, c;
+            sincos(q + cam.theta_offset[lane], &s, &c);
+            s_sin[w][lane] = s;
+            s_cos[w][lane] = c;
+        }
+        __syncthreads();
+        // ---- projection (camera_features_kernel's)
+        if (lane < npts) {
+            double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
+#pragma unroll 1                                                 // a rolled loop reads the DH table where it is used: unrolled, the whole table sits in SGPRs
+            for (int i = 0; i < cam.n_joints; ++i) chain_link(cam, i, s_sin[w][i], s_cos[w][i], pose);
+            project_disc(cam, lane, pose, &s_disc[w][3 * lane]);
+        }
+        __syncthreads();
+        // ---- frame-free detection: feature pair j is the centre of mass of disc j's colour
+#pragma unroll 1
+        for (int j = j_first; j < npts; j += j_step) {
+            const Disc me = load_disc(&s_disc[w][3 * j], true);  // disc j shows colour j (npts == 1: green)
+            int x0, x1, y0, y1;
+            disc_box(me, x0, x1, y0, y1);
+            ColourSum sum;
+#pragma unroll 1
+            for (int b = 0; b < 4; ++b) {                        // the colour's four wavefronts of centre_of_mass, in index order
+                const int lo = 64 * b, hi = lo + 63;
+                // outside the clipped box disc_counts_at returns (0, 0) for all 64 indices, whose partial is (+0.0, +0.0, 0)
+                const bool touched = me.r2 >= 0.0 && ((x0 <= hi && x1 >= lo) || (y0 <= hi && y1 >= lo));
+                double su = 0.0, sv = 0.0;
+                int n = 0;
+                if (__builtin_amdgcn_readfirstlane(static_cast<int>(touched))) {   // the same discs in every lane: wavefront-uniform
+                    int cc, rc;
+                    disc_counts_in_box(s_disc[w], npts, j, me, x0, x1, y0, y1, lo + lane, cc, rc);
+                    wave_partial(cc, rc, lo + lane, su, sv, n);
+                }
+                sum.add(su, sv, n);
+            }
+            if (lane == 0) {                                     // the lane the shuffle tree ends in
+                double u, v;
+                sum.centre(u, v);
+                if (noise_at != nullptr) {                       // f += noise (experiment.py:135)
+                    u += noise_at[2 * j];
+                    v += noise_at[2 * j + 1];
+                }
+                s_f[ws][2 * j] = u;
+                s_f[ws][2 * j + 1] = v;
+                if (seen) {
+                    s_pix[ws][j] = sum.count < s_pix[ws][j] ? sum.count : s_pix[ws][j];
+                    if (f_at != nullptr) {
+                        f_at[2 * j] = u;
+                        f_at[2 * j + 1] = v;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // ---- estimator and control law of the workgroup's four trials (step_kernel's sequence)
+        if (w == 0) {
+            double z[R], err[R], kap[R], cmd[N];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double fv = s_f[slot][sub * R + r];
+                z[r] = fv - f_prev[r];
+                f_prev[r] = fv;
+                err[r] = fv - des[r];
+            }
+            double sigma, gain;
+            if constexpr (PTP) {                                 // the trial's scalars wait in LDS and are read where a step needs them
+                asm volatile("" ::: "memory");
+                sigma = uvs::bandwidth_of(fp, s_tp[slot][0], k);
+                gain = s_tp[slot][1];
+                fp_trial.reg = s_tp[slot][2];
+                fp_trial.fpi_threshold = s_tp[slot][3];
+            } else {
+                sigma = uvs::bandwidth(fp, k);
+                gain = fp.gain;
+            }
+            st.template update<METHOD_T>(fpe, z, dq, sigma, kap);   // h = the previous command; zero on k = 0
+            const int bad = st.any_nonfinite();
+            if (alive && bad) {                                  // FAIL at this step; the trial stops
+                alive = false;
+                status = UVS_STATUS_FAIL;
+                k_done = k;
+            }
+            if constexpr (PARK) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int e = 0; e < uvs::Sym<N>::NP; ++e) s_park[r * uvs::Sym<N>::NP + e][lane] = st.p[r][e];
+                asm volatile("" ::: "memory");                   // the loads below are loads: nothing of P is carried in registers
+            }
+            const bool suspect = strict || uvs::control_law<M, N, L, false>(st, kap, err, gain, sub, cmd);
+            if (__any(suspect)) {                                // the careful solve for a filter whose watch fires, or for every one when strict
+                double careful[N];
+                uvs::control_law<M, N, L, true>(st, kap, err, gain, sub, careful);
+#pragma unroll
+                for (int j = 0; j < N; ++j) cmd[j] = suspect ? careful[j] : cmd[j];
+            }
+            if constexpr (PARK) {
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int e = 0; e < uvs::Sym<N>::NP; ++e) st.p[r][e] = s_park[r * uvs::Sym<N>::NP + e][lane];
+            }
+            if (alive && estore) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (err_at != nullptr) err_at[r] = err[r];
+                    if (kappa_at != nullptr) kappa_at[r] = kap[r];
+                    const double ae = fabs(err[r]);              // stats_kernel's sums, in its order over k
+                    ise[r] = fma(err[r], err[r], ise[r]);
+                    iae[r] += ae;
+                    itae[r] = fma(t, ae, itae[r]);
+                }
+                if (dq_at != nullptr) {
+#pragma unroll
+                    for (int j = 0; j < N; ++j) dq_at[j] = cmd[j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < N; ++j) dq[j] = cmd[j];
+            if (owner && sub == 0) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) s_dq[slot][j] = cmd[j];
+                s_alive[slot] = (alive && !evoid) ? 1 : 0;
+            }
+        }
+        __syncthreads();
+        t += fp.dt;
+        if (q_at != nullptr) q_at += step_rows * N;
+        if (f_at != nullptr) f_at += step_rows * M;
+        if (noise_at != nullptr) noise_at += in_rows * M;
+        if (err_at != nullptr) err_at += step_rows * M;
+        if (kappa_at != nullptr) kappa_at += step_rows * M;
+        if (dq_at != nullptr) dq_at += step_rows * N;
+        seen = s_alive[ws] != 0;
+        int any_alive = 0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) any_alive |= s_alive[g];
+        if (any_alive == 0) break;                               // the same G words in all 256 threads: a uniform exit
+    }
+
+    if (w == 0 && owner) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            s_sum[slot][0][sub * R + r] = ise[r];
+            s_sum[slot][1][sub * R + r] = iae[r];
+            s_sum[slot][2][sub * R + r] = itae[r];
+        }
+        if (evalid && sub == 0) {
+            A.status[etrial] = evoid ? UVS_STATUS_FAIL : status;
+            A.k_done[etrial] = evoid ? 0 : k_done;
+        }
+    }
+    __syncthreads();
+    if (lane < 3 && valid && writer) {                           // lane i: the norm over the features in order, as stats_kernel forms it
+        double acc = 0.0;
+        for (int i = 0; i < M; ++i) acc = fma(s_sum[ws][lane][i], s_sum[ws][lane][i], acc);
+        A.stats[3 * trial + lane] = sqrt(acc);
+    }
+    if (lane < npts && valid && writer && A.pixels != nullptr) A.pixels[trial * npts + lane] = s_pix[ws][lane];
+}
+
+// MCKF: the fixed-point iteration's working set next to three rows per lane spills at (6,6,2) (684 B of scratch per lane), so that one
+// instantiation is not built in either flavour and the entry points refuse it; at (8,6,4) and (2,6,1) it has none and is built.
+template <int M, int N, int L, bool WITH_MCKF>
+bool launch_loop(int method, hipStream_t s, const CameraLoopKernelArgs &A) {
+    const bool small = A.T <= kSmallBatch;
+    const unsigned blocks = static_cast<unsigned>(small ? A.T : (A.T + kLoopTrials - 1) / kLoopTrials);
+#define UVS_LOOP_METHOD(METHOD)                                                                                                          \
+    if (method == METHOD) {                                                                                                              \
+        if (small) hipLaunchKernelGGL((UVS_CAMERA_LOOP_KERNEL<M, N, L, METHOD, 1>), dim3(blocks), dim3(kLoopThreads), 0, s, A);           \
+        else hipLaunchKernelGGL((UVS_CAMERA_LOOP_KERNEL<M, N, L, METHOD, kLoopTrials>), dim3(blocks), dim3(kLoopThreads), 0, s, A);       \
+        return true;                                                                                                                     \
+    }
+    UVS_LOOP_METHOD(UVS_METHOD_GMCKF)
+    UVS_LOOP_METHOD(UVS_METHOD_KF)
+    UVS_LOOP_METHOD(UVS_METHOD_IMCCKF)
+    if constexpr (WITH_MCKF) {
+        UVS_LOOP_METHOD(UVS_METHOD_MCKF)
+    }
+#undef UVS_LOOP_METHOD
+    return false;
+}
+
+// The refusals uvs_camera_closed_loop_f64 and uvs_camera_closed_loop_grid_f64 share, in the order the former always made them; UVS_OK = go on.
+inline int check_loop_args(const uvs_filter_params *fp, const uvs_camera *cam, int64_t T, const double *q_start, const double *x0, const double *f0,
+                           const int32_t *status, const int32_t *k_done, const double *stats) {
+    if (fp == nullptr || cam == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL fp or cam");
+    if (q_start == nullptr || x0 == nullptr || f0 == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL q_start, x0 or f0");
+    if (status == nullptr || k_done == nullptr || stats == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL status, k_done or stats");
+    if (T < 0 || T > INT32_MAX) return fail(UVS_ERR_ARG, "%s", "T out of range");
+    if (fp->steps < 1 || fp->k_max <= 0) return fail(UVS_ERR_ARG, "%s", "steps must be >= 1 and k_max > 0");
+    if (cam->n_joints < 1 || cam->n_joints > UVS_CAMERA_MAX_JOINTS) return fail(UVS_ERR_ARG, "%s", "n_joints must be 1 .. 8");
+    if (!colours_ok(cam->n_points)) return fail(UVS_ERR_ARG, "%s", "n_points must be 1 (green), 3 (RGB) or 4 (RGB + pink)");
+    if (fp->method != UVS_METHOD_KF && fp->method != UVS_METHOD_MCKF && fp->method != UVS_METHOD_IMCCKF && fp->method != UVS_METHOD_GMCKF)
+        return fail(UVS_ERR_METHOD, "%s", "method must be KF, MCKF, IMCCKF or GMCKF (the calibrated baseline's pixel loop is uvs_camera_analytical_loop_f64)");
+    if (fp->method == UVS_METHOD_MCKF && fp->fpi_epoch_max < 1) return fail(UVS_ERR_ARG, "%s", "MCKF needs fpi_epoch_max >= 1");
+    if (fp->lanes_per_filter != 0) return fail(UVS_ERR_SHAPE, "%s", "lanes_per_filter must be 0: the loop kernel has one mapping per shape");
+    if (fp->m != 2 * cam->n_points) return fail(UVS_ERR_SHAPE, "%s", "fp->m must be 2 * cam->n_points");
+    if (fp->n != cam->n_joints) return fail(UVS_ERR_SHAPE, "%s", "fp->n must be cam->n_joints");
+    if (fp->n != kJoints || (fp->m != 8 && fp->m != 6 && fp->m != 2)) return fail(UVS_ERR_SHAPE, "%s", "(m, n) must be (8, 6), (6, 6) or (2, 6)");
+    if (fp->method == UVS_METHOD_MCKF && fp->m == 6) return fail(UVS_ERR_METHOD, "%s", "MCKF is not built at (6, 6): use the two-launch loop");
+    return UVS_OK;
+}
+
+// the lane counts uvs_rmckf_step_f64 resolves for lanes_per_filter == 0
+inline bool launch_loop_shape(const uvs_filter_params &fp, hipStream_t s, const CameraLoopKernelArgs &A) {
+    if (fp.m == 8) return launch_loop<8, 6, 4, true>(fp.method, s, A);
+    if (fp.m == 6) return launch_loop<6, 6, 2, false>(fp.method, s, A);
+    if (fp.m == 2) return launch_loop<2, 6, 1, true>(fp.method, s, A);
+    return false;
+}
+
+}  // namespace uvs_vision
+#endif  // UVS_CAMERA_LOOP_DEVICE_HPP

@@ -637,38 +637,90 @@ def _reduce_camera_logs(fp, log, status_log, pixel_log, want):
     return out
 
 
-def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want):
-    """camera_closed_loop(fused=True): at most three launches and no host loop."""
+def _check_camera_trial_params(trial_params, n_in):
+    """What can be said of camera_closed_loop's ``trial_params`` on the host alone, before any device work: ValueError, or (the number of
+    output trials, 'source' as a checked host int32 array | the caller's device tensor | None)."""
+    import torch                                                     # not _torch(): these refusals need no GPU
+    if not isinstance(trial_params, dict):
+        raise ValueError(f'camera_closed_loop: trial_params is a dict with keys of {TRIAL_PARAM_KEYS}')
+    unknown = set(trial_params) - set(TRIAL_PARAM_KEYS)
+    if unknown:
+        raise ValueError(f'camera_closed_loop: trial_params: unknown keys {sorted(unknown)}; known: {TRIAL_PARAM_KEYS}')
+    source = trial_params.get('source')
+    if source is None:
+        return n_in, None
+    if torch.is_tensor(source) and source.is_cuda:                   # the kernel FAILs a trial whose index names no input trial
+        if source.dim() != 1:
+            raise ValueError("camera_closed_loop: trial_params['source'] is (T,) integers, one per output trial")
+        return source.shape[0], source
+    host = np.asarray(source.numpy() if torch.is_tensor(source) else source)
+    if host.ndim != 1 or host.dtype.kind not in 'iu':
+        raise ValueError("camera_closed_loop: trial_params['source'] is (T,) integers, one per output trial")
+    if host.size and (host.min() < 0 or host.max() >= n_in):
+        raise ValueError(f"camera_closed_loop: trial_params['source'] must lie in [0, {n_in}), the trials q_start holds, got "
+                         f'{int(host.min())} .. {int(host.max())}')
+    return host.shape[0], np.ascontiguousarray(host, np.int32)
+
+
+def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
+    """(uvs_camera_trial_params over the tensors of ``trial_params``, tensors to keep alive): closed_loop's shapes and dtypes."""
+    from . import _vision
+    torch = _torch()
+    _, source = _check_camera_trial_params(trial_params, n_in)
+    tp = _vision.CameraTrialParams(None, None, None, None, None, None, n_in)
+    keep = []
+    for key, value in trial_params.items():
+        if value is None:
+            continue
+        if key == 'source':
+            value = source if torch.is_tensor(source) else torch.from_numpy(source).to(dev)
+        shape, dtype = ((T, m), torch.float64) if key == 'desired' else ((T,), torch.int32 if key == 'source' else torch.float64)
+        if not torch.is_tensor(value) or tuple(value.shape) != shape or value.dtype != dtype or value.device != dev or not value.is_contiguous():
+            raise ValueError(f'camera_closed_loop: trial_params[{key!r}]: a contiguous {dtype} tensor of shape {shape} on {dev} is needed, got '
+                             f'{getattr(value, "dtype", type(value))} {tuple(getattr(value, "shape", ()))} on {getattr(value, "device", "the host")}')
+        setattr(tp, key, value.data_ptr())
+        keep.append(value)
+    return tp, keep
+
+
+def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None):
+    """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
+    then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
-    T, dev = q_start.shape[0], q_start.device
+    n_in, dev = q_start.shape[0], q_start.device
+    T = n_in if trial_params is None else _check_camera_trial_params(trial_params, n_in)[0]
+    tp, _keep = (None, ()) if trial_params is None else _camera_trial_params_struct(trial_params, T, n_in, m, dev)
     f64 = dict(dtype=torch.float64, device=dev)
-    q0 = _operand(q_start, 'q_start', torch.float64, (T, n))
-    noise_ptr = _operand(noise, 'noise', torch.float64, (K, T, m), True)
-    f0 = torch.zeros((T, m), **f64)
+    q0 = _operand(q_start, 'q_start', torch.float64, (n_in, n))
+    noise_ptr = _operand(noise, 'noise', torch.float64, (K, n_in, m), True)
+    f0 = torch.zeros((n_in, m), **f64)
     if fp.initial_guess:
         camera_features(cam, q_start, out=f0)
         if x0 is None and guess == 'device':
             x0 = camera_guess(cam, q_start, f0)
     if x0 is None:
         raise ValueError("camera_closed_loop: fused=True takes x0, or guess='device' with fp.initial_guess")
-    X0 = torch.as_tensor(x0, **f64).reshape(T, m * n).contiguous()
+    X0 = torch.as_tensor(x0, **f64).reshape(n_in, m * n).contiguous()
     comps = dict(err=m, q=n, f=m, dq=n, kappa=m)
     log = {key: torch.empty((K, T, comps[key]), **f64) for key in CAMERA_LOGS if key in want}
     ptr = lambda key: log[key].data_ptr() if key in log else None   # noqa: E731
     status, k_done = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2))
     stats = torch.empty((T, 3), **f64)
     pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
-    rc = _vision.lib().uvs_camera_closed_loop_f64(C.byref(fp), C.byref(cam), T, q0, noise_ptr, X0.data_ptr(), f0.data_ptr(), ptr('q'), ptr('f'),
-                                                  ptr('dq'), ptr('err'), ptr('kappa'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(),
-                                                  pixels.data_ptr(), _stream())
+    operands = (q0, noise_ptr, X0.data_ptr(), f0.data_ptr(), ptr('q'), ptr('f'), ptr('dq'), ptr('err'), ptr('kappa'), status.data_ptr(),
+                k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
+    if tp is None:
+        rc = _vision.lib().uvs_camera_closed_loop_f64(C.byref(fp), C.byref(cam), T, *operands)
+    else:
+        rc = _vision.lib().uvs_camera_closed_loop_grid_f64(C.byref(fp), C.byref(cam), T, C.byref(tp), *operands)
     _vision.check(rc)
     return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
 
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
-                       believed_index=None):
+                       believed_index=None, trial_params=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -694,11 +746,28 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     camera, uvs_camera_believed_step_f64); the same bits, and with the true model as ``believed`` the bits of the call without it).  With an
     estimator the believed models feed the initial guess alone (``camera_guess(believed=...)``) and the estimator's loop is untouched; that
     needs guess='device', and guess='host' or an explicit ``x0`` next to ``believed`` is a ValueError, like ``believed_index`` without
-    ``believed`` and a host-side index out of range."""
+    ``believed`` and a host-side index out of range.
+    ``trial_params``: per-trial estimator parameters, ONE launch for a whole hyperparameter grid through pixels
+    (uvs_camera_closed_loop_grid_f64): a dict with any of the keys of ``TRIAL_PARAM_KEYS``, in ``closed_loop``'s shapes and dtypes --
+    'kernel_bw', 'gain', 'reg', 'fpi_threshold' ((T,) fp64 cuda tensors), 'desired' ((T, m)) and 'source' ((T,) int32 on the device, or host
+    integers: trial t reads q_start / noise / x0 and the first f_old of input trial source[t]).  With 'source' T is len(source) and
+    ``q_start`` / ``noise`` / ``x0`` hold n_in = q_start.shape[0] trials, over which f0 and the initial guess are computed; every output has
+    T trials.  A host-side 'source' outside [0, n_in) is a ValueError; one on the device makes its trial FAIL with k_done = 0, alone.  A
+    trial's results are bit-identical to those of the uniform fused call with its values; ``{}`` is that call through the per-trial
+    kernel, None (the default) the uniform call itself.  It needs fused=True (the two-launch step has no per-trial flavour) and an
+    estimator (not ANALYTICAL), and excludes ``believed``: each a ValueError before any device work."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
     analytical = fp.method == _lib.METHOD_ANALYTICAL
+    if trial_params is not None:
+        if not fused:
+            raise ValueError('camera_closed_loop: trial_params needs fused=True: the two-launch step kernel has no per-trial flavour')
+        if analytical:
+            raise ValueError('camera_closed_loop: trial_params are estimator parameters: the calibrated baseline (ANALYTICAL) takes none')
+        if believed is not None or believed_index is not None:
+            raise ValueError('camera_closed_loop: trial_params and believed models do not combine')
+        _check_camera_trial_params(trial_params, q_start.shape[0])
     if believed is None and believed_index is not None:
         raise ValueError('camera_closed_loop: believed_index without believed')
     if believed is not None and not analytical:
@@ -742,7 +811,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want))
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -768,7 +837,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         raise ValueError('camera_closed_loop: x0 is needed when fp.initial_guess is 0 (the reference draws it unseeded, experiment.py:117)')
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want))
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params)
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
