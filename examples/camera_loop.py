@@ -15,8 +15,11 @@ same starts and the same noise at every level.  Prints the median ISE / IAE / IT
 --grid asks which kernel bandwidth and which gain survive pixel quantisation: kernel_bw x gain (GRID_BANDWIDTHS x GRID_GAINS below) over the SAME
 starts and the same noise is ONE launch (engine.camera_closed_loop(fused=True, trial_params=...) with a 'source' index, so the inputs are
 uploaded once, not once per cell).  Prints the median ISE / IAE / ITAE per cell over the trials that ran to the end, and the FAIL count.
+--occlusion asks who survives a real outlier: a 12 px bar of full height crosses the frame at constant speed while the servo runs
+(engine.camera_closed_loop(occluders=...)); a disc behind it loses a side of its mask and its centroid jumps.  GMCKF, KF and the calibrated law
+(stepwise) on the same starts and noise; prints the median ISE / IAE / ITAE and the FAIL count without and with the bar.
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid]"""
+       [--grid] [--occlusion]"""
 import argparse
 import os
 import sys
@@ -108,6 +111,40 @@ def grid_table(uvs, method='GMCKF', trials=16, sigma=0.3, radius=None, seed=0, b
     return lines
 
 
+BAR = (-12, 0, 12, 256, 1, 0, 0, 2 ** 31 - 1)                         # x, y, w, h, vx, vy, k_on, k_off: a 12 px bar of full height, 1 px per step
+
+
+def occlusion_table(uvs, trials=64, sigma=0.3, radius=None, seed=0, bar=BAR):
+    """The occlusion table as a list of lines: GMCKF, KF (one launch each) and the calibrated law (stepwise: its one-launch loop has no
+    occluders) on the same starts and noise, without and with the bar crossing the frame while the servo runs."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    fps = {method: uvs.engine.make_params(8, 6, method, 10.0, False, 0.05, 15.0, 0.2, desired, True) for method in ('GMCKF', 'KF', 'ANALYTICAL')}
+    K = fps['GMCKF'].steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    q0_d = torch.as_tensor(q0, device='cuda')
+    noise_d = torch.as_tensor(rng.standard_normal((K, trials, 8)) * sigma, device='cuda')
+    occluders = uvs.engine.occluders([bar], trials)
+    lines = [f'a {bar[2]} px bar of full height crossing the frame at {bar[4]} px per step, {trials} trials of {K} steps, white noise {sigma} px; '
+             'median over the trials that ran to the end',
+             f'{"":28s}{"without the bar":^36s}{"FAIL":>6s}   {"behind the bar":^36s}{"FAIL":>6s}{"mask":>6s}',
+             f'{"":28s}{"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"":6s}   {"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"":6s}{"min":>6s}']
+    for method, fp in fps.items():
+        kw = dict(radius=radius, want=()) if method == 'ANALYTICAL' else dict(radius=radius, fused=True, guess='device', want=())
+        row = f'{method + (" (calibrated, stepwise)" if method == "ANALYTICAL" else ""):28s}'
+        for occ in (None, occluders):
+            out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, occluders=occ, **kw)
+            torch.cuda.synchronize()
+            done = (out['status'] == 0).cpu().numpy()
+            med = np.median(out['stats'].cpu().numpy()[done], axis=0) if done.any() else np.full(3, np.nan)
+            row += f'{med[0]:12.3f}{med[1]:12.3f}{med[2]:12.3f}{int((~done).sum()):>6d}' + ('   ' if occ is None else f'{int(out["pixels"].min()):>6d}')
+        lines.append(row)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -119,9 +156,13 @@ def main():
     ap.add_argument('--baseline', action='store_true', help='pair the estimator with the calibrated law (ANALYTICAL) through the same pixels')
     ap.add_argument('--miscalibration', action='store_true', help='a ladder of wrong models x trials in one launch per side, and nothing else')
     ap.add_argument('--grid', action='store_true', help='kernel_bw x gain over the same starts and noise in one launch, and nothing else')
+    ap.add_argument('--occlusion', action='store_true', help='a bar crosses the frame while the servo runs: GMCKF, KF and the calibrated law, and nothing else')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
+    if args.occlusion:
+        print('\n'.join(occlusion_table(uvs, args.trials, args.sigma, args.radius, args.seed)))
+        return
     if args.grid:
         print('\n'.join(grid_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
         return

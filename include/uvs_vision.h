@@ -156,6 +156,41 @@ int uvs_camera_features_f64(const uvs_camera *cam, int64_t T, const double *q_pr
                             void *stream);
 
 /*
+ * Occluders: opaque rectangles that slide in front of the discs while the loop runs -- the event that gives a centre-of-mass detector its
+ * heavy-tailed errors (the mask loses a side and the centroid jumps).  The rule, in integers, is part of the pixel rule above:
+ *   - At step k >= 0 an occluder is ACTIVE iff k_on <= k < k_off, w > 0 and h > 0.  It then covers columns [x_k, x_k + w - 1] and flipped
+ *     rows [y_k, y_k + h - 1], clipped to the frame, with x_k = x + vx * k and y_k = y + vy * k formed in 64-bit integers: with k < 2^31
+ *     nothing overflows, whatever the int32 fields hold, and the clip to [0, 255] comes before any narrowing.
+ *   - A covered pixel belongs to NO disc, whatever the painter's order; the rasteriser gives it `shade` in all three channels (0 .. 249,
+ *     for background's reason).  Occluders may overlap: the covered set is the union.  Everything else is the rule above, unchanged.
+ * plant.occluder_rects and plant.render_discs (Python) state the rule once in numpy; every kernel below is held to it byte for byte.
+ * The operand of every entry point: occ [T][n_occ] structs in device (or pinned host) memory, trial t's at occ + t * n_occ; n_occ in
+ * 0 .. UVS_CAMERA_MAX_OCCLUDERS (occ may be NULL only with 0); the step k >= 0.
+ */
+#define UVS_CAMERA_MAX_OCCLUDERS 4
+typedef struct uvs_occluder {      /* 8 x int32, 32 bytes */
+    int32_t x, y;                  /* column and FLIPPED row of the top-left pixel at step 0 */
+    int32_t w, h;                  /* size in pixels; w <= 0 or h <= 0 covers nothing */
+    int32_t vx, vy;                /* pixels per step */
+    int32_t k_on, k_off;           /* active at steps k_on <= k < k_off */
+} uvs_occluder;
+
+/*
+ * The three entry points above with occluders at step k; without any (n_occ == 0) each gives the bits of its namesake.  The detectors
+ * decide per disc: when no active rectangle meets the disc's bounding box the walk is the unoccluded one, so an unoccluded disc costs what
+ * it costs there.  A disc that is covered completely has an empty mask: a NaN pair and a mask size of 0, like a disc outside the frame.
+ * Errors: those of the namesake, then UVS_ERR_ARG for n_occ outside 0 .. 4, a NULL occ with n_occ > 0, k < 0, or (rasteriser) shade
+ * outside 0 .. 249.  T == 0 returns UVS_OK and launches nothing.
+ */
+int uvs_render_discs_occluded_u8(int64_t T, const double *discs, int32_t n_colours, int32_t background, const uvs_occluder *occ,
+                                 int32_t n_occ, int32_t k, int32_t shade, uint8_t *frames, int64_t frame_stride_bytes, void *stream);
+int uvs_disc_features_occluded_f64(int64_t T, const double *discs, int32_t n_colours, const uvs_occluder *occ, int32_t n_occ, int32_t k,
+                                   const double *noise, double *f_out, int32_t *pixels_out, void *stream);
+int uvs_camera_features_occluded_f64(const uvs_camera *cam, int64_t T, const double *q_prev, const double *dq, double dt, double *q_out,
+                                     const uvs_occluder *occ, int32_t n_occ, int32_t k, const double *noise, double *f_out,
+                                     int32_t *pixels_out, double *discs_out, void *stream);
+
+/*
  * The pixel closed loop in ONE launch: K steps of { joints, projection, frame-free detection, estimator, control law } for T trials, with the
  * filter state resident in registers.  Step for step it is the loop a caller writes with the camera-features entry point above and the
  * single-step entry point of libuvs_rmckf (state in HBM, two launches per step), and since both libraries compile with -ffp-contract=off
@@ -222,6 +257,29 @@ int uvs_camera_closed_loop_grid_f64(const struct uvs_filter_params *fp, const uv
                                     const uvs_camera_trial_params *tp, const double *q_start, const double *noise, const double *x0,
                                     const double *f0, double *q_log, double *f_log, double *dq_log, double *err_log, double *kappa_log,
                                     int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, void *stream);
+
+/*
+ * The same loop with OCCLUDERS in front of the camera, per output trial: the detection of step k is that of the frame with trial t's
+ * occluders at step k (the rule at uvs_occluder above).  One flavour carries both the per-trial block and the occluders -- the study it
+ * serves is occlusion scenario x bandwidth x estimator over the same starts and noise.
+ *   tp: the block of uvs_camera_closed_loop_grid_f64, or NULL = every member NULL.
+ *   occ [T][n_occ]: indexed by OUTPUT trial, like every output (not by source); n_occ 0 .. 4, occ NULL only with 0.
+ *   The fourteen operands that follow are those of uvs_camera_closed_loop_grid_f64, in its order.  f0 is the caller's: for the loop of the
+ *     reference it is the noise-free detection of the step-0 frame, occluders at k = 0 included.
+ * A trial without an active occluder near its discs has the bits of uvs_camera_closed_loop_grid_f64; a padding or void trial evaluates
+ * the rectangles of the trial it shadows and stores nothing.  FULL OCCLUSION: an occluder that covers a disc completely gives an empty
+ * mask, a NaN pair, a non-finite X and FAIL at that step -- the loop's behaviour for a disc that leaves the frame, and the documented
+ * meaning of full occlusion; the last feature is not held.
+ * Built: what uvs_camera_closed_loop_grid_f64 builds (MCKF at (6, 6) is refused with UVS_ERR_METHOD), each in both workgroup forms with
+ * 0 B of scratch memory.
+ * Errors, all before the first HIP call: those of uvs_camera_closed_loop_grid_f64, in its order, except that a NULL tp is allowed; then
+ * UVS_ERR_ARG for n_occ outside 0 .. 4 or a NULL occ with n_occ > 0.  T == 0 returns UVS_OK and launches nothing.
+ */
+int uvs_camera_closed_loop_occluded_f64(const struct uvs_filter_params *fp, const uvs_camera *cam, int64_t T,
+                                        const uvs_camera_trial_params *tp, const uvs_occluder *occ, int32_t n_occ, const double *q_start,
+                                        const double *noise, const double *x0, const double *f0, double *q_log, double *f_log,
+                                        double *dq_log, double *err_log, double *kappa_log, int32_t *status, int32_t *k_done,
+                                        double *stats, int32_t *pixels, void *stream);
 
 /*
  * The analytic initial guess X0 of the loop (experiment.py:94-114) for T trials, one lane each: the geometric Jacobian of the DH chain in the

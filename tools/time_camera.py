@@ -40,7 +40,17 @@ With --grid only the per-trial pixel loop is timed, into profiles/camera_grid.tx
       host clock around synchronised calls, alternating blocks of one process.  The acceptance condition is (k) below (j); (e) new against
       (e) parent and (k) / (e) are reported next to the parent's own spread.  Every cell of (k) is checked against its launch of (j), bit
       for bit, before anything is timed.  Then the table of examples/camera_loop.py --grid.
-usage: tools/time_camera.py --grid [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --grid [--parent-lib=PATH] [out.txt]
+With --occluded only the occluded pixel loop is timed, into profiles/camera_occluded.txt (or the path given): GMCKF, 1 024 trials x 299
+steps, white noise 0.3 px, x0 handed in, medians of 20 with p10-p90;
+  (e) the uniform fused launch -- with this library and, given --parent-lib=PATH, with the parent's in turn;
+  (m) (e)'s trials through camera_occluded_kernel with n_occ = 0: what the kernel flavour costs;
+  (n) the sweeping bar of examples/camera_loop.py --occlusion on every trial, one launch;
+  (o) (n) stepwise: K x (occluded camera features, estimator step).
+      The acceptance condition is (n) below (o); (e) new against (e) parent is reported next to the parent's own spread; (m) / (e) and
+      (n) / (m) are reported, not gated.  (m) is checked against (e) and (n) against (o), bit for bit, before anything is timed.  Then the
+      table of examples/camera_loop.py --occlusion.
+usage: tools/time_camera.py --occluded [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -53,9 +63,10 @@ import uvs_amd as uvs  # noqa: E402
 import torch  # noqa: E402
 
 ANALYTICAL, BELIEVED, GRID = '--analytical' in sys.argv[1:], '--believed' in sys.argv[1:], '--grid' in sys.argv[1:]
+OCCLUDED = '--occluded' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -348,6 +359,95 @@ def grid_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def occluded_section():
+    """(e), (m), (n), (o): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T = 299, 1024
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    assert fp.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --occluded on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in; the sweeping bar: rows {example.BAR} of (x, y, w, h, vx, vy, k_on, k_off)')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+    x0 = uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+    none, bar = uvs.engine.occluders(np.zeros((T, 0, 8), np.int64), T), uvs.engine.occluders([example.BAR], T)
+    fns = {'e': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True),
+           'm': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=none),
+           'n': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=bar),
+           'o': lambda: loop(fp, plant, q_d, noise, x0=x0, occluders=bar)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+    logs = ('err', 'q', 'f', 'dq', 'kappa', 'stats')
+
+    def same(a, b):
+        done = a['k_done']
+        ok = all(torch.equal(a[key], b[key]) for key in ('status', 'k_done', 'pixels')) and torch.equal(a['stats'].view(torch.int64), b['stats'].view(torch.int64))
+        for key in logs[:5]:                                         # the specified rows: q, f up to and including k_done, the others before it
+            spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+            ok = ok and torch.equal(a[key].view(torch.int64)[spec], b[key].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['m'], first['e']), 'the occluded kernel without occluders and the uniform kernel disagree'
+    assert same(first['n'], first['o']), 'the one launch and the stepwise loop behind the bar disagree'
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_occluded_f64'), 'the parent library has no occluders'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def run_e_parent():
+            mine, uvs._vision._lib = uvs._vision._lib, parent
+            try:
+                return fns['e']()
+            finally:
+                uvs._vision._lib = mine
+
+        old = run_e_parent()
+        torch.cuda.synchronize()
+        assert same(first['e'], old), 'this library and the parent disagree on the uniform launch'
+        fns['e_parent'] = run_e_parent
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    spread = lambda v: (np.percentile(v, 90) - np.percentile(v, 10)) / np.median(v)   # noqa: E731
+    say()
+    say(f'  (e) uniform fused launch, this library                          {fmt_ms(ms["e"])}   = {med["e"] / K * 1e3:.1f} us per step')
+    if 'e_parent' in ms:
+        say(f'  (e) the same with the parent\'s library                          {fmt_ms(ms["e_parent"])}')
+        say(f'  (e) new / (e) parent = {med["e"] / med["e_parent"]:.4f}; the parent\'s own p10-p90 spread is {spread(ms["e_parent"]) * 100:.2f} % of its median, '
+            f'this library\'s {spread(ms["e"]) * 100:.2f} %; the outputs of the two are bit-identical')
+    say(f'  (m) (e)\'s trials through camera_occluded_kernel, n_occ = 0        {fmt_ms(ms["m"])}')
+    say(f'  (n) the sweeping bar on every trial, one launch                  {fmt_ms(ms["n"])}   = {med["n"] / K * 1e3:.1f} us per step')
+    say(f'  (o) (n) stepwise: K x (occluded camera features, estimator step) {fmt_ms(ms["o"])}   = {med["o"] / K * 1e3:.1f} us per step')
+    say(f'  (n) / (o) = {med["n"] / med["o"]:.4f}: (n) is {"BELOW" if med["n"] < med["o"] else "NOT below"} (o); specified log rows, stats, status, k_done, '
+        'pixels bit-identical')
+    say(f'  (m) / (e) = {med["m"] / med["e"]:.4f}, (n) / (m) = {med["n"] / med["m"]:.4f} (reported, not gated); (m) has the bits of (e)')
+    failed = lambda out: int((out['k_done'] < K).sum())              # noqa: E731
+    say(f'  trials that FAILed: (e) {failed(first["e"])}, (n) {failed(first["n"])}; smallest mask behind the bar {int(first["n"]["pixels"].min())} px')
+    say()
+    say(f'acceptance: (n) below (o): {"yes" if med["n"] < med["o"] else "NO"}')
+    say()
+    say('# examples/camera_loop.py --occlusion (its defaults)')
+    for line in example.occlusion_table(uvs):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if OCCLUDED:
+    occluded_section()
+    sys.exit(0)
 if GRID:
     grid_section()
     sys.exit(0)

@@ -17,6 +17,7 @@ SIDE = 256                                                          # UVS_VISION
 N_COLOURS = (1, 3, 4)                                               # green | red, green, blue | red, green, blue, pink
 
 MAX_JOINTS, MAX_POINTS = 8, 4                                       # UVS_CAMERA_MAX_JOINTS, UVS_CAMERA_MAX_POINTS
+MAX_OCCLUDERS = 4                                                   # UVS_CAMERA_MAX_OCCLUDERS
 
 
 class Camera(C.Structure):
@@ -34,6 +35,11 @@ class CameraTrialParams(C.Structure):
                 ('desired', C.c_void_p), ('source', C.c_void_p), ('n_in', C.c_int64)]
 
 
+class Occluder(C.Structure):
+    """uvs_occluder of include/uvs_vision.h: eight int32, the row layout of the (T, n_occ, 8) tensor ``engine.occluders`` packs."""
+    _fields_ = [(name, C.c_int32) for name in ('x', 'y', 'w', 'h', 'vx', 'vy', 'k_on', 'k_off')]
+
+
 # name -> (restype, argtypes); every symbol include/uvs_vision.h declares
 _VP, _I64, _I32, _F64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double
 _CAM = C.POINTER(Camera)
@@ -45,10 +51,16 @@ SYMBOLS = {
     'uvs_render_discs_u8': (C.c_int, [_I64, _VP, _I32, _I32, _VP, _I64, _VP]),
     'uvs_disc_features_f64': (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP, _VP]),
     'uvs_camera_features_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    # the three above with the occluder operand (occ: device int32 [T][n_occ][8] or None, n_occ, k; the rasteriser's shade after it)
+    'uvs_render_discs_occluded_u8': (C.c_int, [_I64, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _VP, _I64, _VP]),
+    'uvs_disc_features_occluded_f64': (C.c_int, [_I64, _VP, _I32, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
+    'uvs_camera_features_occluded_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     # fp (a pointer to _lib.FilterParams, passed with byref), cam, T, q_start, noise, x0, f0, five logs, status, k_done, stats, pixels, stream
     'uvs_camera_closed_loop_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 14),
     # the same with tp (a pointer to CameraTrialParams, passed with byref) after T
     'uvs_camera_closed_loop_grid_f64': (C.c_int, [_VP, _CAM, _I64, _VP] + [_VP] * 14),
+    # the same with tp (or None), occ and n_occ after T
+    'uvs_camera_closed_loop_occluded_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _I32] + [_VP] * 14),
     'uvs_camera_guess_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _VP, _VP]),
     # fp, cam, T, q, f, dq_out, err_out, j_out, status, stream
     'uvs_camera_analytical_step_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 7),
@@ -70,7 +82,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 5)), '-C', CSRC], check=True)         # five translation units, one rule each
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 6)), '-C', CSRC], check=True)         # six translation units, one rule each
     return LIB_PATH
 
 

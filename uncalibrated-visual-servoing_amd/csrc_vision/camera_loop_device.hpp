@@ -31,6 +31,12 @@
 // doubles a lane reads once per step: MCKF at (8,6,4) has no four register pairs to spare over the step) and its own desired features in
 // the register array that held fp's.  A source index outside [0, n_in) never becomes an address: the trial is `void`, computes on input
 // trial 0 so that every barrier is still reached, counts as failed for the early exit, and stores status FAIL, k_done = 0 and nothing else.
+//
+// OCC.  A third flavour: a unit that defines UVS_CAMERA_OCCLUDED next to UVS_CAMERA_PER_TRIAL (uvs_camera_occluded.hip) sees
+// camera_occluded_kernel(OccludedLoopArgs) with both switches on.  Lane o < 4 of each sensor-side wavefront evaluates rectangle o of its OUTPUT
+// trial for step k (occluder_rect; lanes from n_occ on write "covers nothing") into s_occ[w] next to the projection, before the second barrier;
+// the detection loop reads the four dwords from there and hands them to disc_counts_in_box<true>, which takes the unoccluded walk for every
+// disc no rectangle meets.  A padding or void trial evaluates the rectangles of the trial it shadows.  Barriers and exits are where they were.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -63,7 +69,25 @@ struct GridLoopArgs : LoopArgs {
     uvs_camera_trial_params tp;
 };
 
-#ifdef UVS_CAMERA_PER_TRIAL
+// uvs_camera_closed_loop_occluded_f64: the per-trial block and the occluders, [T][n_occ] by output trial; only camera_occluded_kernel takes it
+struct OccludedLoopArgs : GridLoopArgs {
+    const uvs_occluder *occ;
+    int32_t n_occ;
+};
+
+#ifdef UVS_CAMERA_OCCLUDED
+#ifndef UVS_CAMERA_PER_TRIAL
+#error "the occluded flavour is a per-trial flavour: define UVS_CAMERA_PER_TRIAL too"
+#endif
+constexpr bool kCameraOccluded = true;
+#else
+constexpr bool kCameraOccluded = false;
+#endif
+#if defined(UVS_CAMERA_OCCLUDED)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = OccludedLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL camera_occluded_kernel
+#elif defined(UVS_CAMERA_PER_TRIAL)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = GridLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL camera_grid_kernel
@@ -74,10 +98,16 @@ using CameraLoopKernelArgs = LoopArgs;
 #endif
 __device__ __forceinline__ const uvs_camera_trial_params *trial_params_of(const LoopArgs &) { return nullptr; }
 __device__ __forceinline__ const uvs_camera_trial_params *trial_params_of(const GridLoopArgs &a) { return &a.tp; }
+// the occluders of output trial `trial` and their number (never called on the other two blocks: OCC is off there)
+__device__ __forceinline__ const uvs_occluder *occluders_of(const LoopArgs &, long long, int &n_occ) { n_occ = 0; return nullptr; }
+__device__ __forceinline__ const uvs_occluder *occluders_of(const OccludedLoopArgs &a, long long trial, int &n_occ) {
+    n_occ = a.n_occ;
+    return a.occ + trial * a.n_occ;
+}
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
-    constexpr bool PTP = kCameraPerTrial;
+    constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -92,6 +122,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     constexpr bool PARK = R * uvs::Sym<N>::NP > 42;
     __shared__ double s_park[PARK ? R * uvs::Sym<N>::NP : 1][PARK ? 64 : 1];
     __shared__ double s_tp[PTP ? G : 1][4];                      // PTP: the trial's kernel_bw, gain, reg, fpi_threshold
+    __shared__ uint32_t s_occ[OCC ? W : 1][kOccluders];          // OCC: this step's rectangles of the wavefront's trial (occluder_rect's packing)
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -120,6 +151,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
             }
         }
     }
+    const uvs_occluder *occ_at = nullptr;                        // OCC: the occluders of the OUTPUT trial (a padding wavefront: of the one it shadows)
+    int n_occ = 0;
+    if constexpr (OCC) occ_at = occluders_of(A, trial, n_occ);
     double q = lane < N ? A.q_start[src * N + lane] : 0.0;
     // Row k of a [K][T][comp] log is step_rows * comp doubles past row k - 1.  The cursors below are this lane's own addresses in row 0 (NULL for
     // a log that is not wanted, or where this lane has nothing to store), kept in vector registers: fifteen pointers as scalars did not fit.
@@ -205,8 +239,16 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
             for (int i = 0; i < cam.n_joints; ++i) chain_link(cam, i, s_sin[w][i], s_cos[w][i], pose);
             project_disc(cam, lane, pose, &s_disc[w][3 * lane]);
         }
+        if constexpr (OCC) {                                     // lane o: rectangle o of this step, next to the projection
+            if (lane < kOccluders) s_occ[w][lane] = lane < n_occ ? occluder_rect(occ_at[lane], k) : kNoRect;
+        }
         __syncthreads();
         // ---- frame-free detection: feature pair j is the centre of mass of disc j's colour
+        Rects rects;
+        if constexpr (OCC) {
+#pragma unroll
+            for (int o = 0; o < kOccluders; ++o) rects.r[o] = s_occ[w][o];
+        }
 #pragma unroll 1
         for (int j = j_first; j < npts; j += j_step) {
             const Disc me = load_disc(&s_disc[w][3 * j], true);  // disc j shows colour j (npts == 1: green)
@@ -222,7 +264,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
                 int n = 0;
                 if (__builtin_amdgcn_readfirstlane(static_cast<int>(touched))) {   // the same discs in every lane: wavefront-uniform
                     int cc, rc;
-                    disc_counts_in_box(s_disc[w], npts, j, me, x0, x1, y0, y1, lo + lane, cc, rc);
+                    disc_counts_in_box<OCC>(s_disc[w], npts, j, me, x0, x1, y0, y1, lo + lane, cc, rc, rects);
                     wave_partial(cc, rc, lo + lane, su, sv, n);
                 }
                 sum.add(su, sv, n);

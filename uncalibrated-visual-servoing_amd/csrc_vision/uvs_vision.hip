@@ -114,8 +114,26 @@ __device__ __forceinline__ uint32_t colour_word(int k, int n) {
     return slot == 0 ? 0x0000ffu : slot == 1 ? 0x00ff00u : slot == 2 ? 0xff0000u : 0xff00ffu;
 }
 
+// The occluder operand of the OCC flavours below: nothing at all in the kernels that always were
+template <bool OCC>
+struct OccluderArgs {};
+template <>
+struct OccluderArgs<true> {
+    const uvs_occluder *occ;                                     // [T][n_occ]
+    int n_occ, k;
+    uint32_t shade;                                              // the rasteriser's
+};
+// the rectangles of this workgroup's trial at the launch's step
+__device__ __forceinline__ Rects rects_of_block(const OccluderArgs<true> &oa) {
+    Rects rects = occluder_rects(oa.occ + static_cast<int64_t>(blockIdx.x) * oa.n_occ, oa.n_occ, oa.k);
+#pragma unroll
+    for (int o = 0; o < kOccluders; ++o) rects.r[o] = __builtin_amdgcn_readfirstlane(rects.r[o]);   // the same in every thread: scalar registers
+    return rects;
+}
+
+template <bool OCC>
 __global__ __launch_bounds__(kThreads) void render_discs_kernel(const double *__restrict__ discs, int n_colours, uint32_t background,
-                                                                uint8_t *__restrict__ frames, int64_t frame_stride) {
+                                                                uint8_t *__restrict__ frames, int64_t frame_stride, const OccluderArgs<OCC> oa) {
     const int tid = threadIdx.x;
     const int cg = tid & 15, rg = tid >> 4;                      // the detector's lane unit: 16 pixels = 48 B of row j * 64 + rg
     uint8_t *frame = frames + static_cast<int64_t>(blockIdx.x) * frame_stride;
@@ -128,6 +146,8 @@ __global__ __launch_bounds__(kThreads) void render_discs_kernel(const double *__
         disc_box(d[k], x0[k], x1[k], y0[k], y1[k]);
     }
     const uint32_t bg = background * 0x010101u;
+    Rects rects;
+    if constexpr (OCC) rects = rects_of_block(oa);
 #pragma unroll
     for (int j = 0; j < kPasses; ++j) {
         const int row = j * 64 + rg, i = kSide - 1 - row;        // stored row, flipped row
@@ -140,6 +160,7 @@ __global__ __launch_bounds__(kThreads) void render_discs_kernel(const double *__
             dy2[k] = dy * dy;
             any = any || (d[k].r2 >= 0.0 && i >= y0[k] && i <= y1[k] && x0[k] <= 16 * cg + 15 && x1[k] >= 16 * cg);
         }
+        if constexpr (OCC) any = any || rects_meet(rects, 16 * cg, 16 * cg + 15, i, i);   // a run an active rectangle meets is not skipped
         uint32_t px[16];
 #pragma unroll
         for (int p = 0; p < 16; ++p) px[p] = bg;
@@ -151,6 +172,9 @@ __global__ __launch_bounds__(kThreads) void render_discs_kernel(const double *__
                 for (int k = 0; k < kColours; ++k) {             // painter's order: a later disc overwrites an earlier one
                     const double dx = fj - d[k].u;
                     if (dx * dx + dy2[k] <= d[k].r2) px[p] = colour_word(k, n_colours);
+                }
+                if constexpr (OCC) {                             // a covered pixel belongs to no disc, whatever the painter's order
+                    if (rects_cover(rects, 16 * cg + p, i)) px[p] = oa.shade * 0x010101u;
                 }
             }
         }
@@ -169,10 +193,15 @@ __global__ __launch_bounds__(kThreads) void render_discs_kernel(const double *__
     }
 }
 
+template <bool OCC>
 __global__ __launch_bounds__(kThreads) void disc_features_kernel(const double *__restrict__ discs, int n_colours, const double *__restrict__ noise,
-                                                                 double *__restrict__ f_out, int32_t *__restrict__ pixels_out) {
+                                                                 double *__restrict__ f_out, int32_t *__restrict__ pixels_out,
+                                                                 const OccluderArgs<OCC> oa) {
     int cc, rc;
-    disc_counts(discs + static_cast<int64_t>(blockIdx.x) * (3 * n_colours), n_colours, cc, rc);
+    if constexpr (OCC)
+        disc_counts<true>(discs + static_cast<int64_t>(blockIdx.x) * (3 * n_colours), n_colours, cc, rc, rects_of_block(oa));
+    else
+        disc_counts(discs + static_cast<int64_t>(blockIdx.x) * (3 * n_colours), n_colours, cc, rc);
     centre_of_mass_of_block(cc, rc, n_colours, noise, f_out, pixels_out);
 }
 
@@ -196,10 +225,12 @@ __global__ __launch_bounds__(kProjectThreads) void camera_project_kernel(const u
 // run side by side), the first n_points lanes then each multiply the links (lanes of one wavefront: the time of one) and project their own
 // point into LDS; then every thread counts against those discs and the detector's phase 2 follows.  Same arithmetic on the same operands
 // as camera_project_kernel, so the same bits.
+template <bool OCC>
 __global__ __launch_bounds__(kThreads) void camera_features_kernel(const uvs_camera cam, const double *__restrict__ q_prev,
                                                                    const double *__restrict__ dq, double dt, double *__restrict__ q_out,
                                                                    const double *__restrict__ noise, double *__restrict__ f_out,
-                                                                   int32_t *__restrict__ pixels_out, double *__restrict__ discs_out) {
+                                                                   int32_t *__restrict__ pixels_out, double *__restrict__ discs_out,
+                                                                   const OccluderArgs<OCC> oa) {
     __shared__ double sdisc[kColours * 3];
     __shared__ double ssin[UVS_CAMERA_MAX_JOINTS], scos[UVS_CAMERA_MAX_JOINTS];
     const int tid = threadIdx.x;
@@ -217,7 +248,10 @@ __global__ __launch_bounds__(kThreads) void camera_features_kernel(const uvs_cam
     }
     __syncthreads();
     int cc, rc;
-    disc_counts(sdisc, cam.n_points, cc, rc);
+    if constexpr (OCC)
+        disc_counts<true>(sdisc, cam.n_points, cc, rc, rects_of_block(oa));
+    else
+        disc_counts(sdisc, cam.n_points, cc, rc);
     centre_of_mass_of_block(cc, rc, cam.n_points, noise, f_out, pixels_out);
 }
 
@@ -240,6 +274,12 @@ int check_camera(const uvs_camera *cam, int64_t T, const double *q_prev, const d
         const uintptr_t bytes = static_cast<uintptr_t>(T > 0 ? T : 1) * cam->n_joints * sizeof(double);
         if (a < b + bytes && b < a + bytes) return fail(UVS_ERR_ARG, "%s", "q_out overlaps q_prev");
     }
+    return UVS_OK;
+}
+
+int check_occluders(const uvs_occluder *occ, int32_t n_occ) {
+    if (n_occ < 0 || n_occ > UVS_CAMERA_MAX_OCCLUDERS) return fail(UVS_ERR_ARG, "%s", "n_occ must be 0 .. 4");
+    if (occ == nullptr && n_occ > 0) return fail(UVS_ERR_ARG, "%s", "NULL occ with n_occ > 0");
     return UVS_OK;
 }
 
@@ -289,9 +329,7 @@ int uvs_camera_project_f64(const uvs_camera *cam, int64_t T, const double *q_pre
     return launched("camera_project_kernel launch: %s");
 }
 
-int uvs_render_discs_u8(int64_t T, const double *discs, int32_t n_colours, int32_t background, uint8_t *frames, int64_t frame_stride_bytes,
-                        void *stream) {
-    g_err[0] = '\0';
+static int check_render(int64_t T, const double *discs, int32_t n_colours, int32_t background, const uint8_t *frames, int64_t frame_stride_bytes) {
     if (discs == nullptr || frames == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL discs or frames");
     if (T < 0 || T > INT32_MAX) return fail(UVS_ERR_ARG, "%s", "T out of range");
     if (!colours_ok(n_colours)) return fail(UVS_ERR_ARG, "%s", "n_colours must be 1 (green), 3 (RGB) or 4 (RGB + pink)");
@@ -299,22 +337,60 @@ int uvs_render_discs_u8(int64_t T, const double *discs, int32_t n_colours, int32
     if (frame_stride_bytes < static_cast<int64_t>(kSide) * kRowBytes) return fail(UVS_ERR_ARG, "%s", "frame stride below 256 * 256 * 3");
     if (frame_stride_bytes % 16 != 0) return fail(UVS_ERR_ARG, "%s", "frame stride must be a multiple of 16 bytes");
     if (reinterpret_cast<uintptr_t>(frames) % 16 != 0) return fail(UVS_ERR_ARG, "%s", "frames must be 16-byte aligned");
+    return UVS_OK;
+}
+
+int uvs_render_discs_u8(int64_t T, const double *discs, int32_t n_colours, int32_t background, uint8_t *frames, int64_t frame_stride_bytes,
+                        void *stream) {
+    g_err[0] = '\0';
+    if (const int rc = check_render(T, discs, n_colours, background, frames, frame_stride_bytes)) return rc;
     if (T == 0) return UVS_OK;
-    hipLaunchKernelGGL(render_discs_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), discs,
-                       static_cast<int>(n_colours), static_cast<uint32_t>(background), frames, frame_stride_bytes);
+    hipLaunchKernelGGL(render_discs_kernel<false>, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), discs,
+                       static_cast<int>(n_colours), static_cast<uint32_t>(background), frames, frame_stride_bytes, OccluderArgs<false>{});
     return launched("render_discs_kernel launch: %s");
+}
+
+int uvs_render_discs_occluded_u8(int64_t T, const double *discs, int32_t n_colours, int32_t background, const uvs_occluder *occ, int32_t n_occ,
+                                 int32_t k, int32_t shade, uint8_t *frames, int64_t frame_stride_bytes, void *stream) {
+    g_err[0] = '\0';
+    if (const int rc = check_render(T, discs, n_colours, background, frames, frame_stride_bytes)) return rc;
+    if (const int rc = check_occluders(occ, n_occ)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (shade < 0 || shade >= kThreshold) return fail(UVS_ERR_ARG, "%s", "shade must be 0 .. 249 (250 and above would enter a mask)");
+    if (T == 0) return UVS_OK;
+    hipLaunchKernelGGL(render_discs_kernel<true>, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), discs,
+                       static_cast<int>(n_colours), static_cast<uint32_t>(background), frames, frame_stride_bytes,
+                       OccluderArgs<true>{occ, n_occ, k, static_cast<uint32_t>(shade)});
+    return launched("render_discs_kernel<occluded> launch: %s");
+}
+
+static int check_disc_features(int64_t T, const double *discs, int32_t n_colours, const double *f_out) {
+    if (discs == nullptr || f_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL discs or f_out");
+    if (T < 0 || T > INT32_MAX) return fail(UVS_ERR_ARG, "%s", "T out of range");
+    if (!colours_ok(n_colours)) return fail(UVS_ERR_ARG, "%s", "n_colours must be 1 (green), 3 (RGB) or 4 (RGB + pink)");
+    return UVS_OK;
 }
 
 int uvs_disc_features_f64(int64_t T, const double *discs, int32_t n_colours, const double *noise, double *f_out, int32_t *pixels_out,
                           void *stream) {
     g_err[0] = '\0';
-    if (discs == nullptr || f_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL discs or f_out");
-    if (T < 0 || T > INT32_MAX) return fail(UVS_ERR_ARG, "%s", "T out of range");
-    if (!colours_ok(n_colours)) return fail(UVS_ERR_ARG, "%s", "n_colours must be 1 (green), 3 (RGB) or 4 (RGB + pink)");
+    if (const int rc = check_disc_features(T, discs, n_colours, f_out)) return rc;
     if (T == 0) return UVS_OK;
-    hipLaunchKernelGGL(disc_features_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), discs,
-                       static_cast<int>(n_colours), noise, f_out, pixels_out);
+    hipLaunchKernelGGL(disc_features_kernel<false>, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), discs,
+                       static_cast<int>(n_colours), noise, f_out, pixels_out, OccluderArgs<false>{});
     return launched("disc_features_kernel launch: %s");
+}
+
+int uvs_disc_features_occluded_f64(int64_t T, const double *discs, int32_t n_colours, const uvs_occluder *occ, int32_t n_occ, int32_t k,
+                                   const double *noise, double *f_out, int32_t *pixels_out, void *stream) {
+    g_err[0] = '\0';
+    if (const int rc = check_disc_features(T, discs, n_colours, f_out)) return rc;
+    if (const int rc = check_occluders(occ, n_occ)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (T == 0) return UVS_OK;
+    hipLaunchKernelGGL(disc_features_kernel<true>, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), discs,
+                       static_cast<int>(n_colours), noise, f_out, pixels_out, OccluderArgs<true>{occ, n_occ, k, 0u});
+    return launched("disc_features_kernel<occluded> launch: %s");
 }
 
 int uvs_camera_features_f64(const uvs_camera *cam, int64_t T, const double *q_prev, const double *dq, double dt, double *q_out,
@@ -323,9 +399,23 @@ int uvs_camera_features_f64(const uvs_camera *cam, int64_t T, const double *q_pr
     if (f_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL f_out");
     if (const int rc = check_camera(cam, T, q_prev, q_out)) return rc;
     if (T == 0) return UVS_OK;
-    hipLaunchKernelGGL(camera_features_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), *cam, q_prev,
-                       dq, dt, q_out, noise, f_out, pixels_out, discs_out);
+    hipLaunchKernelGGL(camera_features_kernel<false>, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), *cam,
+                       q_prev, dq, dt, q_out, noise, f_out, pixels_out, discs_out, OccluderArgs<false>{});
     return launched("camera_features_kernel launch: %s");
+}
+
+int uvs_camera_features_occluded_f64(const uvs_camera *cam, int64_t T, const double *q_prev, const double *dq, double dt, double *q_out,
+                                     const uvs_occluder *occ, int32_t n_occ, int32_t k, const double *noise, double *f_out,
+                                     int32_t *pixels_out, double *discs_out, void *stream) {
+    g_err[0] = '\0';
+    if (f_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL f_out");
+    if (const int rc = check_camera(cam, T, q_prev, q_out)) return rc;
+    if (const int rc = check_occluders(occ, n_occ)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (T == 0) return UVS_OK;
+    hipLaunchKernelGGL(camera_features_kernel<true>, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), *cam,
+                       q_prev, dq, dt, q_out, noise, f_out, pixels_out, discs_out, OccluderArgs<true>{occ, n_occ, k, 0u});
+    return launched("camera_features_kernel<occluded> launch: %s");
 }
 
 }  // extern "C"

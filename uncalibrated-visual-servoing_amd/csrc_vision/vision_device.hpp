@@ -1,5 +1,5 @@
-// Device code shared by the translation units of libuvs_vision.so (uvs_vision.hip, uvs_camera_loop.hip, uvs_camera_analytical.hip, uvs_camera_believed.hip): the detector's phase 2 in the two
-// forms its callers need, the disc geometry of the synthetic camera, and the DH chain.  The summation order of the phase 2 is a contract
+// Device code shared by the translation units of libuvs_vision.so (uvs_vision.hip, the three uvs_camera_loop / _grid / _occluded units, uvs_camera_analytical.hip, uvs_camera_believed.hip): the detector's phase 2 in the two
+// forms its callers need, the disc geometry of the synthetic camera with its occluders, and the DH chain.  The summation order of the phase 2 is a contract
 // (see centre_of_mass): every unit that sums mask pixels goes through wave_partial and ColourSum, so they all give the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -140,10 +140,91 @@ __device__ __forceinline__ bool may_cover(const Disc &o, int x0, int x1, int y0,
     return ox0 <= x1 && ox1 >= x0 && oy0 <= y1 && oy1 >= y0;
 }
 
-// The two walks of disc_counts_at over the box of `me`; OVER = false leaves the tests against the discs painted later out (none can cover a
-// pixel of the box), which is three of the four distance tests of every pixel.
-template <bool OVER>
-__device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kColours - 1], int x0, int x1, int y0, int y1, int i, int &cc, int &rc) {
+// ---------------------------------------------------------------------------------------------------------------- occluders
+// An occluder's rectangle at one step, clipped to the frame, as the kernels hold it: x0 | x1 << 8 | y0 << 16 | y1 << 24, inclusive bounds
+// in 0 .. 255.  A rectangle that covers nothing -- inactive at k, no size, or wholly outside the frame -- is kNoRect: x0 = 1 > x1 = 0.
+constexpr int kOccluders = UVS_CAMERA_MAX_OCCLUDERS;
+constexpr uint32_t kNoRect = 0x00010001u;
+
+struct Rects {
+    uint32_t r[kOccluders] = {kNoRect, kNoRect, kNoRect, kNoRect};
+};
+
+__device__ __forceinline__ int rect_x0(uint32_t r) { return static_cast<int>(r & 255u); }
+__device__ __forceinline__ int rect_x1(uint32_t r) { return static_cast<int>((r >> 8) & 255u); }
+__device__ __forceinline__ int rect_y0(uint32_t r) { return static_cast<int>((r >> 16) & 255u); }
+__device__ __forceinline__ int rect_y1(uint32_t r) { return static_cast<int>(r >> 24); }
+
+// THE rectangle of the rule (uvs_vision.h, uvs_occluder), shared by every kernel: position in 64-bit integers -- |x + vx * k| < 2^62 + 2^31
+// for any int32 fields and 0 <= k < 2^31 -- and the clip to the frame before the narrowing.
+__device__ __forceinline__ uint32_t occluder_rect(const uvs_occluder &o, int k) {
+    if (!(k >= o.k_on && k < o.k_off && o.w > 0 && o.h > 0)) return kNoRect;
+    const long long xk = static_cast<long long>(o.x) + static_cast<long long>(o.vx) * k;
+    const long long yk = static_cast<long long>(o.y) + static_cast<long long>(o.vy) * k;
+    const long long last = kSide - 1;
+    const long long x0 = xk > 0 ? xk : 0, x1 = xk + o.w - 1 < last ? xk + o.w - 1 : last;
+    const long long y0 = yk > 0 ? yk : 0, y1 = yk + o.h - 1 < last ? yk + o.h - 1 : last;
+    if (x0 > x1 || y0 > y1) return kNoRect;                      // here 0 <= x0 <= x1 <= 255, and likewise y
+    return static_cast<uint32_t>(x0) | static_cast<uint32_t>(x1) << 8 | static_cast<uint32_t>(y0) << 16 | static_cast<uint32_t>(y1) << 24;
+}
+
+// The rectangles of one trial at step k: occ names the trial's n_occ structs (read only when n_occ > 0)
+__device__ __forceinline__ Rects occluder_rects(const uvs_occluder *occ, int n_occ, int k) {
+    Rects out;
+#pragma unroll
+    for (int o = 0; o < kOccluders; ++o)
+        if (o < n_occ) out.r[o] = occluder_rect(occ[o], k);
+    return out;
+}
+
+// Does a rectangle of `rects` hold a pixel of the box [x0, x1] x [y0, y1]?
+__device__ __forceinline__ bool rects_meet(const Rects &rects, int x0, int x1, int y0, int y1) {
+    bool meets = false;
+#pragma unroll
+    for (int o = 0; o < kOccluders; ++o) {
+        const uint32_t r = rects.r[o];
+        meets = meets || (rect_x0(r) <= rect_x1(r) && rect_x0(r) <= x1 && rect_x1(r) >= x0 && rect_y0(r) <= y1 && rect_y1(r) >= y0);
+    }
+    return meets;
+}
+
+__device__ __forceinline__ bool rects_cover(const Rects &rects, int x, int y) {
+    bool covered = false;
+#pragma unroll
+    for (int o = 0; o < kOccluders; ++o) {
+        const uint32_t r = rects.r[o];
+        covered = covered || (x >= rect_x0(r) && x <= rect_x1(r) && y >= rect_y0(r) && y <= rect_y1(r));
+    }
+    return covered;
+}
+
+// The same test for a walk along one line of the frame: what each rectangle covers of column x (along = false: flipped rows [lo, hi]) or
+// of flipped row y (along = true: columns [lo, hi]), formed once per line; a rectangle that misses the line leaves lo = 1 > hi = 0.
+struct LineCover {
+    int lo[kOccluders], hi[kOccluders];
+    __device__ __forceinline__ LineCover(const Rects &rects, int line, bool along) {
+#pragma unroll
+        for (int o = 0; o < kOccluders; ++o) {
+            const uint32_t r = rects.r[o];
+            const bool on = along ? (line >= rect_y0(r) && line <= rect_y1(r)) : (line >= rect_x0(r) && line <= rect_x1(r));
+            lo[o] = on ? (along ? rect_x0(r) : rect_y0(r)) : 1;
+            hi[o] = on ? (along ? rect_x1(r) : rect_y1(r)) : 0;
+        }
+    }
+    __device__ __forceinline__ bool at(int p) const {
+        bool covered = false;
+#pragma unroll
+        for (int o = 0; o < kOccluders; ++o) covered = covered || (p >= lo[o] && p <= hi[o]);
+        return covered;
+    }
+};
+
+// The walks of disc_counts_at over the box of `me`; OVER = false leaves the tests against the discs painted later out (none can cover a
+// pixel of the box), which is three of the four distance tests of every pixel.  OCC = true adds the occluders: a pixel counts when it is
+// the topmost disc's AND no rectangle covers it -- integer compares; OCC = false is the walk as it always was and never reads `rects`.
+template <bool OVER, bool OCC = false>
+__device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kColours - 1], int x0, int x1, int y0, int y1, int i, int &cc, int &rc,
+                                           const Rects &rects = Rects{}) {
     const double fi = static_cast<double>(i);
     if (i >= x0 && i <= x1) {                                    // column i: walk the rows of the box
         const double dx = fi - me.u, dx2 = dx * dx;
@@ -155,6 +236,7 @@ __device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kC
                 ox2[k] = o * o;
             }
         }
+        const LineCover cover(rects, i, false);                  // OCC = false: never read
         for (int y = y0; y <= y1; ++y) {
             const double fy = static_cast<double>(y), dy = fy - me.v;
             bool top = dx2 + dy * dy <= me.r2;
@@ -165,6 +247,7 @@ __device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kC
                     top = top && !(ox2[k] + o * o <= over[k].r2);
                 }
             }
+            if constexpr (OCC) top = top && !cover.at(y);
             cc += top ? 1 : 0;
         }
     }
@@ -178,6 +261,7 @@ __device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kC
                 oy2[k] = o * o;
             }
         }
+        const LineCover cover(rects, i, true);
         for (int x = x0; x <= x1; ++x) {
             const double fx = static_cast<double>(x), dx = fx - me.u;
             bool top = dx * dx + dy2 <= me.r2;
@@ -188,6 +272,7 @@ __device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kC
                     top = top && !(o * o + oy2[k] <= over[k].r2);
                 }
             }
+            if constexpr (OCC) top = top && !cover.at(x);
             rc += top ? 1 : 0;
         }
     }
@@ -197,9 +282,11 @@ __device__ __forceinline__ void box_counts(const Disc &me, const Disc (&over)[kC
 // which it is the topmost one in column i, rc = columns at which it is in flipped row i.  `me` is that disc, loaded (me.r2 >= 0), and
 // [x0, x1] x [y0, y1] its disc_box: a caller that has both in hand -- the closed loops, which skip whole blocks of indices by the box --
 // passes them on instead of having them formed again.  The discs are the same in all lanes of a wavefront (every caller's are), so which
-// of the two walks runs is a scalar branch.
+// of the two walks runs is a scalar branch.  OCC: so are the trial's rectangles, and so is the decision whether one of them meets the box;
+// when none does the walks are the unoccluded ones -- an unoccluded disc costs what it always cost and trivially has those bits.
+template <bool OCC = false>
 __device__ __forceinline__ void disc_counts_in_box(const double *discs, int n_colours, int own, const Disc &me, int x0, int x1, int y0, int y1, int i,
-                                                   int &cc, int &rc) {
+                                                   int &cc, int &rc, const Rects &rects = Rects{}) {
     cc = 0;
     rc = 0;
     Disc over[kColours - 1];                                     // the discs painted after mine; absent ones never cover a pixel
@@ -210,6 +297,15 @@ __device__ __forceinline__ void disc_counts_in_box(const double *discs, int n_co
         over[k] = load_disc(discs + 3 * (other < n_colours ? other : own), other < n_colours);
         covered = covered || may_cover(over[k], x0, x1, y0, y1);
     }
+    if constexpr (OCC) {
+        if (__builtin_amdgcn_readfirstlane(static_cast<int>(rects_meet(rects, x0, x1, y0, y1)))) {
+            if (__builtin_amdgcn_readfirstlane(static_cast<int>(covered)))
+                box_counts<true, true>(me, over, x0, x1, y0, y1, i, cc, rc, rects);
+            else
+                box_counts<false, true>(me, over, x0, x1, y0, y1, i, cc, rc, rects);
+            return;
+        }
+    }
     if (__builtin_amdgcn_readfirstlane(static_cast<int>(covered)))
         box_counts<true>(me, over, x0, x1, y0, y1, i, cc, rc);
     else
@@ -217,7 +313,8 @@ __device__ __forceinline__ void disc_counts_in_box(const double *discs, int n_co
 }
 
 // Counts of (colour c, index i) from the discs alone; c is the same in all lanes of a wavefront.
-__device__ __forceinline__ void disc_counts_at(const double *discs, int n_colours, int c, int i, int &cc, int &rc) {
+template <bool OCC = false>
+__device__ __forceinline__ void disc_counts_at(const double *discs, int n_colours, int c, int i, int &cc, int &rc, const Rects &rects = Rects{}) {
     const int own = disc_of_colour(c, n_colours);
     cc = 0;
     rc = 0;
@@ -226,12 +323,13 @@ __device__ __forceinline__ void disc_counts_at(const double *discs, int n_colour
     if (!(me.r2 >= 0.0)) return;
     int x0, x1, y0, y1;
     disc_box(me, x0, x1, y0, y1);
-    disc_counts_in_box(discs, n_colours, own, me, x0, x1, y0, y1, i, cc, rc);
+    disc_counts_in_box<OCC>(discs, n_colours, own, me, x0, x1, y0, y1, i, cc, rc, rects);
 }
 
 // The same for thread (colour c = tid >> 8, index i = tid & 255) of a one-workgroup-per-frame kernel; c is wavefront-uniform there.
-__device__ __forceinline__ void disc_counts(const double *discs, int n_colours, int &cc, int &rc) {
-    disc_counts_at(discs, n_colours, threadIdx.x >> 8, threadIdx.x & 255, cc, rc);
+template <bool OCC = false>
+__device__ __forceinline__ void disc_counts(const double *discs, int n_colours, int &cc, int &rc, const Rects &rects = Rects{}) {
+    disc_counts_at<OCC>(discs, n_colours, threadIdx.x >> 8, threadIdx.x & 255, cc, rc, rects);
 }
 
 // Joint i of trial t -- q = q_prev + dq * dt when dq is given, written to q_out when that is given -- and the sine and cosine of its DH angle.
@@ -279,5 +377,6 @@ extern thread_local char g_err[256];
 int fail(int code, const char *fmt, const char *detail = "");
 int launched(const char *what);
 bool colours_ok(int32_t n);
+int check_occluders(const uvs_occluder *occ, int32_t n_occ);    // UVS_ERR_ARG for n_occ outside 0 .. 4 or a NULL occ with n_occ > 0
 
 }  // namespace uvs_vision

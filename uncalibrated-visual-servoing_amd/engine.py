@@ -390,11 +390,54 @@ def _discs_arg(discs, n_colours):
     return discs.shape[0], _operand(discs, 'discs', torch.float64, discs.shape)
 
 
-def render_discs(discs, n_colours=4, background=96, out=None):
+def _check_occluders(spec, T, k=0, shade=32, who='occluders'):
+    """What can be said of an occluder operand on the host alone, before any device work: ValueError, or the operand -- None, the caller's
+    own packed device (or pinned) int32 tensor (T, n_occ, 8), or a checked host int32 array (T, n_occ, 8)."""
+    import torch                                                     # not _torch(): these refusals need no GPU
+    from . import plant as plant_mod
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 2 ** 31:
+        raise ValueError(f'{who}: k is a step count, an integer >= 0, got {k!r}')
+    if isinstance(shade, bool) or not isinstance(shade, (int, np.integer)) or not 0 <= shade < 250:
+        raise ValueError(f'{who}: shade must be an integer 0 .. 249 (250 and above would enter a mask of the detectors), got {shade!r}')
+    if spec is None:
+        return None
+    if torch.is_tensor(spec) and (spec.is_cuda or spec.is_pinned()):
+        if spec.dtype != torch.int32 or spec.dim() != 3 or spec.shape[0] != T or spec.shape[2] != 8 or not spec.is_contiguous():
+            raise ValueError(f'{who}: a packed tensor is contiguous int32 ({T}, n_occ, 8), got {spec.dtype} {tuple(spec.shape)}')
+        if spec.shape[1] > plant_mod.MAX_OCCLUDERS:
+            raise ValueError(f'{who}: at most {plant_mod.MAX_OCCLUDERS} per trial, got {spec.shape[1]}')
+        return spec
+    return plant_mod.occluder_array(spec.numpy() if torch.is_tensor(spec) else spec, T).astype(np.int32)
+
+
+def occluders(spec, T, device=None):
+    """Pack occluders for the kernels (uvs_occluder of include/uvs_vision.h): ``spec`` is a (T, n_occ, 8) or (n_occ, 8) integer array-like of
+    rows (x, y, w, h, vx, vy, k_on, k_off) -- ``plant.OCCLUDER_FIELDS``; the second form is broadcast over the trials -- with n_occ <= 4.
+    Returns a contiguous int32 tensor (T, n_occ, 8) on ``device``.  Indexing per scenario is the caller's, by gathering on the host or with
+    torch: the C ABI has no index operand."""
+    host = _check_occluders(spec, T)
+    torch = _torch()
+    if host is None:
+        raise ValueError('occluders: nothing to pack')
+    dev = current_device(device)
+    return host.to(dev) if torch.is_tensor(host) else torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+
+
+def _occluder_operand(checked, dev):
+    """(pointer or None, n_occ, tensor to keep alive) of what _check_occluders returned."""
+    torch = _torch()
+    t = checked if torch.is_tensor(checked) else torch.from_numpy(np.ascontiguousarray(checked)).to(dev)
+    return (t.data_ptr() if t.numel() else None), t.shape[1], t
+
+
+def render_discs(discs, n_colours=4, background=96, out=None, occluders=None, k=0, shade=32):
     """Rasterise ``discs`` (T, n_colours, 3) fp64 rows (u, v, r) into camera frames on the current stream (uvs_render_discs_u8; the pixel rule
     is ``plant.render_discs``'s, byte for byte).  Returns ``out``: uint8 (T, 256, 256, 3), unflipped as the detectors expect them, on the device
-    unless the caller passes its own device or pinned tensor -- whose frame stride is free (bytes between frames are not written)."""
+    unless the caller passes its own device or pinned tensor -- whose frame stride is free (bytes between frames are not written).
+    ``occluders`` (what ``occluders()`` takes or returns), the step ``k`` and ``shade``: the frames with those rectangles in front
+    (uvs_render_discs_occluded_u8; ``plant.render_discs(..., occluders, k, shade)`` byte for byte).  None is the call above."""
     from . import _vision
+    checked = _check_occluders(occluders, getattr(discs, 'shape', (0,))[0], k, shade, 'render_discs')
     torch = _torch()
     T, ptr = _discs_arg(discs, n_colours)
     if out is None:
@@ -402,44 +445,59 @@ def render_discs(discs, n_colours=4, background=96, out=None):
     frames, Tf = _frames_arg(out)
     if Tf != T or tuple(frames.shape[1:3]) != (_vision.SIDE, _vision.SIDE):
         raise ValueError(f'out: ({T}, 256, 256, 3) uint8, got {tuple(out.shape)}')
-    rc = _vision.lib().uvs_render_discs_u8(T, ptr, int(n_colours), int(background), frames.data_ptr(),
-                                           frames.stride(0) if T > 1 else _vision.SIDE * _vision.SIDE * 3, _stream())
+    stride = frames.stride(0) if T > 1 else _vision.SIDE * _vision.SIDE * 3
+    if checked is None:
+        rc = _vision.lib().uvs_render_discs_u8(T, ptr, int(n_colours), int(background), frames.data_ptr(), stride, _stream())
+    else:
+        occ, n_occ, _keep = _occluder_operand(checked, _device_of(discs))
+        rc = _vision.lib().uvs_render_discs_occluded_u8(T, ptr, int(n_colours), int(background), occ, n_occ, int(k), int(shade),
+                                                        frames.data_ptr(), stride, _stream())
     _vision.check(rc)
     return out
 
 
-def disc_features(discs, n_colours=4, noise=None, out=None, pixels=None):
+def disc_features(discs, n_colours=4, noise=None, out=None, pixels=None, occluders=None, k=0):
     """The frame-free detector (uvs_disc_features_f64): what ``detect_circles(render_discs(discs))`` returns, bit for bit, in one launch that
-    never writes a frame.  Arguments and result as ``detect_circles`` with ``discs`` (T, n_colours, 3) in place of the frames."""
+    never writes a frame.  Arguments and result as ``detect_circles`` with ``discs`` (T, n_colours, 3) in place of the frames.  With
+    ``occluders`` at step ``k`` (uvs_disc_features_occluded_f64) it is ``detect_circles(render_discs(discs, occluders=..., k=k))``."""
     from . import _vision
+    checked = _check_occluders(occluders, getattr(discs, 'shape', (0,))[0], k, who='disc_features')
     torch = _torch()
     T, ptr = _discs_arg(discs, n_colours)
     m = 2 * int(n_colours)
     if out is None:
         out = torch.empty((T, m), dtype=torch.float64, device=_device_of(discs))
-    rc = _vision.lib().uvs_disc_features_f64(T, ptr, int(n_colours), _operand(noise, 'noise', torch.float64, (T, m), True),
-                                             _operand(out, 'out', torch.float64, (T, m)),
-                                             _operand(pixels, 'pixels', torch.int32, (T, int(n_colours)), True), _stream())
+    rest = (_operand(noise, 'noise', torch.float64, (T, m), True), _operand(out, 'out', torch.float64, (T, m)),
+            _operand(pixels, 'pixels', torch.int32, (T, int(n_colours)), True), _stream())
+    if checked is None:
+        rc = _vision.lib().uvs_disc_features_f64(T, ptr, int(n_colours), *rest)
+    else:
+        occ, n_occ, _keep = _occluder_operand(checked, _device_of(discs))
+        rc = _vision.lib().uvs_disc_features_occluded_f64(T, ptr, int(n_colours), occ, n_occ, int(k), *rest)
     _vision.check(rc)
     return out
 
 
-def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_out=None, out=None, pixels=None, discs=None):
+def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_out=None, out=None, pixels=None, discs=None, occluders=None, k=0):
     """``camera_project`` and ``disc_features`` in one launch (uvs_camera_features_f64), bit-identical to the two in a row: joints in, noisy
-    detected features (T, 2 n_points) out.  ``discs`` (T, n_points, 3) receives the projection when given."""
+    detected features (T, 2 n_points) out.  ``discs`` (T, n_points, 3) receives the projection when given.  ``occluders`` at step ``k``:
+    uvs_camera_features_occluded_f64, the two occluded calls in a row."""
     from . import _vision, plant as plant_mod
+    checked = _check_occluders(occluders, getattr(q_prev, 'shape', (0,))[0], k, who='camera_features')
     torch = _torch()
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
     T, n, npts = q_prev.shape[0], cam.n_joints, cam.n_points
     if out is None:
         out = torch.empty((T, 2 * npts), dtype=torch.float64, device=_device_of(q_prev))
-    rc = _vision.lib().uvs_camera_features_f64(C.byref(cam), T, _operand(q_prev, 'q_prev', torch.float64, (T, n)),
-                                               _operand(dq, 'dq', torch.float64, (T, n), True), float(dt),
-                                               _operand(q_out, 'q_out', torch.float64, (T, n), True),
-                                               _operand(noise, 'noise', torch.float64, (T, 2 * npts), True),
-                                               _operand(out, 'out', torch.float64, (T, 2 * npts)),
-                                               _operand(pixels, 'pixels', torch.int32, (T, npts), True),
-                                               _operand(discs, 'discs', torch.float64, (T, npts, 3), True), _stream())
+    joints = (C.byref(cam), T, _operand(q_prev, 'q_prev', torch.float64, (T, n)), _operand(dq, 'dq', torch.float64, (T, n), True), float(dt),
+              _operand(q_out, 'q_out', torch.float64, (T, n), True))
+    rest = (_operand(noise, 'noise', torch.float64, (T, 2 * npts), True), _operand(out, 'out', torch.float64, (T, 2 * npts)),
+            _operand(pixels, 'pixels', torch.int32, (T, npts), True), _operand(discs, 'discs', torch.float64, (T, npts, 3), True), _stream())
+    if checked is None:
+        rc = _vision.lib().uvs_camera_features_f64(*joints, *rest)
+    else:
+        occ, n_occ, _keep = _occluder_operand(checked, _device_of(q_prev))
+        rc = _vision.lib().uvs_camera_features_occluded_f64(*joints, occ, n_occ, int(k), *rest)
     _vision.check(rc)
     return out
 
@@ -579,9 +637,22 @@ CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
 ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
 
 
-def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None):
+def _features_step(cam_ref, T, dt, occ, stream):
+    """The stepwise loops' sensor launch at step k: uvs_camera_features_f64, or its occluded namesake when ``occ`` -- None, or the
+    (pointer, n_occ, tensor) of ``_occluder_operand`` -- is given.  Returns f(k, q_prev, dq_prev, q, noise, f, pixels) -> return code."""
+    from . import _vision
+    if occ is None:
+        plain = _vision.lib().uvs_camera_features_f64
+        return lambda k, q_prev, dq_prev, q, noise, f, pixels: plain(cam_ref, T, q_prev, dq_prev, dt, q, noise, f, pixels, None, stream)
+    occluded = _vision.lib().uvs_camera_features_occluded_f64
+    return lambda k, q_prev, dq_prev, q, noise, f, pixels: occluded(cam_ref, T, q_prev, dq_prev, dt, q, occ[0], occ[1], k, noise, f, pixels,
+                                                                    None, stream)
+
+
+def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
-    ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models."""
+    ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models.
+    ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none)."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -606,7 +677,8 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in comps.items()}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
-    features, cam_ref, fp_ref, stream = _vision.lib().uvs_camera_features_f64, C.byref(cam), C.byref(fp), _stream()
+    cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
+    features = _features_step(cam_ref, T, fp.dt, occ, stream)
     if believed is None:
         step = lambda *rows: _vision.lib().uvs_camera_analytical_step_f64(fp_ref, cam_ref, T, *rows)          # noqa: E731
     else:
@@ -616,8 +688,7 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     noise_row = 0 if noise is None else noise.stride(0) * 8
     for k in range(K):
         q_prev, dq_prev = (q0, None) if k == 0 else (at('q', k - 1), at('dq', k - 1))
-        _vision.check(features(cam_ref, T, q_prev, dq_prev, fp.dt, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k),
-                               at('pixels', k), None, stream))
+        _vision.check(features(k, q_prev, dq_prev, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k), at('pixels', k)))
         _vision.check(step(at('q', k), at('f', k), at('dq', k), at('err', k), None, at('status', k), stream))
     return _reduce_camera_logs(fp, log, status_log, pixel_log, want)
 
@@ -683,9 +754,11 @@ def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
     return tp, keep
 
 
-def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None):
+def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None):
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
-    then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one."""
+    then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
+    ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
+    ``_gather_by_source``) -- the launch is then uvs_camera_closed_loop_occluded_f64, with or without trial_params."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -696,8 +769,9 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     q0 = _operand(q_start, 'q_start', torch.float64, (n_in, n))
     noise_ptr = _operand(noise, 'noise', torch.float64, (K, n_in, m), True)
     f0 = torch.zeros((n_in, m), **f64)
+    occ = None if occluders is None else _occluder_operand(occluders, dev)
     if fp.initial_guess:
-        camera_features(cam, q_start, out=f0)
+        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2])     # the step-0 frame, occluders at k = 0 included
         if x0 is None and guess == 'device':
             x0 = camera_guess(cam, q_start, f0)
     if x0 is None:
@@ -711,7 +785,10 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
     operands = (q0, noise_ptr, X0.data_ptr(), f0.data_ptr(), ptr('q'), ptr('f'), ptr('dq'), ptr('err'), ptr('kappa'), status.data_ptr(),
                 k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
-    if tp is None:
+    if occ is not None:
+        rc = _vision.lib().uvs_camera_closed_loop_occluded_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp), occ[0], occ[1],
+                                                               *operands)
+    elif tp is None:
         rc = _vision.lib().uvs_camera_closed_loop_f64(C.byref(fp), C.byref(cam), T, *operands)
     else:
         rc = _vision.lib().uvs_camera_closed_loop_grid_f64(C.byref(fp), C.byref(cam), T, C.byref(tp), *operands)
@@ -719,8 +796,25 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
 
 
+def _gather_by_source(q_start, noise, x0, trial_params):
+    """Occluders belong to OUTPUT trials, and with them the step-0 frame, f0 and the initial guess: where 'source' and occluders meet, the
+    inputs are gathered by source here (torch, on the device) and the launch runs without an index.  Returns (q_start, noise, x0,
+    trial_params without 'source').  'source' was checked on the host, or is the caller's device tensor, whose range is checked here."""
+    torch = _torch()
+    source = trial_params['source']
+    n_in, dev = q_start.shape[0], q_start.device
+    index = source.to(torch.int64) if torch.is_tensor(source) else torch.as_tensor(np.asarray(source), dtype=torch.int64)
+    index = index.to(dev)
+    if index.numel() and bool(((index < 0) | (index >= n_in)).any()):
+        raise ValueError(f"camera_closed_loop: trial_params['source'] must lie in [0, {n_in}) next to occluders")
+    if x0 is not None:
+        x0 = torch.as_tensor(x0, dtype=torch.float64, device=dev).reshape(n_in, -1).index_select(0, index)
+    return (q_start.index_select(0, index).contiguous(), None if noise is None else noise.index_select(1, index).contiguous(), x0,
+            {key: value for key, value in trial_params.items() if key != 'source'})
+
+
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
-                       believed_index=None, trial_params=None):
+                       believed_index=None, trial_params=None, occluders=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -755,11 +849,28 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     T trials.  A host-side 'source' outside [0, n_in) is a ValueError; one on the device makes its trial FAIL with k_done = 0, alone.  A
     trial's results are bit-identical to those of the uniform fused call with its values; ``{}`` is that call through the per-trial
     kernel, None (the default) the uniform call itself.  It needs fused=True (the two-launch step has no per-trial flavour) and an
-    estimator (not ANALYTICAL), and excludes ``believed``: each a ValueError before any device work."""
+    estimator (not ANALYTICAL), and excludes ``believed``: each a ValueError before any device work.
+    ``occluders``: rectangles that slide in front of the discs while the loop runs, per OUTPUT trial -- what ``occluders()`` takes or returns:
+    (T, n_occ, 8) or (n_occ, 8) integer rows (x, y, w, h, vx, vy, k_on, k_off), n_occ <= 4 (the rule: include/uvs_vision.h, uvs_occluder;
+    ``plant.render_discs`` states it).  The detection of step k is that of the frame with the occluders at step k; f0, the first f_old, and
+    with it the initial guess, come from the step-0 frame, occluders at k = 0 included.  fused=False passes k to
+    uvs_camera_features_occluded_f64 at every step, for the estimators and for the calibrated and believed baselines alike; fused=True with an
+    estimator is ONE launch, uvs_camera_closed_loop_occluded_f64, with or without ``trial_params``, and returns the stepwise loop's bits.
+    fused=True with ANALYTICAL and occluders is a ValueError -- use fused=False: the baseline's one-launch loop has no occluders.  A disc
+    that is covered completely has an empty mask: NaN features and FAIL at that step, like a disc that leaves the frame.  Next to
+    trial_params['source'] the inputs are gathered by source before the launch (an out-of-range index is then a ValueError, also on the
+    device), because the step-0 frame belongs to the output trial."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
     analytical = fp.method == _lib.METHOD_ANALYTICAL
+    if occluders is not None:
+        if analytical and fused:
+            raise ValueError('camera_closed_loop: the calibrated baseline has no one-launch loop with occluders: use fused=False')
+        n_out = q_start.shape[0]
+        if isinstance(trial_params, dict) and trial_params.get('source') is not None:
+            n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
+        occluders = _check_occluders(occluders, n_out, who='camera_closed_loop: occluders')
     if trial_params is not None:
         if not fused:
             raise ValueError('camera_closed_loop: trial_params needs fused=True: the two-launch step kernel has no per-trial flavour')
@@ -788,6 +899,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     if fused and not getattr(q_start, 'is_cuda', False):
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     torch = _torch()
+    if occluders is not None and trial_params is not None and trial_params.get('source') is not None:
+        q_start, noise, x0, trial_params = _gather_by_source(q_start, noise, x0, trial_params)
     K, m, n = fp.steps, fp.m, fp.n
     T, dev = q_start.shape[0], q_start.device
     if K < 1 or T < 1:
@@ -798,20 +911,22 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
+        occ = None if occluders is None else _occluder_operand(occluders, dev)
         if believed is None:
-            return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want)
+            return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, occ=occ)
         *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
-        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand))
+        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ)
     if believed is not None:                                         # an estimator that starts from the wrong model; the rest is the x0= path
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        x0 = camera_guess(cam, q_start, camera_features(cam, q_start), radius=radius, believed=believed, believed_index=believed_index)
+        x0 = camera_guess(cam, q_start, camera_features(cam, q_start, occluders=occluders), radius=radius, believed=believed,
+                          believed_index=believed_index)
     if fused and (x0 is not None or guess == 'device' or not fp.initial_guess):
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -822,8 +937,9 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     noise_ptr = _operand(noise, 'noise', torch.float64, (K, T, m), True)
     f64 = dict(dtype=torch.float64, device=dev)
     f0 = torch.zeros((T, m), **f64)
+    occ = None if occluders is None else _occluder_operand(occluders, dev)
     if fp.initial_guess:
-        camera_features(cam, q_start, out=f0)
+        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2])     # the step-0 frame, occluders at k = 0 included
         if x0 is None and guess == 'device':
             x0 = camera_guess(cam, q_start, f0)
         if x0 is None:
@@ -837,21 +953,21 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         raise ValueError('camera_closed_loop: x0 is needed when fp.initial_guess is 0 (the reference draws it unseeded, experiment.py:117)')
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2])
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
     dq_zero = torch.zeros((T, n), **f64)
-    features, step = _vision.lib().uvs_camera_features_f64, _lib.lib().uvs_rmckf_step_f64
+    step = _lib.lib().uvs_rmckf_step_f64
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
+    features = _features_step(cam_ref, T, fp.dt, occ, stream)
     row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
     at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
     noise_row = 0 if noise is None else noise.stride(0) * 8
     for k in range(K):
         q_prev, dq_prev, f_old = (q0, None, f0.data_ptr()) if k == 0 else (at('q', k - 1), at('dq', k - 1), at('f', k - 1))
-        _vision.check(features(cam_ref, T, q_prev, dq_prev, fp.dt, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k),
-                               at('pixels', k), None, stream))
+        _vision.check(features(k, q_prev, dq_prev, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k), at('pixels', k)))
         _lib.check(step(fp_ref, T, X.data_ptr(), P.data_ptr(), at('f', k), f_old, dq_zero.data_ptr() if k == 0 else dq_prev, int(k == 0), k,
                         at('dq', k), at('err', k), at('kappa', k), at('status', k), stream))
     return _reduce_camera_logs(fp, log, status_log, pixel_log, want)

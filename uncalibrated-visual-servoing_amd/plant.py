@@ -37,28 +37,88 @@ def camera_pose(T):
     return pose
 
 
-def render_discs(discs, n_colours=4, background=96):
+MAX_OCCLUDERS = 4                       # UVS_CAMERA_MAX_OCCLUDERS
+OCCLUDER_FIELDS = ('x', 'y', 'w', 'h', 'vx', 'vy', 'k_on', 'k_off')         # uvs_occluder of include/uvs_vision.h: eight int32
+NO_RECT = (1, 0, 1, 0)                  # a rectangle that covers nothing: x0 > x1
+
+
+def occluder_array(occluders, T=None):
+    """``occluders`` as an int64 host array (T, n_occ, 8) of ``OCCLUDER_FIELDS`` rows whose values are int32: from (n_occ, 8) -- every trial
+    the same -- or (T, n_occ, 8) integers.  ValueError for anything else, more than ``MAX_OCCLUDERS`` rows, or a T that does not match."""
+    try:
+        a = np.asarray(occluders)
+    except Exception as exc:                                         # ragged lists
+        raise ValueError(f'occluders: (n_occ, 8) or (T, n_occ, 8) integers, rows of {OCCLUDER_FIELDS}') from exc
+    if a.size == 0 and a.ndim in (1, 2) and a.shape[-1] in (0, 8):   # [] and np.empty((0, 8)): no occluder
+        a = np.zeros((0, 8), np.int64)
+    if a.dtype.kind not in 'iu' or a.ndim not in (2, 3) or a.shape[-1] != 8:
+        raise ValueError(f'occluders: (n_occ, 8) or (T, n_occ, 8) integers, rows of {OCCLUDER_FIELDS}, got {a.dtype} {a.shape}')
+    if a.shape[-2] > MAX_OCCLUDERS:
+        raise ValueError(f'occluders: at most {MAX_OCCLUDERS} per trial, got {a.shape[-2]}')
+    if a.size and (a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1):
+        raise ValueError('occluders: every field is an int32')
+    a = a.astype(np.int64)
+    if a.ndim == 2:
+        a = np.broadcast_to(a, (1 if T is None else T,) + a.shape)
+    elif T is not None and a.shape[0] != T:
+        raise ValueError(f'occluders: {a.shape[0]} trials of occluders for {T} trials')
+    return np.ascontiguousarray(a)
+
+
+def occluder_rects(occluders, k):
+    """The rule of uvs_occluder (include/uvs_vision.h) in Python-int arithmetic: for (n_occ, 8) rows of ``OCCLUDER_FIELDS`` the list of the
+    clipped inclusive rectangles (x0, x1, y0, y1) at step ``k`` -- columns and FLIPPED rows.  An occluder is active iff k_on <= k < k_off,
+    w > 0 and h > 0, and then covers columns [x + vx k, x + vx k + w - 1] and flipped rows [y + vy k, y + vy k + h - 1], clipped to the
+    frame.  One that covers nothing is returned as ``NO_RECT``: x0 > x1."""
+    k = int(k)
+    if k < 0:
+        raise ValueError('k must be >= 0')
+    out = []
+    for row in np.asarray(occluders).reshape(-1, 8).tolist():
+        x, y, w, h, vx, vy, k_on, k_off = (int(v) for v in row)
+        rect = NO_RECT
+        if k_on <= k < k_off and w > 0 and h > 0:
+            xk, yk = x + vx * k, y + vy * k
+            x0, x1, y0, y1 = max(xk, 0), min(xk + w - 1, RESOLUTION - 1), max(yk, 0), min(yk + h - 1, RESOLUTION - 1)
+            if x0 <= x1 and y0 <= y1:
+                rect = (x0, x1, y0, y1)
+        out.append(rect)
+    return out
+
+
+def render_discs(discs, n_colours=4, background=96, occluders=None, k=0, shade=32):
     """Camera frames of coloured discs: the numpy statement of the pixel rule uvs_render_discs_u8 (include/uvs_vision.h) is held to.
     ``discs``: (n_colours, 3) or (T, n_colours, 3) rows (u, v, r) in pixels of the flipped frame (u right, v down), colour order red,
     green, blue, pink (n_colours == 1: the green disc).  Pixel (flipped row i, column j) belongs to disc c iff r_c >= 0 and
     fl(fl(dx * dx) + fl(dy * dy)) <= fl(r_c * r_c) with dx = j - u_c, dy = i - v_c; a NaN gives nothing; a later disc overwrites an earlier
-    one; everything else is ``background``.  A disc is drawn as a circle (no perspective-correct ellipse).  Returns uint8 (256, 256, 3) or
-    (T, 256, 256, 3), UNFLIPPED as the sensor hands frames over (flipped row i is row 255 - i)."""
+    one; everything else is ``background``.  A disc is drawn as a circle (no perspective-correct ellipse).
+    ``occluders``: None, or (n_occ, 8) / (T, n_occ, 8) integer rows of ``OCCLUDER_FIELDS`` -- rectangles in front of the discs at step ``k``
+    (``occluder_rects``): a covered pixel belongs to no disc and is ``shade`` (0 .. 249) in all three channels; the covered set is the union.
+    This function is the statement of that rule too (uvs_render_discs_occluded_u8 and the occluded detectors are held to it).
+    Returns uint8 (256, 256, 3) or (T, 256, 256, 3), UNFLIPPED as the sensor hands frames over (flipped row i is row 255 - i)."""
     discs = np.asarray(discs, float)
     if n_colours not in (1, 3, 4) or discs.shape[-2:] != (n_colours, 3) or discs.ndim not in (2, 3):
         raise ValueError(f'discs: (n_colours, 3) or (T, n_colours, 3) with n_colours in (1, 3, 4), got {discs.shape} for n_colours = {n_colours}')
     if not 0 <= background < 250:
         raise ValueError('background must be 0 .. 249: 250 and above would enter a mask of the detectors')
     batch = discs.reshape((-1,) + discs.shape[-2:])
+    if occluders is not None:
+        if not 0 <= shade < 250:
+            raise ValueError('shade must be 0 .. 249: 250 and above would enter a mask of the detectors')
+        occluders = occluder_array(occluders, len(batch))
+        rects = [occluder_rects(rows, k) for rows in occluders]     # refuses k < 0
     grid = np.arange(RESOLUTION, dtype=float)
     frames = np.full((len(batch), RESOLUTION, RESOLUTION, 3), background, np.uint8)
     with np.errstate(invalid='ignore', over='ignore'):
-        for frame, scene in zip(frames, batch):
+        for t, (frame, scene) in enumerate(zip(frames, batch)):
             for c, (u, v, r) in enumerate(scene):
                 if not r >= 0:
                     continue
                 dx, dy = grid[None, :] - u, grid[:, None] - v
                 frame[(dx * dx + dy * dy) <= r * r] = DISC_COLOURS[1 if n_colours == 1 else c]
+            if occluders is not None:
+                for x0, x1, y0, y1 in rects[t]:                      # NO_RECT: an empty slice
+                    frame[y0:y1 + 1, x0:x1 + 1] = shade
     frames = frames[:, ::-1].copy()
     return frames[0] if discs.ndim == 2 else frames
 
@@ -357,19 +417,35 @@ class CameraRobot:
     projected centres and radii -- so that ``Experiment`` detects its features from pixels, on the host or (perception='device') on the GPU.
     Deliberately NOT a ``SyntheticRobot``: ``Experiment.run()`` sends those down the plant-in-kernel route, and this robot has to take the
     external-robot route.  ``radius``: physical disc radius in metres; the default 0.024 m measures 8.01 px at ``SyntheticPlant.ur10()``'s
-    goal pose (depth 0.602 m, focal 200.9 px).  A disc is drawn as a circle, not as the ellipse a tilted camera would see."""
+    goal pose (depth 0.602 m, focal 200.9 px).  A disc is drawn as a circle, not as the ellipse a tilted camera would see.
+    ``occluders``: None, or (n_occ, 8) integer rows of ``OCCLUDER_FIELDS``, drawn in ``shade`` at the robot's step count ``k`` -- 0 from
+    ``start()`` on, one more with every ``step()`` after it, so that the loop's guess image and its first image are both the step-0 frame,
+    as in ``engine.camera_closed_loop(occluders=...)``."""
 
-    def __init__(self, plant=None, radius=DISC_RADIUS, dt=0.05, background=96):
+    def __init__(self, plant=None, radius=DISC_RADIUS, dt=0.05, background=96, occluders=None, shade=32):
         self._robot = SyntheticRobot(plant, dt)
-        self.radius, self.background = radius, background
+        self.radius, self.background, self.shade = radius, background, shade
+        self.occluders = None if occluders is None else occluder_array(occluders, 1)[0]
+        if not 0 <= shade < 250:
+            raise ValueError('shade must be 0 .. 249: 250 and above would enter a mask of the detectors')
+        self.k = 0
 
     def __getattr__(self, name):                                    # everything but the camera: the synthetic robot's
         if name == '_robot':
             raise AttributeError(name)
         return getattr(self._robot, name)
 
+    def start(self, q=None):
+        self._robot.start(q)
+        self.k = 0
+
+    def step(self):
+        self._robot.step()
+        self.k += 1
+
     def discs(self):
         return self._robot.plant.discs(self._robot.q, self.radius)
 
     def getCameraImage(self):
-        return render_discs(self.discs(), self._robot.plant.n_points, self.background), (RESOLUTION, RESOLUTION)
+        frame = render_discs(self.discs(), self._robot.plant.n_points, self.background, self.occluders, self.k, self.shade)
+        return frame, (RESOLUTION, RESOLUTION)
