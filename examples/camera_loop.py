@@ -18,8 +18,13 @@ uploaded once, not once per cell).  Prints the median ISE / IAE / ITAE per cell 
 --occlusion asks who survives a real outlier: a 12 px bar of full height crosses the frame at constant speed while the servo runs
 (engine.camera_closed_loop(occluders=...)); a disc behind it loses a side of its mask and its centroid jumps.  GMCKF, KF and the calibrated law
 (stepwise) on the same starts and noise; prints the median ISE / IAE / ITAE and the FAIL count without and with the bar.
+--occlusion --hold N asks the question the narrow bar could not: who survives a FULL occlusion?  The bar is 28 px wide -- a disc is about 17 px
+across at the goal -- and crosses the discs during the transient, so every mask is empty for a few steps.  Without a hold every trial FAILs
+there; with engine.camera_closed_loop(hold=N) a lost disc's last detection is reported again for up to N steps (df = 0 while dq != 0, then a
+jump: the outlier the correntropy estimators exist for).  KF, MCKF, IMCC-KF, GMCKF (one launch each) and the calibrated law (stepwise) on the
+same starts and noise; prints the FAIL count at hold = 0 beside the median ISE / IAE / ITAE, the FAIL count and the held steps at hold = N.
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid] [--occlusion]"""
+       [--grid] [--occlusion [--hold N]]"""
 import argparse
 import os
 import sys
@@ -145,6 +150,41 @@ def occlusion_table(uvs, trials=64, sigma=0.3, radius=None, seed=0, bar=BAR):
     return lines
 
 
+WIDE_BAR = (20, 0, 28, 256, 2, 0, 0, 2 ** 31 - 1)                     # a 28 px bar of full height, 2 px per step: over the discs in steps 20 .. 70
+
+
+def hold_table(uvs, hold, trials=64, sigma=0.3, radius=None, seed=0, bar=WIDE_BAR):
+    """The full-occlusion table as a list of lines: the four estimators (one launch each) and the calibrated law (stepwise) behind a bar wider
+    than a disc, on the same starts and noise, with hold = 0 and with hold = ``hold``."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    methods = ('KF', 'MCKF', 'IMCCKF', 'GMCKF', 'ANALYTICAL')
+    fps = {method: uvs.engine.make_params(8, 6, method, 10.0, False, 0.05, 15.0, 0.2, desired, True) for method in methods}
+    K = fps['GMCKF'].steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    q0_d = torch.as_tensor(q0, device='cuda')
+    noise_d = torch.as_tensor(rng.standard_normal((K, trials, 8)) * sigma, device='cuda')
+    occluders = uvs.engine.occluders([bar], trials)
+    lines = [f'a {bar[2]} px bar of full height crossing the frame at {bar[4]} px per step from column {bar[0]}, {trials} trials of {K} steps, '
+             f'white noise {sigma} px; median over the trials that ran to the end',
+             f'{"":28s}{"hold = 0":>10s}   {"hold = " + str(hold):^36s}{"FAIL":>6s}{"held":>8s}{"most":>9s}',
+             f'{"":28s}{"FAIL":>10s}   {"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"":6s}{"steps":>8s}{"per disc":>9s}']
+    for method, fp in fps.items():
+        kw = dict(radius=radius, want=()) if method == 'ANALYTICAL' else dict(radius=radius, fused=True, guess='device', want=())
+        unheld = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, occluders=occluders, **kw)
+        out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, occluders=occluders, hold=hold, **kw)
+        torch.cuda.synchronize()
+        done = (out['status'] == 0).cpu().numpy()
+        med = np.median(out['stats'].cpu().numpy()[done], axis=0) if done.any() else np.full(3, np.nan)
+        held = out['held'].cpu().numpy()
+        lines.append(f'{method + (" (stepwise)" if method == "ANALYTICAL" else ""):28s}{int((unheld["status"] != 0).sum()):>10d}   '
+                     f'{med[0]:12.3f}{med[1]:12.3f}{med[2]:12.3f}{int((~done).sum()):>6d}{int(held.sum()):>8d}{int(held.max()):>9d}')
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -157,9 +197,16 @@ def main():
     ap.add_argument('--miscalibration', action='store_true', help='a ladder of wrong models x trials in one launch per side, and nothing else')
     ap.add_argument('--grid', action='store_true', help='kernel_bw x gain over the same starts and noise in one launch, and nothing else')
     ap.add_argument('--occlusion', action='store_true', help='a bar crosses the frame while the servo runs: GMCKF, KF and the calibrated law, and nothing else')
+    ap.add_argument('--hold', type=int, default=0, metavar='N',
+                    help='with --occlusion: a bar wider than a disc, and a lost disc keeps its last detection for up to N steps (0: the narrow bar)')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
+    if args.hold and not args.occlusion:
+        ap.error('--hold goes with --occlusion')
+    if args.occlusion and args.hold:
+        print('\n'.join(hold_table(uvs, args.hold, args.trials, args.sigma, args.radius, args.seed)))
+        return
     if args.occlusion:
         print('\n'.join(occlusion_table(uvs, args.trials, args.sigma, args.radius, args.seed)))
         return

@@ -269,7 +269,7 @@ int uvs_camera_closed_loop_grid_f64(const struct uvs_filter_params *fp, const uv
  * A trial without an active occluder near its discs has the bits of uvs_camera_closed_loop_grid_f64; a padding or void trial evaluates
  * the rectangles of the trial it shadows and stores nothing.  FULL OCCLUSION: an occluder that covers a disc completely gives an empty
  * mask, a NaN pair, a non-finite X and FAIL at that step -- the loop's behaviour for a disc that leaves the frame, and the documented
- * meaning of full occlusion; the last feature is not held.
+ * meaning of full occlusion; the last feature is not held here (uvs_camera_closed_loop_held_f64 below holds it).
  * Built: what uvs_camera_closed_loop_grid_f64 builds (MCKF at (6, 6) is refused with UVS_ERR_METHOD), each in both workgroup forms with
  * 0 B of scratch memory.
  * Errors, all before the first HIP call: those of uvs_camera_closed_loop_grid_f64, in its order, except that a NULL tp is allowed; then
@@ -280,6 +280,47 @@ int uvs_camera_closed_loop_occluded_f64(const struct uvs_filter_params *fp, cons
                                         const double *noise, const double *x0, const double *f0, double *q_log, double *f_log,
                                         double *dq_log, double *err_log, double *kappa_log, int32_t *status, int32_t *k_done,
                                         double *stats, int32_t *pixels, void *stream);
+
+/*
+ * The same loop HOLDING a lost disc's last detection, as a servo loop reuses the last detection when its detector returns nothing for a
+ * few frames.  The rule (plant.hold_features states it in numpy; every kernel is held to it bit for bit):
+ *   hold >= 0, one for the launch: the largest number of consecutive steps for which a disc's pair may be held.
+ *   Disc j of a trial is LOST at step k iff its mask count at step k is 0 -- covered completely, out of the frame, behind the camera or a
+ *     NaN projection alike: the integer count decides, never the floating-point pair.  Each trial keeps a counter miss[j], 0 at the start.
+ *   detected: miss[j] = 0 and the pair is the detector's, noise included.
+ *   lost, k >= 1 and miss[j] < hold: the reported pair of step k is the reported pair of step k - 1 -- row k - 1 of the f log, with that
+ *     step's noise in it and no noise of step k added; miss[j] += 1; the disc counts as HELD at step k.
+ *   lost otherwise (step 0, where f0 is the same empty frame, or a hold that is used up): the NaN pair, which FAILs the trial at this step.
+ * A held pair is an ordinary input to the estimator: z = f_k - f_{k-1} is exactly +0.0 in its two rows, err repeats, the statistics sum it.
+ *   The twenty operands of uvs_camera_closed_loop_occluded_f64, in its order, with two more: hold after n_occ, held after pixels.
+ *   held [T][n_points] out or NULL: the number of steps k <= k_done (and k < K) at which the disc was held -- the steps pixels looks at;
+ *     pixels is the smallest mask seen, as before, so a trial that SUCCEEDs after a hold shows 0 there.
+ * occ = NULL with n_occ = 0 and hold > 0 is legal: a disc that leaves the frame is held too.  hold = 0 gives the bits of
+ * uvs_camera_closed_loop_occluded_f64 (and held = 0 everywhere).  A padding or void trial stores nothing, held included.
+ * Built: what uvs_camera_closed_loop_occluded_f64 builds (MCKF at (6, 6) is refused with UVS_ERR_METHOD), each in both workgroup forms
+ * with 0 B of scratch memory.
+ * Errors, all before the first HIP call: those of uvs_camera_closed_loop_occluded_f64, in its order; then UVS_ERR_ARG for hold < 0.
+ * T == 0 returns UVS_OK and launches nothing.
+ */
+int uvs_camera_closed_loop_held_f64(const struct uvs_filter_params *fp, const uvs_camera *cam, int64_t T,
+                                    const uvs_camera_trial_params *tp, const uvs_occluder *occ, int32_t n_occ, int32_t hold,
+                                    const double *q_start, const double *noise, const double *x0, const double *f0, double *q_log,
+                                    double *f_log, double *dq_log, double *err_log, double *kappa_log, int32_t *status, int32_t *k_done,
+                                    double *stats, int32_t *pixels, int32_t *held, void *stream);
+
+/*
+ * The rule above for the stepwise loops: one small launch, one thread per (trial, disc), applied to the row that
+ * uvs_camera_features_f64 or uvs_camera_features_occluded_f64 has just written on the same stream.
+ *   k: the step; f_prev_row [T][2*n_points] in: the reported row of step k - 1 (read only where a pair is held; may be NULL at k == 0).
+ *   f_row [T][2*n_points] in, out: the detector's row of step k; a held pair is overwritten with f_prev_row's, nothing else is written.
+ *   pixels_row [T][n_points] in: the mask counts of step k.
+ *   miss [T][4] in, out: the loop's counters of consecutive held steps, zero before step 0 (disc j of trial t at 4 t + j).
+ *   held_row [T][n_points] out or NULL: 1 where the disc was held at this step, else 0.
+ * hold == 0 holds nothing (and still resets miss).  Errors, before the HIP call: UVS_ERR_ARG for a NULL f_row, pixels_row or miss, T < 0,
+ * n_points not in {1, 3, 4}, hold < 0, k < 0, or a NULL f_prev_row with k >= 1.  T == 0 returns UVS_OK and launches nothing.
+ */
+int uvs_hold_features_f64(int64_t T, int32_t n_points, int32_t hold, int32_t k, const double *f_prev_row, double *f_row,
+                          const int32_t *pixels_row, int32_t *miss, int32_t *held_row, void *stream);
 
 /*
  * The analytic initial guess X0 of the loop (experiment.py:94-114) for T trials, one lane each: the geometric Jacobian of the DH chain in the

@@ -50,7 +50,18 @@ steps, white noise 0.3 px, x0 handed in, medians of 20 with p10-p90;
       The acceptance condition is (n) below (o); (e) new against (e) parent is reported next to the parent's own spread; (m) / (e) and
       (n) / (m) are reported, not gated.  (m) is checked against (e) and (n) against (o), bit for bit, before anything is timed.  Then the
       table of examples/camera_loop.py --occlusion.
-usage: tools/time_camera.py --occluded [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --occluded [--parent-lib=PATH] [out.txt]
+With --held only the pixel loop that holds a lost disc's last detection is timed, into profiles/camera_hold.txt (or the path given): GMCKF,
+1 024 trials x 299 steps, white noise 0.3 px, x0 handed in, medians of 20 with p10-p90;
+  (n) the 12 px bar of --occluded through camera_occluded_kernel -- with this library and, given --parent-lib=PATH, with the parent's in
+      turn: the existing kernel was not to move (the gate is its resource figures; the time is the evidence);
+  (p) (n)'s trials through camera_held_kernel with hold = 0: what the kernel flavour costs;
+  (q) the wide bar of examples/camera_loop.py --occlusion --hold on every trial with hold = 30, one launch;
+  (r) (q) stepwise: K x (occluded camera features, hold, estimator step), three launches a step.
+      The acceptance condition is (q) below (r); (n) new against (n) parent is reported next to the parent's own spread; (p) / (n) and
+      (q) / (n) are reported, not gated.  (n) is checked against the parent's (n), (p) against (n) and (q) against (r), bit for bit,
+      before anything is timed.  Then the table of examples/camera_loop.py --occlusion --hold 30.
+usage: tools/time_camera.py --held [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -63,10 +74,10 @@ import uvs_amd as uvs  # noqa: E402
 import torch  # noqa: E402
 
 ANALYTICAL, BELIEVED, GRID = '--analytical' in sys.argv[1:], '--believed' in sys.argv[1:], '--grid' in sys.argv[1:]
-OCCLUDED = '--occluded' in sys.argv[1:]
+OCCLUDED, HELD = '--occluded' in sys.argv[1:], '--held' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -445,6 +456,114 @@ def occluded_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def held_section():
+    """(n), (p), (q), (r): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T, HOLD = 299, 1024, 30
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    assert fp.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --held on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in; rows of (x, y, w, h, vx, vy, k_on, k_off): the 12 px bar '
+        f'{example.BAR}, the wide bar {example.WIDE_BAR}; hold = {HOLD}')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+    x0 = uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+    bar, wide = uvs.engine.occluders([example.BAR], T), uvs.engine.occluders([example.WIDE_BAR], T)
+    held_entry = uvs._vision.lib().uvs_camera_closed_loop_held_f64
+
+    def run_p():
+        """(n)'s call through the held entry point with hold = 0 (engine.camera_closed_loop(hold=0) takes the occluded route), with (n)'s allocations."""
+        cam = plant.to_camera(uvs.plant.DISC_RADIUS)
+        f64 = dict(dtype=torch.float64, device='cuda')
+        f0 = torch.zeros((T, 8), **f64)
+        uvs.engine.camera_features(cam, q_d, out=f0, occluders=bar)
+        log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('q', 6), ('f', 8), ('dq', 6), ('err', 8), ('kappa', 8))}
+        status, k_done = (torch.empty(T, dtype=torch.int32, device='cuda') for _ in range(2))
+        stats_t, pixels, held = torch.empty((T, 3), **f64), *(torch.empty((T, 4), dtype=torch.int32, device='cuda') for _ in range(2))
+        uvs._vision.check(held_entry(ctypes.byref(fp), ctypes.byref(cam), T, None, bar.data_ptr(), bar.shape[1], 0, q_d.data_ptr(), noise.data_ptr(),
+                                     x0.data_ptr(), f0.data_ptr(), log['q'].data_ptr(), log['f'].data_ptr(), log['dq'].data_ptr(),
+                                     log['err'].data_ptr(), log['kappa'].data_ptr(), status.data_ptr(), k_done.data_ptr(), stats_t.data_ptr(),
+                                     pixels.data_ptr(), held.data_ptr(), uvs.engine._stream()))
+        return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats_t, held=held)
+
+    fns = {'n': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=bar),
+           'p': run_p,
+           'q': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=wide, hold=HOLD),
+           'r': lambda: loop(fp, plant, q_d, noise, x0=x0, occluders=wide, hold=HOLD)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+
+    def same(a, b):
+        done = a['k_done']
+        ok = all(torch.equal(a[key], b[key]) for key in ('status', 'k_done', 'pixels')) and torch.equal(a['stats'].view(torch.int64), b['stats'].view(torch.int64))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):                 # the specified rows: q, f up to and including k_done, the others before it
+            spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+            ok = ok and torch.equal(a[key].view(torch.int64)[spec], b[key].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['p'], first['n']) and int(first['p']['held'].sum()) == 0, 'the held kernel with hold = 0 and the occluded kernel disagree'
+    assert same(first['q'], first['r']) and torch.equal(first['q']['held'], first['r']['held']), 'the one launch and the stepwise loop disagree'
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_held_f64'), 'the parent library holds nothing'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def run_n_parent():
+            mine, uvs._vision._lib = uvs._vision._lib, parent
+            try:
+                return fns['n']()
+            finally:
+                uvs._vision._lib = mine
+
+        old = run_n_parent()
+        torch.cuda.synchronize()
+        assert same(first['n'], old), 'this library and the parent disagree on the occluded launch'
+        fns['n_parent'] = run_n_parent
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    spread = lambda v: (np.percentile(v, 90) - np.percentile(v, 10)) / np.median(v)   # noqa: E731
+    failed = lambda out: int((out['k_done'] < K).sum())              # noqa: E731
+    say()
+    say(f'  (n) the 12 px bar, camera_occluded_kernel, this library           {fmt_ms(ms["n"])}   = {med["n"] / K * 1e3:.1f} us per step')
+    if 'n_parent' in ms:
+        say(f'  (n) the same with the parent\'s library                           {fmt_ms(ms["n_parent"])}')
+        say(f'  (n) new / (n) parent = {med["n"] / med["n_parent"]:.4f}; the parent\'s own p10-p90 spread is {spread(ms["n_parent"]) * 100:.2f} % of its median, '
+            f'this library\'s {spread(ms["n"]) * 100:.2f} %; the outputs of the two are bit-identical')
+    say(f'  (p) (n)\'s trials through camera_held_kernel, hold = 0             {fmt_ms(ms["p"])}')
+    say(f'  (q) the wide bar, hold = {HOLD}, one launch                           {fmt_ms(ms["q"])}   = {med["q"] / K * 1e3:.1f} us per step')
+    say(f'  (r) (q) stepwise: K x (occluded features, hold, estimator step)   {fmt_ms(ms["r"])}   = {med["r"] / K * 1e3:.1f} us per step')
+    say(f'  (q) / (r) = {med["q"] / med["r"]:.4f}: (q) is {"BELOW" if med["q"] < med["r"] else "NOT below"} (r); specified log rows, stats, status, k_done, '
+        'pixels, held bit-identical')
+    say(f'  (p) / (n) = {med["p"] / med["n"]:.4f}, (q) / (n) = {med["q"] / med["n"]:.4f} (reported, not gated); (p) has the bits of (n)')
+    say(f'  trials that FAILed: (n) {failed(first["n"])}, (q) {failed(first["q"])}; held steps in (q): {int(first["q"]["held"].sum())} over {T} trials, '
+        f'at most {int(first["q"]["held"].max())} per disc; the wide bar without a hold FAILs '
+        f'{failed(loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=wide, want=()))}')
+    say()
+    say(f'acceptance: (q) below (r): {"yes" if med["q"] < med["r"] else "NO"}')
+    say()
+    say(f'# examples/camera_loop.py --occlusion --hold {HOLD} (its defaults)')
+    for line in example.hold_table(uvs, HOLD):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if HELD:
+    held_section()
+    sys.exit(0)
 if OCCLUDED:
     occluded_section()
     sys.exit(0)

@@ -61,6 +61,10 @@ SYMBOLS = {
     'uvs_camera_closed_loop_grid_f64': (C.c_int, [_VP, _CAM, _I64, _VP] + [_VP] * 14),
     # the same with tp (or None), occ and n_occ after T
     'uvs_camera_closed_loop_occluded_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _I32] + [_VP] * 14),
+    # the same with hold after n_occ and held (or None) after pixels
+    'uvs_camera_closed_loop_held_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
+    # T, n_points, hold, k, f_prev_row, f_row, pixels_row, miss, held_row, stream
+    'uvs_hold_features_f64': (C.c_int, [_I64, _I32, _I32, _I32] + [_VP] * 6),
     'uvs_camera_guess_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _VP, _VP]),
     # fp, cam, T, q, f, dq_out, err_out, j_out, status, stream
     'uvs_camera_analytical_step_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 7),
@@ -82,7 +86,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 6)), '-C', CSRC], check=True)         # six translation units, one rule each
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 7)), '-C', CSRC], check=True)         # seven translation units, one rule each
     return LIB_PATH
 
 

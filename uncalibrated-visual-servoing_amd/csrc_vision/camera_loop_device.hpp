@@ -37,6 +37,13 @@
 // trial for step k (occluder_rect; lanes from n_occ on write "covers nothing") into s_occ[w] next to the projection, before the second barrier;
 // the detection loop reads the four dwords from there and hands them to disc_counts_in_box<true>, which takes the unoccluded walk for every
 // disc no rectangle meets.  A padding or void trial evaluates the rectangles of the trial it shadows.  Barriers and exits are where they were.
+//
+// HOLD.  A fourth flavour: a unit that defines UVS_CAMERA_HELD next to the other two switches (uvs_camera_held.hip) sees
+// camera_held_kernel(HeldLoopArgs) with all three on.  A disc whose mask is empty at step k >= 1 keeps the pair reported at step k - 1 for up
+// to `hold` steps in a row (plant.hold_features states the rule).  That pair is still in s_f[ws][2 j] when lane 0 of the sensor-side wavefront
+// is about to write disc j -- the estimator read it before the last barrier and nothing wrote it since -- so holding is "leave it there and
+// log it".  The counters of consecutive misses and of held steps sit in LDS next to s_pix, written by that lane alone (G = 1: wavefront j owns
+// colour j).  Barriers and exits are where they were; padding and void trials store nothing, `held` included.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -75,6 +82,20 @@ struct OccludedLoopArgs : GridLoopArgs {
     int32_t n_occ;
 };
 
+// uvs_camera_closed_loop_held_f64: the occluded block, the longest hold and the held-step counts; only camera_held_kernel takes it
+struct HeldLoopArgs : OccludedLoopArgs {
+    int32_t hold;
+    int32_t *held;                                               // [T][n_points] or NULL
+};
+
+#ifdef UVS_CAMERA_HELD
+#ifndef UVS_CAMERA_OCCLUDED
+#error "the held flavour is an occluded flavour: define UVS_CAMERA_OCCLUDED (and UVS_CAMERA_PER_TRIAL) too"
+#endif
+constexpr bool kCameraHeld = true;
+#else
+constexpr bool kCameraHeld = false;
+#endif
 #ifdef UVS_CAMERA_OCCLUDED
 #ifndef UVS_CAMERA_PER_TRIAL
 #error "the occluded flavour is a per-trial flavour: define UVS_CAMERA_PER_TRIAL too"
@@ -83,7 +104,11 @@ constexpr bool kCameraOccluded = true;
 #else
 constexpr bool kCameraOccluded = false;
 #endif
-#if defined(UVS_CAMERA_OCCLUDED)
+#if defined(UVS_CAMERA_HELD)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = HeldLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL camera_held_kernel
+#elif defined(UVS_CAMERA_OCCLUDED)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = OccludedLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL camera_occluded_kernel
@@ -104,10 +129,13 @@ __device__ __forceinline__ const uvs_occluder *occluders_of(const OccludedLoopAr
     n_occ = a.n_occ;
     return a.occ + trial * a.n_occ;
 }
+// the longest hold and where the held-step counts go (never called on the other three blocks: HOLD is off there)
+__device__ __forceinline__ int hold_of(const LoopArgs &, int32_t *&held) { held = nullptr; return 0; }
+__device__ __forceinline__ int hold_of(const HeldLoopArgs &a, int32_t *&held) { held = a.held; return a.hold; }
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
-    constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded;
+    constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -123,6 +151,8 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     __shared__ double s_park[PARK ? R * uvs::Sym<N>::NP : 1][PARK ? 64 : 1];
     __shared__ double s_tp[PTP ? G : 1][4];                      // PTP: the trial's kernel_bw, gain, reg, fpi_threshold
     __shared__ uint32_t s_occ[OCC ? W : 1][kOccluders];          // OCC: this step's rectangles of the wavefront's trial (occluder_rect's packing)
+    __shared__ int s_miss[HOLD ? G : 1][kColours];               // HOLD: steps in a row, up to this one, at which the disc's pair was held
+    __shared__ int s_held[HOLD ? G : 1][kColours];               // HOLD: steps at which it was held, while the trial's rows were due
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -163,6 +193,15 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     const double *noise_at = A.noise != nullptr ? A.noise + src * M : nullptr;
     bool seen = true;                                            // this trial has not FAILed before this step: its rows q[k], f[k] are due
     if (lane < kColours) s_pix[ws][lane] = INT_MAX;
+    int hold = 0;
+    int32_t *held_out = nullptr;
+    if constexpr (HOLD) {
+        hold = hold_of(A, held_out);
+        if (lane < kColours) {
+            s_miss[ws][lane] = 0;
+            s_held[ws][lane] = 0;
+        }
+    }
 
     // estimator side (wavefront 0): this lane's trial and rows
     const int slot = (lane / L) & (G - 1), sub = lane % L;
@@ -275,6 +314,16 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
                 if (noise_at != nullptr) {                       // f += noise (experiment.py:135)
                     u += noise_at[2 * j];
                     v += noise_at[2 * j + 1];
+                }
+                if constexpr (HOLD) {                            // the integer count decides, never the pair
+                    if (sum.count != 0) {
+                        s_miss[ws][j] = 0;
+                    } else if (k >= 1 && s_miss[ws][j] < hold) { // lost, and the hold is not used up: step k - 1's reported pair, no noise of step k
+                        u = s_f[ws][2 * j];
+                        v = s_f[ws][2 * j + 1];
+                        s_miss[ws][j] += 1;
+                        if (seen) s_held[ws][j] += 1;
+                    }                                            // lost otherwise: the NaN pair, which FAILs the trial at this step
                 }
                 s_f[ws][2 * j] = u;
                 s_f[ws][2 * j + 1] = v;
@@ -394,6 +443,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         A.stats[3 * trial + lane] = sqrt(acc);
     }
     if (lane < npts && valid && writer && A.pixels != nullptr) A.pixels[trial * npts + lane] = s_pix[ws][lane];
+    if constexpr (HOLD) {
+        if (lane < npts && valid && writer && held_out != nullptr) held_out[trial * npts + lane] = s_held[ws][lane];
+    }
 }
 
 // MCKF: the fixed-point iteration's working set next to three rows per lane spills at (6,6,2) (684 B of scratch per lane), so that one

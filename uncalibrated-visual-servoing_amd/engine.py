@@ -502,6 +502,39 @@ def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_o
     return out
 
 
+def _check_hold(hold, who='camera_closed_loop'):
+    """``hold`` as the other integers are checked, on the host alone: an int >= 0 (below 2^31)."""
+    if isinstance(hold, bool) or not isinstance(hold, (int, np.integer)) or not 0 <= hold < 2 ** 31:
+        raise ValueError(f'{who}: hold is a number of steps, an integer >= 0, got {hold!r}')
+    return int(hold)
+
+
+def hold_features(f, f_prev, pixels, miss, hold, k, held=None):
+    """Hold a lost disc's last detection, one step of T trials on the current stream (uvs_hold_features_f64; ``plant.hold_features`` states
+    the rule, and this is it bit for bit).  ``f`` (T, 2 n_points) fp64: the row ``camera_features(..., pixels=pixels, k=k)`` has just
+    written, rewritten IN PLACE where a pair is held; ``f_prev`` (T, 2 n_points): the reported row of step k - 1, or None at k == 0;
+    ``pixels`` (T, n_points) int32: the mask counts of step k; ``miss`` (T, 4) int32: the loop's counters, zeros before step 0, updated in
+    place (disc j of trial t at [t, j]); ``hold`` >= 0; ``held`` (T, n_points) int32 receives 1 where the disc was held at this step, else 0
+    (a new tensor when None).  Returns (f, miss, held)."""
+    from . import _vision
+    hold = _check_hold(hold, 'hold_features')
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 2 ** 31:
+        raise ValueError(f'hold_features: k is a step count, an integer >= 0, got {k!r}')
+    if f_prev is None and k >= 1:
+        raise ValueError('hold_features: f_prev, the reported row of step k - 1, is needed from step 1 on')
+    torch = _torch()
+    if not torch.is_tensor(f) or f.dim() != 2 or f.shape[1] % 2:
+        raise ValueError('hold_features: f is a torch fp64 tensor (T, 2 n_points)')
+    T, npts = f.shape[0], f.shape[1] // 2
+    if held is None:
+        held = torch.empty((T, npts), dtype=torch.int32, device=_device_of(f))
+    rc = _vision.lib().uvs_hold_features_f64(T, npts, hold, int(k), _operand(f_prev, 'f_prev', torch.float64, (T, 2 * npts), True),
+                                             _operand(f, 'f', torch.float64, (T, 2 * npts)), _operand(pixels, 'pixels', torch.int32, (T, npts)),
+                                             _operand(miss, 'miss', torch.int32, (T, 4)), _operand(held, 'held', torch.int32, (T, npts)), _stream())
+    _vision.check(rc)
+    return f, miss, held
+
+
 def believed_models(models, radius=None, device=None):
     """The believed-model operand of the calibrated baseline on a wrong model: ``models`` -- a ``SyntheticPlant``, a ``Camera`` struct, or a
     sequence of either (``plant.miscalibrated`` makes wrong plants) -- packed as the device array of ``uvs_camera`` structs that
@@ -637,22 +670,35 @@ CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
 ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
 
 
-def _features_step(cam_ref, T, dt, occ, stream):
+def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None):
     """The stepwise loops' sensor launch at step k: uvs_camera_features_f64, or its occluded namesake when ``occ`` -- None, or the
-    (pointer, n_occ, tensor) of ``_occluder_operand`` -- is given.  Returns f(k, q_prev, dq_prev, q, noise, f, pixels) -> return code."""
+    (pointer, n_occ, tensor) of ``_occluder_operand`` -- is given.  Returns f(k, q_prev, dq_prev, q, noise, f, pixels) -> return code.
+    With ``hold`` > 0 the step is that launch and uvs_hold_features_f64 behind it on the same stream, on the same rows: the callable then
+    takes two more row pointers, f(..., pixels, f_prev, held), and keeps the counters of consecutive held steps (T, 4) itself."""
     from . import _vision
     if occ is None:
         plain = _vision.lib().uvs_camera_features_f64
-        return lambda k, q_prev, dq_prev, q, noise, f, pixels: plain(cam_ref, T, q_prev, dq_prev, dt, q, noise, f, pixels, None, stream)
-    occluded = _vision.lib().uvs_camera_features_occluded_f64
-    return lambda k, q_prev, dq_prev, q, noise, f, pixels: occluded(cam_ref, T, q_prev, dq_prev, dt, q, occ[0], occ[1], k, noise, f, pixels,
-                                                                    None, stream)
+        detect = lambda k, q_prev, dq_prev, q, noise, f, pixels: plain(cam_ref, T, q_prev, dq_prev, dt, q, noise, f, pixels, None, stream)   # noqa: E731
+    else:
+        occluded = _vision.lib().uvs_camera_features_occluded_f64
+        detect = lambda k, q_prev, dq_prev, q, noise, f, pixels: occluded(cam_ref, T, q_prev, dq_prev, dt, q, occ[0], occ[1], k, noise, f,   # noqa: E731
+                                                                          pixels, None, stream)
+    if hold == 0:
+        return detect
+    miss = _torch().zeros((T, 4), dtype=_torch().int32, device=dev)
+    hold_row = _vision.lib().uvs_hold_features_f64
+
+    def held_step(k, q_prev, dq_prev, q, noise, f, pixels, f_prev, held):
+        rc = detect(k, q_prev, dq_prev, q, noise, f, pixels)
+        return rc if rc else hold_row(T, npts, hold, k, f_prev, f, pixels, miss.data_ptr(), held, stream)
+    return held_step
 
 
-def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None):
+def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
     ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models.
-    ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none)."""
+    ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none).  ``hold`` > 0 (stepwise alone): a third launch per
+    step, uvs_hold_features_f64, between the two."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -678,23 +724,29 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream)
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev)
+    held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     if believed is None:
         step = lambda *rows: _vision.lib().uvs_camera_analytical_step_f64(fp_ref, cam_ref, T, *rows)          # noqa: E731
     else:
         step = lambda *rows: _vision.lib().uvs_camera_believed_step_f64(fp_ref, T, *believed, *rows)          # noqa: E731
     row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
+    if hold:
+        row['held'] = (held_log.data_ptr(), held_log.stride(0) * held_log.element_size())
     at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
     noise_row = 0 if noise is None else noise.stride(0) * 8
     for k in range(K):
         q_prev, dq_prev = (q0, None) if k == 0 else (at('q', k - 1), at('dq', k - 1))
-        _vision.check(features(k, q_prev, dq_prev, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k), at('pixels', k)))
+        extra = (None if k == 0 else at('f', k - 1), at('held', k)) if hold else ()
+        _vision.check(features(k, q_prev, dq_prev, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k), at('pixels', k),
+                               *extra))
         _vision.check(step(at('q', k), at('f', k), at('dq', k), at('err', k), None, at('status', k), stream))
-    return _reduce_camera_logs(fp, log, status_log, pixel_log, want)
+    return _reduce_camera_logs(fp, log, status_log, pixel_log, want, held_log)
 
 
-def _reduce_camera_logs(fp, log, status_log, pixel_log, want):
-    """k_done, status, pixels and stats of a stepwise pixel loop from its per-step status words and mask sizes."""
+def _reduce_camera_logs(fp, log, status_log, pixel_log, want, held_log=None):
+    """k_done, status, pixels and stats of a stepwise pixel loop from its per-step status words and mask sizes -- and, where the loop holds
+    lost discs, 'held' from its per-step held flags (K, T, n_points): the steps pixels looks at."""
     torch = _torch()
     K, dev = status_log.shape[0], status_log.device
     failed = status_log != 0
@@ -704,6 +756,8 @@ def _reduce_camera_logs(fp, log, status_log, pixel_log, want):
     seen = steps <= k_done[None, :]                                  # the failing step's own masks count: an empty one shows as 0
     pixels = torch.where(seen[:, :, None], pixel_log, torch.full_like(pixel_log, 2 ** 31 - 1)).amin(0)
     out = dict({key: t for key, t in log.items() if key in want}, pixels=pixels, status=status, k_done=k_done)
+    if held_log is not None:
+        out['held'] = torch.where(seen[:, :, None], held_log, torch.zeros_like(held_log)).sum(0, dtype=torch.int32)
     out['stats'] = stats_reduce(log['err'], _loop_times(fp.dt, K), k_done, layout='ktc')
     return out
 
@@ -754,11 +808,12 @@ def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
     return tp, keep
 
 
-def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None):
+def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0):
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
     then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
     ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
-    ``_gather_by_source``) -- the launch is then uvs_camera_closed_loop_occluded_f64, with or without trial_params."""
+    ``_gather_by_source``) -- the launch is then uvs_camera_closed_loop_occluded_f64, with or without trial_params.  ``hold`` > 0: the launch
+    is uvs_camera_closed_loop_held_f64, with or without either, and the result has 'held'."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -785,6 +840,13 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
     operands = (q0, noise_ptr, X0.data_ptr(), f0.data_ptr(), ptr('q'), ptr('f'), ptr('dq'), ptr('err'), ptr('kappa'), status.data_ptr(),
                 k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
+    if hold:
+        held = torch.empty((T, npts), dtype=torch.int32, device=dev)
+        rc = _vision.lib().uvs_camera_closed_loop_held_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp),
+                                                           None if occ is None else occ[0], 0 if occ is None else occ[1], hold, *operands[:-1],
+                                                           held.data_ptr(), operands[-1])
+        _vision.check(rc)
+        return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats, held=held)
     if occ is not None:
         rc = _vision.lib().uvs_camera_closed_loop_occluded_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp), occ[0], occ[1],
                                                                *operands)
@@ -814,7 +876,7 @@ def _gather_by_source(q_start, noise, x0, trial_params):
 
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
-                       believed_index=None, trial_params=None, occluders=None):
+                       believed_index=None, trial_params=None, occluders=None, hold=0):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -859,11 +921,24 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     fused=True with ANALYTICAL and occluders is a ValueError -- use fused=False: the baseline's one-launch loop has no occluders.  A disc
     that is covered completely has an empty mask: NaN features and FAIL at that step, like a disc that leaves the frame.  Next to
     trial_params['source'] the inputs are gathered by source before the launch (an out-of-range index is then a ValueError, also on the
-    device), because the step-0 frame belongs to the output trial."""
+    device), because the step-0 frame belongs to the output trial.
+    ``hold``: an integer >= 0, one for the call: the largest number of consecutive steps for which a LOST disc's pair is held -- the rule of
+    ``plant.hold_features`` (include/uvs_vision.h, uvs_camera_closed_loop_held_f64).  A disc is lost at step k iff its mask is empty there,
+    behind an occluder or out of the frame alike; from step 1 on, and while its run of misses is shorter than ``hold``, the loop reports
+    step k - 1's pair again (that step's noise in it, none of step k's) instead of NaN, and the estimator or the law takes it like any
+    other.  Once the hold is used up, and at step 0, a lost disc is the NaN pair and FAIL of above.  0 (the default) is the call without
+    the argument: its routes, its entry points, its bits.  With hold > 0 the result has 'held' (T, n_points) int32: the steps up to and
+    including k_done at which each disc was held ('pixels' still shows the smallest mask, 0 after a hold).  fused=True with an estimator
+    is ONE launch (uvs_camera_closed_loop_held_f64), with or without ``occluders`` and ``trial_params``; fused=False is three launches per
+    step (uvs_hold_features_f64 between the two) for the estimators and the calibrated and believed baselines alike; the two return the
+    same bits.  fused=True with ANALYTICAL and hold > 0 is a ValueError -- use fused=False: the baseline's one-launch loops hold nothing."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
     analytical = fp.method == _lib.METHOD_ANALYTICAL
+    hold = _check_hold(hold)
+    if hold and analytical and fused:
+        raise ValueError('camera_closed_loop: the calibrated baseline has no one-launch loop that holds a lost disc: use fused=False')
     if occluders is not None:
         if analytical and fused:
             raise ValueError('camera_closed_loop: the calibrated baseline has no one-launch loop with occluders: use fused=False')
@@ -913,9 +988,9 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
         occ = None if occluders is None else _occluder_operand(occluders, dev)
         if believed is None:
-            return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, occ=occ)
+            return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, occ=occ, hold=hold)
         *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
-        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ)
+        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold)
     if believed is not None:                                         # an estimator that starts from the wrong model; the rest is the x0= path
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -926,7 +1001,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -953,7 +1028,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         raise ValueError('camera_closed_loop: x0 is needed when fp.initial_guess is 0 (the reference draws it unseeded, experiment.py:117)')
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2])
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2], hold)
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
@@ -961,16 +1036,21 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     dq_zero = torch.zeros((T, n), **f64)
     step = _lib.lib().uvs_rmckf_step_f64
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream)
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev)
+    held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
+    if hold:
+        row['held'] = (held_log.data_ptr(), held_log.stride(0) * held_log.element_size())
     at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
     noise_row = 0 if noise is None else noise.stride(0) * 8
     for k in range(K):
         q_prev, dq_prev, f_old = (q0, None, f0.data_ptr()) if k == 0 else (at('q', k - 1), at('dq', k - 1), at('f', k - 1))
-        _vision.check(features(k, q_prev, dq_prev, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k), at('pixels', k)))
+        extra = (None if k == 0 else f_old, at('held', k)) if hold else ()
+        _vision.check(features(k, q_prev, dq_prev, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k), at('pixels', k),
+                               *extra))
         _lib.check(step(fp_ref, T, X.data_ptr(), P.data_ptr(), at('f', k), f_old, dq_zero.data_ptr() if k == 0 else dq_prev, int(k == 0), k,
                         at('dq', k), at('err', k), at('kappa', k), at('status', k), stream))
-    return _reduce_camera_logs(fp, log, status_log, pixel_log, want)
+    return _reduce_camera_logs(fp, log, status_log, pixel_log, want, held_log)
 
 
 def _loop_times(t_s, K):

@@ -123,6 +123,35 @@ def render_discs(discs, n_colours=4, background=96, occluders=None, k=0, shade=3
     return frames[0] if discs.ndim == 2 else frames
 
 
+def hold_features(f, f_prev, pixels, miss, hold):
+    """Hold a lost disc's last detection: the numpy statement of the rule uvs_camera_closed_loop_held_f64 and uvs_hold_features_f64
+    (include/uvs_vision.h) are held to, for ONE step of T trials.  ``f`` (T, 2 n_points): the detector's row of step k, noise included;
+    ``f_prev`` (T, 2 n_points): the REPORTED row of step k - 1 (what this function returned then), or None at step 0; ``pixels``
+    (T, n_points) integers: the mask counts of step k; ``miss`` (T, n_points) integers: the counters, zeros before step 0; ``hold`` >= 0:
+    the largest number of consecutive steps for which a pair may be held.
+    Disc j is lost iff pixels[j] == 0 -- the count decides, never the pair.  Detected: miss[j] = 0 and the pair is f's.  Lost, not step 0
+    and miss[j] < hold: the pair is f_prev's (that step's noise in it, none of this step's), miss[j] += 1, held[j] = 1.  Lost otherwise:
+    the pair stays f's (NaN, which FAILs the trial at this step).
+    Returns new arrays (f, miss, held); the arguments are not written."""
+    if isinstance(hold, bool) or not isinstance(hold, (int, np.integer)) or hold < 0:
+        raise ValueError(f'hold is a number of steps, an integer >= 0, got {hold!r}')
+    f, pixels, miss = np.array(f, float), np.asarray(pixels), np.array(miss)
+    if f.ndim != 2 or pixels.shape != (f.shape[0], f.shape[1] // 2) or miss.shape != pixels.shape or f.shape[1] % 2:
+        raise ValueError(f'f (T, 2 n_points), pixels and miss (T, n_points), got {f.shape}, {pixels.shape}, {miss.shape}')
+    if pixels.dtype.kind not in 'iu' or miss.dtype.kind not in 'iu':
+        raise ValueError('pixels and miss are integers')
+    lost = pixels == 0
+    held = lost & (miss < hold) if f_prev is not None else np.zeros_like(lost)
+    if held.any():
+        f_prev = np.asarray(f_prev, float)
+        if f_prev.shape != f.shape:
+            raise ValueError(f'f_prev has the shape of f, got {f_prev.shape} for {f.shape}')
+        pairs = np.repeat(held, 2, axis=1)
+        f[pairs] = f_prev[pairs]
+    miss = np.where(held, miss + 1, np.where(lost, miss, 0)).astype(miss.dtype)
+    return f, miss, held.astype(np.int32)
+
+
 def analytic_guess(robot, f, resolution, m, n):
     """X0 for an external robot (experiment.py:94-114), evaluated once on the host from the robot's own kinematics."""
     depth = robot.computeZ(m // 2)
