@@ -1,18 +1,23 @@
-// The step of the calibrated IBVS baseline, defined ONCE for the units that run it: uvs_camera_analytical.hip (the model is the camera that
-// renders the frames, uniform over the launch) and uvs_camera_believed.hip (the model is a per-trial uvs_camera read from memory).  Both
-// compile it with -ffp-contract=off on the same operands in the same order, so a believed model that equals the true one gives the bits of
-// the calibrated kernels.  Next to it: what every entry point of the two units asks of (fp, cam, T) before its first HIP call.
+// The calibrated IBVS baseline, defined ONCE for the units that run it: uvs_camera_analytical.hip (the model is the camera that renders the
+// frames, uniform over the launch) and uvs_camera_believed.hip (the model is a per-trial uvs_camera read from memory).  Two things live here.
+// (1) The step, analytical_step, which every kernel of the two units calls.  Both compile it with -ffp-contract=off on the same operands in
+// the same order, so a believed model that equals the true one gives the bits of the calibrated kernels.
+// (2) The pixel loop as ONE launch per batch: one kernel text in two flavours, chosen per TRANSLATION UNIT as camera_loop_device.hpp chooses
+// its four.  A unit that defines UVS_CAMERA_BELIEVED before it includes this header sees camera_believed_loop_kernel(BLoopArgs): the control
+// side's model of every trial is staged from memory into s_cam[G], and a trial whose index names no model starts FAILed (not alive, not seen),
+// so that it logs no row and writes status and k_done alone.  Every other unit sees camera_analytical_loop_kernel(ALoopArgs): one model, taken
+// from the kernel argument, every trial known.  Same names, argument blocks, registers and LDS as when each was written out in its unit.
+// Next to them: what every entry point of the two units asks of (fp, cam, T) before its first HIP call.
+//
+// The loop's mapping is the one of camera_loop_kernel (camera_loop_device.hpp), decided and measured there -- 256 threads = one wavefront per
+// SIMD, G = 1 trial per workgroup up to 256 trials and G = 4 beyond, the sensor side of camera_sensor_device.hpp on the camera that renders
+// the frames -- with the estimator side of wavefront 0 replaced by the step, for which the sensor side hands the joints over in LDS next to
+// the features.  Every barrier is at the top level of the step loop and reached by all 256 threads; padding and FAILed trials keep computing
+// and store nothing; the one early exit ("every trial of this workgroup has failed") is read by every thread from the same G LDS words.
 #pragma once
-#include "../csrc/rmckf_device.hpp"
-
-#include <climits>
-
-#include "uvs_vision.h"
-#include "vision_device.hpp"
+#include "camera_sensor_device.hpp"
 
 namespace uvs_vision {
-
-constexpr int kAJoints = 6;                                      // the DH arms of this project (camera_jacobian<6>)
 
 // One step of the calibrated law for this lane's R rows of its trial.  q: the trial's joints; feat(i): component i of the trial's detected
 // features (raw pixels, noise added).  Writes this lane's rows of J into st.x and of f - desired into err, and the command (replicated in
@@ -56,6 +61,232 @@ __device__ __forceinline__ int analytical_step(const uvs_camera &cam, const uvs_
     return bad;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- believed models
+constexpr int kCamWords = static_cast<int>(sizeof(uvs_camera) / 8);
+static_assert(sizeof(uvs_camera) % 8 == 0, "copied as doubles");
+
+struct Believed {
+    const uvs_camera *models;                                    // [n]
+    long long n;
+    const int32_t *index;                                        // [T] or NULL: n == 1 (all trials the one model) or n == T (trial t model t)
+};
+
+// The model of `trial`, or -1 when its index names none.
+__device__ __forceinline__ long long model_of(const Believed &B, long long trial) {
+    const long long i = B.index != nullptr ? static_cast<long long>(B.index[trial]) : (B.n == 1 ? 0 : trial);
+    return (i >= 0 && i < B.n) ? i : -1;
+}
+
+// The models of the trials first .. first + COUNT - 1 (clamped to the last trial: padding shadows it) into s_cam[COUNT], by all THREADS threads;
+// zeros for a trial without a model.  The caller's next barrier stands between this and the first read.
+template <int COUNT, int THREADS>
+__device__ __forceinline__ void stage_models(const Believed &B, long long first, long long T, uvs_camera *s_cam) {
+    for (int i = threadIdx.x; i < COUNT * kCamWords; i += THREADS) {
+        const int slot = i / kCamWords, word = i - slot * kCamWords;
+        long long trial = first + slot;
+        if (trial >= T) trial = T - 1;
+        const long long model = model_of(B, trial);
+        reinterpret_cast<double *>(s_cam)[i] = model >= 0 ? reinterpret_cast<const double *>(B.models + model)[word] : 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the loop, one launch
+struct ALoopArgs {
+    uvs_filter_params fp;
+    uvs_camera cam;
+    long long T;
+    const double *q_start, *noise;
+    double *q_log, *f_log, *dq_log, *err_log;                    // [K][T][comp], each or NULL
+    int32_t *status, *k_done;
+    double *stats;
+    int32_t *pixels;
+};
+
+struct BLoopArgs {
+    uvs_filter_params fp;
+    uvs_camera cam;                                              // the sensor side's: the camera that renders the frames
+    Believed B;                                                  // the control side's
+    long long T;
+    const double *q_start, *noise;
+    double *q_log, *f_log, *dq_log, *err_log;                    // [K][T][comp], each or NULL
+    int32_t *status, *k_done;
+    double *stats;
+    int32_t *pixels;
+};
+
+#ifdef UVS_CAMERA_BELIEVED
+constexpr bool kCameraBelieved = true;
+using BaselineLoopArgs = BLoopArgs;
+#define UVS_BASELINE_LOOP_KERNEL camera_believed_loop_kernel
+#else
+constexpr bool kCameraBelieved = false;
+using BaselineLoopArgs = ALoopArgs;
+#define UVS_BASELINE_LOOP_KERNEL camera_analytical_loop_kernel
+#endif
+// Has `trial` a model?  Calibrated: always, folded away.  Believed: the same word in all 64 lanes of a sensor-side wavefront.
+__device__ __forceinline__ bool has_model(const ALoopArgs &, long long) { return true; }
+__device__ __forceinline__ bool has_model(const BLoopArgs &a, long long trial) { return model_of(a.B, trial) >= 0; }
+// The control side's models of the workgroup's trials into LDS, by all kLoopThreads threads.  Calibrated: the one model of the launch -- the
+// 6 x 6 camera Jacobian uses the whole DH table in every step, and held in scalar registers next to the sensor side's the table spilled (36 B
+// of scratch per lane in the four-trial form).
+template <int G>
+__device__ __forceinline__ void stage_loop_models(const ALoopArgs &a, uvs_camera *s_cam) {
+    for (int i = threadIdx.x; i < kCamWords; i += kLoopThreads) reinterpret_cast<double *>(s_cam)[i] = reinterpret_cast<const double *>(&a.cam)[i];
+}
+template <int G>
+__device__ __forceinline__ void stage_loop_models(const BLoopArgs &a, uvs_camera *s_cam) {
+    stage_models<G, kLoopThreads>(a.B, static_cast<long long>(blockIdx.x) * G, a.T, s_cam);
+}
+
+template <int M, int N, int L, int G>
+__global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const BaselineLoopArgs A) {
+    constexpr bool BELIEVED = kCameraBelieved;
+    constexpr int R = M / L, W = kLoopThreads / 64;
+    static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
+    __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
+    __shared__ double s_disc[W][kColours * 3];
+    __shared__ double s_q[G][N];                                 // this step's joints, sensor side -> control side
+    __shared__ double s_f[G][M];                                 // this step's features, sensor side -> control side
+    __shared__ double s_dq[G][N];                                // this step's command, control side -> sensor side
+    __shared__ int s_alive[G];                                   // trial has not FAILed, as of the end of this step
+    __shared__ int s_pix[G][kColours];                           // smallest mask so far
+    __shared__ double s_sum[G][3][M];                            // per-feature ISE, IAE, ITAE after the loop
+    __shared__ uvs_camera s_cam[BELIEVED ? G : 1];               // the control side's models; written once here, and the step loop's barriers
+    stage_loop_models<G>(A, s_cam);                              // stand between this and the first read
+
+    const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const uvs_filter_params &fp = A.fp;
+    const uvs_camera &cam = A.cam;                               // the sensor side keeps reading the true camera from the kernel arguments
+    const long long T = A.T;
+    const int K = fp.steps, npts = cam.n_points;
+
+    // sensor side: this wavefront's trial, and the feature pairs it detects: all of its own trial's, or every fourth of the workgroup's one trial
+    const int ws = G == 1 ? 0 : w;
+    const bool writer = G == W || w == 0;                        // G = 1: the four wavefronts hold the same joints; the first one logs them
+    const int j_first = G == 1 ? w : 0, j_step = G == 1 ? W : 1;
+    long long trial = static_cast<long long>(blockIdx.x) * G + ws;
+    const bool valid = trial < T;
+    if (!valid) trial = T - 1;                                   // a padding wavefront shadows the last trial and stores nothing
+    const bool known = has_model(A, trial);
+    double q = lane < N ? A.q_start[trial * N + lane] : 0.0;
+    // this lane's own addresses in row 0 of the [K][T][comp] logs (NULL: not wanted, or nothing of this lane's), advanced by a row per step
+    const long long step_rows = T;
+    double *q_at = (valid && writer && lane < N && A.q_log != nullptr) ? A.q_log + trial * N + lane : nullptr;
+    double *f_at = (valid && lane == 0 && A.f_log != nullptr) ? A.f_log + trial * M : nullptr;
+    const double *noise_at = A.noise != nullptr ? A.noise + trial * M : nullptr;
+    bool seen = known;                                           // this trial has not FAILed before this step: its rows q[k], f[k] are due
+    if (lane < kColours) s_pix[ws][lane] = INT_MAX;
+
+    // control side (wavefront 0): this lane's trial and rows; the lanes from G L on shadow the first ones and store nothing
+    const int slot = (lane / L) & (G - 1), sub = lane % L;
+    long long etrial = static_cast<long long>(blockIdx.x) * G + slot;
+    const bool owner = lane < G * L;
+    const bool evalid = owner && etrial < T;
+    if (etrial >= T) etrial = T - 1;
+    double *err_at = (evalid && A.err_log != nullptr) ? A.err_log + etrial * M + sub * R : nullptr;
+    double *dq_at = (evalid && sub == 0 && A.dq_log != nullptr) ? A.dq_log + etrial * N : nullptr;
+    double ise[R], iae[R], itae[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) ise[r] = iae[r] = itae[r] = 0.0;
+    double t = 0.0 + fp.dt;                                      // engine._loop_times: t_s accumulated in floating point
+    bool alive = has_model(A, etrial);                           // no model: FAILed before step 0
+    int status = alive ? UVS_STATUS_SUCCESS : UVS_STATUS_FAIL, k_done = alive ? K : 0;
+
+    for (int k = 0; k < K; ++k) {
+        // ---- the sensor side of the step (camera_sensor_device.hpp): joints, projection, detection
+        if (lane < N) {
+            advance_joint(lane, k, s_dq[ws], fp.dt, q);
+            if (seen && q_at != nullptr) *q_at = q;              // before the sines: where this text measured fastest
+            if (writer) s_q[ws][lane] = q;
+            joint_sincos_rows(cam, lane, q, s_sin[w], s_cos[w]);
+        }
+        __syncthreads();
+        if (lane < npts) project_lane_disc(cam, lane, s_sin[w], s_cos[w], s_disc[w]);
+        __syncthreads();
+#pragma unroll 1
+        for (int j = j_first; j < npts; j += j_step) {
+            const ColourSum sum = detect_pair<false>(s_disc[w], npts, j, lane);
+            if (lane == 0) {                                     // the lane the shuffle tree ends in
+                double u, v;
+                noisy_centre(sum, noise_at, j, u, v);
+                report_pair(sum.count, j, u, v, seen, s_f[ws], s_pix[ws], f_at);
+            }
+        }
+        __syncthreads();
+        // ---- the law of the workgroup's trials, each on its model (the step kernel's sequence)
+        if (w == 0) {
+            double qk[N], err[R], cmd[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) qk[j] = s_q[slot][j];
+            uvs::Rows<M, N, L> st;
+            const int bad = analytical_step<M, N, L>(s_cam[BELIEVED ? slot : 0], fp, qk, [slot](int i) { return s_f[slot][i]; }, sub, st, err, cmd);
+            if (alive && bad) {                                  // FAIL at this step; the trial stops
+                alive = false;
+                status = UVS_STATUS_FAIL;
+                k_done = k;
+            }
+            if (alive && evalid) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (err_at != nullptr) err_at[r] = err[r];
+                    const double ae = fabs(err[r]);              // stats_kernel's sums, in its order over k
+                    ise[r] = fma(err[r], err[r], ise[r]);
+                    iae[r] += ae;
+                    itae[r] = fma(t, ae, itae[r]);
+                }
+                if (dq_at != nullptr) {
+#pragma unroll
+                    for (int j = 0; j < N; ++j) dq_at[j] = cmd[j];
+                }
+            }
+            if (owner && sub == 0) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) s_dq[slot][j] = cmd[j];
+                s_alive[slot] = alive ? 1 : 0;
+            }
+        }
+        __syncthreads();
+        t += fp.dt;
+        if (q_at != nullptr) q_at += step_rows * N;
+        if (f_at != nullptr) f_at += step_rows * M;
+        if (noise_at != nullptr) noise_at += step_rows * M;
+        if (err_at != nullptr) err_at += step_rows * M;
+        if (dq_at != nullptr) dq_at += step_rows * N;
+        seen = s_alive[ws] != 0;
+        int any_alive = 0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) any_alive |= s_alive[g];
+        if (any_alive == 0) break;                               // the same G words in all 256 threads: a uniform exit
+    }
+
+    if (w == 0 && owner) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            s_sum[slot][0][sub * R + r] = ise[r];
+            s_sum[slot][1][sub * R + r] = iae[r];
+            s_sum[slot][2][sub * R + r] = itae[r];
+        }
+        if (evalid && sub == 0) {
+            A.status[etrial] = status;
+            A.k_done[etrial] = k_done;
+        }
+    }
+    __syncthreads();
+    store_norms_and_pixels<M>(valid && writer && known, lane, npts, trial, s_sum[ws], s_pix[ws], A.stats, A.pixels);
+}
+
+inline void launch_baseline_loop(const uvs_filter_params &fp, hipStream_t s, const BaselineLoopArgs &A) {
+    const LoopLaunch at = loop_launch(A.T);
+#define UVS_BASELINE_SHAPE(M, N, L)                                                                                                      \
+    if (at.small) hipLaunchKernelGGL((UVS_BASELINE_LOOP_KERNEL<M, N, L, 1>), dim3(at.blocks), dim3(kLoopThreads), 0, s, A);               \
+    else hipLaunchKernelGGL((UVS_BASELINE_LOOP_KERNEL<M, N, L, kLoopTrials>), dim3(at.blocks), dim3(kLoopThreads), 0, s, A);
+    if (fp.m == 8) { UVS_BASELINE_SHAPE(8, 6, 4) }               // the lane counts of the estimators' step and loop kernels
+    else if (fp.m == 6) { UVS_BASELINE_SHAPE(6, 6, 2) }
+    else { UVS_BASELINE_SHAPE(2, 6, 1) }
+#undef UVS_BASELINE_SHAPE
+}
+
 // What the entry points ask of (fp, cam, T); every refusal comes before the first HIP call.
 inline int check_analytical(const uvs_filter_params *fp, const uvs_camera *cam, int64_t T) {
     if (fp == nullptr || cam == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL fp or cam");
@@ -68,7 +299,7 @@ inline int check_analytical(const uvs_filter_params *fp, const uvs_camera *cam, 
     if (fp->lanes_per_filter != 0) return fail(UVS_ERR_SHAPE, "%s", "lanes_per_filter must be 0: the kernels have one mapping per shape");
     if (fp->m != 2 * cam->n_points) return fail(UVS_ERR_SHAPE, "%s", "fp->m must be 2 * cam->n_points");
     if (fp->n != cam->n_joints) return fail(UVS_ERR_SHAPE, "%s", "fp->n must be cam->n_joints");
-    if (fp->n != kAJoints || (fp->m != 8 && fp->m != 6 && fp->m != 2)) return fail(UVS_ERR_SHAPE, "%s", "(m, n) must be (8, 6), (6, 6) or (2, 6)");
+    if (fp->n != kJoints || (fp->m != 8 && fp->m != 6 && fp->m != 2)) return fail(UVS_ERR_SHAPE, "%s", "(m, n) must be (8, 6), (6, 6) or (2, 6)");
     return UVS_OK;
 }
 

@@ -5,8 +5,9 @@
 // kernel it always was -- same name, same argument block, same registers, LDS and time per instantiation.  (A shared
 // __device__ body behind two __global__ wrappers moved the register allocation there; nothing here is shared at run time.)
 // The estimator is the one of libuvs_rmckf.so, read from its device header (Rows::update, control_law, bandwidth, bandwidth_of); the sensor
-// side is vision_device.hpp.  Both libraries compile with -ffp-contract=off, so every value a kernel here forms has the bits the two-launch
-// loop (uvs_camera_features_f64, then uvs_rmckf_step_f64, K times) forms.
+// side is camera_sensor_device.hpp: inlined functions over this kernel's LDS rows, which the baseline loop (camera_analytical_device.hpp)
+// calls too, together with the mapping's constants and the launch decision.  Both libraries compile with -ffp-contract=off, so every
+// value a kernel here forms has the bits the two-launch loop (uvs_camera_features_f64, then uvs_rmckf_step_f64, K times) forms.
 //
 // Mapping.  A workgroup of 256 threads = four wavefronts is alone on its compute unit (one wavefront per SIMD, so the kernel may take the
 // whole register file: the estimator state alone is 108 dwords per lane at (8,6,4)).  It carries G trials:
@@ -47,19 +48,9 @@
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
-#include "../csrc/rmckf_device.hpp"
-
-#include <climits>
-
-#include "uvs_vision.h"
-#include "vision_device.hpp"
+#include "camera_sensor_device.hpp"
 
 namespace uvs_vision {
-
-constexpr int kLoopTrials = 4;                                   // trials per workgroup of a large batch = wavefronts per workgroup
-constexpr int kLoopThreads = 64 * kLoopTrials;
-constexpr long long kSmallBatch = 256;                           // up to one trial per compute unit of an MI355X: one trial per workgroup
-constexpr int kJoints = 6;                                       // the DH arms of this project (camera_jacobian<6>)
 
 struct LoopArgs {
     uvs_filter_params fp;
@@ -258,63 +249,29 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     const uvs_filter_params &fpe = PTP ? fp_trial : A.fp;        // what the estimator update reads
 
     for (int k = 0; k < K; ++k) {
-        // ---- joints: q_k = q_{k-1} + dq_{k-1} * dt, one rounded multiply and one rounded add (joint_sincos)
+        // ---- the sensor side of the step (camera_sensor_device.hpp): joints, projection, detection
         if (lane < N) {
-            if (k > 0) {
-                const double step = s_dq[ws][lane] * fp.dt;
-                q = q + step;
-            }
-            if (seen && q_at != nullptr) *q_at = q;
-            double s, c;
-            sincos(q + cam.theta_offset[lane], &s, &c);
-            s_sin[w][lane] = s;
-            s_cos[w][lane] = c;
+            advance_joint(lane, k, s_dq[ws], fp.dt, q);
+            joint_sincos_rows(cam, lane, q, s_sin[w], s_cos[w]);
+            if (seen && q_at != nullptr) *q_at = q;              // after the sines: where this text measured fastest
         }
         __syncthreads();
-        // ---- projection (camera_features_kernel's)
-        if (lane < npts) {
-            double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
-#pragma unroll 1                                                 // a rolled loop reads the DH table where it is used: unrolled, the whole table sits in SGPRs
-            for (int i = 0; i < cam.n_joints; ++i) chain_link(cam, i, s_sin[w][i], s_cos[w][i], pose);
-            project_disc(cam, lane, pose, &s_disc[w][3 * lane]);
-        }
+        if (lane < npts) project_lane_disc(cam, lane, s_sin[w], s_cos[w], s_disc[w]);
         if constexpr (OCC) {                                     // lane o: rectangle o of this step, next to the projection
             if (lane < kOccluders) s_occ[w][lane] = lane < n_occ ? occluder_rect(occ_at[lane], k) : kNoRect;
         }
         __syncthreads();
-        // ---- frame-free detection: feature pair j is the centre of mass of disc j's colour
-        Rects rects;
+        Rects rects;                                             // OCC off: never read
         if constexpr (OCC) {
 #pragma unroll
             for (int o = 0; o < kOccluders; ++o) rects.r[o] = s_occ[w][o];
         }
 #pragma unroll 1
         for (int j = j_first; j < npts; j += j_step) {
-            const Disc me = load_disc(&s_disc[w][3 * j], true);  // disc j shows colour j (npts == 1: green)
-            int x0, x1, y0, y1;
-            disc_box(me, x0, x1, y0, y1);
-            ColourSum sum;
-#pragma unroll 1
-            for (int b = 0; b < 4; ++b) {                        // the colour's four wavefronts of centre_of_mass, in index order
-                const int lo = 64 * b, hi = lo + 63;
-                // outside the clipped box disc_counts_at returns (0, 0) for all 64 indices, whose partial is (+0.0, +0.0, 0)
-                const bool touched = me.r2 >= 0.0 && ((x0 <= hi && x1 >= lo) || (y0 <= hi && y1 >= lo));
-                double su = 0.0, sv = 0.0;
-                int n = 0;
-                if (__builtin_amdgcn_readfirstlane(static_cast<int>(touched))) {   // the same discs in every lane: wavefront-uniform
-                    int cc, rc;
-                    disc_counts_in_box<OCC>(s_disc[w], npts, j, me, x0, x1, y0, y1, lo + lane, cc, rc, rects);
-                    wave_partial(cc, rc, lo + lane, su, sv, n);
-                }
-                sum.add(su, sv, n);
-            }
+            const ColourSum sum = detect_pair<OCC>(s_disc[w], npts, j, lane, rects);
             if (lane == 0) {                                     // the lane the shuffle tree ends in
                 double u, v;
-                sum.centre(u, v);
-                if (noise_at != nullptr) {                       // f += noise (experiment.py:135)
-                    u += noise_at[2 * j];
-                    v += noise_at[2 * j + 1];
-                }
+                noisy_centre(sum, noise_at, j, u, v);
                 if constexpr (HOLD) {                            // the integer count decides, never the pair
                     if (sum.count != 0) {
                         s_miss[ws][j] = 0;
@@ -325,15 +282,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
                         if (seen) s_held[ws][j] += 1;
                     }                                            // lost otherwise: the NaN pair, which FAILs the trial at this step
                 }
-                s_f[ws][2 * j] = u;
-                s_f[ws][2 * j + 1] = v;
-                if (seen) {
-                    s_pix[ws][j] = sum.count < s_pix[ws][j] ? sum.count : s_pix[ws][j];
-                    if (f_at != nullptr) {
-                        f_at[2 * j] = u;
-                        f_at[2 * j + 1] = v;
-                    }
-                }
+                report_pair(sum.count, j, u, v, seen, s_f[ws], s_pix[ws], f_at);
             }
         }
         __syncthreads();
@@ -437,12 +386,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         }
     }
     __syncthreads();
-    if (lane < 3 && valid && writer) {                           // lane i: the norm over the features in order, as stats_kernel forms it
-        double acc = 0.0;
-        for (int i = 0; i < M; ++i) acc = fma(s_sum[ws][lane][i], s_sum[ws][lane][i], acc);
-        A.stats[3 * trial + lane] = sqrt(acc);
-    }
-    if (lane < npts && valid && writer && A.pixels != nullptr) A.pixels[trial * npts + lane] = s_pix[ws][lane];
+    store_norms_and_pixels<M>(valid && writer, lane, npts, trial, s_sum[ws], s_pix[ws], A.stats, A.pixels);
     if constexpr (HOLD) {
         if (lane < npts && valid && writer && held_out != nullptr) held_out[trial * npts + lane] = s_held[ws][lane];
     }
@@ -452,12 +396,11 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
 // instantiation is not built in either flavour and the entry points refuse it; at (8,6,4) and (2,6,1) it has none and is built.
 template <int M, int N, int L, bool WITH_MCKF>
 bool launch_loop(int method, hipStream_t s, const CameraLoopKernelArgs &A) {
-    const bool small = A.T <= kSmallBatch;
-    const unsigned blocks = static_cast<unsigned>(small ? A.T : (A.T + kLoopTrials - 1) / kLoopTrials);
+    const LoopLaunch at = loop_launch(A.T);
 #define UVS_LOOP_METHOD(METHOD)                                                                                                          \
     if (method == METHOD) {                                                                                                              \
-        if (small) hipLaunchKernelGGL((UVS_CAMERA_LOOP_KERNEL<M, N, L, METHOD, 1>), dim3(blocks), dim3(kLoopThreads), 0, s, A);           \
-        else hipLaunchKernelGGL((UVS_CAMERA_LOOP_KERNEL<M, N, L, METHOD, kLoopTrials>), dim3(blocks), dim3(kLoopThreads), 0, s, A);       \
+        if (at.small) hipLaunchKernelGGL((UVS_CAMERA_LOOP_KERNEL<M, N, L, METHOD, 1>), dim3(at.blocks), dim3(kLoopThreads), 0, s, A);     \
+        else hipLaunchKernelGGL((UVS_CAMERA_LOOP_KERNEL<M, N, L, METHOD, kLoopTrials>), dim3(at.blocks), dim3(kLoopThreads), 0, s, A);    \
         return true;                                                                                                                     \
     }
     UVS_LOOP_METHOD(UVS_METHOD_GMCKF)

@@ -5,38 +5,12 @@
 
 namespace uvs_vision {
 
-// The analytic initial guess of plant.analytic_guess, one lane per trial: the geometric Jacobian in the camera frame at q_start, the depths
-// |camera - point|, and the image Jacobian rows at the DETECTED features.
+// The analytic initial guess (guess_trial, camera_sensor_device.hpp) on the camera that renders the frames, one lane per trial.
 __global__ __launch_bounds__(64) void camera_guess_kernel(const uvs_camera cam, long long T, const double *__restrict__ q_start,
                                                           const double *__restrict__ f0, double *__restrict__ x0_out) {
-    constexpr int N = kJoints;
     const long long t = static_cast<long long>(blockIdx.x) * 64 + threadIdx.x;
     if (t >= T) return;
-    uvs_plant pl;                                                // camera_jacobian reads the DH table alone
-    double q[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        pl.theta_offset[i] = cam.theta_offset[i];
-        pl.d[i] = cam.d[i];
-        pl.a[i] = cam.a[i];
-        pl.cos_alpha[i] = cam.cos_alpha[i];
-        pl.sin_alpha[i] = cam.sin_alpha[i];
-        q[i] = q_start[t * N + i];
-    }
-    double rot[9], pos[3], Jc[6][N];
-    uvs::camera_jacobian<N>(pl, q, rot, pos, Jc);
-    const int m = 2 * cam.n_points;
-    for (int p = 0; p < cam.n_points; ++p) {
-        const double depth = uvs::point_depth(pos, cam.points[p]);
-        const double u = f0[t * m + 2 * p], v = f0[t * m + 2 * p + 1];
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            double x[N];
-            uvs::feature_jacobian_row<N>(cam.focal, u, v, depth, half, Jc, x);
-#pragma unroll
-            for (int j = 0; j < N; ++j) x0_out[(t * m + 2 * p + half) * N + j] = x[j];
-        }
-    }
+    guess_trial(cam, t, cam.n_points, q_start, f0, x0_out);
 }
 
 }  // namespace uvs_vision
