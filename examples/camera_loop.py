@@ -23,8 +23,14 @@ across at the goal -- and crosses the discs during the transient, so every mask 
 there; with engine.camera_closed_loop(hold=N) a lost disc's last detection is reported again for up to N steps (df = 0 while dq != 0, then a
 jump: the outlier the correntropy estimators exist for).  KF, MCKF, IMCC-KF, GMCKF (one launch each) and the calibrated law (stepwise) on the
 same starts and noise; prints the FAIL count at hold = 0 beside the median ISE / IAE / ITAE, the FAIL count and the held steps at hold = N.
+--distractor asks about the outlier a colour threshold is best known for: something else in the scene has the target's colour.  A still
+6 x 6 px rectangle of the green disc's colour sits 20 px from green's goal position (engine.camera_closed_loop(occluders=, occluder_colours=)):
+its pixels enter green's mask and pull the centroid towards it, by an amount that grows as the disc shrinks or is covered -- and the detector
+never reports a loss.  KF, MCKF, IMCC-KF, GMCKF (one launch each) and the calibrated law (stepwise) on the same starts and noise; prints the
+median ISE / IAE / ITAE and the FAIL count without and with the distractor.  With --occlusion --hold N the wide bar of above crosses the
+frame as well, behind the distractor, and lost discs are held: green, whose distractor stays visible, is never lost.
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid] [--occlusion [--hold N]]"""
+       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]]"""
 import argparse
 import os
 import sys
@@ -185,6 +191,46 @@ def hold_table(uvs, hold, trials=64, sigma=0.3, radius=None, seed=0, bar=WIDE_BA
     return lines
 
 
+DISTRACTOR = (139, 100, 6, 6, 0, 0, 0, 2 ** 31 - 1)                   # still, 20 px from green's goal position (125, 121), beside its disc
+GREEN = 1
+
+
+def distractor_table(uvs, trials=64, sigma=0.3, radius=None, seed=0, rect=DISTRACTOR, bar=None, hold=0):
+    """The distractor table as a list of lines: the four estimators (one launch each) and the calibrated law (stepwise) on the same starts
+    and noise, with the rectangle opaque and with it painted green.  ``bar``: an opaque occluder behind the rectangle, or None; ``hold``."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    methods = ('KF', 'MCKF', 'IMCCKF', 'GMCKF', 'ANALYTICAL')
+    fps = {method: uvs.engine.make_params(8, 6, method, 10.0, False, 0.05, 15.0, 0.2, desired, True) for method in methods}
+    K = fps['GMCKF'].steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    q0_d = torch.as_tensor(q0, device='cuda')
+    noise_d = torch.as_tensor(rng.standard_normal((K, trials, 8)) * sigma, device='cuda')
+    rows = ([] if bar is None else [bar]) + [rect]                    # the rectangle last: in front of the bar
+    occluders = uvs.engine.occluders(rows, trials)
+    paints = {'opaque': [-1] * len(rows), 'green': [-1] * (len(rows) - 1) + [GREEN]}
+    behind = '' if bar is None else f', in front of a {bar[2]} px opaque bar at {bar[4]} px per step, hold = {hold}'
+    lines = [f'a still {rect[2]} x {rect[3]} px rectangle at ({rect[0]}, {rect[1]}){behind}, {trials} trials of {K} steps, white noise {sigma} px; '
+             'median over the trials that ran to the end',
+             f'{"":28s}{"the rectangle opaque":^36s}{"FAIL":>6s}   {"painted green: a distractor":^36s}{"FAIL":>6s}{"green":>7s}',
+             f'{"":28s}{"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"":6s}   {"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"":6s}{"held":>7s}']
+    for method, fp in fps.items():
+        kw = dict(radius=radius, want=()) if method == 'ANALYTICAL' else dict(radius=radius, fused=True, guess='device', want=())
+        row = f'{method + (" (calibrated, stepwise)" if method == "ANALYTICAL" else ""):28s}'
+        for name in ('opaque', 'green'):
+            out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, occluders=occluders, occluder_colours=paints[name], hold=hold, **kw)
+            torch.cuda.synchronize()
+            done = (out['status'] == 0).cpu().numpy()
+            med = np.median(out['stats'].cpu().numpy()[done], axis=0) if done.any() else np.full(3, np.nan)
+            row += f'{med[0]:12.3f}{med[1]:12.3f}{med[2]:12.3f}{int((~done).sum()):>6d}'
+            row += '   ' if name == 'opaque' else (f'{int(out["held"][:, GREEN].sum()):>7d}' if hold else f'{"-":>7s}')
+        lines.append(row)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -199,11 +245,20 @@ def main():
     ap.add_argument('--occlusion', action='store_true', help='a bar crosses the frame while the servo runs: GMCKF, KF and the calibrated law, and nothing else')
     ap.add_argument('--hold', type=int, default=0, metavar='N',
                     help='with --occlusion: a bar wider than a disc, and a lost disc keeps its last detection for up to N steps (0: the narrow bar)')
+    ap.add_argument('--distractor', action='store_true',
+                    help='a still rectangle of the green disc\'s colour near its goal: the estimators and the calibrated law, and nothing else '
+                         '(with --occlusion --hold N: in front of the wide bar, lost discs held)')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
     if args.hold and not args.occlusion:
         ap.error('--hold goes with --occlusion')
+    if args.distractor:
+        if args.occlusion and not args.hold:
+            ap.error('--distractor --occlusion needs --hold N: the wide bar empties every mask')
+        print('\n'.join(distractor_table(uvs, args.trials, args.sigma, args.radius, args.seed, bar=WIDE_BAR if args.occlusion else None,
+                                          hold=args.hold)))
+        return
     if args.occlusion and args.hold:
         print('\n'.join(hold_table(uvs, args.hold, args.trials, args.sigma, args.radius, args.seed)))
         return

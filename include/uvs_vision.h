@@ -323,6 +323,44 @@ int uvs_hold_features_f64(int64_t T, int32_t n_points, int32_t hold, int32_t k, 
                           const int32_t *pixels_row, int32_t *miss, int32_t *held_row, void *stream);
 
 /*
+ * PAINTED occluders: distractors.  A colour-threshold detector's best-known outlier ADDS pixels to a mask -- something else in the scene has
+ * the target's colour -- where the occluders above only remove them.  An occluder may therefore carry a PAINT, a parallel operand; the
+ * uvs_occluder struct is as it was:
+ *   paint [T][n_occ] int32 in, device (or pinned host) memory, trial t's values at paint + t * n_occ, or NULL = every rectangle opaque.
+ *   A value p in 0 .. n_colours - 1 paints the rectangle the colour of disc p (n_colours == 1: 0 is the green one).  EVERY other int32
+ *   (-1 by convention) is opaque, as above: the device rule is total and validates nothing.
+ * Order: the rectangles are in front of every disc, and rectangle o' is in front of rectangle o when o' > o.  A pixel belongs to the
+ * highest-index ACTIVE rectangle that contains it; otherwise to the topmost disc by the painter's order; otherwise to the background.
+ *   Rasteriser: a pixel of a rectangle painted p gets disc p's colour in its three channels, a pixel of an opaque one `shade`.
+ *   Detectors: the mask of colour c is { pixels of disc c } + { pixels of the rectangles painted c } -- disjoint sets, so the integer
+ *     column and row counts add; the sums, the centre and the noise add are those of the pixel rule above.  The mask size includes the
+ *     distractor's pixels.  A colour whose disc draws nothing (r < 0, out of the frame, NaN) still has a mask where a rectangle is painted it.
+ *   Hold: "lost iff the count is 0" stays the rule, so a disc that is gone while a distractor of its colour is visible is NOT lost: it
+ *     reports the distractor's centroid.
+ * plant.render_discs(..., occluder_colours=) states the rule once in numpy; every kernel below is held to it byte for byte.
+ * Bit for bit: paint == NULL, or every paint opaque, gives the occluded (or held) namesake -- for opaque rectangles "a later one in front"
+ * is the union of above -- and n_occ == 0 the unoccluded one.
+ * The three stand-alone entry points and the loop: each its occluded (held) namesake's operands with `paint` directly after `occ`, its
+ * refusals in its order (a NULL paint is legal with any n_occ), its instantiations (the loop: GMCKF, KF and IMCC-KF at (8, 6), (6, 6) and
+ * (2, 6), MCKF at (8, 6) and (2, 6), each in both workgroup forms with 0 B of scratch memory; MCKF at (6, 6) is refused with
+ * UVS_ERR_METHOD).  In the loop paints are indexed by OUTPUT trial, like occluders; f0 is the caller's: for the loop of the reference the
+ * noise-free detection of the step-0 frame, painted rectangles included.
+ */
+int uvs_render_discs_painted_u8(int64_t T, const double *discs, int32_t n_colours, int32_t background, const uvs_occluder *occ,
+                                const int32_t *paint, int32_t n_occ, int32_t k, int32_t shade, uint8_t *frames, int64_t frame_stride_bytes,
+                                void *stream);
+int uvs_disc_features_painted_f64(int64_t T, const double *discs, int32_t n_colours, const uvs_occluder *occ, const int32_t *paint,
+                                  int32_t n_occ, int32_t k, const double *noise, double *f_out, int32_t *pixels_out, void *stream);
+int uvs_camera_features_painted_f64(const uvs_camera *cam, int64_t T, const double *q_prev, const double *dq, double dt, double *q_out,
+                                    const uvs_occluder *occ, const int32_t *paint, int32_t n_occ, int32_t k, const double *noise,
+                                    double *f_out, int32_t *pixels_out, double *discs_out, void *stream);
+int uvs_camera_closed_loop_painted_f64(const struct uvs_filter_params *fp, const uvs_camera *cam, int64_t T,
+                                       const uvs_camera_trial_params *tp, const uvs_occluder *occ, const int32_t *paint, int32_t n_occ,
+                                       int32_t hold, const double *q_start, const double *noise, const double *x0, const double *f0,
+                                       double *q_log, double *f_log, double *dq_log, double *err_log, double *kappa_log, int32_t *status,
+                                       int32_t *k_done, double *stats, int32_t *pixels, int32_t *held, void *stream);
+
+/*
  * The analytic initial guess X0 of the loop (experiment.py:94-114) for T trials, one lane each: the geometric Jacobian of the DH chain in the
  * camera frame at q_start, the depths |camera - point|, and the image-Jacobian rows at the DETECTED features f0 (raw pixels).
  *   q_start [T][6] in; f0 [T][2*n_points] in; x0_out [T][2*n_points*6] out.

@@ -61,7 +61,20 @@ With --held only the pixel loop that holds a lost disc's last detection is timed
       The acceptance condition is (q) below (r); (n) new against (n) parent is reported next to the parent's own spread; (p) / (n) and
       (q) / (n) are reported, not gated.  (n) is checked against the parent's (n), (p) against (n) and (q) against (r), bit for bit,
       before anything is timed.  Then the table of examples/camera_loop.py --occlusion --hold 30.
-usage: tools/time_camera.py --held [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --held [--parent-lib=PATH] [out.txt]
+With --painted only the pixel loop behind painted occluders (distractors) is timed, into profiles/camera_painted.txt (or the path given):
+GMCKF, 1 024 trials x 299 steps, white noise 0.3 px, x0 handed in, medians of 20 with p10-p90;
+  (e) the uniform fused launch, (n) the 12 px bar of --occluded through camera_occluded_kernel and (q) the wide bar of --held with
+      hold = 30 through camera_held_kernel -- each with this library and, given --parent-lib=PATH, with the parent's TWICE (two entries of
+      the same alternating blocks): the existing kernels were not to move.  A figure passes when it is no slower than the slower of the two
+      parent runs by more than the two parent runs differ; the outputs must be bit-identical;
+  (s) (q)'s trials through camera_painted_kernel with paint = NULL: what the kernel flavour costs;
+  (t) (q) with a still distractor of green's colour in front of the bar on every trial (examples/camera_loop.py --distractor --occlusion
+      --hold 30), one launch;
+  (u) (t) stepwise: K x (painted camera features, hold, estimator step), three launches a step.
+      (s), (t), (u) are reported, not gated.  (s) is checked against (q) and (t) against (u), bit for bit, before anything is timed.  Then
+      the tables of examples/camera_loop.py --distractor and --distractor --occlusion --hold 30.
+usage: tools/time_camera.py --painted [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -74,10 +87,10 @@ import uvs_amd as uvs  # noqa: E402
 import torch  # noqa: E402
 
 ANALYTICAL, BELIEVED, GRID = '--analytical' in sys.argv[1:], '--believed' in sys.argv[1:], '--grid' in sys.argv[1:]
-OCCLUDED, HELD = '--occluded' in sys.argv[1:], '--held' in sys.argv[1:]
+OCCLUDED, HELD, PAINTED = '--occluded' in sys.argv[1:], '--held' in sys.argv[1:], '--painted' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -561,6 +574,134 @@ def held_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def painted_section():
+    """(e), (n), (q) against the parent's; (s), (t), (u): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T, HOLD = 299, 1024, 30
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    assert fp.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --painted on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in; rows of (x, y, w, h, vx, vy, k_on, k_off): the 12 px bar '
+        f'{example.BAR}, the wide bar {example.WIDE_BAR}, the distractor {example.DISTRACTOR} painted green; hold = {HOLD}')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+    x0 = uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+    bar, wide = uvs.engine.occluders([example.BAR], T), uvs.engine.occluders([example.WIDE_BAR], T)
+    both = uvs.engine.occluders([example.WIDE_BAR, example.DISTRACTOR], T)
+    paints = torch.as_tensor(np.tile(np.array([-1, example.GREEN], np.int32), (T, 1)), device='cuda')
+    painted_entry = uvs._vision.lib().uvs_camera_closed_loop_painted_f64
+
+    def run_s():
+        """(q)'s call through the painted entry point with paint = NULL (engine.camera_closed_loop without paints takes the held route)."""
+        cam = plant.to_camera(uvs.plant.DISC_RADIUS)
+        f64 = dict(dtype=torch.float64, device='cuda')
+        f0 = torch.zeros((T, 8), **f64)
+        uvs.engine.camera_features(cam, q_d, out=f0, occluders=wide)
+        log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('q', 6), ('f', 8), ('dq', 6), ('err', 8), ('kappa', 8))}
+        status, k_done = (torch.empty(T, dtype=torch.int32, device='cuda') for _ in range(2))
+        stats_t, pixels, held = torch.empty((T, 3), **f64), *(torch.empty((T, 4), dtype=torch.int32, device='cuda') for _ in range(2))
+        uvs._vision.check(painted_entry(ctypes.byref(fp), ctypes.byref(cam), T, None, wide.data_ptr(), None, wide.shape[1], HOLD, q_d.data_ptr(),
+                                        noise.data_ptr(), x0.data_ptr(), f0.data_ptr(), log['q'].data_ptr(), log['f'].data_ptr(),
+                                        log['dq'].data_ptr(), log['err'].data_ptr(), log['kappa'].data_ptr(), status.data_ptr(), k_done.data_ptr(),
+                                        stats_t.data_ptr(), pixels.data_ptr(), held.data_ptr(), uvs.engine._stream()))
+        return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats_t, held=held)
+
+    fns = {'e': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True),
+           'n': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=bar),
+           'q': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=wide, hold=HOLD),
+           's': run_s,
+           't': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=both, occluder_colours=paints, hold=HOLD),
+           'u': lambda: loop(fp, plant, q_d, noise, x0=x0, occluders=both, occluder_colours=paints, hold=HOLD)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+
+    def same(a, b):
+        done = a['k_done']
+        ok = all(torch.equal(a[key], b[key]) for key in ('status', 'k_done', 'pixels')) and torch.equal(a['stats'].view(torch.int64), b['stats'].view(torch.int64))
+        ok = ok and ('held' in a) == ('held' in b) and ('held' not in a or torch.equal(a['held'], b['held']))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):                 # the specified rows: q, f up to and including k_done, the others before it
+            spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+            ok = ok and torch.equal(a[key].view(torch.int64)[spec], b[key].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['s'], first['q']), 'the painted kernel with paint = NULL and the held kernel disagree'
+    assert same(first['t'], first['u']), 'the one launch and the stepwise loop disagree'
+    assert not torch.equal(first['t']['f'].view(torch.int64), first['q']['f'].view(torch.int64)), 'the distractor moves no feature'
+    gated = ('e', 'n', 'q')
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_painted_f64'), 'the parent library paints nothing'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def with_parent(fn):
+            def run():
+                mine, uvs._vision._lib = uvs._vision._lib, parent
+                try:
+                    return fn()
+                finally:
+                    uvs._vision._lib = mine
+            return run
+
+        for name in gated:
+            run = with_parent(fns[name])
+            old = run()
+            torch.cuda.synchronize()
+            assert same(first[name], old), f'this library and the parent disagree on ({name})'
+            fns[name + '_parent_a'], fns[name + '_parent_b'] = run, with_parent(fns[name])
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    failed = lambda out: int((out['k_done'] < K).sum())              # noqa: E731
+    say()
+    what = {'e': 'the uniform fused launch, camera_loop_kernel', 'n': 'the 12 px bar, camera_occluded_kernel', 'q': f'the wide bar, hold = {HOLD}, camera_held_kernel'}
+    passed = True
+    for name in gated:
+        say(f'  ({name}) {what[name]:48s} this library   {fmt_ms(ms[name])}   = {med[name] / K * 1e3:.1f} us per step')
+        if PARENT_LIB is not None:
+            a, b = med[name + '_parent_a'], med[name + '_parent_b']
+            say(f'  ({name}) {"":48s} the parent\'s, 1  {fmt_ms(ms[name + "_parent_a"])}')
+            say(f'  ({name}) {"":48s} the parent\'s, 2  {fmt_ms(ms[name + "_parent_b"])}')
+            ok = med[name] <= max(a, b) + abs(a - b)
+            passed = passed and ok
+            say(f'  ({name}) new / slower parent run = {med[name] / max(a, b):.4f}; the two parent runs differ by {abs(a - b) / max(a, b) * 100:.2f} %: '
+                f'{"passes" if ok else "DOES NOT pass"}; outputs bit-identical')
+    say(f'  (s) (q)\'s trials through camera_painted_kernel, paint = NULL        {fmt_ms(ms["s"])}')
+    say(f'  (t) (q) with a still distractor on every trial, one launch         {fmt_ms(ms["t"])}   = {med["t"] / K * 1e3:.1f} us per step')
+    say(f'  (u) (t) stepwise: K x (painted features, hold, estimator step)     {fmt_ms(ms["u"])}   = {med["u"] / K * 1e3:.1f} us per step')
+    say(f'  (s) / (q) = {med["s"] / med["q"]:.4f}, (t) / (q) = {med["t"] / med["q"]:.4f}, (t) / (u) = {med["t"] / med["u"]:.4f} (reported, not gated); '
+        '(s) has the bits of (q), (t) those of (u)')
+    say(f'  trials that FAILed: (q) {failed(first["q"])}, (t) {failed(first["t"])}; held steps of green: (q) {int(first["q"]["held"][:, 1].sum())}, '
+        f'(t) {int(first["t"]["held"][:, 1].sum())}; smallest green mask: (q) {int(first["q"]["pixels"][:, 1].min())}, (t) {int(first["t"]["pixels"][:, 1].min())}')
+    say()
+    if PARENT_LIB is not None:
+        say(f'gate: (e), (n), (q) against two runs of the parent\'s library: {"pass" if passed else "DO NOT pass"}')
+        say()
+    say('# examples/camera_loop.py --distractor (its defaults)')
+    for line in example.distractor_table(uvs):
+        say(line)
+    say()
+    say(f'# examples/camera_loop.py --distractor --occlusion --hold {HOLD}')
+    for line in example.distractor_table(uvs, bar=example.WIDE_BAR, hold=HOLD):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if PAINTED:
+    painted_section()
+    sys.exit(0)
 if HELD:
     held_section()
     sys.exit(0)

@@ -63,6 +63,11 @@ SYMBOLS = {
     'uvs_camera_closed_loop_occluded_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _I32] + [_VP] * 14),
     # the same with hold after n_occ and held (or None) after pixels
     'uvs_camera_closed_loop_held_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
+    # the four occluded (held) calls with the paints (device int32 [T][n_occ] or None) directly after occ
+    'uvs_render_discs_painted_u8': (C.c_int, [_I64, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _I32, _VP, _I64, _VP]),
+    'uvs_disc_features_painted_f64': (C.c_int, [_I64, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
+    'uvs_camera_features_painted_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    'uvs_camera_closed_loop_painted_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
     # T, n_points, hold, k, f_prev_row, f_row, pixels_row, miss, held_row, stream
     'uvs_hold_features_f64': (C.c_int, [_I64, _I32, _I32, _I32] + [_VP] * 6),
     'uvs_camera_guess_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _VP, _VP]),
@@ -86,7 +91,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 7)), '-C', CSRC], check=True)         # seven translation units, one rule each
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 8)), '-C', CSRC], check=True)         # eight translation units, one rule each
     return LIB_PATH
 
 

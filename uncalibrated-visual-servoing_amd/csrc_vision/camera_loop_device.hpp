@@ -45,6 +45,12 @@
 // is about to write disc j -- the estimator read it before the last barrier and nothing wrote it since -- so holding is "leave it there and
 // log it".  The counters of consecutive misses and of held steps sit in LDS next to s_pix, written by that lane alone (G = 1: wavefront j owns
 // colour j).  Barriers and exits are where they were; padding and void trials store nothing, `held` included.
+//
+// PAINT.  A fifth flavour: a unit that defines UVS_CAMERA_PAINTED next to the other three switches (uvs_camera_painted.hip)
+// sees camera_painted_kernel(PaintedLoopArgs) with all four on.  An occluder may be painted a disc's colour: a distractor, whose pixels enter
+// that colour's mask.  Lane o < 4, where it evaluates rectangle o into s_occ[w], also leaves the rectangle's paint as byte o of s_paint[w]
+// (paint_slot; opaque from n_occ on and for a NULL operand) -- one dword per trial, indexed by OUTPUT trial like the occluders -- and the
+// detection loop hands both to detect_pair<true, true>.  Barriers and exits are where they were.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -79,6 +85,19 @@ struct HeldLoopArgs : OccludedLoopArgs {
     int32_t *held;                                               // [T][n_points] or NULL
 };
 
+// uvs_camera_closed_loop_painted_f64: the held block and the occluders' paints, [T][n_occ] by output trial or NULL; only camera_painted_kernel takes it
+struct PaintedLoopArgs : HeldLoopArgs {
+    const int32_t *paint;
+};
+
+#ifdef UVS_CAMERA_PAINTED
+#ifndef UVS_CAMERA_HELD
+#error "the painted flavour is a held flavour: define UVS_CAMERA_HELD (and UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
+#endif
+constexpr bool kCameraPainted = true;
+#else
+constexpr bool kCameraPainted = false;
+#endif
 #ifdef UVS_CAMERA_HELD
 #ifndef UVS_CAMERA_OCCLUDED
 #error "the held flavour is an occluded flavour: define UVS_CAMERA_OCCLUDED (and UVS_CAMERA_PER_TRIAL) too"
@@ -95,7 +114,11 @@ constexpr bool kCameraOccluded = true;
 #else
 constexpr bool kCameraOccluded = false;
 #endif
-#if defined(UVS_CAMERA_HELD)
+#if defined(UVS_CAMERA_PAINTED)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = PaintedLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL camera_painted_kernel
+#elif defined(UVS_CAMERA_HELD)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = HeldLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL camera_held_kernel
@@ -123,10 +146,13 @@ __device__ __forceinline__ const uvs_occluder *occluders_of(const OccludedLoopAr
 // the longest hold and where the held-step counts go (never called on the other three blocks: HOLD is off there)
 __device__ __forceinline__ int hold_of(const LoopArgs &, int32_t *&held) { held = nullptr; return 0; }
 __device__ __forceinline__ int hold_of(const HeldLoopArgs &a, int32_t *&held) { held = a.held; return a.hold; }
+// the paints of the launch, or NULL (never called on the other four blocks: PAINT is off there)
+__device__ __forceinline__ const int32_t *paints_of(const LoopArgs &) { return nullptr; }
+__device__ __forceinline__ const int32_t *paints_of(const PaintedLoopArgs &a) { return a.paint; }
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
-    constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld;
+    constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld, PAINT = kCameraPainted;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -142,6 +168,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     __shared__ double s_park[PARK ? R * uvs::Sym<N>::NP : 1][PARK ? 64 : 1];
     __shared__ double s_tp[PTP ? G : 1][4];                      // PTP: the trial's kernel_bw, gain, reg, fpi_threshold
     __shared__ uint32_t s_occ[OCC ? W : 1][kOccluders];          // OCC: this step's rectangles of the wavefront's trial (occluder_rect's packing)
+    __shared__ uint32_t s_paint[PAINT ? W : 1];                  // PAINT: the paints of those rectangles, a byte each (paint_slot)
     __shared__ int s_miss[HOLD ? G : 1][kColours];               // HOLD: steps in a row, up to this one, at which the disc's pair was held
     __shared__ int s_held[HOLD ? G : 1][kColours];               // HOLD: steps at which it was held, while the trial's rows were due
 
@@ -260,15 +287,24 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         if constexpr (OCC) {                                     // lane o: rectangle o of this step, next to the projection
             if (lane < kOccluders) s_occ[w][lane] = lane < n_occ ? occluder_rect(occ_at[lane], k) : kNoRect;
         }
+        if constexpr (PAINT) {                                   // and its paint: byte o of the trial's dword
+            if (lane < kOccluders) {
+                const int32_t *paint = paints_of(A);
+                const bool given = paint != nullptr && lane < n_occ;
+                reinterpret_cast<uint8_t *>(&s_paint[w])[lane] = static_cast<uint8_t>(given ? paint_slot(paint[trial * n_occ + lane], npts) : kOpaque);
+            }
+        }
         __syncthreads();
         Rects rects;                                             // OCC off: never read
         if constexpr (OCC) {
 #pragma unroll
             for (int o = 0; o < kOccluders; ++o) rects.r[o] = s_occ[w][o];
         }
+        uint32_t paints = kNoPaints;                             // PAINT off: never read
+        if constexpr (PAINT) paints = s_paint[w];
 #pragma unroll 1
         for (int j = j_first; j < npts; j += j_step) {
-            const ColourSum sum = detect_pair<OCC>(s_disc[w], npts, j, lane, rects);
+            const ColourSum sum = detect_pair<OCC, PAINT>(s_disc[w], npts, j, lane, rects, paints);
             if (lane == 0) {                                     // the lane the shuffle tree ends in
                 double u, v;
                 noisy_centre(sum, noise_at, j, u, v);

@@ -1,5 +1,5 @@
 // What the one-launch pixel loops share, written ONCE: the sensor side of a step -- joints, projection, frame-free detection, lane 0's report,
-// the epilogue's stores -- for the estimator loop (camera_loop_device.hpp, four flavours) and the baseline loop (camera_analytical_device.hpp,
+// the epilogue's stores -- for the estimator loop (camera_loop_device.hpp, five flavours) and the baseline loop (camera_analytical_device.hpp,
 // two); the analytic initial guess of a trial for the two guess kernels; and the mapping's constants with the launch decision that goes with them.
 // The pieces are __device__ __forceinline__ functions over LDS row pointers and plain values: they declare no LDS and nothing is shared at
 // run time, so every kernel keeps the registers, LDS and scratch it had when the text was written out in it (a shared
@@ -57,22 +57,34 @@ __device__ __forceinline__ void project_lane_disc(const uvs_camera &cam, int p, 
 // ---- frame-free detection: feature pair j is the centre of mass of disc j's colour (npts == 1: green).  The 64 lanes walk the colour's four
 // 64-index blocks of centre_of_mass in index order -- only the blocks the disc's clipped bounding box touches.  All 64 lanes must call it,
 // on the same discs (and, OCC, the same rectangles); lane 0, where the shuffle tree ends, holds the sums.
-template <bool OCC>
-__device__ __forceinline__ ColourSum detect_pair(const double *disc_row, int npts, int j, int lane, const Rects &rects = Rects{}) {
+// PAINT (with OCC): the rectangles carry paints (vision_device.hpp).  The mask of the colour is then the disc's and that of the rectangles
+// painted it, so a block is touched when the disc's box OR such a rectangle reaches it -- also where the disc draws nothing at all.
+template <bool OCC, bool PAINT = false>
+__device__ __forceinline__ ColourSum detect_pair(const double *disc_row, int npts, int j, int lane, const Rects &rects = Rects{},
+                                                 uint32_t paints = kNoPaints) {
+    static_assert(OCC || !PAINT, "paints belong to rectangles");
     const Disc me = load_disc(disc_row + 3 * j, true);
     int x0, x1, y0, y1;
     disc_box(me, x0, x1, y0, y1);
     ColourSum sum;
+    int any_painted = 0;                                         // PAINT: is an active rectangle painted this colour?  Once per colour, uniform
+    if constexpr (PAINT) any_painted = painted_at_all(rects, paints, npts == 1 ? 1 : j);
 #pragma unroll 1
     for (int b = 0; b < 4; ++b) {
         const int lo = 64 * b, hi = lo + 63;
         // outside the clipped box disc_counts_at returns (0, 0) for all 64 indices, whose partial is (+0.0, +0.0, 0): exact to add, so not formed
-        const bool touched = me.r2 >= 0.0 && ((x0 <= hi && x1 >= lo) || (y0 <= hi && y1 >= lo));
+        bool touched = me.r2 >= 0.0 && ((x0 <= hi && x1 >= lo) || (y0 <= hi && y1 >= lo));
+        if constexpr (PAINT) {
+            if (any_painted) touched = touched || paint_reaches(rects, paints, npts == 1 ? 1 : j, lo, hi);
+        }
         double su = 0.0, sv = 0.0;
         int n = 0;
         if (__builtin_amdgcn_readfirstlane(static_cast<int>(touched))) {   // the same discs in every lane: wavefront-uniform
             int cc, rc;
-            disc_counts_in_box<OCC>(disc_row, npts, j, me, x0, x1, y0, y1, lo + lane, cc, rc, rects);
+            if constexpr (PAINT)
+                painted_counts_in_box(disc_row, npts, j, npts == 1 ? 1 : j, me, x0, x1, y0, y1, lo + lane, cc, rc, rects, paints, any_painted);
+            else
+                disc_counts_in_box<OCC>(disc_row, npts, j, me, x0, x1, y0, y1, lo + lane, cc, rc, rects);
             wave_partial(cc, rc, lo + lane, su, sv, n);
         }
         sum.add(su, sv, n);

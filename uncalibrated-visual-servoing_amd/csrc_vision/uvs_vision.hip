@@ -255,6 +255,121 @@ __global__ __launch_bounds__(kThreads) void camera_features_kernel(const uvs_cam
     centre_of_mass_of_block(cc, rc, cam.n_points, noise, f_out, pixels_out);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- painted occluders
+// The three kernels above with PAINTED rectangles (vision_device.hpp): kernels of their own names and texts, so that the six above keep
+// their code and their resource figures; what they compute with is the shared device functions.
+struct PaintArgs {
+    OccluderArgs<true> oa;
+    const int32_t *paint;                                        // [T][n_occ] or NULL: every rectangle opaque
+};
+// the paints of this workgroup's trial, in scalar registers like its rectangles
+__device__ __forceinline__ uint32_t paints_of_block(const PaintArgs &pa, int n_colours) {
+    const int32_t *mine = pa.paint != nullptr ? pa.paint + static_cast<int64_t>(blockIdx.x) * pa.oa.n_occ : nullptr;
+    return __builtin_amdgcn_readfirstlane(occluder_paints(mine, pa.oa.n_occ, n_colours));
+}
+// colour word of a slot (colour_word's, without the n == 1 mapping that paint_slot has already made)
+__device__ __forceinline__ uint32_t slot_word(uint32_t slot) { return colour_word(static_cast<int>(slot), kColours); }
+
+// render_discs_kernel<true>'s lane unit and skips; then the rectangles in index order, a later one in front: painted ones in their colour
+__global__ __launch_bounds__(kThreads) void paint_frames_kernel(const double *__restrict__ discs, int n_colours, uint32_t background,
+                                                                uint8_t *__restrict__ frames, int64_t frame_stride, const PaintArgs pa) {
+    const int tid = threadIdx.x;
+    const int cg = tid & 15, rg = tid >> 4;
+    uint8_t *frame = frames + static_cast<int64_t>(blockIdx.x) * frame_stride;
+    const double *mine = discs + static_cast<int64_t>(blockIdx.x) * (3 * n_colours);
+    Disc d[kColours];
+    int x0[kColours], x1[kColours], y0[kColours], y1[kColours];
+#pragma unroll
+    for (int k = 0; k < kColours; ++k) {
+        d[k] = load_disc(mine + 3 * (k < n_colours ? k : 0), k < n_colours);
+        disc_box(d[k], x0[k], x1[k], y0[k], y1[k]);
+    }
+    const uint32_t bg = background * 0x010101u;
+    const Rects rects = rects_of_block(pa.oa);
+    const uint32_t paints = paints_of_block(pa, n_colours);
+    uint32_t ink[kOccluders];                                    // what each rectangle shows
+#pragma unroll
+    for (int o = 0; o < kOccluders; ++o) ink[o] = paint_of(paints, o) == kOpaque ? pa.oa.shade * 0x010101u : slot_word(paint_of(paints, o));
+#pragma unroll
+    for (int j = 0; j < kPasses; ++j) {
+        const int row = j * 64 + rg, i = kSide - 1 - row;        // stored row, flipped row
+        const double fi = static_cast<double>(i);
+        double dy2[kColours];
+        bool any = rects_meet(rects, 16 * cg, 16 * cg + 15, i, i);
+#pragma unroll
+        for (int k = 0; k < kColours; ++k) {
+            const double dy = fi - d[k].v;
+            dy2[k] = dy * dy;
+            any = any || (d[k].r2 >= 0.0 && i >= y0[k] && i <= y1[k] && x0[k] <= 16 * cg + 15 && x1[k] >= 16 * cg);
+        }
+        const LineCover cover(rects, i, true);                   // the columns each rectangle covers of this row
+        uint32_t px[16];
+#pragma unroll
+        for (int p = 0; p < 16; ++p) px[p] = bg;
+        if (any) {
+#pragma unroll
+            for (int p = 0; p < 16; ++p) {
+                const int x = 16 * cg + p;
+                const double fj = static_cast<double>(x);
+#pragma unroll
+                for (int k = 0; k < kColours; ++k) {             // painter's order among the discs
+                    const double dx = fj - d[k].u;
+                    if (dx * dx + dy2[k] <= d[k].r2) px[p] = colour_word(k, n_colours);
+                }
+#pragma unroll
+                for (int o = 0; o < kOccluders; ++o)             // then among the rectangles: the highest index that holds the pixel owns it
+                    if (x >= cover.lo[o] && x <= cover.hi[o]) px[p] = ink[o];
+            }
+        }
+        uint4 *dst = reinterpret_cast<uint4 *>(frame + row * kRowBytes + cg * 48);
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {                            // render_discs_kernel's three 16-byte stores
+            uint32_t w[4];
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const int e = 4 * g + h;
+                const int q = (4 * e) / 3, s = (4 * e) % 3;
+                w[h] = s == 0 ? (px[q] | (px[q + 1] << 24)) : s == 1 ? ((px[q] >> 8) | (px[q + 1] << 16)) : ((px[q] >> 16) | (px[q + 1] << 8));
+            }
+            dst[g] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void paint_detect_kernel(const double *__restrict__ discs, int n_colours, const double *__restrict__ noise,
+                                                                double *__restrict__ f_out, int32_t *__restrict__ pixels_out, const PaintArgs pa) {
+    int cc, rc;
+    painted_counts(discs + static_cast<int64_t>(blockIdx.x) * (3 * n_colours), n_colours, cc, rc, rects_of_block(pa.oa), paints_of_block(pa, n_colours));
+    centre_of_mass_of_block(cc, rc, n_colours, noise, f_out, pixels_out);
+}
+
+// camera_features_kernel's joints and projection, on the same operands in the same order, then the painted counts
+__global__ __launch_bounds__(kThreads) void paint_camera_detect_kernel(const uvs_camera cam, const double *__restrict__ q_prev,
+                                                                       const double *__restrict__ dq, double dt, double *__restrict__ q_out,
+                                                                       const double *__restrict__ noise, double *__restrict__ f_out,
+                                                                       int32_t *__restrict__ pixels_out, double *__restrict__ discs_out,
+                                                                       const PaintArgs pa) {
+    __shared__ double sdisc[kColours * 3];
+    __shared__ double ssin[UVS_CAMERA_MAX_JOINTS], scos[UVS_CAMERA_MAX_JOINTS];
+    const int tid = threadIdx.x;
+    const int64_t t = blockIdx.x;
+    if (tid < cam.n_joints) joint_sincos(cam, t, tid, q_prev, dq, dt, q_out, ssin[tid], scos[tid]);
+    __syncthreads();
+    if (tid < cam.n_points) {
+        double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
+        for (int i = 0; i < cam.n_joints; ++i) chain_link(cam, i, ssin[i], scos[i], pose);
+        project_disc(cam, tid, pose, &sdisc[3 * tid]);
+        if (discs_out != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) discs_out[(t * cam.n_points + tid) * 3 + k] = sdisc[3 * tid + k];
+        }
+    }
+    __syncthreads();
+    int cc, rc;
+    painted_counts(sdisc, cam.n_points, cc, rc, rects_of_block(pa.oa), paints_of_block(pa, cam.n_points));
+    centre_of_mass_of_block(cc, rc, cam.n_points, noise, f_out, pixels_out);
+}
+
 thread_local char g_err[256] = "";
 
 int fail(int code, const char *fmt, const char *detail) {
@@ -416,6 +531,48 @@ int uvs_camera_features_occluded_f64(const uvs_camera *cam, int64_t T, const dou
     hipLaunchKernelGGL(camera_features_kernel<true>, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), *cam,
                        q_prev, dq, dt, q_out, noise, f_out, pixels_out, discs_out, OccluderArgs<true>{occ, n_occ, k, 0u});
     return launched("camera_features_kernel<occluded> launch: %s");
+}
+
+// The three occluded entry points with `paint` after `occ`: their refusals, in their order; a NULL paint is legal (every rectangle opaque)
+int uvs_render_discs_painted_u8(int64_t T, const double *discs, int32_t n_colours, int32_t background, const uvs_occluder *occ,
+                                const int32_t *paint, int32_t n_occ, int32_t k, int32_t shade, uint8_t *frames, int64_t frame_stride_bytes,
+                                void *stream) {
+    g_err[0] = '\0';
+    if (const int rc = check_render(T, discs, n_colours, background, frames, frame_stride_bytes)) return rc;
+    if (const int rc = check_occluders(occ, n_occ)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (shade < 0 || shade >= kThreshold) return fail(UVS_ERR_ARG, "%s", "shade must be 0 .. 249 (250 and above would enter a mask)");
+    if (T == 0) return UVS_OK;
+    hipLaunchKernelGGL(paint_frames_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), discs,
+                       static_cast<int>(n_colours), static_cast<uint32_t>(background), frames, frame_stride_bytes,
+                       PaintArgs{{occ, n_occ, k, static_cast<uint32_t>(shade)}, paint});
+    return launched("paint_frames_kernel launch: %s");
+}
+
+int uvs_disc_features_painted_f64(int64_t T, const double *discs, int32_t n_colours, const uvs_occluder *occ, const int32_t *paint, int32_t n_occ,
+                                  int32_t k, const double *noise, double *f_out, int32_t *pixels_out, void *stream) {
+    g_err[0] = '\0';
+    if (const int rc = check_disc_features(T, discs, n_colours, f_out)) return rc;
+    if (const int rc = check_occluders(occ, n_occ)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (T == 0) return UVS_OK;
+    hipLaunchKernelGGL(paint_detect_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), discs,
+                       static_cast<int>(n_colours), noise, f_out, pixels_out, PaintArgs{{occ, n_occ, k, 0u}, paint});
+    return launched("paint_detect_kernel launch: %s");
+}
+
+int uvs_camera_features_painted_f64(const uvs_camera *cam, int64_t T, const double *q_prev, const double *dq, double dt, double *q_out,
+                                    const uvs_occluder *occ, const int32_t *paint, int32_t n_occ, int32_t k, const double *noise,
+                                    double *f_out, int32_t *pixels_out, double *discs_out, void *stream) {
+    g_err[0] = '\0';
+    if (f_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL f_out");
+    if (const int rc = check_camera(cam, T, q_prev, q_out)) return rc;
+    if (const int rc = check_occluders(occ, n_occ)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (T == 0) return UVS_OK;
+    hipLaunchKernelGGL(paint_camera_detect_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), *cam,
+                       q_prev, dq, dt, q_out, noise, f_out, pixels_out, discs_out, PaintArgs{{occ, n_occ, k, 0u}, paint});
+    return launched("paint_camera_detect_kernel launch: %s");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// Device code shared by all seven translation units of libuvs_vision.so (uvs_vision.hip directly, the six loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
-// forms its callers need, the disc geometry of the synthetic camera with its occluders, and the DH chain.  The summation order of the phase 2 is a contract
+// Device code shared by all eight translation units of libuvs_vision.so (uvs_vision.hip directly, the seven loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
+// forms its callers need, the disc geometry of the synthetic camera with its occluders and their paints, and the DH chain.  The summation order of the phase 2 is a contract
 // (see centre_of_mass): every unit that sums mask pixels goes through wave_partial and ColourSum, so they all give the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -330,6 +330,105 @@ __device__ __forceinline__ void disc_counts_at(const double *discs, int n_colour
 template <bool OCC = false>
 __device__ __forceinline__ void disc_counts(const double *discs, int n_colours, int &cc, int &rc, const Rects &rects = Rects{}) {
     disc_counts_at<OCC>(discs, n_colours, threadIdx.x >> 8, threadIdx.x & 255, cc, rc, rects);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- painted occluders
+// The paints of a trial's rectangles as the kernels hold them: one dword, byte o = the colour SLOT (red, green, blue, pink: 0 .. 3) that
+// rectangle o is painted, or kOpaque.  paint_slot is THE rule of the header (uvs_vision.h, "paint"), total: a value p in
+// 0 .. n_colours - 1 is the colour of disc p (n_colours == 1: the green one), every other int32 is opaque.
+constexpr uint32_t kOpaque = 0xffu;
+constexpr uint32_t kNoPaints = 0xffffffffu;                     // four opaque rectangles
+
+__device__ __forceinline__ uint32_t paint_slot(int32_t p, int n_colours) {
+    if (p < 0 || p >= n_colours) return kOpaque;
+    return n_colours == 1 ? 1u : static_cast<uint32_t>(p);
+}
+__device__ __forceinline__ uint32_t paint_of(uint32_t paints, int o) { return (paints >> (8 * o)) & 0xffu; }
+
+// The paints of one trial: paint names the trial's n_occ values (read only when it is not NULL and n_occ > 0)
+__device__ __forceinline__ uint32_t occluder_paints(const int32_t *paint, int n_occ, int n_colours) {
+    uint32_t out = kNoPaints;
+    if (paint == nullptr) return out;
+#pragma unroll
+    for (int o = 0; o < kOccluders; ++o)
+        if (o < n_occ) out = (out & ~(0xffu << (8 * o))) | (paint_slot(paint[o], n_colours) << (8 * o));
+    return out;
+}
+
+// Rectangle o is active and painted slot c
+__device__ __forceinline__ bool painted(const Rects &rects, uint32_t paints, int o, int c) {
+    return paint_of(paints, o) == static_cast<uint32_t>(c) && rect_x0(rects.r[o]) <= rect_x1(rects.r[o]);
+}
+
+// Does an active rectangle painted slot c reach the indices [lo, hi], in columns or in flipped rows?  (All of them: lo = 0, hi = 255.)
+__device__ __forceinline__ bool paint_reaches(const Rects &rects, uint32_t paints, int c, int lo, int hi) {
+    bool reaches = false;
+#pragma unroll
+    for (int o = 0; o < kOccluders; ++o) {
+        const uint32_t r = rects.r[o];
+        reaches = reaches || (painted(rects, paints, o, c) && ((rect_x0(r) <= hi && rect_x1(r) >= lo) || (rect_y0(r) <= hi && rect_y1(r) >= lo)));
+    }
+    return reaches;
+}
+
+// Pixels of [a, b] on one line that the rectangles in front of rectangle o (those of a higher index) leave to it.  lo / hi: what each
+// rectangle covers of the line (LineCover's members).  Inclusion and exclusion over the at most three ranges in front, each clipped to
+// [a, b]; an empty range has lo > hi, stays empty in every intersection and counts 0.  Integers only.
+__device__ __forceinline__ int owned_on_line(const int (&lo)[kOccluders], const int (&hi)[kOccluders], int o, int a, int b) {
+    int l[kOccluders - 1], h[kOccluders - 1];
+#pragma unroll
+    for (int k = 0; k < kOccluders - 1; ++k) {
+        const int f = o + 1 + k;                                 // in front of o, or no rectangle at all: nothing
+        const bool is_rect = f >= 0 && f < kOccluders;
+        l[k] = is_rect ? max(lo[is_rect ? f : o], a) : 1;
+        h[k] = is_rect ? min(hi[is_rect ? f : o], b) : 0;
+    }
+    const auto len = [](int x, int y) { return y >= x ? y - x + 1 : 0; };
+    const int two = len(max(l[0], l[1]), min(h[0], h[1])) + len(max(l[0], l[2]), min(h[0], h[2])) + len(max(l[1], l[2]), min(h[1], h[2]));
+    const int three = len(max(max(l[0], l[1]), l[2]), min(min(h[0], h[1]), h[2]));
+    return len(a, b) - (len(l[0], h[0]) + len(l[1], h[1]) + len(l[2], h[2]) - two + three);
+}
+
+// What the rectangles painted slot c add to the counts of index i: for every such rectangle that meets column i the rows of it that no
+// rectangle in front of it takes, and likewise for flipped row i.  A pixel has one owner, so nothing is counted twice -- neither among the
+// rectangles nor with the disc's own walk, which leaves out every pixel an active rectangle covers.
+__device__ __forceinline__ void paint_counts(const Rects &rects, uint32_t paints, int c, int i, int &cc, int &rc) {
+    const LineCover column(rects, i, false), row(rects, i, true);    // formed once per line
+#pragma unroll
+    for (int o = 0; o < kOccluders; ++o) {
+        const bool mine = painted(rects, paints, o, c);
+        if (mine && column.lo[o] <= column.hi[o]) cc += owned_on_line(column.lo, column.hi, o, column.lo[o], column.hi[o]);
+        if (mine && row.lo[o] <= row.hi[o]) rc += owned_on_line(row.lo, row.hi, o, row.lo[o], row.hi[o]);
+    }
+}
+
+// Counts of index i for colour slot c = the colour of disc `own` in the frame with painted rectangles: the disc's pixels behind ALL active
+// rectangles (the occluded walk as it is, when the disc draws anything: me.r2 >= 0), and the pixels of the rectangles painted c.
+// `any_painted` = painted_at_all(rects, paints, c), formed ONCE per colour by the caller: a colour no active rectangle is painted takes
+// exactly the occluded path, and pays one test per colour for it, not one per index block.  Both decisions are wavefront-uniform.
+__device__ __forceinline__ int painted_at_all(const Rects &rects, uint32_t paints, int c) {
+    return __builtin_amdgcn_readfirstlane(static_cast<int>(paint_reaches(rects, paints, c, 0, kSide - 1)));
+}
+__device__ __forceinline__ void painted_counts_in_box(const double *discs, int n_colours, int own, int c, const Disc &me, int x0, int x1, int y0, int y1,
+                                                      int i, int &cc, int &rc, const Rects &rects, uint32_t paints, int any_painted) {
+    cc = 0;
+    rc = 0;
+    if (__builtin_amdgcn_readfirstlane(static_cast<int>(me.r2 >= 0.0)))
+        disc_counts_in_box<true>(discs, n_colours, own, me, x0, x1, y0, y1, i, cc, rc, rects);
+    if (any_painted) paint_counts(rects, paints, c, i, cc, rc);
+}
+
+// disc_counts<true> for thread (colour c = tid >> 8, index i = tid & 255) of a one-workgroup-per-frame kernel, with paints
+__device__ __forceinline__ void painted_counts(const double *discs, int n_colours, int &cc, int &rc, const Rects &rects, uint32_t paints) {
+    const int c = threadIdx.x >> 8, i = threadIdx.x & 255;
+    const int own = disc_of_colour(c, n_colours);
+    cc = 0;
+    rc = 0;
+    if (own < 0) return;                                         // no disc of this colour, so no paint of it either (paint_slot)
+    const Disc me = load_disc(discs + 3 * own, true);
+    int x0, x1, y0, y1;
+    disc_box(me, x0, x1, y0, y1);
+    painted_counts_in_box(discs, n_colours, own, c, me, x0, x1, y0, y1, i, cc, rc, rects, paints, painted_at_all(rects, paints, c));
 }
 
 // Joint i of trial t -- q = q_prev + dq * dt when dq is given, written to q_out when that is given -- and the sine and cosine of its DH angle.

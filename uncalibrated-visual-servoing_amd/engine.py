@@ -430,14 +430,46 @@ def _occluder_operand(checked, dev):
     return (t.data_ptr() if t.numel() else None), t.shape[1], t
 
 
-def render_discs(discs, n_colours=4, background=96, out=None, occluders=None, k=0, shade=32):
+def _check_occluder_colours(spec, checked, T, n_colours, who='occluder_colours'):
+    """What can be said of the occluders' paints on the host alone, before any device work: ValueError, or the operand -- None, the
+    caller's own packed device (or pinned) int32 tensor (T, n_occ), or a checked host int32 array (T, n_occ).  ``checked``: what
+    ``_check_occluders`` returned for the same call (None: there are no occluders to paint, a ValueError)."""
+    import torch                                                     # not _torch(): these refusals need no GPU
+    from . import plant as plant_mod
+    if spec is None:
+        return None
+    n_occ = None if checked is None else checked.shape[1]
+    if torch.is_tensor(spec) and (spec.is_cuda or spec.is_pinned()):
+        if n_occ is None:
+            raise ValueError(f'{who}: occluder_colours without occluders: a paint belongs to a rectangle')
+        if spec.dtype != torch.int32 or tuple(spec.shape) != (T, n_occ) or not spec.is_contiguous():
+            raise ValueError(f'{who}: a packed tensor of paints is contiguous int32 ({T}, {n_occ}), got {spec.dtype} {tuple(spec.shape)}')
+        return spec                                                  # its values are the device's to read: anything but a disc is opaque
+    try:
+        return plant_mod.occluder_colour_array(spec.numpy() if torch.is_tensor(spec) else spec, n_occ, int(n_colours), T).astype(np.int32)
+    except ValueError as exc:
+        raise ValueError(f'{who}: {exc}') from exc
+
+
+def _paint_operand(checked, dev):
+    """(pointer or None, tensor to keep alive) of what _check_occluder_colours returned (not None)."""
+    torch = _torch()
+    t = checked if torch.is_tensor(checked) else torch.from_numpy(np.ascontiguousarray(checked)).to(dev)
+    return (t.data_ptr() if t.numel() else None), t
+
+
+def render_discs(discs, n_colours=4, background=96, out=None, occluders=None, k=0, shade=32, occluder_colours=None):
     """Rasterise ``discs`` (T, n_colours, 3) fp64 rows (u, v, r) into camera frames on the current stream (uvs_render_discs_u8; the pixel rule
     is ``plant.render_discs``'s, byte for byte).  Returns ``out``: uint8 (T, 256, 256, 3), unflipped as the detectors expect them, on the device
     unless the caller passes its own device or pinned tensor -- whose frame stride is free (bytes between frames are not written).
     ``occluders`` (what ``occluders()`` takes or returns), the step ``k`` and ``shade``: the frames with those rectangles in front
-    (uvs_render_discs_occluded_u8; ``plant.render_discs(..., occluders, k, shade)`` byte for byte).  None is the call above."""
+    (uvs_render_discs_occluded_u8; ``plant.render_discs(..., occluders, k, shade)`` byte for byte).  None is the call above.
+    ``occluder_colours``: the occluders' paints, (n_occ,) or (T, n_occ) integers or a packed int32 tensor (T, n_occ): a rectangle painted
+    p shows disc p's colour, -1 is opaque (uvs_render_discs_painted_u8; ``plant.render_discs(..., occluder_colours=)`` byte for byte).
+    None is the call without the argument, through the entry point it always used."""
     from . import _vision
     checked = _check_occluders(occluders, getattr(discs, 'shape', (0,))[0], k, shade, 'render_discs')
+    paints = _check_occluder_colours(occluder_colours, checked, getattr(discs, 'shape', (0,))[0], n_colours, 'render_discs')
     torch = _torch()
     T, ptr = _discs_arg(discs, n_colours)
     if out is None:
@@ -450,18 +482,25 @@ def render_discs(discs, n_colours=4, background=96, out=None, occluders=None, k=
         rc = _vision.lib().uvs_render_discs_u8(T, ptr, int(n_colours), int(background), frames.data_ptr(), stride, _stream())
     else:
         occ, n_occ, _keep = _occluder_operand(checked, _device_of(discs))
-        rc = _vision.lib().uvs_render_discs_occluded_u8(T, ptr, int(n_colours), int(background), occ, n_occ, int(k), int(shade),
-                                                        frames.data_ptr(), stride, _stream())
+        if paints is None:
+            rc = _vision.lib().uvs_render_discs_occluded_u8(T, ptr, int(n_colours), int(background), occ, n_occ, int(k), int(shade),
+                                                            frames.data_ptr(), stride, _stream())
+        else:
+            paint, _keep_paint = _paint_operand(paints, _device_of(discs))
+            rc = _vision.lib().uvs_render_discs_painted_u8(T, ptr, int(n_colours), int(background), occ, paint, n_occ, int(k), int(shade),
+                                                           frames.data_ptr(), stride, _stream())
     _vision.check(rc)
     return out
 
 
-def disc_features(discs, n_colours=4, noise=None, out=None, pixels=None, occluders=None, k=0):
+def disc_features(discs, n_colours=4, noise=None, out=None, pixels=None, occluders=None, k=0, occluder_colours=None):
     """The frame-free detector (uvs_disc_features_f64): what ``detect_circles(render_discs(discs))`` returns, bit for bit, in one launch that
     never writes a frame.  Arguments and result as ``detect_circles`` with ``discs`` (T, n_colours, 3) in place of the frames.  With
-    ``occluders`` at step ``k`` (uvs_disc_features_occluded_f64) it is ``detect_circles(render_discs(discs, occluders=..., k=k))``."""
+    ``occluders`` at step ``k`` (uvs_disc_features_occluded_f64) it is ``detect_circles(render_discs(discs, occluders=..., k=k))``, and with
+    ``occluder_colours``, their paints as ``render_discs`` takes them (uvs_disc_features_painted_f64), that of the painted frames."""
     from . import _vision
     checked = _check_occluders(occluders, getattr(discs, 'shape', (0,))[0], k, who='disc_features')
+    paints = _check_occluder_colours(occluder_colours, checked, getattr(discs, 'shape', (0,))[0], n_colours, 'disc_features')
     torch = _torch()
     T, ptr = _discs_arg(discs, n_colours)
     m = 2 * int(n_colours)
@@ -473,19 +512,26 @@ def disc_features(discs, n_colours=4, noise=None, out=None, pixels=None, occlude
         rc = _vision.lib().uvs_disc_features_f64(T, ptr, int(n_colours), *rest)
     else:
         occ, n_occ, _keep = _occluder_operand(checked, _device_of(discs))
-        rc = _vision.lib().uvs_disc_features_occluded_f64(T, ptr, int(n_colours), occ, n_occ, int(k), *rest)
+        if paints is None:
+            rc = _vision.lib().uvs_disc_features_occluded_f64(T, ptr, int(n_colours), occ, n_occ, int(k), *rest)
+        else:
+            paint, _keep_paint = _paint_operand(paints, _device_of(discs))
+            rc = _vision.lib().uvs_disc_features_painted_f64(T, ptr, int(n_colours), occ, paint, n_occ, int(k), *rest)
     _vision.check(rc)
     return out
 
 
-def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_out=None, out=None, pixels=None, discs=None, occluders=None, k=0):
+def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_out=None, out=None, pixels=None, discs=None, occluders=None, k=0,
+                    occluder_colours=None):
     """``camera_project`` and ``disc_features`` in one launch (uvs_camera_features_f64), bit-identical to the two in a row: joints in, noisy
     detected features (T, 2 n_points) out.  ``discs`` (T, n_points, 3) receives the projection when given.  ``occluders`` at step ``k``:
-    uvs_camera_features_occluded_f64, the two occluded calls in a row."""
+    uvs_camera_features_occluded_f64, the two occluded calls in a row; with ``occluder_colours`` uvs_camera_features_painted_f64, the two
+    painted ones."""
     from . import _vision, plant as plant_mod
     checked = _check_occluders(occluders, getattr(q_prev, 'shape', (0,))[0], k, who='camera_features')
-    torch = _torch()
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    paints = _check_occluder_colours(occluder_colours, checked, getattr(q_prev, 'shape', (0,))[0], cam.n_points, 'camera_features')
+    torch = _torch()
     T, n, npts = q_prev.shape[0], cam.n_joints, cam.n_points
     if out is None:
         out = torch.empty((T, 2 * npts), dtype=torch.float64, device=_device_of(q_prev))
@@ -497,7 +543,11 @@ def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_o
         rc = _vision.lib().uvs_camera_features_f64(*joints, *rest)
     else:
         occ, n_occ, _keep = _occluder_operand(checked, _device_of(q_prev))
-        rc = _vision.lib().uvs_camera_features_occluded_f64(*joints, occ, n_occ, int(k), *rest)
+        if paints is None:
+            rc = _vision.lib().uvs_camera_features_occluded_f64(*joints, occ, n_occ, int(k), *rest)
+        else:
+            paint, _keep_paint = _paint_operand(paints, _device_of(q_prev))
+            rc = _vision.lib().uvs_camera_features_painted_f64(*joints, occ, paint, n_occ, int(k), *rest)
     _vision.check(rc)
     return out
 
@@ -670,13 +720,18 @@ CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
 ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
 
 
-def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None):
+def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=None):
     """The stepwise loops' sensor launch at step k: uvs_camera_features_f64, or its occluded namesake when ``occ`` -- None, or the
     (pointer, n_occ, tensor) of ``_occluder_operand`` -- is given.  Returns f(k, q_prev, dq_prev, q, noise, f, pixels) -> return code.
     With ``hold`` > 0 the step is that launch and uvs_hold_features_f64 behind it on the same stream, on the same rows: the callable then
-    takes two more row pointers, f(..., pixels, f_prev, held), and keeps the counters of consecutive held steps (T, 4) itself."""
+    takes two more row pointers, f(..., pixels, f_prev, held), and keeps the counters of consecutive held steps (T, 4) itself.
+    ``paint``: None, or the (pointer, tensor) of ``_paint_operand`` next to ``occ`` -- the launch is then uvs_camera_features_painted_f64."""
     from . import _vision
-    if occ is None:
+    if paint is not None:
+        painted = _vision.lib().uvs_camera_features_painted_f64
+        detect = lambda k, q_prev, dq_prev, q, noise, f, pixels: painted(cam_ref, T, q_prev, dq_prev, dt, q, occ[0], paint[0], occ[1], k, noise,   # noqa: E731
+                                                                         f, pixels, None, stream)
+    elif occ is None:
         plain = _vision.lib().uvs_camera_features_f64
         detect = lambda k, q_prev, dq_prev, q, noise, f, pixels: plain(cam_ref, T, q_prev, dq_prev, dt, q, noise, f, pixels, None, stream)   # noqa: E731
     else:
@@ -694,11 +749,11 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None):
     return held_step
 
 
-def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0):
+def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
     ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models.
     ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none).  ``hold`` > 0 (stepwise alone): a third launch per
-    step, uvs_hold_features_f64, between the two."""
+    step, uvs_hold_features_f64, between the two.  ``paint``: None, or the paint operand next to ``occ`` (stepwise alone)."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -724,7 +779,7 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev)
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint)
     held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     if believed is None:
         step = lambda *rows: _vision.lib().uvs_camera_analytical_step_f64(fp_ref, cam_ref, T, *rows)          # noqa: E731
@@ -808,12 +863,14 @@ def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
     return tp, keep
 
 
-def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0):
+def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0, paints=None):
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
     then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
     ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
     ``_gather_by_source``) -- the launch is then uvs_camera_closed_loop_occluded_f64, with or without trial_params.  ``hold`` > 0: the launch
-    is uvs_camera_closed_loop_held_f64, with or without either, and the result has 'held'."""
+    is uvs_camera_closed_loop_held_f64, with or without either, and the result has 'held'.  ``paints``: None, or what
+    ``_check_occluder_colours`` returned next to ``occluders`` -- the launch is then uvs_camera_closed_loop_painted_f64 for any hold >= 0,
+    and the result has 'held' only with hold > 0."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -825,8 +882,9 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     noise_ptr = _operand(noise, 'noise', torch.float64, (K, n_in, m), True)
     f0 = torch.zeros((n_in, m), **f64)
     occ = None if occluders is None else _occluder_operand(occluders, dev)
-    if fp.initial_guess:
-        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2])     # the step-0 frame, occluders at k = 0 included
+    paint = None if paints is None else _paint_operand(paints, dev)
+    if fp.initial_guess:                                             # the step-0 frame, occluders at k = 0 and their paints included
+        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2], occluder_colours=None if paint is None else paint[1])
         if x0 is None and guess == 'device':
             x0 = camera_guess(cam, q_start, f0)
     if x0 is None:
@@ -840,6 +898,14 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
     operands = (q0, noise_ptr, X0.data_ptr(), f0.data_ptr(), ptr('q'), ptr('f'), ptr('dq'), ptr('err'), ptr('kappa'), status.data_ptr(),
                 k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
+    if paint is not None:
+        held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
+        rc = _vision.lib().uvs_camera_closed_loop_painted_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp), occ[0], paint[0],
+                                                              occ[1], hold, *operands[:-1], None if held is None else held.data_ptr(),
+                                                              operands[-1])
+        _vision.check(rc)
+        out = dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
+        return dict(out, held=held) if hold else out
     if hold:
         held = torch.empty((T, npts), dtype=torch.int32, device=dev)
         rc = _vision.lib().uvs_camera_closed_loop_held_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp),
@@ -876,7 +942,7 @@ def _gather_by_source(q_start, noise, x0, trial_params):
 
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
-                       believed_index=None, trial_params=None, occluders=None, hold=0):
+                       believed_index=None, trial_params=None, occluders=None, hold=0, occluder_colours=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -931,7 +997,16 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     including k_done at which each disc was held ('pixels' still shows the smallest mask, 0 after a hold).  fused=True with an estimator
     is ONE launch (uvs_camera_closed_loop_held_f64), with or without ``occluders`` and ``trial_params``; fused=False is three launches per
     step (uvs_hold_features_f64 between the two) for the estimators and the calibrated and believed baselines alike; the two return the
-    same bits.  fused=True with ANALYTICAL and hold > 0 is a ValueError -- use fused=False: the baseline's one-launch loops hold nothing."""
+    same bits.  fused=True with ANALYTICAL and hold > 0 is a ValueError -- use fused=False: the baseline's one-launch loops hold nothing.
+    ``occluder_colours``: the PAINT of every occluder, per OUTPUT trial like the occluders -- (n_occ,) or (T, n_occ) integers, or a packed
+    int32 tensor (T, n_occ): p in 0 .. n_points - 1 paints the rectangle the colour of disc p, a DISTRACTOR whose pixels enter that
+    colour's mask and pull its centroid; -1 leaves it opaque (the rule: ``plant.render_discs(occluder_colours=)``; include/uvs_vision.h).
+    The detector never reports a loss for a colour whose distractor is visible, so ``hold`` does not step in there.  f0 and the initial
+    guess come from the step-0 frame, painted rectangles included.  None (the default) is the call without the argument.  fused=True with
+    an estimator is ONE launch, uvs_camera_closed_loop_painted_f64, with or without ``trial_params`` and for any ``hold``; fused=False
+    passes the paints to uvs_camera_features_painted_f64 at every step, for the estimators and the calibrated and believed baselines
+    alike; the two return the same bits.  It needs ``occluders`` (ValueError), and fused=True with ANALYTICAL stays the ValueError it is
+    for occluders."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
@@ -946,6 +1021,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         if isinstance(trial_params, dict) and trial_params.get('source') is not None:
             n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
         occluders = _check_occluders(occluders, n_out, who='camera_closed_loop: occluders')
+    paints = _check_occluder_colours(occluder_colours, occluders, None if occluders is None else occluders.shape[0], fp.m // 2,
+                                     'camera_closed_loop')
     if trial_params is not None:
         if not fused:
             raise ValueError('camera_closed_loop: trial_params needs fused=True: the two-launch step kernel has no per-trial flavour')
@@ -987,21 +1064,22 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
         occ = None if occluders is None else _occluder_operand(occluders, dev)
+        paint = None if paints is None else _paint_operand(paints, dev)
         if believed is None:
-            return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, occ=occ, hold=hold)
+            return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, occ=occ, hold=hold, paint=paint)
         *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
-        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold)
+        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold, paint=paint)
     if believed is not None:                                         # an estimator that starts from the wrong model; the rest is the x0= path
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        x0 = camera_guess(cam, q_start, camera_features(cam, q_start, occluders=occluders), radius=radius, believed=believed,
+        x0 = camera_guess(cam, q_start, camera_features(cam, q_start, occluders=occluders, occluder_colours=paints), radius=radius, believed=believed,
                           believed_index=believed_index)
     if fused and (x0 is not None or guess == 'device' or not fp.initial_guess):
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -1013,8 +1091,9 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     f64 = dict(dtype=torch.float64, device=dev)
     f0 = torch.zeros((T, m), **f64)
     occ = None if occluders is None else _occluder_operand(occluders, dev)
-    if fp.initial_guess:
-        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2])     # the step-0 frame, occluders at k = 0 included
+    paint = None if paints is None else _paint_operand(paints, dev)
+    if fp.initial_guess:                                             # the step-0 frame, occluders at k = 0 and their paints included
+        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2], occluder_colours=None if paint is None else paint[1])
         if x0 is None and guess == 'device':
             x0 = camera_guess(cam, q_start, f0)
         if x0 is None:
@@ -1028,7 +1107,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         raise ValueError('camera_closed_loop: x0 is needed when fp.initial_guess is 0 (the reference draws it unseeded, experiment.py:117)')
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2], hold)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2], hold,
+                                         None if paint is None else paint[1])
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
@@ -1036,7 +1116,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     dq_zero = torch.zeros((T, n), **f64)
     step = _lib.lib().uvs_rmckf_step_f64
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev)
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint)
     held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
     if hold:

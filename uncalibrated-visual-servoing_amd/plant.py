@@ -86,7 +86,37 @@ def occluder_rects(occluders, k):
     return out
 
 
-def render_discs(discs, n_colours=4, background=96, occluders=None, k=0, shade=32):
+OPAQUE = -1                             # the paint of an occluder that takes no disc's colour
+
+
+def occluder_colour_array(occluder_colours, n_occ, n_colours, T=None):
+    """``occluder_colours`` -- the PAINT of every occluder -- as an int64 host array (T, n_occ): from (n_occ,) -- every trial the same -- or
+    (T, n_occ) integers.  A value p in 0 .. n_colours - 1 paints the rectangle the colour of disc p (n_colours == 1: 0 is the green one),
+    ``OPAQUE`` (-1) leaves it the opaque occluder it was.  ValueError for any other value, for anything that is not such an array, for a
+    length that is not ``n_occ`` (None: the caller has no occluders), or for a T that does not match."""
+    if n_occ is None:
+        raise ValueError('occluder_colours without occluders: a paint belongs to a rectangle')
+    try:
+        a = np.asarray(occluder_colours)
+    except Exception as exc:                                         # ragged lists
+        raise ValueError('occluder_colours: (n_occ,) or (T, n_occ) integers') from exc
+    if a.size == 0 and a.ndim == 1:                                  # []: no occluder to paint
+        a = np.zeros((0,), np.int64)
+    if a.dtype.kind not in 'iu' or a.ndim not in (1, 2):
+        raise ValueError(f'occluder_colours: (n_occ,) or (T, n_occ) integers, got {a.dtype} {a.shape}')
+    if a.shape[-1] != n_occ:
+        raise ValueError(f'occluder_colours: {a.shape[-1]} paints for {n_occ} occluders')
+    if a.size and (a.min() < OPAQUE or a.max() >= n_colours):
+        raise ValueError(f'occluder_colours: every value is {OPAQUE} (opaque) or a disc 0 .. {n_colours - 1}')
+    a = a.astype(np.int64)
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (1 if T is None else T,) + a.shape)
+    elif T is not None and a.shape[0] != T:
+        raise ValueError(f'occluder_colours: {a.shape[0]} trials of paints for {T} trials')
+    return np.ascontiguousarray(a)
+
+
+def render_discs(discs, n_colours=4, background=96, occluders=None, k=0, shade=32, occluder_colours=None):
     """Camera frames of coloured discs: the numpy statement of the pixel rule uvs_render_discs_u8 (include/uvs_vision.h) is held to.
     ``discs``: (n_colours, 3) or (T, n_colours, 3) rows (u, v, r) in pixels of the flipped frame (u right, v down), colour order red,
     green, blue, pink (n_colours == 1: the green disc).  Pixel (flipped row i, column j) belongs to disc c iff r_c >= 0 and
@@ -95,6 +125,10 @@ def render_discs(discs, n_colours=4, background=96, occluders=None, k=0, shade=3
     ``occluders``: None, or (n_occ, 8) / (T, n_occ, 8) integer rows of ``OCCLUDER_FIELDS`` -- rectangles in front of the discs at step ``k``
     (``occluder_rects``): a covered pixel belongs to no disc and is ``shade`` (0 .. 249) in all three channels; the covered set is the union.
     This function is the statement of that rule too (uvs_render_discs_occluded_u8 and the occluded detectors are held to it).
+    ``occluder_colours``: None, or the PAINT of every occluder (``occluder_colour_array``: (n_occ,) or (T, n_occ) integers).  Rectangle o' is
+    in front of rectangle o when o' > o, and all are in front of every disc: a pixel belongs to the highest-index active rectangle that
+    contains it, else to the topmost disc, else to the background.  A rectangle painted p shows ``DISC_COLOURS`` of disc p -- a DISTRACTOR:
+    its pixels enter that colour's mask -- and an ``OPAQUE`` one shows ``shade``.  None, or all opaque, is the union of above.
     Returns uint8 (256, 256, 3) or (T, 256, 256, 3), UNFLIPPED as the sensor hands frames over (flipped row i is row 255 - i)."""
     discs = np.asarray(discs, float)
     if n_colours not in (1, 3, 4) or discs.shape[-2:] != (n_colours, 3) or discs.ndim not in (2, 3):
@@ -107,6 +141,8 @@ def render_discs(discs, n_colours=4, background=96, occluders=None, k=0, shade=3
             raise ValueError('shade must be 0 .. 249: 250 and above would enter a mask of the detectors')
         occluders = occluder_array(occluders, len(batch))
         rects = [occluder_rects(rows, k) for rows in occluders]     # refuses k < 0
+    if occluder_colours is not None:
+        paints = occluder_colour_array(occluder_colours, None if occluders is None else occluders.shape[1], n_colours, len(batch))
     grid = np.arange(RESOLUTION, dtype=float)
     frames = np.full((len(batch), RESOLUTION, RESOLUTION, 3), background, np.uint8)
     with np.errstate(invalid='ignore', over='ignore'):
@@ -117,8 +153,9 @@ def render_discs(discs, n_colours=4, background=96, occluders=None, k=0, shade=3
                 dx, dy = grid[None, :] - u, grid[:, None] - v
                 frame[(dx * dx + dy * dy) <= r * r] = DISC_COLOURS[1 if n_colours == 1 else c]
             if occluders is not None:
-                for x0, x1, y0, y1 in rects[t]:                      # NO_RECT: an empty slice
-                    frame[y0:y1 + 1, x0:x1 + 1] = shade
+                for o, (x0, x1, y0, y1) in enumerate(rects[t]):      # NO_RECT: an empty slice; a later rectangle overwrites an earlier one
+                    p = OPAQUE if occluder_colours is None else int(paints[t, o])
+                    frame[y0:y1 + 1, x0:x1 + 1] = shade if p == OPAQUE else DISC_COLOURS[1 if n_colours == 1 else p]
     frames = frames[:, ::-1].copy()
     return frames[0] if discs.ndim == 2 else frames
 
@@ -449,12 +486,17 @@ class CameraRobot:
     goal pose (depth 0.602 m, focal 200.9 px).  A disc is drawn as a circle, not as the ellipse a tilted camera would see.
     ``occluders``: None, or (n_occ, 8) integer rows of ``OCCLUDER_FIELDS``, drawn in ``shade`` at the robot's step count ``k`` -- 0 from
     ``start()`` on, one more with every ``step()`` after it, so that the loop's guess image and its first image are both the step-0 frame,
-    as in ``engine.camera_closed_loop(occluders=...)``."""
+    as in ``engine.camera_closed_loop(occluders=...)``.  ``occluder_colours``: None, or (n_occ,) paints of those occluders
+    (``occluder_colour_array``): a painted one is a distractor of that disc's colour."""
 
-    def __init__(self, plant=None, radius=DISC_RADIUS, dt=0.05, background=96, occluders=None, shade=32):
+    def __init__(self, plant=None, radius=DISC_RADIUS, dt=0.05, background=96, occluders=None, shade=32, occluder_colours=None):
         self._robot = SyntheticRobot(plant, dt)
         self.radius, self.background, self.shade = radius, background, shade
         self.occluders = None if occluders is None else occluder_array(occluders, 1)[0]
+        self.occluder_colours = None
+        if occluder_colours is not None:
+            self.occluder_colours = occluder_colour_array(occluder_colours, None if occluders is None else len(self.occluders),
+                                                          self._robot.plant.n_points, 1)[0]
         if not 0 <= shade < 250:
             raise ValueError('shade must be 0 .. 249: 250 and above would enter a mask of the detectors')
         self.k = 0
@@ -476,5 +518,6 @@ class CameraRobot:
         return self._robot.plant.discs(self._robot.q, self.radius)
 
     def getCameraImage(self):
-        frame = render_discs(self.discs(), self._robot.plant.n_points, self.background, self.occluders, self.k, self.shade)
+        frame = render_discs(self.discs(), self._robot.plant.n_points, self.background, self.occluders, self.k, self.shade,
+                             self.occluder_colours)
         return frame, (RESOLUTION, RESOLUTION)
