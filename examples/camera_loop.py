@@ -29,8 +29,13 @@ its pixels enter green's mask and pull the centroid towards it, by an amount tha
 never reports a loss.  KF, MCKF, IMCC-KF, GMCKF (one launch each) and the calibrated law (stepwise) on the same starts and noise; prints the
 median ISE / IAE / ITAE and the FAIL count without and with the distractor.  With --occlusion --hold N the wide bar of above crosses the
 frame as well, behind the distractor, and lost discs are held: green, whose distractor stays visible, is never lost.
+--scenes N asks the question an UNCALIBRATED method exists for: what if the scene itself is not the nominal one?  N true scenes drawn around
+the nominal plant (plant.miscalibrated, seeded: focal length +-10 %, targets +-2 cm, camera roll +-3 degrees, links +-2 %) times the trials is
+ONE launch per method (engine.camera_closed_loop(cameras=..., camera_index=...)): every trial's frames come from its own camera.  KF, MCKF,
+IMCC-KF and GMCKF start from the nominal model's guess, next to the calibrated law on the nominal model and on the truth.  Prints the median
+ISE / IAE / ITAE over the trials that ran to the end, the FAIL count and the FAILs of the worst scene.
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]]"""
+       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N]"""
 import argparse
 import os
 import sys
@@ -231,6 +236,53 @@ def distractor_table(uvs, trials=64, sigma=0.3, radius=None, seed=0, rect=DISTRA
     return lines
 
 
+def scene_plants(uvs, plant, n, seed):
+    """n plausible true scenes around ``plant``, seeded: focal length +-10 %, every target +-2 cm, camera roll +-3 degrees, links +-2 %."""
+    rng = np.random.default_rng(seed + 1000)
+    roll = np.zeros(6)
+    out = []
+    for _ in range(n):
+        roll[5] = np.deg2rad(rng.uniform(-3.0, 3.0))
+        out.append(uvs.plant.miscalibrated(plant, focal_scale=rng.uniform(0.9, 1.1), point_offset=rng.uniform(-0.02, 0.02, (plant.n_points, 3)),
+                                           joint_offset=roll.copy(), link_scale=rng.uniform(0.98, 1.02)))
+    return out
+
+
+def scenes_table(uvs, n_scenes, trials=64, sigma=0.3, radius=None, seed=0):
+    """The Monte-Carlo over TRUE scenes as a list of lines: n_scenes x trials in ONE launch per method
+    (engine.camera_closed_loop(cameras=..., camera_index=...)).  The four estimators start from the NOMINAL model's analytic guess -- they
+    do not know the scene -- next to the calibrated law on the nominal model (wrong in every scene) and on the truth of every trial."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    nominal = uvs.SyntheticPlant.ur10(desired)
+    methods = ('KF', 'MCKF', 'IMCCKF', 'GMCKF', 'ANALYTICAL')
+    fps = {method: uvs.engine.make_params(8, 6, method, 10.0, False, 0.05, 15.0, 0.2, desired, True) for method in methods}
+    K = fps['GMCKF'].steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    noise = rng.standard_normal((K, trials, 8)) * sigma
+    q0_d = torch.as_tensor(np.tile(q0, (n_scenes, 1)), device='cuda')            # the same starts and the same noise in every scene
+    noise_d = torch.as_tensor(np.tile(noise, (1, n_scenes, 1)), device='cuda')
+    cameras = uvs.engine.camera_scenes(scene_plants(uvs, nominal, n_scenes, seed), radius)
+    index = np.repeat(np.arange(n_scenes, dtype=np.int32), trials)
+    kw = dict(radius=radius, fused=True, want=(), cameras=cameras, camera_index=index)
+    lines = [f'{n_scenes} true scenes (focal +-10 %, targets +-2 cm, camera roll +-3 deg, links +-2 %) x {trials} trials of {K} steps in one launch '
+             f'per method, white noise {sigma} px; median over the trials that ran to the end',
+             f'{"":44s}{"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"FAIL":>8s}{"worst scene":>13s}',
+             f'{"":44s}{"":36s}{"":8s}{"FAILs":>13s}']
+    runs = [(method + ', started from the nominal guess', fps[method], dict(guess='device', believed=nominal)) for method in methods[:4]]
+    runs += [('ANALYTICAL on the nominal model', fps['ANALYTICAL'], dict(believed=nominal)), ('ANALYTICAL on the truth', fps['ANALYTICAL'], dict())]
+    for name, fp, more in runs:
+        out = uvs.engine.camera_closed_loop(fp, nominal, q0_d, noise_d, **kw, **more)
+        torch.cuda.synchronize()
+        done = (out['status'] == 0).cpu().numpy()
+        med = np.median(out['stats'].cpu().numpy()[done], axis=0) if done.any() else np.full(3, np.nan)
+        worst = int((~done).reshape(n_scenes, trials).sum(axis=1).max())
+        lines.append(f'{name:44s}{med[0]:12.3f}{med[1]:12.3f}{med[2]:12.3f}{int((~done).sum()):>8d}{worst:>13d}')
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -248,11 +300,16 @@ def main():
     ap.add_argument('--distractor', action='store_true',
                     help='a still rectangle of the green disc\'s colour near its goal: the estimators and the calibrated law, and nothing else '
                          '(with --occlusion --hold N: in front of the wide bar, lost discs held)')
+    ap.add_argument('--scenes', type=int, default=0, metavar='N',
+                    help='N seeded true scenes x the trials in one launch per method: the estimators and the calibrated law, and nothing else')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
     if args.hold and not args.occlusion:
         ap.error('--hold goes with --occlusion')
+    if args.scenes:
+        print('\n'.join(scenes_table(uvs, args.scenes, args.trials, args.sigma, args.radius, args.seed)))
+        return
     if args.distractor:
         if args.occlusion and not args.hold:
             ap.error('--distractor --occlusion needs --hold N: the wide bar empties every mask')

@@ -454,6 +454,52 @@ int uvs_camera_believed_loop_f64(const struct uvs_filter_params *fp, const uvs_c
 int uvs_camera_believed_guess_f64(int64_t T, int32_t n_points, const uvs_camera *believed, int64_t n_believed,
                                   const int32_t *believed_index, const double *q_start, const double *f0, double *x0_out, void *stream);
 
+/*
+ * A SCENE PER TRIAL: Monte-Carlo over true cameras in one launch.  Every entry point above that takes `cam` renders the frames of all T
+ * trials with that one host struct.  Below, a SCENE is the uvs_camera that renders a trial's frames, and every trial has its own.  The
+ * scene operand is a triple, with the rules of the believed operand above word for word:
+ *   cams [n_cams] in: uvs_camera structs IN DEVICE (or pinned host) MEMORY.
+ *   cam_index [T] int32 in (device or pinned) or NULL.  With an index trial t is rendered by cams[cam_index[t]].  Without one n_cams must
+ *     be 1 (every trial cams[0]) or T (trial t cams[t]), else UVS_ERR_ARG.
+ *   An index outside [0, n_cams) never becomes an address.  That trial is VOID: a stand-alone call writes nothing for it; a loop writes
+ *     status FAIL and k_done = 0 and nothing else (no log row, no stats, no pixels, no held); its neighbours keep their bits.
+ *   The index is by OUTPUT trial, like occluders and paints (not by trial_params' source).
+ *   Shapes come from fp (n_points = fp->m / 2), or from the n_points argument where there is no fp; six joints everywhere.  The structs'
+ *     own n_joints / n_points are not read.  Read per trial: theta_offset, d, a, cos_alpha, sin_alpha, points, focal, center, radius.
+ * Each entry point has its namesake's operands with `cam` replaced by the triple (the two without an fp: by the triple and n_points), its
+ * namesake's refusals in their order on that shape, then the triple's: UVS_ERR_ARG for NULL cams, n_cams outside 1 .. 2^31 - 1, or
+ * n_cams not in {1, T} without an index.  T == 0 (with n_cams == 1 or an index) returns UVS_OK and launches nothing.  Every value is
+ * formed by the namesake's operations in its order: trial t has the bits of the namesake called with cam = the scene of t.
+ *
+ * uvs_camera_project_scenes_f64: uvs_camera_project_f64 per trial, so that the frames of a scene batch can be rendered with the
+ *   rasterisers above.
+ * uvs_camera_features_scenes_f64: uvs_camera_features_painted_f64 per trial, the step of the stepwise loops; occ, paint and n_occ = 0 stay
+ *   legal as they are there (n_occ = 0: the bits of uvs_camera_features_f64).
+ * uvs_camera_closed_loop_scenes_f64: uvs_camera_closed_loop_painted_f64 per trial, with tp, occluders, paints, hold and held; f0 and x0
+ *   are the caller's (for the loop of the reference: from the step-0 frame of the trial's own scene).  Built: GMCKF, KF and IMCC-KF at
+ *   (8, 6), (6, 6) and (2, 6), MCKF at (8, 6) and (2, 6), each in both workgroup forms with 0 B of scratch memory -- what the painted
+ *   flavour builds, no instantiation is missing beyond MCKF at (6, 6), which is refused with UVS_ERR_METHOD as everywhere.  The kernel
+ *   stages its workgroup's scenes through LDS (472 B per trial) once, before the first step.
+ * uvs_camera_believed_loop_scenes_f64: uvs_camera_believed_loop_f64 with the sensor side on the trial's scene and the law on its believed
+ *   model; a trial without a scene or without a model is void.  No occluders and no hold, as there.  With believed == cams and
+ *   believed_index == cam_index it is the calibrated law on every trial's own camera.  All three shapes, both forms, 0 B of scratch.
+ */
+int uvs_camera_project_scenes_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, int32_t n_points, int64_t T,
+                                  const double *q_prev, const double *dq, double dt, double *q_out, double *discs_out, void *stream);
+int uvs_camera_features_scenes_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, int32_t n_points, int64_t T,
+                                   const double *q_prev, const double *dq, double dt, double *q_out, const uvs_occluder *occ,
+                                   const int32_t *paint, int32_t n_occ, int32_t k, const double *noise, double *f_out, int32_t *pixels_out,
+                                   double *discs_out, void *stream);
+int uvs_camera_closed_loop_scenes_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                      int64_t T, const uvs_camera_trial_params *tp, const uvs_occluder *occ, const int32_t *paint,
+                                      int32_t n_occ, int32_t hold, const double *q_start, const double *noise, const double *x0,
+                                      const double *f0, double *q_log, double *f_log, double *dq_log, double *err_log, double *kappa_log,
+                                      int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, int32_t *held, void *stream);
+int uvs_camera_believed_loop_scenes_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                        int64_t T, const uvs_camera *believed, int64_t n_believed, const int32_t *believed_index,
+                                        const double *q_start, const double *noise, double *q_log, double *f_log, double *dq_log,
+                                        double *err_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

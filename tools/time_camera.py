@@ -74,7 +74,18 @@ GMCKF, 1 024 trials x 299 steps, white noise 0.3 px, x0 handed in, medians of 20
   (u) (t) stepwise: K x (painted camera features, hold, estimator step), three launches a step.
       (s), (t), (u) are reported, not gated.  (s) is checked against (q) and (t) against (u), bit for bit, before anything is timed.  Then
       the tables of examples/camera_loop.py --distractor and --distractor --occlusion --hold 30.
-usage: tools/time_camera.py --painted [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --painted [--parent-lib=PATH] [out.txt]
+With --scenes only the scene-per-trial pixel loops are timed, into profiles/camera_scenes_timing.txt (or the path given): GMCKF, 1 024
+trials x 299 steps, white noise 0.3 px, x0 handed in, medians of 20 with p10-p90;
+  (e), (n), (q) as under --painted, gated against two runs of the parent's library by the same rule: the existing kernels were not to move;
+  (v) (e)'s trials through camera_scene_kernel with n_cams = 1: what the kernel flavour costs;
+  (w) 16 scenes (examples/camera_loop.py --scenes) x 64 trials in ONE launch, (x) the same as 16 uniform launches of 64 trials, one per
+      scene, (z) (w) stepwise: K x (scene features, estimator step);
+  (k) the believed baseline loop on the nominal model, (y) its trials through scene_baseline_loop_kernel with n_cams = 1, (y16) the
+      baseline over the 16 scenes in one launch.
+      (v) .. (y16) are reported, not gated.  (v) is checked against (e), (w) against (x) and (z), (y) against (k), bit for bit, before
+      anything is timed.  Then the table of examples/camera_loop.py --scenes 8.
+usage: tools/time_camera.py --scenes [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -88,9 +99,10 @@ import torch  # noqa: E402
 
 ANALYTICAL, BELIEVED, GRID = '--analytical' in sys.argv[1:], '--believed' in sys.argv[1:], '--grid' in sys.argv[1:]
 OCCLUDED, HELD, PAINTED = '--occluded' in sys.argv[1:], '--held' in sys.argv[1:], '--painted' in sys.argv[1:]
+SCENES = '--scenes' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -699,6 +711,135 @@ def painted_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def scenes_section():
+    """(e), (n), (q) against the parent's; (v) .. (z): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T, HOLD, N_SCENES = 299, 1024, 30, 16
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    fa = uvs.engine.make_params(8, 6, 'ANALYTICAL', 10.0, False, 0.05, 15.0, 0.2, DESIRED)
+    assert fp.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --scenes on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in (the nominal model\'s guess); the 12 px bar {example.BAR}, the wide '
+        f'bar {example.WIDE_BAR} with hold = {HOLD}; {N_SCENES} scenes of examples/camera_loop.py --scenes (seed 0) x {T // N_SCENES} trials')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+    x0 = uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+    bar, wide = uvs.engine.occluders([example.BAR], T), uvs.engine.occluders([example.WIDE_BAR], T)
+    one = uvs.engine.camera_scenes(plant)
+    scene_plants = example.scene_plants(uvs, plant, N_SCENES, 0)
+    scenes = uvs.engine.camera_scenes(scene_plants)
+    per = T // N_SCENES
+    index = torch.as_tensor(np.repeat(np.arange(N_SCENES, dtype=np.int32), per), device='cuda')
+    nominal = uvs.engine.believed_models(plant)
+    parts = [(c, slice(c * per, (c + 1) * per)) for c in range(N_SCENES)]
+    cut = {c: (q_d[rows].contiguous(), noise[:, rows].contiguous(), x0[rows].contiguous()) for c, rows in parts}
+
+    def run_x():
+        return [loop(fp, scene_plants[c], *cut[c][:2], x0=cut[c][2], fused=True) for c, _ in parts]
+
+    fns = {'e': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True),
+           'n': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=bar),
+           'q': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=wide, hold=HOLD),
+           'v': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, cameras=one),
+           'w': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, cameras=scenes, camera_index=index),
+           'x': run_x,
+           'z': lambda: loop(fp, plant, q_d, noise, x0=x0, cameras=scenes, camera_index=index),
+           'k': lambda: loop(fa, plant, q_d, noise, fused=True, believed=nominal),
+           'y': lambda: loop(fa, plant, q_d, noise, fused=True, believed=nominal, cameras=one),
+           'y16': lambda: loop(fa, plant, q_d, noise, fused=True, believed=nominal, cameras=scenes, camera_index=index)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+
+    def same(a, b, rows=slice(None), rows_b=slice(None)):
+        done = a['k_done'][rows]
+        ok = all(torch.equal(a[key][rows], b[key][rows_b]) for key in ('status', 'k_done', 'pixels'))
+        ok = ok and torch.equal(a['stats'][rows].view(torch.int64), b['stats'][rows_b].view(torch.int64))
+        ok = ok and ('held' in a) == ('held' in b) and ('held' not in a or torch.equal(a['held'][rows], b['held'][rows_b]))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):                 # the specified rows: q, f up to and including k_done, the others before it
+            if key in a:
+                spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+                ok = ok and torch.equal(a[key][:, rows].view(torch.int64)[spec], b[key][:, rows_b].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['v'], first['e']), 'the scenes kernel on the one nominal camera and the uniform kernel disagree'
+    assert same(first['w'], first['z']), 'the one launch and the stepwise loop disagree'
+    assert same(first['y'], first['k']), 'the scenes baseline on the one nominal camera and the believed loop disagree'
+    for c, rows in parts:
+        assert same(first['w'], first['x'][c], rows), f'scene {c}: the one launch and the launch per scene disagree'
+    gated = ('e', 'n', 'q')
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_scenes_f64'), 'the parent library has one scene per launch'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def with_parent(fn):
+            def run():
+                mine, uvs._vision._lib = uvs._vision._lib, parent
+                try:
+                    return fn()
+                finally:
+                    uvs._vision._lib = mine
+            return run
+
+        for name in gated:
+            run = with_parent(fns[name])
+            old = run()
+            torch.cuda.synchronize()
+            assert same(first[name], old), f'this library and the parent disagree on ({name})'
+            fns[name + '_parent_a'], fns[name + '_parent_b'] = run, with_parent(fns[name])
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    say()
+    what = {'e': 'the uniform fused launch, camera_loop_kernel', 'n': 'the 12 px bar, camera_occluded_kernel', 'q': f'the wide bar, hold = {HOLD}, camera_held_kernel'}
+    passed = True
+    for name in gated:
+        say(f'  ({name}) {what[name]:48s} this library   {fmt_ms(ms[name])}   = {med[name] / K * 1e3:.1f} us per step')
+        if PARENT_LIB is not None:
+            a, b = med[name + '_parent_a'], med[name + '_parent_b']
+            say(f'  ({name}) {"":48s} the parent\'s, 1  {fmt_ms(ms[name + "_parent_a"])}')
+            say(f'  ({name}) {"":48s} the parent\'s, 2  {fmt_ms(ms[name + "_parent_b"])}')
+            ok = med[name] <= max(a, b) + abs(a - b)
+            passed = passed and ok
+            say(f'  ({name}) new / slower parent run = {med[name] / max(a, b):.4f}; the two parent runs differ by {abs(a - b) / max(a, b) * 100:.2f} %: '
+                f'{"passes" if ok else "DOES NOT pass"}; outputs bit-identical')
+    say(f'  (v) (e)\'s trials through camera_scene_kernel, n_cams = 1                  {fmt_ms(ms["v"])}   = {med["v"] / K * 1e3:.1f} us per step')
+    say(f'  (w) {N_SCENES} scenes x {per} trials, one launch                                   {fmt_ms(ms["w"])}   = {med["w"] / K * 1e3:.1f} us per step')
+    say(f'  (x) the same as {N_SCENES} uniform launches of {per} trials, one per scene             {fmt_ms(ms["x"])}')
+    say(f'  (z) (w) stepwise: K x (scene features, estimator step)                    {fmt_ms(ms["z"])}   = {med["z"] / K * 1e3:.1f} us per step')
+    say(f'  (k) the believed baseline loop, camera_believed_loop_kernel               {fmt_ms(ms["k"])}')
+    say(f'  (y) (k)\'s trials through scene_baseline_loop_kernel, n_cams = 1           {fmt_ms(ms["y"])}')
+    say(f'  (y16) the baseline on the nominal model over the {N_SCENES} scenes, one launch       {fmt_ms(ms["y16"])}')
+    say(f'  (v) / (e) = {med["v"] / med["e"]:.4f}, (w) / (x) = {med["w"] / med["x"]:.4f}, (w) / (z) = {med["w"] / med["z"]:.4f}, (y) / (k) = '
+        f'{med["y"] / med["k"]:.4f} (reported, not gated); (v) has the bits of (e), (w) those of (x) and of (z), (y) those of (k)')
+    failed = lambda out: int((out['k_done'] < K).sum())              # noqa: E731
+    say(f'  trials that FAILed: (e) {failed(first["e"])}, (w) {failed(first["w"])}, (k) {failed(first["k"])}, (y16) {failed(first["y16"])}')
+    say()
+    if PARENT_LIB is not None:
+        say(f'gate: (e), (n), (q) against two runs of the parent\'s library: {"pass" if passed else "DO NOT pass"}')
+        say()
+    say('# examples/camera_loop.py --scenes 8 (its defaults)')
+    for line in example.scenes_table(uvs, 8):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if SCENES:
+    scenes_section()
+    sys.exit(0)
 if PAINTED:
     painted_section()
     sys.exit(0)

@@ -82,6 +82,15 @@ SYMBOLS = {
     'uvs_camera_believed_loop_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _I64, _VP] + [_VP] * 11),
     # T, n_points, believed operand, q_start, f0, x0_out, stream
     'uvs_camera_believed_guess_f64': (C.c_int, [_I64, _I32, _VP, _I64, _VP] + [_VP] * 4),
+    # the scene operand is (cams: device array of Camera, n_cams, cam_index: device int32 [T] or None): it stands where the namesake has cam
+    # scene operand, n_points, T, q_prev, dq, dt, q_out, discs_out, stream
+    'uvs_camera_project_scenes_f64': (C.c_int, [_VP, _I64, _VP, _I32, _I64, _VP, _VP, _F64, _VP, _VP, _VP]),
+    # scene operand, n_points, T, q_prev, dq, dt, q_out, occ, paint, n_occ, k, noise, f_out, pixels_out, discs_out, stream
+    'uvs_camera_features_scenes_f64': (C.c_int, [_VP, _I64, _VP, _I32, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    # fp, scene operand, then uvs_camera_closed_loop_painted_f64's operands from T on
+    'uvs_camera_closed_loop_scenes_f64': (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
+    # fp, scene operand, then uvs_camera_believed_loop_f64's operands from T on
+    'uvs_camera_believed_loop_scenes_f64': (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
 }
 
 _lib = None
@@ -91,7 +100,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 8)), '-C', CSRC], check=True)         # eight translation units, one rule each
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 10)), '-C', CSRC], check=True)        # ten translation units, one rule each
     return LIB_PATH
 
 

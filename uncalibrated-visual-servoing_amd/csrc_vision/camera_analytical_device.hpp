@@ -7,6 +7,8 @@
 // side's model of every trial is staged from memory into s_cam[G], and a trial whose index names no model starts FAILed (not alive, not seen),
 // so that it logs no row and writes status and k_done alone.  Every other unit sees camera_analytical_loop_kernel(ALoopArgs): one model, taken
 // from the kernel argument, every trial known.  Same names, argument blocks, registers and LDS as when each was written out in its unit.
+// A unit that defines UVS_CAMERA_SCENES (uvs_camera_scenes_baseline.hip) sees a third flavour, scene_baseline_loop_kernel(SLoopArgs): the
+// believed one whose sensor side reads the trial's own camera as well, from a second staged array.
 // Next to them: what every entry point of the two units asks of (fp, cam, T) before its first HIP call.
 //
 // The loop's mapping is the one of camera_loop_kernel (camera_loop_device.hpp), decided and measured there -- 256 threads = one wavefront per
@@ -61,36 +63,8 @@ __device__ __forceinline__ int analytical_step(const uvs_camera &cam, const uvs_
     return bad;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- believed models
-constexpr int kCamWords = static_cast<int>(sizeof(uvs_camera) / 8);
-static_assert(sizeof(uvs_camera) % 8 == 0, "copied as doubles");
-
-struct Believed {
-    const uvs_camera *models;                                    // [n]
-    long long n;
-    const int32_t *index;                                        // [T] or NULL: n == 1 (all trials the one model) or n == T (trial t model t)
-};
-
-// The model of `trial`, or -1 when its index names none.
-__device__ __forceinline__ long long model_of(const Believed &B, long long trial) {
-    const long long i = B.index != nullptr ? static_cast<long long>(B.index[trial]) : (B.n == 1 ? 0 : trial);
-    return (i >= 0 && i < B.n) ? i : -1;
-}
-
-// The models of the trials first .. first + COUNT - 1 (clamped to the last trial: padding shadows it) into s_cam[COUNT], by all THREADS threads;
-// zeros for a trial without a model.  The caller's next barrier stands between this and the first read.
-template <int COUNT, int THREADS>
-__device__ __forceinline__ void stage_models(const Believed &B, long long first, long long T, uvs_camera *s_cam) {
-    for (int i = threadIdx.x; i < COUNT * kCamWords; i += THREADS) {
-        const int slot = i / kCamWords, word = i - slot * kCamWords;
-        long long trial = first + slot;
-        if (trial >= T) trial = T - 1;
-        const long long model = model_of(B, trial);
-        reinterpret_cast<double *>(s_cam)[i] = model >= 0 ? reinterpret_cast<const double *>(B.models + model)[word] : 0.0;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------- the loop, one launch
+// (Believed, model_of and stage_models, which the believed flavour reads its models with, are vision_device.hpp's: the scenes share them.)
 struct ALoopArgs {
     uvs_filter_params fp;
     uvs_camera cam;
@@ -114,11 +88,31 @@ struct BLoopArgs {
     int32_t *pixels;
 };
 
-#ifdef UVS_CAMERA_BELIEVED
-constexpr bool kCameraBelieved = true;
+// The third flavour (a unit that defines UVS_CAMERA_SCENES, uvs_camera_scenes_baseline.hip): scene_baseline_loop_kernel, the
+// believed flavour whose SENSOR side reads the trial's own camera too, from a second staged array, s_scene[G].  `cam` is the shape alone.
+struct SLoopArgs {
+    uvs_filter_params fp;
+    uvs_camera cam;                                              // n_joints and n_points of the launch (fp's); word 0 of every staged scene
+    Believed B;                                                  // the control side's
+    Scenes S;                                                    // the sensor side's: the cameras that render the trials' frames
+    long long T;
+    const double *q_start, *noise;
+    double *q_log, *f_log, *dq_log, *err_log;                    // [K][T][comp], each or NULL
+    int32_t *status, *k_done;
+    double *stats;
+    int32_t *pixels;
+};
+
+#if defined(UVS_CAMERA_SCENES)
+constexpr bool kCameraBelieved = true, kBaselineScenes = true;
+using BaselineLoopArgs = SLoopArgs;
+#define UVS_BASELINE_LOOP_KERNEL scene_baseline_loop_kernel
+#elif defined(UVS_CAMERA_BELIEVED)
+constexpr bool kCameraBelieved = true, kBaselineScenes = false;
 using BaselineLoopArgs = BLoopArgs;
 #define UVS_BASELINE_LOOP_KERNEL camera_believed_loop_kernel
 #else
+constexpr bool kBaselineScenes = false;
 constexpr bool kCameraBelieved = false;
 using BaselineLoopArgs = ALoopArgs;
 #define UVS_BASELINE_LOOP_KERNEL camera_analytical_loop_kernel
@@ -126,6 +120,8 @@ using BaselineLoopArgs = ALoopArgs;
 // Has `trial` a model?  Calibrated: always, folded away.  Believed: the same word in all 64 lanes of a sensor-side wavefront.
 __device__ __forceinline__ bool has_model(const ALoopArgs &, long long) { return true; }
 __device__ __forceinline__ bool has_model(const BLoopArgs &a, long long trial) { return model_of(a.B, trial) >= 0; }
+// Scenes: a model to believe in AND a scene to be rendered by; a trial without either starts FAILed
+__device__ __forceinline__ bool has_model(const SLoopArgs &a, long long trial) { return model_of(a.B, trial) >= 0 && model_of(a.S, trial) >= 0; }
 // The control side's models of the workgroup's trials into LDS, by all kLoopThreads threads.  Calibrated: the one model of the launch -- the
 // 6 x 6 camera Jacobian uses the whole DH table in every step, and held in scalar registers next to the sensor side's the table spilled (36 B
 // of scratch per lane in the four-trial form).
@@ -136,6 +132,19 @@ __device__ __forceinline__ void stage_loop_models(const ALoopArgs &a, uvs_camera
 template <int G>
 __device__ __forceinline__ void stage_loop_models(const BLoopArgs &a, uvs_camera *s_cam) {
     stage_models<G, kLoopThreads>(a.B, static_cast<long long>(blockIdx.x) * G, a.T, s_cam);
+}
+template <int G>
+__device__ __forceinline__ void stage_loop_models(const SLoopArgs &a, uvs_camera *s_cam) {
+    stage_models<G, kLoopThreads>(a.B, static_cast<long long>(blockIdx.x) * G, a.T, s_cam);
+}
+// The sensor side's cameras of the workgroup's trials into LDS.  The other two flavours have the one camera of the launch: nothing to stage.
+template <int G>
+__device__ __forceinline__ void stage_loop_scenes(const ALoopArgs &, uvs_camera *) {}
+template <int G>
+__device__ __forceinline__ void stage_loop_scenes(const BLoopArgs &, uvs_camera *) {}
+template <int G>
+__device__ __forceinline__ void stage_loop_scenes(const SLoopArgs &a, uvs_camera *s_scene) {
+    stage_scenes<G, kLoopThreads>(a.S, a.cam, static_cast<long long>(blockIdx.x) * G, a.T, s_scene);
 }
 
 template <int M, int N, int L, int G>
@@ -153,6 +162,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     __shared__ double s_sum[G][3][M];                            // per-feature ISE, IAE, ITAE after the loop
     __shared__ uvs_camera s_cam[BELIEVED ? G : 1];               // the control side's models; written once here, and the step loop's barriers
     stage_loop_models<G>(A, s_cam);                              // stand between this and the first read
+    constexpr bool SCENES = kBaselineScenes;
+    __shared__ uvs_camera s_scene[SCENES ? G : 1];               // SCENES: the sensor side's cameras; the barrier before the step loop stands
+    stage_loop_scenes<G>(A, s_scene);                            // between this and step 0's sines
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -163,6 +175,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
 
     // sensor side: this wavefront's trial, and the feature pairs it detects: all of its own trial's, or every fourth of the workgroup's one trial
     const int ws = G == 1 ? 0 : w;
+    const uvs_camera &scene = SCENES ? s_scene[ws] : cam;        // the camera that renders this trial's frames
     const bool writer = G == W || w == 0;                        // G = 1: the four wavefronts hold the same joints; the first one logs them
     const int j_first = G == 1 ? w : 0, j_step = G == 1 ? W : 1;
     long long trial = static_cast<long long>(blockIdx.x) * G + ws;
@@ -192,6 +205,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     double t = 0.0 + fp.dt;                                      // engine._loop_times: t_s accumulated in floating point
     bool alive = has_model(A, etrial);                           // no model: FAILed before step 0
     int status = alive ? UVS_STATUS_SUCCESS : UVS_STATUS_FAIL, k_done = alive ? K : 0;
+    if constexpr (SCENES) __syncthreads();                       // the staged scenes: step 0's sines read them before the step's first barrier
 
     for (int k = 0; k < K; ++k) {
         // ---- the sensor side of the step (camera_sensor_device.hpp): joints, projection, detection
@@ -199,10 +213,10 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
             advance_joint(lane, k, s_dq[ws], fp.dt, q);
             if (seen && q_at != nullptr) *q_at = q;              // before the sines: where this text measured fastest
             if (writer) s_q[ws][lane] = q;
-            joint_sincos_rows(cam, lane, q, s_sin[w], s_cos[w]);
+            joint_sincos_rows(scene, lane, q, s_sin[w], s_cos[w]);
         }
         __syncthreads();
-        if (lane < npts) project_lane_disc(cam, lane, s_sin[w], s_cos[w], s_disc[w]);
+        if (lane < npts) project_lane_disc(scene, lane, s_sin[w], s_cos[w], s_disc[w]);
         __syncthreads();
 #pragma unroll 1
         for (int j = j_first; j < npts; j += j_step) {

@@ -51,6 +51,15 @@
 // that colour's mask.  Lane o < 4, where it evaluates rectangle o into s_occ[w], also leaves the rectangle's paint as byte o of s_paint[w]
 // (paint_slot; opaque from n_occ on and for a NULL operand) -- one dword per trial, indexed by OUTPUT trial like the occluders -- and the
 // detection loop hands both to detect_pair<true, true>.  Barriers and exits are where they were.
+//
+// SCENES.  A sixth flavour: a unit that defines UVS_CAMERA_SCENES next to the other four switches (uvs_camera_scenes.hip) sees
+// camera_scene_kernel(ScenesLoopArgs) with all five on.  The camera that renders a trial's frames is the trial's own: a uvs_camera struct in
+// memory, picked by OUTPUT trial through (cams, n_cams, cam_index) as the believed loop picks its models.  The workgroup's G scenes are staged
+// once, before the step loop, into s_cam[G] (472 B each, by all 256 threads; one barrier of its own, before the first step, because the first
+// reader -- the sines -- comes before the step's first barrier), and joint_sincos_rows and project_lane_disc read s_cam[ws] where the other
+// flavours read the kernel argument.  A.cam holds the launch's shape alone (n_joints, n_points, from fp) and is word 0 of every staged
+// struct.  A padding trial stages the scene of the trial it shadows; a trial whose index names no scene stages zeros and is `void` exactly as
+// one whose source index names no input trial is: FAILed by its flag, not by what the zeros give.  The step's barriers and exits are where they were.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -90,6 +99,19 @@ struct PaintedLoopArgs : HeldLoopArgs {
     const int32_t *paint;
 };
 
+// uvs_camera_closed_loop_scenes_f64: the painted block (whose `cam` is then the shape alone) and the scenes; only camera_scene_kernel takes it
+struct ScenesLoopArgs : PaintedLoopArgs {
+    Scenes S;
+};
+
+#ifdef UVS_CAMERA_SCENES
+#ifndef UVS_CAMERA_PAINTED
+#error "the scenes flavour is a painted flavour: define UVS_CAMERA_PAINTED (and UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
+#endif
+constexpr bool kCameraScenes = true;
+#else
+constexpr bool kCameraScenes = false;
+#endif
 #ifdef UVS_CAMERA_PAINTED
 #ifndef UVS_CAMERA_HELD
 #error "the painted flavour is a held flavour: define UVS_CAMERA_HELD (and UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
@@ -114,7 +136,11 @@ constexpr bool kCameraOccluded = true;
 #else
 constexpr bool kCameraOccluded = false;
 #endif
-#if defined(UVS_CAMERA_PAINTED)
+#if defined(UVS_CAMERA_SCENES)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = ScenesLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL camera_scene_kernel
+#elif defined(UVS_CAMERA_PAINTED)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = PaintedLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL camera_painted_kernel
@@ -149,10 +175,13 @@ __device__ __forceinline__ int hold_of(const HeldLoopArgs &a, int32_t *&held) { 
 // the paints of the launch, or NULL (never called on the other four blocks: PAINT is off there)
 __device__ __forceinline__ const int32_t *paints_of(const LoopArgs &) { return nullptr; }
 __device__ __forceinline__ const int32_t *paints_of(const PaintedLoopArgs &a) { return a.paint; }
+// the scenes of the launch (never called on the other five blocks: SCENES is off there)
+__device__ __forceinline__ Scenes scenes_of(const LoopArgs &) { return Scenes{nullptr, 0, nullptr}; }
+__device__ __forceinline__ Scenes scenes_of(const ScenesLoopArgs &a) { return a.S; }
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
-    constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld, PAINT = kCameraPainted;
+    constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld, PAINT = kCameraPainted, SCENES = kCameraScenes;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -171,6 +200,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     __shared__ uint32_t s_paint[PAINT ? W : 1];                  // PAINT: the paints of those rectangles, a byte each (paint_slot)
     __shared__ int s_miss[HOLD ? G : 1][kColours];               // HOLD: steps in a row, up to this one, at which the disc's pair was held
     __shared__ int s_held[HOLD ? G : 1][kColours];               // HOLD: steps at which it was held, while the trial's rows were due
+    __shared__ uvs_camera s_cam[SCENES ? G : 1];                 // SCENES: the cameras that render the workgroup's trials, staged once below
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -181,6 +211,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
 
     // sensor side: this wavefront's trial, and the feature pairs it detects: all of its own trial's, or every fourth of the workgroup's one trial
     const int ws = G == 1 ? 0 : w;
+    const uvs_camera &scene = SCENES ? s_cam[ws] : cam;          // the camera that renders this trial's frames
     const bool writer = G == W || w == 0;                        // G = 1: the four wavefronts hold the same joints; the first one logs them
     const int j_first = G == 1 ? w : 0, j_step = G == 1 ? W : 1;
     long long trial = static_cast<long long>(blockIdx.x) * G + ws;
@@ -198,6 +229,10 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
                 valid = false;
             }
         }
+    }
+    if constexpr (SCENES) {                                      // the scene of the OUTPUT trial (a padding wavefront: of the one it shadows)
+        stage_scenes<G, kLoopThreads>(scenes_of(A), cam, static_cast<long long>(blockIdx.x) * G, T, s_cam);
+        if (model_of(scenes_of(A), trial) < 0) valid = false;    // names no scene: void.  Never an address; nothing of it is stored
     }
     const uvs_occluder *occ_at = nullptr;                        // OCC: the occluders of the OUTPUT trial (a padding wavefront: of the one it shadows)
     int n_occ = 0;
@@ -245,6 +280,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
             s_tp[slot][3] = tp.fpi_threshold != nullptr ? tp.fpi_threshold[etrial] : fp.fpi_threshold;
         }
     }
+    if constexpr (SCENES) {
+        if (model_of(scenes_of(A), etrial) < 0) evoid = true;
+    }
     const bool estore = evalid && !evoid;                        // this lane's trial has rows to log
     double *err_at = (estore && A.err_log != nullptr) ? A.err_log + etrial * M + sub * R : nullptr;
     double *kappa_at = (estore && A.kappa_log != nullptr) ? A.kappa_log + etrial * M + sub * R : nullptr;
@@ -274,16 +312,17 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     uvs_filter_params fp_trial;                                  // PTP: the launch's block with the trial's own reg and fpi_threshold, per lane
     if constexpr (PTP) fp_trial = A.fp;
     const uvs_filter_params &fpe = PTP ? fp_trial : A.fp;        // what the estimator update reads
+    if constexpr (SCENES) __syncthreads();                       // the staged scenes: step 0's sines read them before the step's first barrier
 
     for (int k = 0; k < K; ++k) {
         // ---- the sensor side of the step (camera_sensor_device.hpp): joints, projection, detection
         if (lane < N) {
             advance_joint(lane, k, s_dq[ws], fp.dt, q);
-            joint_sincos_rows(cam, lane, q, s_sin[w], s_cos[w]);
+            joint_sincos_rows(scene, lane, q, s_sin[w], s_cos[w]);
             if (seen && q_at != nullptr) *q_at = q;              // after the sines: where this text measured fastest
         }
         __syncthreads();
-        if (lane < npts) project_lane_disc(cam, lane, s_sin[w], s_cos[w], s_disc[w]);
+        if (lane < npts) project_lane_disc(scene, lane, s_sin[w], s_cos[w], s_disc[w]);
         if constexpr (OCC) {                                     // lane o: rectangle o of this step, next to the projection
             if (lane < kOccluders) s_occ[w][lane] = lane < n_occ ? occluder_rect(occ_at[lane], k) : kNoRect;
         }

@@ -370,6 +370,57 @@ __global__ __launch_bounds__(kThreads) void paint_camera_detect_kernel(const uvs
     centre_of_mass_of_block(cc, rc, cam.n_points, noise, f_out, pixels_out);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- a scene per trial
+// camera_project_kernel and paint_camera_detect_kernel with the camera of THEIR trial, read from memory where a value is used (DESIGN.md
+// 4.22): kernels of their own names and texts, so that the ones above keep their code and their resource figures.  The arithmetic is the
+// shared device functions' on the same operands in the same order, so trial t has the bits of the call with cam = its scene.  The shape is
+// the launch's (six joints, n_points), never a struct's; a trial whose index names no scene reads none and stores nothing.
+__global__ __launch_bounds__(kProjectThreads) void scene_project_kernel(const Scenes S, int n_points, int64_t T, const double *__restrict__ q_prev,
+                                                                        const double *__restrict__ dq, double dt, double *__restrict__ q_out,
+                                                                        double *__restrict__ discs_out) {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * kProjectThreads + threadIdx.x;
+    if (t >= T) return;
+    const long long scene = model_of(S, t);
+    if (scene < 0) return;
+    const uvs_camera &cam = S.models[scene];
+    double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
+    for (int i = 0; i < kSceneJoints; ++i) {
+        double s, c;
+        scene_joint_sincos(cam, t, i, q_prev, dq, dt, q_out, s, c);
+        chain_link(cam, i, s, c, pose);
+    }
+    for (int p = 0; p < n_points; ++p) project_disc(cam, p, pose, discs_out + (t * n_points + p) * 3);
+}
+
+__global__ __launch_bounds__(kThreads) void scene_camera_detect_kernel(const Scenes S, int n_points, const double *__restrict__ q_prev,
+                                                                       const double *__restrict__ dq, double dt, double *__restrict__ q_out,
+                                                                       const double *__restrict__ noise, double *__restrict__ f_out,
+                                                                       int32_t *__restrict__ pixels_out, double *__restrict__ discs_out,
+                                                                       const PaintArgs pa) {
+    __shared__ double sdisc[kColours * 3];
+    __shared__ double ssin[UVS_CAMERA_MAX_JOINTS], scos[UVS_CAMERA_MAX_JOINTS];
+    const int tid = threadIdx.x;
+    const int64_t t = blockIdx.x;
+    const long long scene = model_of(S, t);                      // the same word in all 1024 threads: the workgroup leaves as one
+    if (scene < 0) return;
+    const uvs_camera &cam = S.models[scene];
+    if (tid < kSceneJoints) scene_joint_sincos(cam, t, tid, q_prev, dq, dt, q_out, ssin[tid], scos[tid]);
+    __syncthreads();
+    if (tid < n_points) {
+        double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
+        for (int i = 0; i < kSceneJoints; ++i) chain_link(cam, i, ssin[i], scos[i], pose);
+        project_disc(cam, tid, pose, &sdisc[3 * tid]);
+        if (discs_out != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) discs_out[(t * n_points + tid) * 3 + k] = sdisc[3 * tid + k];
+        }
+    }
+    __syncthreads();
+    int cc, rc;
+    painted_counts(sdisc, n_points, cc, rc, rects_of_block(pa.oa), paints_of_block(pa, n_points));
+    centre_of_mass_of_block(cc, rc, n_points, noise, f_out, pixels_out);
+}
+
 thread_local char g_err[256] = "";
 
 int fail(int code, const char *fmt, const char *detail) {
@@ -396,6 +447,20 @@ int check_occluders(const uvs_occluder *occ, int32_t n_occ) {
     if (n_occ < 0 || n_occ > UVS_CAMERA_MAX_OCCLUDERS) return fail(UVS_ERR_ARG, "%s", "n_occ must be 0 .. 4");
     if (occ == nullptr && n_occ > 0) return fail(UVS_ERR_ARG, "%s", "NULL occ with n_occ > 0");
     return UVS_OK;
+}
+
+int check_scenes(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, int64_t T) {
+    if (cams == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL cams");
+    if (n_cams < 1 || n_cams > INT32_MAX) return fail(UVS_ERR_ARG, "%s", "n_cams must be 1 .. 2^31 - 1");
+    if (cam_index == nullptr && n_cams != 1 && n_cams != T) return fail(UVS_ERR_ARG, "%s", "without cam_index, n_cams must be 1 or T");
+    return UVS_OK;
+}
+
+uvs_camera scene_shape(int32_t n_joints, int32_t n_points) {
+    uvs_camera shape{};
+    shape.n_joints = n_joints;
+    shape.n_points = n_points;
+    return shape;
 }
 
 int launched(const char *what) {
@@ -573,6 +638,39 @@ int uvs_camera_features_painted_f64(const uvs_camera *cam, int64_t T, const doub
     hipLaunchKernelGGL(paint_camera_detect_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), *cam,
                        q_prev, dq, dt, q_out, noise, f_out, pixels_out, discs_out, PaintArgs{{occ, n_occ, k, 0u}, paint});
     return launched("paint_camera_detect_kernel launch: %s");
+}
+
+// The scene per trial: the namesakes' refusals in their order on the launch's shape (six joints, n_points), then the triple's
+int uvs_camera_project_scenes_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, int32_t n_points, int64_t T,
+                                  const double *q_prev, const double *dq, double dt, double *q_out, double *discs_out, void *stream) {
+    g_err[0] = '\0';
+    if (discs_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL discs_out");
+    const uvs_camera shape = scene_shape(kSceneJoints, n_points);
+    if (const int rc = check_camera(&shape, T, q_prev, q_out)) return rc;
+    if (const int rc = check_scenes(cams, n_cams, cam_index, T)) return rc;
+    if (T == 0) return UVS_OK;
+    const unsigned blocks = static_cast<unsigned>((T + kProjectThreads - 1) / kProjectThreads);
+    hipLaunchKernelGGL(scene_project_kernel, dim3(blocks), dim3(kProjectThreads), 0, static_cast<hipStream_t>(stream),
+                       Scenes{cams, n_cams, cam_index}, static_cast<int>(n_points), T, q_prev, dq, dt, q_out, discs_out);
+    return launched("scene_project_kernel launch: %s");
+}
+
+int uvs_camera_features_scenes_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, int32_t n_points, int64_t T,
+                                   const double *q_prev, const double *dq, double dt, double *q_out, const uvs_occluder *occ,
+                                   const int32_t *paint, int32_t n_occ, int32_t k, const double *noise, double *f_out, int32_t *pixels_out,
+                                   double *discs_out, void *stream) {
+    g_err[0] = '\0';
+    if (f_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL f_out");
+    const uvs_camera shape = scene_shape(kSceneJoints, n_points);
+    if (const int rc = check_camera(&shape, T, q_prev, q_out)) return rc;
+    if (const int rc = check_occluders(occ, n_occ)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (const int rc = check_scenes(cams, n_cams, cam_index, T)) return rc;
+    if (T == 0) return UVS_OK;
+    hipLaunchKernelGGL(scene_camera_detect_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       Scenes{cams, n_cams, cam_index}, static_cast<int>(n_points), q_prev, dq, dt, q_out, noise, f_out, pixels_out, discs_out,
+                       PaintArgs{{occ, n_occ, k, 0u}, paint});
+    return launched("scene_camera_detect_kernel launch: %s");
 }
 
 }  // extern "C"

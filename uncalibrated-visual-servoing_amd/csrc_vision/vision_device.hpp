@@ -1,4 +1,4 @@
-// Device code shared by all eight translation units of libuvs_vision.so (uvs_vision.hip directly, the seven loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
+// Device code shared by all ten translation units of libuvs_vision.so (uvs_vision.hip directly, the nine loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
 // forms its callers need, the disc geometry of the synthetic camera with its occluders and their paints, and the DH chain.  The summation order of the phase 2 is a contract
 // (see centre_of_mass): every unit that sums mask pixels goes through wave_partial and ColourSum, so they all give the same bits.
 #pragma once
@@ -444,6 +444,20 @@ __device__ __forceinline__ void joint_sincos(const uvs_camera &cam, int64_t t, i
     sincos(q + cam.theta_offset[i], &s, &c);
 }
 
+// The same for a camera whose own n_joints is not read (a scene in memory): the arms of this project have six joints.
+constexpr int kSceneJoints = 6;
+__device__ __forceinline__ void scene_joint_sincos(const uvs_camera &cam, int64_t t, int i, const double *__restrict__ q_prev,
+                                                   const double *__restrict__ dq, double dt, double *__restrict__ q_out, double &s, double &c) {
+    constexpr int n = kSceneJoints;
+    double q = q_prev[t * n + i];
+    if (dq != nullptr) {
+        const double step = dq[t * n + i] * dt;                  // one rounded multiply, then one rounded add
+        q = q + step;
+    }
+    if (q_out != nullptr) q_out[t * n + i] = q;
+    sincos(q + cam.theta_offset[i], &s, &c);
+}
+
 // One more link of the chain: T <- T * Rz(theta) Tz(d) Rx(alpha) Tx(a), summed left to right as a plain matrix product.
 __device__ __forceinline__ void chain_link(const uvs_camera &cam, int i, double s, double c, double (&T)[3][4]) {
     const double ca = cam.cos_alpha[i], sa = cam.sin_alpha[i], aa = cam.a[i], dd = cam.d[i];
@@ -470,6 +484,54 @@ __device__ __forceinline__ void project_disc(const uvs_camera &cam, int p, const
     out[2] = (zc > 0.0 && isfinite(zc)) ? cam.focal * cam.radius[p] / zc : -1.0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- cameras in memory
+// The operand (structs, number, index) of every entry point that reads a uvs_camera PER TRIAL from device memory: the believed models of the
+// calibrated law (uvs_camera_believed.hip) and the scenes that render a trial's frames.  One rule for both: an index outside
+// [0, n) never becomes an address.
+constexpr int kCamWords = static_cast<int>(sizeof(uvs_camera) / 8);
+static_assert(sizeof(uvs_camera) % 8 == 0, "copied as doubles");
+
+struct Believed {
+    const uvs_camera *models;                                    // [n]
+    long long n;
+    const int32_t *index;                                        // [T] or NULL: n == 1 (all trials the one model) or n == T (trial t model t)
+};
+using Scenes = Believed;                                         // the same triple, naming the cameras of the sensor side
+
+// The model of `trial`, or -1 when its index names none.
+__device__ __forceinline__ long long model_of(const Believed &B, long long trial) {
+    const long long i = B.index != nullptr ? static_cast<long long>(B.index[trial]) : (B.n == 1 ? 0 : trial);
+    return (i >= 0 && i < B.n) ? i : -1;
+}
+
+// The models of the trials first .. first + COUNT - 1 (clamped to the last trial: padding shadows it) into s_cam[COUNT], by all THREADS threads;
+// zeros for a trial without a model.  The caller's next barrier stands between this and the first read.
+template <int COUNT, int THREADS>
+__device__ __forceinline__ void stage_models(const Believed &B, long long first, long long T, uvs_camera *s_cam) {
+    for (int i = threadIdx.x; i < COUNT * kCamWords; i += THREADS) {
+        const int slot = i / kCamWords, word = i - slot * kCamWords;
+        long long trial = first + slot;
+        if (trial >= T) trial = T - 1;
+        const long long model = model_of(B, trial);
+        reinterpret_cast<double *>(s_cam)[i] = model >= 0 ? reinterpret_cast<const double *>(B.models + model)[word] : 0.0;
+    }
+}
+
+// The same for the SCENES of those trials, whose structs' own n_joints / n_points are not read: word 0 of every staged struct is `shape`'s
+// (the launch's n_joints and n_points, from fp), also for a trial without a scene, whose other words are zeros.
+template <int COUNT, int THREADS>
+__device__ __forceinline__ void stage_scenes(const Scenes &S, const uvs_camera &shape, long long first, long long T, uvs_camera *s_cam) {
+    for (int i = threadIdx.x; i < COUNT * kCamWords; i += THREADS) {
+        const int slot = i / kCamWords, word = i - slot * kCamWords;
+        long long trial = first + slot;
+        if (trial >= T) trial = T - 1;
+        const long long model = model_of(S, trial);
+        double value = model >= 0 ? reinterpret_cast<const double *>(S.models + model)[word] : 0.0;
+        if (word == 0) value = reinterpret_cast<const double *>(&shape)[0];
+        reinterpret_cast<double *>(s_cam)[i] = value;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host side, shared
 // The calling thread's error text and the two ways an entry point ends (defined in uvs_vision.hip).
 extern thread_local char g_err[256];
@@ -477,5 +539,8 @@ int fail(int code, const char *fmt, const char *detail = "");
 int launched(const char *what);
 bool colours_ok(int32_t n);
 int check_occluders(const uvs_occluder *occ, int32_t n_occ);    // UVS_ERR_ARG for n_occ outside 0 .. 4 or a NULL occ with n_occ > 0
+// the scene operand: UVS_ERR_ARG for NULL cams, n_cams < 1, or n_cams not in {1, T} without an index
+int check_scenes(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, int64_t T);
+uvs_camera scene_shape(int32_t n_joints, int32_t n_points);    // what a scenes launch passes where its namesake passes *cam: the shape alone
 
 }  // namespace uvs_vision

@@ -364,21 +364,32 @@ def _device_of(*tensors):
     return current_device()
 
 
-def camera_project(plant, q_prev, dq=None, dt=0.0, radius=None, q_out=None, out=None):
+def camera_project(plant, q_prev, dq=None, dt=0.0, radius=None, q_out=None, out=None, cameras=None, camera_index=None):
     """Disc projection of T trials on the current stream (uvs_camera_project_f64).  ``plant``: a ``SyntheticPlant`` (with ``radius`` in metres,
     default plant.DISC_RADIUS) or the ``uvs_camera`` struct of ``SyntheticPlant.to_camera``.  ``q_prev`` (T, n) fp64; with ``dq`` (T, n) the joints
     are q_prev + dq * dt, written to ``q_out`` (T, n) when given.  Returns ``out``: (T, n_points, 3) rows (u, v, r) in pixels; r = -1 for a point
-    that is not in front of the camera."""
+    that is not in front of the camera.
+    ``cameras`` (what ``camera_scenes`` returns or takes) and ``camera_index`` ((T,) integers, host or device): trial t is projected by its
+    own camera (uvs_camera_project_scenes_f64) -- with an index ``cameras[camera_index[t]]``, without one the one camera there is, or
+    ``cameras[t]`` of T -- and ``plant`` only gives the shape.  Trial t has the bits of the call on its camera; a trial whose device-side
+    index names no camera is left unwritten.  None (the default) is the call without the arguments."""
     from . import _vision, plant as plant_mod
-    torch = _torch()
+    if cameras is None and camera_index is not None:
+        raise ValueError('camera_project: camera_index without cameras')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    if cameras is not None:
+        _check_cameras(cameras, camera_index, getattr(q_prev, 'shape', (0,))[0], cam.n_points, cam.n_joints, 'camera_project')
+    torch = _torch()
     T, n = q_prev.shape[0], cam.n_joints
     if out is None:
         out = torch.empty((T, cam.n_points, 3), dtype=torch.float64, device=_device_of(q_prev))
-    rc = _vision.lib().uvs_camera_project_f64(C.byref(cam), T, _operand(q_prev, 'q_prev', torch.float64, (T, n)),
-                                              _operand(dq, 'dq', torch.float64, (T, n), True), float(dt),
-                                              _operand(q_out, 'q_out', torch.float64, (T, n), True),
-                                              _operand(out, 'out', torch.float64, (T, cam.n_points, 3)), _stream())
+    rest = (T, _operand(q_prev, 'q_prev', torch.float64, (T, n)), _operand(dq, 'dq', torch.float64, (T, n), True), float(dt),
+            _operand(q_out, 'q_out', torch.float64, (T, n), True), _operand(out, 'out', torch.float64, (T, cam.n_points, 3)), _stream())
+    if cameras is None:
+        rc = _vision.lib().uvs_camera_project_f64(C.byref(cam), *rest)
+    else:
+        scenes, _keep, _keep_index = _scene_operand(cameras, camera_index, T, cam.n_points, n, radius, _device_of(q_prev), 'camera_project')
+        rc = _vision.lib().uvs_camera_project_scenes_f64(*scenes, cam.n_points, *rest)
     _vision.check(rc)
     return out
 
@@ -522,15 +533,21 @@ def disc_features(discs, n_colours=4, noise=None, out=None, pixels=None, occlude
 
 
 def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_out=None, out=None, pixels=None, discs=None, occluders=None, k=0,
-                    occluder_colours=None):
+                    occluder_colours=None, cameras=None, camera_index=None):
     """``camera_project`` and ``disc_features`` in one launch (uvs_camera_features_f64), bit-identical to the two in a row: joints in, noisy
     detected features (T, 2 n_points) out.  ``discs`` (T, n_points, 3) receives the projection when given.  ``occluders`` at step ``k``:
     uvs_camera_features_occluded_f64, the two occluded calls in a row; with ``occluder_colours`` uvs_camera_features_painted_f64, the two
-    painted ones."""
+    painted ones.
+    ``cameras`` / ``camera_index`` (as ``camera_project`` takes them): trial t on its own camera, with or without occluders and their
+    colours, in one launch (uvs_camera_features_scenes_f64); ``plant`` only gives the shape.  None is the call without the arguments."""
     from . import _vision, plant as plant_mod
+    if cameras is None and camera_index is not None:
+        raise ValueError('camera_features: camera_index without cameras')
     checked = _check_occluders(occluders, getattr(q_prev, 'shape', (0,))[0], k, who='camera_features')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
     paints = _check_occluder_colours(occluder_colours, checked, getattr(q_prev, 'shape', (0,))[0], cam.n_points, 'camera_features')
+    if cameras is not None:
+        _check_cameras(cameras, camera_index, getattr(q_prev, 'shape', (0,))[0], cam.n_points, cam.n_joints, 'camera_features')
     torch = _torch()
     T, n, npts = q_prev.shape[0], cam.n_joints, cam.n_points
     if out is None:
@@ -539,7 +556,13 @@ def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_o
               _operand(q_out, 'q_out', torch.float64, (T, n), True))
     rest = (_operand(noise, 'noise', torch.float64, (T, 2 * npts), True), _operand(out, 'out', torch.float64, (T, 2 * npts)),
             _operand(pixels, 'pixels', torch.int32, (T, npts), True), _operand(discs, 'discs', torch.float64, (T, npts, 3), True), _stream())
-    if checked is None:
+    if cameras is not None:
+        dev = _device_of(q_prev)
+        scenes, _keep, _keep_index = _scene_operand(cameras, camera_index, T, npts, n, radius, dev, 'camera_features')
+        occ, n_occ, _keep_occ = (None, 0, None) if checked is None else _occluder_operand(checked, dev)
+        paint, _keep_paint = (None, None) if paints is None else _paint_operand(paints, dev)
+        rc = _vision.lib().uvs_camera_features_scenes_f64(*scenes, npts, *joints[1:], occ, paint, n_occ, int(k), *rest)
+    elif checked is None:
         rc = _vision.lib().uvs_camera_features_f64(*joints, *rest)
     else:
         occ, n_occ, _keep = _occluder_operand(checked, _device_of(q_prev))
@@ -653,6 +676,89 @@ def _believed_operand(believed, believed_index, T, radius, dev, who):
     return believed.data_ptr(), n, _operand(index, 'believed_index', torch.int32, (T,)), (believed, index)
 
 
+def camera_scenes(models, radius=None, device=None):
+    """The scene operand of the pixel loops: the cameras that RENDER the trials' frames, one ``uvs_camera`` struct each, packed like
+    ``believed_models`` as a uint8 tensor (n_cams, sizeof(uvs_camera)) on the device -- pack once, pass it as ``cameras=`` to as many calls
+    as needed.  ``models``: a ``SyntheticPlant``, a ``Camera`` struct, or a sequence of either (``plant.miscalibrated`` makes variants of a
+    plant).  ``radius`` (metres; default plant.DISC_RADIUS) is read by the sensor side, so it may differ per scene: a scalar, one value per
+    model, or (n_models, n_points); a ``Camera`` struct keeps its own."""
+    from . import _vision, plant as plant_mod
+    torch = _torch()
+    if isinstance(models, (_vision.Camera, plant_mod.SyntheticPlant)):
+        models = [models]
+    models = list(models)
+    if not models:
+        raise ValueError('camera_scenes: at least one model')
+    radii = np.asarray(plant_mod.DISC_RADIUS if radius is None else radius, float)
+    if radii.ndim and radii.shape[0] != len(models):
+        raise ValueError(f'camera_scenes: radius is a scalar or one value (or one row of n_points) per model, got {radii.shape} for {len(models)} models')
+    size = C.sizeof(_vision.Camera)
+    host = np.empty((len(models), size), np.uint8)
+    for i, model in enumerate(models):
+        if not isinstance(model, (_vision.Camera, plant_mod.SyntheticPlant)):
+            raise ValueError('camera_scenes: a SyntheticPlant, a Camera struct, or a sequence of them')
+        cam = _camera(model, radii[i] if radii.ndim else radii)
+        host[i] = np.frombuffer(C.string_at(C.addressof(cam), size), np.uint8)
+    return torch.from_numpy(host).to(current_device(device))
+
+
+def _check_cameras(cameras, camera_index, T, n_points, n_joints, who):
+    """What can be said of a ``cameras=`` / ``camera_index=`` pair for T output trials of the given shape on the host alone, before anything
+    is packed or uploaded: ValueError, or (n_cams, the index as a host int32 array | the caller's device tensor | None)."""
+    import torch                                                     # not _torch(): these refusals need no GPU
+    from . import _vision, plant as plant_mod
+    if cameras is None:
+        raise ValueError(f'{who}: camera_index without cameras')
+    if n_joints != 6:
+        raise ValueError(f'{who}: the scene kernels are built for the six-joint arms of this project, not for {n_joints} joints')
+    size = C.sizeof(_vision.Camera)
+    if torch.is_tensor(cameras):
+        if cameras.dtype != torch.uint8 or cameras.dim() != 2 or cameras.shape[1] != size or not cameras.is_contiguous():
+            raise ValueError(f'{who}: cameras is what camera_scenes returns: a contiguous uint8 tensor (n_cams, {size}) on the device')
+        n = cameras.shape[0]
+    else:
+        models = [cameras] if isinstance(cameras, (_vision.Camera, plant_mod.SyntheticPlant)) else list(cameras)
+        for model in models:
+            if not isinstance(model, (_vision.Camera, plant_mod.SyntheticPlant)):
+                raise ValueError(f'{who}: cameras is a SyntheticPlant, a Camera struct, a sequence of them, or what camera_scenes returns')
+            if (model.n_points, model.n_joints) != (n_points, n_joints):
+                raise ValueError(f'{who}: a camera of {model.n_points} points and {model.n_joints} joints among the scenes of a loop of '
+                                 f'{n_points} points and {n_joints} joints')
+        n = len(models)
+    if n < 1:
+        raise ValueError(f'{who}: at least one camera')
+    if camera_index is None:
+        if n not in (1, T):
+            raise ValueError(f'{who}: {n} cameras for {T} trials: one, or one per trial, or pass camera_index')
+        return n, None
+    if torch.is_tensor(camera_index) and camera_index.is_cuda:       # the kernels void a trial whose index names no camera
+        if tuple(camera_index.shape) != (T,):
+            raise ValueError(f'{who}: camera_index is {T} integers, one per output trial')
+        return n, camera_index
+    host = np.asarray(camera_index.numpy() if torch.is_tensor(camera_index) else camera_index)
+    if host.shape != (T,) or host.dtype.kind not in 'iu':
+        raise ValueError(f'{who}: camera_index is {T} integers, one per output trial')
+    if host.size and (host.min() < 0 or host.max() >= n):
+        raise ValueError(f'{who}: camera_index must lie in [0, {n}), got {int(host.min())} .. {int(host.max())}')
+    return n, np.ascontiguousarray(host, np.int32)
+
+
+def _scene_operand(cameras, camera_index, T, n_points, n_joints, radius, dev, who):
+    """((pointer, n_cams, index pointer or None), the packed tensor, the index tensor or None) of a ``cameras=`` / ``camera_index=`` pair for
+    T output trials; a host-side index is checked before it is uploaded."""
+    torch = _torch()
+    n, index = _check_cameras(cameras, camera_index, T, n_points, n_joints, who)
+    if not torch.is_tensor(cameras):
+        cameras = camera_scenes(cameras, radius, dev)
+    if not (cameras.is_cuda or cameras.is_pinned()):
+        raise ValueError(f'{who}: cameras is what camera_scenes returns: a tensor on the device (or pinned)')
+    if index is None:
+        return (cameras.data_ptr(), n, None), cameras, None
+    if not torch.is_tensor(index):
+        index = torch.from_numpy(index).to(dev)
+    return (cameras.data_ptr(), n, _operand(index, 'camera_index', torch.int32, (T,))), cameras, index
+
+
 def camera_guess(plant, q_start, f0, radius=None, out=None, believed=None, believed_index=None):
     """The analytic initial guess of T trials on the device (uvs_camera_guess_f64): what ``plant.analytic_guess`` returns per trial for the
     joints ``q_start`` (T, 6) and the detected features ``f0`` (T, 2 n_points), both cuda fp64, to about 1e-13 relative (another order of
@@ -720,14 +826,22 @@ CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
 ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
 
 
-def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=None):
+def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=None, scenes=None):
     """The stepwise loops' sensor launch at step k: uvs_camera_features_f64, or its occluded namesake when ``occ`` -- None, or the
     (pointer, n_occ, tensor) of ``_occluder_operand`` -- is given.  Returns f(k, q_prev, dq_prev, q, noise, f, pixels) -> return code.
     With ``hold`` > 0 the step is that launch and uvs_hold_features_f64 behind it on the same stream, on the same rows: the callable then
     takes two more row pointers, f(..., pixels, f_prev, held), and keeps the counters of consecutive held steps (T, 4) itself.
-    ``paint``: None, or the (pointer, tensor) of ``_paint_operand`` next to ``occ`` -- the launch is then uvs_camera_features_painted_f64."""
+    ``paint``: None, or the (pointer, tensor) of ``_paint_operand`` next to ``occ`` -- the launch is then uvs_camera_features_painted_f64.
+    ``scenes``: None, or the (pointer, n_cams, index pointer) of ``_scene_operand`` -- the launch is then uvs_camera_features_scenes_f64 for
+    ``npts`` points, with or without ``occ`` and ``paint``, and ``cam_ref`` is not read."""
     from . import _vision
-    if paint is not None:
+    if scenes is not None:
+        per_scene = _vision.lib().uvs_camera_features_scenes_f64
+        occ_ptr, n_occ = (None, 0) if occ is None else occ[:2]
+        paint_ptr = None if paint is None else paint[0]
+        detect = lambda k, q_prev, dq_prev, q, noise, f, pixels: per_scene(*scenes, npts, T, q_prev, dq_prev, dt, q, occ_ptr, paint_ptr, n_occ,   # noqa: E731
+                                                                           k, noise, f, pixels, None, stream)
+    elif paint is not None:
         painted = _vision.lib().uvs_camera_features_painted_f64
         detect = lambda k, q_prev, dq_prev, q, noise, f, pixels: painted(cam_ref, T, q_prev, dq_prev, dt, q, occ[0], paint[0], occ[1], k, noise,   # noqa: E731
                                                                          f, pixels, None, stream)
@@ -749,11 +863,14 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=
     return held_step
 
 
-def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None):
+def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None, scenes=None):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
     ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models.
     ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none).  ``hold`` > 0 (stepwise alone): a third launch per
-    step, uvs_hold_features_f64, between the two.  ``paint``: None, or the paint operand next to ``occ`` (stepwise alone)."""
+    step, uvs_hold_features_f64, between the two.  ``paint``: None, or the paint operand next to ``occ`` (stepwise alone).
+    ``scenes``: None, or the (pointer, n_cams, index pointer) of ``_scene_operand`` -- every trial's frames come from its own camera
+    (the one launch: uvs_camera_believed_loop_scenes_f64; stepwise: uvs_camera_features_scenes_f64); ``believed`` is then given, and
+    ``cam`` is the shape alone."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -769,7 +886,9 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         stats = torch.empty((T, 3), **f64)
         pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
         outputs = (ptr('q'), ptr('f'), ptr('dq'), ptr('err'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
-        if believed is None:
+        if scenes is not None:
+            rc = _vision.lib().uvs_camera_believed_loop_scenes_f64(C.byref(fp), *scenes, T, *believed, q0, noise_ptr, *outputs)
+        elif believed is None:
             rc = _vision.lib().uvs_camera_analytical_loop_f64(C.byref(fp), C.byref(cam), T, q0, noise_ptr, *outputs)
         else:
             rc = _vision.lib().uvs_camera_believed_loop_f64(C.byref(fp), C.byref(cam), T, *believed, q0, noise_ptr, *outputs)
@@ -779,7 +898,7 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint)
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, scenes)
     held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     if believed is None:
         step = lambda *rows: _vision.lib().uvs_camera_analytical_step_f64(fp_ref, cam_ref, T, *rows)          # noqa: E731
@@ -863,17 +982,20 @@ def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
     return tp, keep
 
 
-def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0, paints=None):
+def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0, paints=None, scenes=None):
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
     then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
     ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
     ``_gather_by_source``) -- the launch is then uvs_camera_closed_loop_occluded_f64, with or without trial_params.  ``hold`` > 0: the launch
     is uvs_camera_closed_loop_held_f64, with or without either, and the result has 'held'.  ``paints``: None, or what
     ``_check_occluder_colours`` returned next to ``occluders`` -- the launch is then uvs_camera_closed_loop_painted_f64 for any hold >= 0,
-    and the result has 'held' only with hold > 0."""
+    and the result has 'held' only with hold > 0.  ``scenes``: None, or the (operand, packed cameras, index tensor or None) of
+    ``_scene_operand`` for the T output trials (no 'source' next to them either) -- the launch is then uvs_camera_closed_loop_scenes_f64,
+    whatever else is given; f0 comes from the step-0 frame of every trial's own scene, and x0 is given (camera_closed_loop has made it)."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
+    scene_kw = {} if scenes is None else dict(cameras=scenes[1], camera_index=scenes[2])
     n_in, dev = q_start.shape[0], q_start.device
     T = n_in if trial_params is None else _check_camera_trial_params(trial_params, n_in)[0]
     tp, _keep = (None, ()) if trial_params is None else _camera_trial_params_struct(trial_params, T, n_in, m, dev)
@@ -884,8 +1006,9 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     occ = None if occluders is None else _occluder_operand(occluders, dev)
     paint = None if paints is None else _paint_operand(paints, dev)
     if fp.initial_guess:                                             # the step-0 frame, occluders at k = 0 and their paints included
-        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2], occluder_colours=None if paint is None else paint[1])
-        if x0 is None and guess == 'device':
+        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2], occluder_colours=None if paint is None else paint[1],
+                        **scene_kw)
+        if x0 is None and guess == 'device' and scenes is None:
             x0 = camera_guess(cam, q_start, f0)
     if x0 is None:
         raise ValueError("camera_closed_loop: fused=True takes x0, or guess='device' with fp.initial_guess")
@@ -898,6 +1021,15 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
     operands = (q0, noise_ptr, X0.data_ptr(), f0.data_ptr(), ptr('q'), ptr('f'), ptr('dq'), ptr('err'), ptr('kappa'), status.data_ptr(),
                 k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
+    if scenes is not None:
+        held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
+        rc = _vision.lib().uvs_camera_closed_loop_scenes_f64(C.byref(fp), *scenes[0], T, None if tp is None else C.byref(tp),
+                                                             None if occ is None else occ[0], None if paint is None else paint[0],
+                                                             0 if occ is None else occ[1], hold, *operands[:-1],
+                                                             None if held is None else held.data_ptr(), operands[-1])
+        _vision.check(rc)
+        out = dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
+        return dict(out, held=held) if hold else out
     if paint is not None:
         held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
         rc = _vision.lib().uvs_camera_closed_loop_painted_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp), occ[0], paint[0],
@@ -942,7 +1074,7 @@ def _gather_by_source(q_start, noise, x0, trial_params):
 
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
-                       believed_index=None, trial_params=None, occluders=None, hold=0, occluder_colours=None):
+                       believed_index=None, trial_params=None, occluders=None, hold=0, occluder_colours=None, cameras=None, camera_index=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -1006,11 +1138,36 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     an estimator is ONE launch, uvs_camera_closed_loop_painted_f64, with or without ``trial_params`` and for any ``hold``; fused=False
     passes the paints to uvs_camera_features_painted_f64 at every step, for the estimators and the calibrated and believed baselines
     alike; the two return the same bits.  It needs ``occluders`` (ValueError), and fused=True with ANALYTICAL stays the ValueError it is
-    for occluders."""
+    for occluders.
+    ``cameras`` (what ``camera_scenes`` returns or takes) and ``camera_index`` ((T,) integers per OUTPUT trial, host or device): a SCENE per
+    trial -- the camera that renders trial t's frames is ``cameras[camera_index[t]]``, or without an index the one camera there is, or
+    ``cameras[t]`` of T -- so that a Monte-Carlo over true cameras (focal length, target positions and sizes, hand-eye geometry) is one
+    batch.  None (the default) is the call without the arguments: its routes, its entry points, its bits.  With cameras ``plant`` stays the
+    NOMINAL model: it gives the shape.  fused=True with an estimator is ONE launch (uvs_camera_closed_loop_scenes_f64) with any of
+    ``trial_params``, ``occluders``, ``occluder_colours`` and ``hold``; fused=False passes the scenes to uvs_camera_features_scenes_f64 at
+    every step, for the estimators and for ANALYTICAL alike; the two return the same bits, and trial t has the bits of the call without
+    cameras on its own camera.  ANALYTICAL runs the law on ``believed`` / ``believed_index`` if given, otherwise on the trial's own scene
+    (fused=True: uvs_camera_believed_loop_scenes_f64; fused=False: uvs_camera_believed_step_f64 behind the scenes' features); with
+    occluders or hold > 0 fused=True stays the ValueError it is.  Estimators: f0 and the initial guess come from the step-0 frame of the
+    trial's own scene; guess='device' computes the guess on ``believed`` if given, otherwise on the trial's scene
+    (uvs_camera_believed_guess_f64); guess='host' without ``x0`` next to cameras is a ValueError.  Next to trial_params['source'] the inputs
+    are gathered by source before the launch, as next to occluders.  A trial whose device-side index names no camera FAILs with
+    k_done = 0, alone.  ValueErrors before any device work: ``camera_index`` without ``cameras``, a host-side index out of range or of the
+    wrong length, a model whose shape is not fp's."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
+    if cameras is None and camera_index is not None:
+        raise ValueError('camera_closed_loop: camera_index without cameras')
     analytical = fp.method == _lib.METHOD_ANALYTICAL
+    if cameras is not None:
+        n_out = getattr(q_start, 'shape', (0,))[0]
+        if isinstance(trial_params, dict) and trial_params.get('source') is not None:
+            n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
+        _check_cameras(cameras, camera_index, n_out, fp.m // 2, fp.n, 'camera_closed_loop')
+        if not analytical and x0 is None and guess == 'host':
+            raise ValueError("camera_closed_loop: next to cameras the host has no per-trial kinematics for the initial guess: pass x0, or "
+                             "guess='device'")
     hold = _check_hold(hold)
     if hold and analytical and fused:
         raise ValueError('camera_closed_loop: the calibrated baseline has no one-launch loop that holds a lost disc: use fused=False')
@@ -1051,7 +1208,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     if fused and not getattr(q_start, 'is_cuda', False):
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     torch = _torch()
-    if occluders is not None and trial_params is not None and trial_params.get('source') is not None:
+    if (occluders is not None or cameras is not None) and trial_params is not None and trial_params.get('source') is not None:
         q_start, noise, x0, trial_params = _gather_by_source(q_start, noise, x0, trial_params)
     K, m, n = fp.steps, fp.m, fp.n
     T, dev = q_start.shape[0], q_start.device
@@ -1059,27 +1216,38 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         raise ValueError('camera_closed_loop: at least one step (fp.steps) and one trial')
     if not q_start.is_cuda:
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
+    scenes, scene_kw = None, {}                                      # the scene operand of the T output trials, and what the calls below take
+    if cameras is not None:
+        scenes = _scene_operand(cameras, camera_index, T, m // 2, n, radius, dev, 'camera_closed_loop')
+        scene_kw = dict(cameras=scenes[1], camera_index=scenes[2])
     if analytical:
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
         occ = None if occluders is None else _occluder_operand(occluders, dev)
         paint = None if paints is None else _paint_operand(paints, dev)
-        if believed is None:
+        if believed is None and scenes is None:
             return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, occ=occ, hold=hold, paint=paint)
-        *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
-        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold, paint=paint)
-    if believed is not None:                                         # an estimator that starts from the wrong model; the rest is the x0= path
-        cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+        if believed is None:                                         # the calibrated law on every trial's own scene
+            operand = scenes[0]
+        else:
+            *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
+        return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold, paint=paint,
+                                              scenes=None if scenes is None else scenes[0])
+    if believed is not None or (scenes is not None and x0 is None):  # an estimator that starts from a model in memory: the believed one, or
+        cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)                           # its own scene; the rest is the x0= path
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        x0 = camera_guess(cam, q_start, camera_features(cam, q_start, occluders=occluders, occluder_colours=paints), radius=radius, believed=believed,
-                          believed_index=believed_index)
+        if not fp.initial_guess:
+            raise ValueError('camera_closed_loop: x0 is needed when fp.initial_guess is 0 (the reference draws it unseeded, experiment.py:117)')
+        models, index = (believed, believed_index) if believed is not None else (scenes[1], scenes[2])
+        x0 = camera_guess(cam, q_start, camera_features(cam, q_start, occluders=occluders, occluder_colours=paints, **scene_kw), radius=radius,
+                          believed=models, believed_index=index)
     if fused and (x0 is not None or guess == 'device' or not fp.initial_guess):
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -1093,7 +1261,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     occ = None if occluders is None else _occluder_operand(occluders, dev)
     paint = None if paints is None else _paint_operand(paints, dev)
     if fp.initial_guess:                                             # the step-0 frame, occluders at k = 0 and their paints included
-        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2], occluder_colours=None if paint is None else paint[1])
+        camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2], occluder_colours=None if paint is None else paint[1],
+                        **scene_kw)
         if x0 is None and guess == 'device':
             x0 = camera_guess(cam, q_start, f0)
         if x0 is None:
@@ -1108,7 +1277,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
         return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2], hold,
-                                         None if paint is None else paint[1])
+                                         None if paint is None else paint[1], scenes)
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
@@ -1116,7 +1285,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     dq_zero = torch.zeros((T, n), **f64)
     step = _lib.lib().uvs_rmckf_step_f64
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint)
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, None if scenes is None else scenes[0])
     held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
     if hold:
