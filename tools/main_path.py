@@ -3,10 +3,16 @@
 branch is taken.  Splits the function into basic blocks (labels and branch instructions), finds the largest loop (backward branch) and runs a
 shortest-path search from its header to its latch, weighing a block by its VALU instructions.
 
-usage: tools/main_path.py listing.s [substring-of-kernel-name] [--blocks]"""
+With --logged the cycle is forced through the blocks that hold the step's global stores (X, err, q, ...) and the LDS writes of the statistics, which
+the cheapest cycle skips when a launch can switch them off: that count is the one to set against the PMC figure of a launch that logs.  --through=REGEX
+does the same for the blocks holding an instruction that matches REGEX.
+
+usage: tools/main_path.py listing.s [substring-of-kernel-name] [--blocks] [--logged | --through=REGEX]"""
 import heapq
 import re
 import sys
+
+LOGGED = r'^(global_store|ds_write)'
 
 
 def kernel_text(path, needle):
@@ -56,9 +62,10 @@ def stats(ins):
     return dict(all=len(ins), valu=v, accvgpr=acc, f64=f64, lds=lds, vmem=vm, salu=sal)
 
 
-def main():
-    args = [a for a in sys.argv[1:] if not a.startswith('--')]
-    name, lines = kernel_text(args[0], args[1] if len(args) > 1 else None)
+def step_path(listing, needle=None, through=None):
+    """(kernel name, blocks, path): the block indices of the cheapest cycle through the step loop, from the anchor block back to it.  through: a regular
+    expression; the cycle is made to pass every loop block that holds a matching instruction (in the order of their distance from the anchor)."""
+    name, lines = kernel_text(listing, needle)
     bl = blocks_of(lines)
     idx = {b[0]: i for i, b in enumerate(bl)}
     succ = []
@@ -100,30 +107,53 @@ def main():
     # anchor of the cycle: the block every step passes -- the control law's QR (most DPP moves); the cheapest cycle through it is the plain step
     head = max(loop, key=lambda k: sum(1 for i in bl[k][1] if 'dpp' in i or i.startswith(('v_permlane', 'global_store'))))
     cost = lambda k: stats(bl[k][1])['valu'] + 0.25 * len(bl[k][1])       # noqa: E731  (VALU first, everything else as a tie-breaker)
-    dist, prev, pq = {}, {}, []
-    for v in succ[head]:
-        if v in loop:
-            dist[v] = cost(v)
-            prev[v] = head
-            heapq.heappush(pq, (dist[v], v))
-    while pq:
-        d, u = heapq.heappop(pq)
-        if d > dist.get(u, 1e18) or u == head:
-            continue
-        for v in succ[u]:
-            if v not in loop:
+    def leg(src, dst):
+        """Blocks after src up to and including dst on the cheapest way from src to dst inside the loop (dst may be src: a cycle); None if there is none."""
+        dist, prev, pq = {}, {}, []
+        for v in succ[src]:
+            if v in loop and cost(v) < dist.get(v, 1e18):
+                dist[v], prev[v] = cost(v), src
+                heapq.heappush(pq, (dist[v], v))
+        while pq:
+            d, u = heapq.heappop(pq)
+            if d > dist.get(u, 1e18) or u == dst or u == head:          # no leg runs on through the anchor: every leg stays inside one step
                 continue
-            nd = d + cost(v)
-            if nd < dist.get(v, 1e18):
-                dist[v], prev[v] = nd, u
-                heapq.heappush(pq, (nd, v))
-    path, u = [], prev[head]
-    while u != head:
-        path.append(u)
-        u = prev[u]
-    path.append(head)
-    path.reverse()
-    latch = path[-1]
+            for v in succ[u]:
+                if v not in loop:
+                    continue
+                nd = d + cost(v)
+                if nd < dist.get(v, 1e18):
+                    dist[v], prev[v] = nd, u
+                    heapq.heappush(pq, (nd, v))
+        if dst not in dist:
+            return None, 1e18
+        way, u = [dst], prev[dst]
+        while u != src:
+            way.append(u)
+            u = prev[u]
+        return way[::-1], dist[dst]
+
+    stops = []
+    if through:
+        want = [k for k in loop if k != head and any(re.search(through, i) for i in bl[k][1])]
+        stops = sorted(want, key=lambda k: leg(head, k)[1])
+    path, at = [head], head
+    for k in stops + [head]:
+        way, _ = leg(at, k)
+        if way is None:                                                  # not on any way from here within one step (a block of another path): left out
+            print(f'  (block {bl[k][0]} cannot be reached from {bl[at][0]} within a step: skipped)', file=sys.stderr)
+            continue
+        path += way
+        at = k
+    return name, bl, path[:-1]                                           # the closing anchor is not repeated
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith('--')]
+    through = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--through=')), None)
+    if '--logged' in sys.argv:
+        through = LOGGED
+    name, bl, path = step_path(args[0], args[1] if len(args) > 1 else None, through)
     tot = {}
     for k in path:
         st = stats(bl[k][1])
@@ -132,7 +162,7 @@ def main():
         if '--blocks' in sys.argv:
             print(f'  {bl[k][0]:12s} {st}')
     whole = stats([i for b in bl for i in b[1]])
-    print(f'{name[:110]}\n  loop {bl[head][0]} .. {bl[latch][0]}: cheapest step {tot}\n  whole kernel {whole}')
+    print(f'{name[:110]}\n  loop {bl[path[0]][0]} .. {bl[path[-1]][0]}: {"step through " + through if through else "cheapest step"} {tot}\n  whole kernel {whole}')
 
 
 if __name__ == '__main__':

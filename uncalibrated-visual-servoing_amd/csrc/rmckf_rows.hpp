@@ -76,6 +76,17 @@ UVS_DEV double in_reg(double x) {
     asm volatile("" : "+v"(x));
     return x;
 }
+// Per-lane choice c ? a : b between two register-resident values, as a select.  Both are pinned BEFORE the choice: with the pin inside the arms
+// ("c ? in_reg(a) : in_reg(b)") the volatile asm cannot be speculated and the choice becomes two exec-mask regions -- two saveexec pairs and a
+// taken branch per choice, which a lone wavefront pays in full (tools/ubench/control.hip) -- instead of two v_cndmask_b32.  The same bits either way.
+// SELECT = false keeps the regions: the kernels that run two wavefronts per SIMD hide them, and IMCC-KF has no register left for the second candidate.
+template <bool SELECT>
+UVS_DEV double pick2(bool c, double a, double b) {
+    if constexpr (!SELECT) return c ? in_reg(a) : in_reg(b);
+    a = in_reg(a);
+    b = in_reg(b);
+    return c ? a : b;
+}
 // Per-lane choice among the L values v[0..L) by the lane's position in its group.
 template <int L>
 UVS_DEV double pick_sub(const double *v, int sub) {

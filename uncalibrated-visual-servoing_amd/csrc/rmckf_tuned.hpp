@@ -104,6 +104,8 @@ void UVS_CLOSED_TUNED_KERNEL(const ClosedKernelArgs A) {
     static_assert(PV >= 0 && PV <= R, "PV counts covariance blocks");
     constexpr int PL = R - PV;                                     // blocks resident in LDS
     constexpr bool SHARED_P = (METHOD == UVS_METHOD_KF || METHOD == UVS_METHOD_IMCCKF) && PV >= 1;   // identical blocks: keep one (RowShare)
+    // Two-lane RMCKF runs one wavefront per SIMD: its per-lane choices in the step loop are selects, not exec-mask regions (pick2, rmckf_rows.hpp)
+    constexpr bool SELECTS = (METHOD == UVS_METHOD_GMCKF && L == 2);
     using PC = PlantLds<M, N>;
     __shared__ double lds_x[XREG ? 1 : R * N][64];
     __shared__ double lds_acc[3 * R][64];
@@ -654,7 +656,7 @@ void UVS_CLOSED_TUNED_KERNEL(const ClosedKernelArgs A) {
                 double va[3], vz[3], vp[3];
                 if constexpr (!SPLIT) {
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) { va[r] = odd ? in_reg(T[r][1]) : in_reg(T[r][0]); vz[r] = T[r][2]; vp[r] = T[r][3]; }
+                    for (int r = 0; r < 3; ++r) { va[r] = pick2<SELECTS>(odd, T[r][1], T[r][0]); vz[r] = T[r][2]; vp[r] = T[r][3]; }
                 } else {
                     // right-to-left: start from the last group's columns, then apply the earlier groups' affine maps
                     {
@@ -664,7 +666,7 @@ void UVS_CLOSED_TUNED_KERNEL(const ClosedKernelArgs A) {
 #pragma unroll
                             for (int c = 0; c < 4; ++c) last[r][c] = pair_from<L, G - 1>(T[r][c]);
 #pragma unroll
-                        for (int r = 0; r < 3; ++r) { va[r] = odd ? in_reg(last[r][1]) : in_reg(last[r][0]); vz[r] = last[r][2]; vp[r] = last[r][3]; }
+                        for (int r = 0; r < 3; ++r) { va[r] = pick2<SELECTS>(odd, last[r][1], last[r][0]); vz[r] = last[r][2]; vp[r] = last[r][3]; }
                     }
 #pragma unroll
                     for (int g = G - 2; g >= 0; --g) {
@@ -1099,7 +1101,7 @@ void UVS_CLOSED_TUNED_KERNEL(const ClosedKernelArgs A) {
 #pragma unroll
         for (int u = 0; u < JG; ++u) {
             if constexpr (G == 1) dq_own[u] = dq[u];
-            else if constexpr (G == 2) dq_own[u] = grp ? in_reg(dq[JG + u]) : in_reg(dq[u]);
+            else if constexpr (G == 2) dq_own[u] = pick2<SELECTS>(grp, dq[JG + u], dq[u]);
             else dq_own[u] = (grp == 0) ? in_reg(dq[u]) : (grp == 1 ? in_reg(dq[JG + u]) : in_reg(dq[2 * JG + u]));
         }
         if (on_q) {
