@@ -34,8 +34,15 @@ the nominal plant (plant.miscalibrated, seeded: focal length +-10 %, targets +-2
 ONE launch per method (engine.camera_closed_loop(cameras=..., camera_index=...)): every trial's frames come from its own camera.  KF, MCKF,
 IMCC-KF and GMCKF start from the nominal model's guess, next to the calibrated law on the nominal model and on the truth.  Prints the median
 ISE / IAE / ITAE over the trials that ran to the end, the FAIL count and the FAILs of the worst scene.
+--moving asks the classic servoing question: can the loop TRACK?  After the servo has converged the target moves for a window of steps
+(MOVING_WINDOW below, every disc with the same seeded world velocity of MOVING_SPEED metres per step in the floor plane, one direction per
+motion) and then stops (engine.camera_closed_loop(target_motion=..., motion_window=...)): N_MOTIONS motions x the trials in ONE launch per
+method.  While the target moves, the features move and dq does not explain it -- the estimators' measurement model is broken at every step
+-- and the calibrated law's depths go stale: its model of the points stays where it was.  The chosen estimator, KF and the calibrated law on
+the same starts and noise; prints the median ISE / IAE / ITAE, the FAIL count, and the median feature error at the window's last step and
+at the last step of the run (re-convergence).
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N]"""
+       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving]"""
 import argparse
 import os
 import sys
@@ -283,6 +290,54 @@ def scenes_table(uvs, n_scenes, trials=64, sigma=0.3, radius=None, seed=0):
     return lines
 
 
+MOVING_WINDOW = (150, 200)                                            # steps: the target moves after the servo has converged, then stops
+MOVING_SPEED = 0.001                                                 # metres per step: 5 cm over the window, some 17 px at the goal
+N_MOTIONS = 8
+
+
+def moving_velocities(n_motions, n_points, seed, speed=MOVING_SPEED):
+    """(n_motions, n_points, 3) world velocities: per motion one seeded direction in the floor plane, the same for every disc."""
+    angle = np.random.default_rng(seed + 2000).uniform(0.0, 2.0 * np.pi, n_motions)
+    v = np.stack([speed * np.cos(angle), speed * np.sin(angle), np.zeros(n_motions)], axis=1)
+    return np.repeat(v[:, None, :], n_points, axis=1)
+
+
+def moving_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed=0, n_motions=N_MOTIONS, window=MOVING_WINDOW):
+    """The tracking table as a list of lines: n_motions x trials in ONE launch per method (engine.camera_closed_loop(target_motion=,
+    motion_window=)).  No finding is drawn here: the table is what the experiment prints."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    methods = tuple(dict.fromkeys((method, 'KF', 'ANALYTICAL')))
+    fps = {name: uvs.engine.make_params(8, 6, name, 10.0, False, 0.05, 15.0, 0.2, desired, True) for name in methods}
+    K = fps[method].steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    noise = rng.standard_normal((K, trials, 8)) * sigma
+    q0_d = torch.as_tensor(np.tile(q0, (n_motions, 1)), device='cuda')           # the same starts and the same noise under every motion
+    noise_d = torch.as_tensor(np.tile(noise, (1, n_motions, 1)), device='cuda')
+    T = n_motions * trials
+    motions = uvs.engine.target_motions(np.repeat(moving_velocities(n_motions, 4, seed), trials, axis=0), window, 4, T)
+    at = (min(window[1], K) - 1, K - 1)
+    lines = [f'{n_motions} target motions ({MOVING_SPEED * 1e3:g} mm per step in the floor plane during steps {window[0]} .. {window[1] - 1}) x {trials} '
+             f'trials of {K} steps in one launch per method, white noise {sigma} px; median over the trials that ran to the end',
+             f'{"":28s}{"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"FAIL":>8s}{"|err| at step " + str(at[0]):>20s}{"|err| at step " + str(at[1]):>20s}']
+    for name, fp in fps.items():
+        kw = dict(radius=radius, fused=True, want=('err',), target_motion=motions)
+        if name != 'ANALYTICAL':
+            kw['guess'] = 'device'
+        for label, more in ((name + ', still target', dict(kw, target_motion=None)), (name + ', moving target', kw)):
+            out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, **more)
+            torch.cuda.synchronize()
+            done = (out['status'] == 0).cpu().numpy()
+            med = np.median(out['stats'].cpu().numpy()[done], axis=0) if done.any() else np.full(3, np.nan)
+            err = out['err'].cpu().numpy()
+            norms = [np.median(np.linalg.norm(err[k][done], axis=1)) if done.any() else np.nan for k in at]
+            lines.append(f'{label:28s}{med[0]:12.3f}{med[1]:12.3f}{med[2]:12.3f}{int((~done).sum()):>8d}{norms[0]:20.3f}{norms[1]:20.3f}')
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -302,11 +357,16 @@ def main():
                          '(with --occlusion --hold N: in front of the wide bar, lost discs held)')
     ap.add_argument('--scenes', type=int, default=0, metavar='N',
                     help='N seeded true scenes x the trials in one launch per method: the estimators and the calibrated law, and nothing else')
+    ap.add_argument('--moving', action='store_true',
+                    help='the target moves for a window of steps after convergence: the estimator, KF and the calibrated law, and nothing else')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
     if args.hold and not args.occlusion:
         ap.error('--hold goes with --occlusion')
+    if args.moving:
+        print('\n'.join(moving_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
+        return
     if args.scenes:
         print('\n'.join(scenes_table(uvs, args.scenes, args.trials, args.sigma, args.radius, args.seed)))
         return

@@ -500,6 +500,59 @@ int uvs_camera_believed_loop_scenes_f64(const struct uvs_filter_params *fp, cons
                                         const double *q_start, const double *noise, double *q_log, double *f_log, double *dq_log,
                                         double *err_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, void *stream);
 
+/*
+ * MOVING TARGETS: the discs move while the loop runs.  Every scene above is static -- the world points a trial looks at at step 0 are the
+ * ones it looks at at step K - 1.  Below each OUTPUT trial may carry a motion, the one disturbance that breaks the estimators'
+ * measurement model z = J dq continuously, and the one the calibrated law is not immune to: its model of the points stays where it was.
+ * The rule (plant.target_at states it once in numpy; every kernel below is held to it bit for bit):
+ *   Each disc p has a world velocity v[p] in metres per step, and one window (k_on, k_off) applies to all discs of the trial.
+ *   At step k >= 0 the target has moved s(k) = clamp(k - k_on, 0, max(k_off - k_on, 0)) steps, formed in 64-bit integers: nothing
+ *     overflows, whatever the int32 fields hold.
+ *   If s == 0 the world point of disc p is points[p] itself, bits untouched, with no arithmetic at all -- also for a -0.0 coordinate
+ *     and for a velocity that is not finite.  Otherwise, per coordinate, points[p][c] + (double)s * v[p][c]: one rounded multiply, then
+ *     one rounded add, as the joint step does it.  On the device the choice is a select, not a branch.
+ *   Everything downstream is the text above on that point: projection, apparent radius focal * radius / zc, the pixel rule, occluders,
+ *     paints and hold.
+ * The operand: motion [T] structs in device (or pinned host) memory, indexed by OUTPUT trial like occluders, paints and cam_index;
+ * NULL = nothing moves.  The struct's values are not validated: the device rule is total.
+ * Each entry point has its *_scenes_* namesake's operands in its order with `motion` directly after cam_index (the project call, which
+ * has no k, also takes the step k after dt), its namesake's refusals in their order, all before the first HIP call; the project call
+ * then adds UVS_ERR_ARG for k < 0.  T == 0 returns UVS_OK and launches nothing.
+ * Bit for bit: (a) motion == NULL, or a trial whose s(k) == 0 at every step, has the bits of the *_scenes_* namesake; (b) at a given k a
+ * stand-alone call has the bits of the scenes namesake on a camera whose points were moved on the host by the numpy rule; (c) a padding
+ * wavefront reads the motion of the trial it shadows and stores nothing; (d) a void trial (no scene, or a void source) is void as
+ * before, and its motion never forms an output.
+ * The loops stage their trials' motions through LDS (104 B per trial) once, next to the scenes, and form a moved point in registers
+ * where it is projected; nothing is written back.  uvs_camera_believed_loop_moving_f64 moves the SENSOR side's points alone: the law's
+ * model (believed, or the trial's own scene) stays where it was -- the controller does not know the target's motion.
+ * Built: what the scenes namesakes build -- the estimator loop for GMCKF, KF and IMCC-KF at (8, 6), (6, 6) and (2, 6), MCKF at (8, 6)
+ * and (2, 6) (at (6, 6) refused with UVS_ERR_METHOD as everywhere), the baseline loop at the three shapes, each in both workgroup forms
+ * with 0 B of scratch memory.
+ */
+typedef struct uvs_target_motion {          /* 104 bytes */
+    double  v[UVS_CAMERA_MAX_POINTS][3];    /* world metres per step */
+    int32_t k_on, k_off;
+} uvs_target_motion;
+
+int uvs_camera_project_moving_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, const uvs_target_motion *motion,
+                                  int32_t n_points, int64_t T, const double *q_prev, const double *dq, double dt, int32_t k, double *q_out,
+                                  double *discs_out, void *stream);
+int uvs_camera_features_moving_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, const uvs_target_motion *motion,
+                                   int32_t n_points, int64_t T, const double *q_prev, const double *dq, double dt, double *q_out,
+                                   const uvs_occluder *occ, const int32_t *paint, int32_t n_occ, int32_t k, const double *noise,
+                                   double *f_out, int32_t *pixels_out, double *discs_out, void *stream);
+int uvs_camera_closed_loop_moving_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                      const uvs_target_motion *motion, int64_t T, const uvs_camera_trial_params *tp, const uvs_occluder *occ,
+                                      const int32_t *paint, int32_t n_occ, int32_t hold, const double *q_start, const double *noise,
+                                      const double *x0, const double *f0, double *q_log, double *f_log, double *dq_log, double *err_log,
+                                      double *kappa_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, int32_t *held,
+                                      void *stream);
+int uvs_camera_believed_loop_moving_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                        const uvs_target_motion *motion, int64_t T, const uvs_camera *believed, int64_t n_believed,
+                                        const int32_t *believed_index, const double *q_start, const double *noise, double *q_log,
+                                        double *f_log, double *dq_log, double *err_log, int32_t *status, int32_t *k_done, double *stats,
+                                        int32_t *pixels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

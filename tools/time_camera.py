@@ -85,7 +85,19 @@ trials x 299 steps, white noise 0.3 px, x0 handed in, medians of 20 with p10-p90
       baseline over the 16 scenes in one launch.
       (v) .. (y16) are reported, not gated.  (v) is checked against (e), (w) against (x) and (z), (y) against (k), bit for bit, before
       anything is timed.  Then the table of examples/camera_loop.py --scenes 8.
-usage: tools/time_camera.py --scenes [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --scenes [--parent-lib=PATH] [out.txt]
+With --moving only the moving-target pixel loops are timed, into profiles/camera_moving_timing.txt (or the path given): GMCKF, 1 024 trials
+x 299 steps, white noise 0.3 px, x0 handed in, medians of 20 with p10-p90;
+  (e), (n), (q), (v), (w) as under --scenes, gated against two runs of the parent's library by the same rule: the existing kernels were
+      not to move;
+  (mv) (v)'s trials through moving_target_kernel with motion = NULL: what the kernel flavour costs;
+  (mw) 16 motions (examples/camera_loop.py --moving) x 64 trials in ONE launch, (mx) the same as 16 launches of 64 trials, one per motion,
+      (mz) (mw) stepwise: K x (moving features, estimator step);
+  (y) the scenes baseline loop on the nominal camera, (my) its trials through moving_baseline_kernel with motion = NULL, (my16) the baseline
+      over the 16 motions in one launch.
+      (mv) .. (my16) are reported, not gated.  (mv) is checked against (v), (mw) against (mx) and (mz), (my) against (y), bit for bit,
+      before anything is timed.  Then the table of examples/camera_loop.py --moving.
+usage: tools/time_camera.py --moving [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -100,9 +112,10 @@ import torch  # noqa: E402
 ANALYTICAL, BELIEVED, GRID = '--analytical' in sys.argv[1:], '--believed' in sys.argv[1:], '--grid' in sys.argv[1:]
 OCCLUDED, HELD, PAINTED = '--occluded' in sys.argv[1:], '--held' in sys.argv[1:], '--painted' in sys.argv[1:]
 SCENES = '--scenes' in sys.argv[1:]
+MOVING = '--moving' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -837,6 +850,156 @@ def scenes_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def moving_section():
+    """(e), (n), (q), (v), (w) against the parent's; (mv) .. (my16): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T, HOLD, N = 299, 1024, 30, 16
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    fa = uvs.engine.make_params(8, 6, 'ANALYTICAL', 10.0, False, 0.05, 15.0, 0.2, DESIRED)
+    assert fp.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --moving on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in (the nominal model\'s guess); the 12 px bar {example.BAR}, the wide '
+        f'bar {example.WIDE_BAR} with hold = {HOLD}; {N} scenes of examples/camera_loop.py --scenes (seed 0) and {N} motions of --moving '
+        f'(seed 0, {example.MOVING_SPEED} m per step in the window {example.MOVING_WINDOW}) x {T // N} trials')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+    x0 = uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+    bar, wide = uvs.engine.occluders([example.BAR], T), uvs.engine.occluders([example.WIDE_BAR], T)
+    one = uvs.engine.camera_scenes(plant)
+    scenes = uvs.engine.camera_scenes(example.scene_plants(uvs, plant, N, 0))
+    per = T // N
+    index = torch.as_tensor(np.repeat(np.arange(N, dtype=np.int32), per), device='cuda')
+    nominal = uvs.engine.believed_models(plant)
+    velocities = example.moving_velocities(N, 4, 0)
+    motions = uvs.engine.target_motions(np.repeat(velocities, per, axis=0), example.MOVING_WINDOW, 4, T)
+    parts = [(c, slice(c * per, (c + 1) * per)) for c in range(N)]
+    cut = {c: (q_d[rows].contiguous(), noise[:, rows].contiguous(), x0[rows].contiguous(), motions[rows].contiguous()) for c, rows in parts}
+    cam = plant.to_camera(uvs.plant.DISC_RADIUS)
+    scene_one = (one.data_ptr(), 1, None), one, None, True           # the nominal camera as the one scene
+    no_motion = (None, None)                                         # the moving entry points with motion = NULL
+
+    def run_mx():
+        return [loop(fp, plant, *cut[c][:2], x0=cut[c][2], fused=True, target_motion=cut[c][3]) for c, _ in parts]
+
+    def run_my_null():                                               # the same call through uvs_camera_believed_loop_moving_f64, motion = NULL
+        import ctypes as C
+        out = {key: torch.empty((K, T, comp), dtype=torch.float64, device='cuda') for key, comp in (('q', 6), ('f', 8), ('dq', 6), ('err', 8))}
+        status, k_done = (torch.empty(T, dtype=torch.int32, device='cuda') for _ in range(2))
+        stats, pixels = torch.empty((T, 3), dtype=torch.float64, device='cuda'), torch.empty((T, 4), dtype=torch.int32, device='cuda')
+        uvs._vision.check(uvs._vision.lib().uvs_camera_believed_loop_moving_f64(
+            C.byref(fa), one.data_ptr(), 1, None, None, T, nominal.data_ptr(), 1, None, q_d.data_ptr(), noise.data_ptr(), out['q'].data_ptr(),
+            out['f'].data_ptr(), out['dq'].data_ptr(), out['err'].data_ptr(), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(),
+            pixels.data_ptr(), uvs.engine._stream()))
+        return dict(out, pixels=pixels, status=status, k_done=k_done, stats=stats)
+
+    fns = {'e': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True),
+           'n': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=bar),
+           'q': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=wide, hold=HOLD),
+           'v': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, cameras=one),
+           'w': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, cameras=scenes, camera_index=index),
+           'mv': lambda: uvs.engine._camera_closed_loop_fused(fp, cam, q_d, noise, x0, 'host', uvs.engine.CAMERA_LOGS, scenes=scene_one,
+                                                              motion=no_motion),
+           'mw': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, target_motion=motions),
+           'mx': run_mx,
+           'mz': lambda: loop(fp, plant, q_d, noise, x0=x0, target_motion=motions),
+           'y': lambda: loop(fa, plant, q_d, noise, fused=True, believed=nominal, cameras=one),
+           'my': run_my_null,
+           'my16': lambda: loop(fa, plant, q_d, noise, fused=True, target_motion=motions)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+
+    def same(a, b, rows=slice(None), rows_b=slice(None)):
+        done = a['k_done'][rows]
+        ok = all(torch.equal(a[key][rows], b[key][rows_b]) for key in ('status', 'k_done', 'pixels'))
+        ok = ok and torch.equal(a['stats'][rows].view(torch.int64), b['stats'][rows_b].view(torch.int64))
+        ok = ok and ('held' in a) == ('held' in b) and ('held' not in a or torch.equal(a['held'][rows], b['held'][rows_b]))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):                 # the specified rows: q, f up to and including k_done, the others before it
+            if key in a:
+                spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+                ok = ok and torch.equal(a[key][:, rows].view(torch.int64)[spec], b[key][:, rows_b].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['mv'], first['v']), 'the moving kernel without a motion and the scenes kernel disagree'
+    assert same(first['mw'], first['mz']), 'the one launch and the stepwise loop disagree'
+    assert same(first['my'], first['y']), 'the moving baseline without a motion and the scenes baseline disagree'
+    assert not same(first['mw'], first['v']), 'the motions show'
+    for c, rows in parts:
+        assert same(first['mw'], first['mx'][c], rows), f'motion {c}: the one launch and the launch per motion disagree'
+    gated = ('e', 'n', 'q', 'v', 'w')
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_moving_f64'), 'the parent library has no moving targets'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def with_parent(fn):
+            def run():
+                mine, uvs._vision._lib = uvs._vision._lib, parent
+                try:
+                    return fn()
+                finally:
+                    uvs._vision._lib = mine
+            return run
+
+        for name in gated:
+            run = with_parent(fns[name])
+            old = run()
+            torch.cuda.synchronize()
+            assert same(first[name], old), f'this library and the parent disagree on ({name})'
+            fns[name + '_parent_a'], fns[name + '_parent_b'] = run, with_parent(fns[name])
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    say()
+    what = {'e': 'the uniform fused launch, camera_loop_kernel', 'n': 'the 12 px bar, camera_occluded_kernel', 'q': f'the wide bar, hold = {HOLD}, camera_held_kernel',
+            'v': "(e)'s trials through camera_scene_kernel, n_cams = 1", 'w': f'{N} scenes x {per} trials, one launch'}
+    passed = True
+    for name in gated:
+        say(f'  ({name}) {what[name]:52s} this library   {fmt_ms(ms[name])}   = {med[name] / K * 1e3:.1f} us per step')
+        if PARENT_LIB is not None:
+            a, b = med[name + '_parent_a'], med[name + '_parent_b']
+            say(f'  ({name}) {"":52s} the parent\'s, 1  {fmt_ms(ms[name + "_parent_a"])}')
+            say(f'  ({name}) {"":52s} the parent\'s, 2  {fmt_ms(ms[name + "_parent_b"])}')
+            ok = med[name] <= max(a, b) + abs(a - b)
+            passed = passed and ok
+            say(f'  ({name}) new / slower parent run = {med[name] / max(a, b):.4f}; the two parent runs differ by {abs(a - b) / max(a, b) * 100:.2f} %: '
+                f'{"passes" if ok else "DOES NOT pass"}; outputs bit-identical')
+    say(f'  (mv) (v)\'s trials through moving_target_kernel, motion = NULL              {fmt_ms(ms["mv"])}   = {med["mv"] / K * 1e3:.1f} us per step')
+    say(f'  (mw) {N} motions x {per} trials, one launch                                  {fmt_ms(ms["mw"])}   = {med["mw"] / K * 1e3:.1f} us per step')
+    say(f'  (mx) the same as {N} launches of {per} trials, one per motion                  {fmt_ms(ms["mx"])}')
+    say(f'  (mz) (mw) stepwise: K x (moving features, estimator step)                  {fmt_ms(ms["mz"])}   = {med["mz"] / K * 1e3:.1f} us per step')
+    say(f'  (y) the scenes baseline loop on the nominal camera, n_cams = 1             {fmt_ms(ms["y"])}')
+    say(f'  (my) (y)\'s trials through moving_baseline_kernel, motion = NULL            {fmt_ms(ms["my"])}')
+    say(f'  (my16) the baseline over the {N} motions, one launch                         {fmt_ms(ms["my16"])}')
+    say(f'  (mv) / (v) = {med["mv"] / med["v"]:.4f}, (mw) / (mx) = {med["mw"] / med["mx"]:.4f}, (mw) / (mz) = {med["mw"] / med["mz"]:.4f}, (my) / (y) = '
+        f'{med["my"] / med["y"]:.4f} (reported, not gated); (mv) has the bits of (v), (mw) those of (mx) and of (mz), (my) those of (y)')
+    failed = lambda out: int((out['k_done'] < K).sum())              # noqa: E731
+    say(f'  trials that FAILed: (e) {failed(first["e"])}, (mw) {failed(first["mw"])}, (y) {failed(first["y"])}, (my16) {failed(first["my16"])}')
+    say()
+    if PARENT_LIB is not None:
+        say(f'gate: (e), (n), (q), (v), (w) against two runs of the parent\'s library: {"pass" if passed else "DO NOT pass"}')
+        say()
+    say('# examples/camera_loop.py --moving (its defaults)')
+    for line in example.moving_table(uvs):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if MOVING:
+    moving_section()
+    sys.exit(0)
 if SCENES:
     scenes_section()
     sys.exit(0)

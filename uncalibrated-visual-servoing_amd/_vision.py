@@ -40,6 +40,11 @@ class Occluder(C.Structure):
     _fields_ = [(name, C.c_int32) for name in ('x', 'y', 'w', 'h', 'vx', 'vy', 'k_on', 'k_off')]
 
 
+class TargetMotion(C.Structure):
+    """uvs_target_motion of include/uvs_vision.h: the row layout of the (T, 104) uint8 tensor ``plant.target_motion_array`` packs."""
+    _fields_ = [('v', (C.c_double * 3) * MAX_POINTS), ('k_on', C.c_int32), ('k_off', C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/uvs_vision.h declares
 _VP, _I64, _I32, _F64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double
 _CAM = C.POINTER(Camera)
@@ -91,6 +96,13 @@ SYMBOLS = {
     'uvs_camera_closed_loop_scenes_f64': (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
     # fp, scene operand, then uvs_camera_believed_loop_f64's operands from T on
     'uvs_camera_believed_loop_scenes_f64': (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
+    # moving targets: the four scenes calls with motion (device array of TargetMotion [T] or None) directly after the scene operand; the
+    # project call, which has no k, takes it after dt
+    'uvs_camera_project_moving_f64': (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I64, _VP, _VP, _F64, _I32, _VP, _VP, _VP]),
+    'uvs_camera_features_moving_f64': (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP,
+                                                 _VP]),
+    'uvs_camera_closed_loop_moving_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
+    'uvs_camera_believed_loop_moving_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
 }
 
 _lib = None
@@ -100,7 +112,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 10)), '-C', CSRC], check=True)        # ten translation units, one rule each
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 12)), '-C', CSRC], check=True)        # twelve translation units, one rule each
     return LIB_PATH
 
 

@@ -9,6 +9,8 @@
 // from the kernel argument, every trial known.  Same names, argument blocks, registers and LDS as when each was written out in its unit.
 // A unit that defines UVS_CAMERA_SCENES (uvs_camera_scenes_baseline.hip) sees a third flavour, scene_baseline_loop_kernel(SLoopArgs): the
 // believed one whose sensor side reads the trial's own camera as well, from a second staged array.
+// A unit that defines UVS_CAMERA_MOVING (uvs_camera_moving_baseline.hip) sees a fourth, moving_baseline_kernel(MovingBaselineArgs): the scenes
+// one whose sensor side projects every disc where its trial's motion has taken it.  The law's model does not move.
 // Next to them: what every entry point of the two units asks of (fp, cam, T) before its first HIP call.
 //
 // The loop's mapping is the one of camera_loop_kernel (camera_loop_device.hpp), decided and measured there -- 256 threads = one wavefront per
@@ -103,15 +105,28 @@ struct SLoopArgs {
     int32_t *pixels;
 };
 
-#if defined(UVS_CAMERA_SCENES)
+// The fourth flavour (a unit that defines UVS_CAMERA_MOVING, uvs_camera_moving_baseline.hip): moving_baseline_kernel, the scenes
+// flavour with a motion per OUTPUT trial, staged into s_mot[G] next to the scenes.  The SENSOR side's points move; the law's model stays.
+struct MovingBaselineArgs : SLoopArgs {
+    const uvs_target_motion *motion;                             // [T] by output trial, or NULL: nothing moves
+};
+
+#if defined(UVS_CAMERA_MOVING)
+constexpr bool kCameraBelieved = true, kBaselineScenes = true, kBaselineMoving = true;
+using BaselineLoopArgs = MovingBaselineArgs;
+#define UVS_BASELINE_LOOP_KERNEL moving_baseline_kernel
+#elif defined(UVS_CAMERA_SCENES)
+constexpr bool kBaselineMoving = false;
 constexpr bool kCameraBelieved = true, kBaselineScenes = true;
 using BaselineLoopArgs = SLoopArgs;
 #define UVS_BASELINE_LOOP_KERNEL scene_baseline_loop_kernel
 #elif defined(UVS_CAMERA_BELIEVED)
+constexpr bool kBaselineMoving = false;
 constexpr bool kCameraBelieved = true, kBaselineScenes = false;
 using BaselineLoopArgs = BLoopArgs;
 #define UVS_BASELINE_LOOP_KERNEL camera_believed_loop_kernel
 #else
+constexpr bool kBaselineMoving = false;
 constexpr bool kBaselineScenes = false;
 constexpr bool kCameraBelieved = false;
 using BaselineLoopArgs = ALoopArgs;
@@ -146,6 +161,17 @@ template <int G>
 __device__ __forceinline__ void stage_loop_scenes(const SLoopArgs &a, uvs_camera *s_scene) {
     stage_scenes<G, kLoopThreads>(a.S, a.cam, static_cast<long long>(blockIdx.x) * G, a.T, s_scene);
 }
+// The motions of the workgroup's trials into LDS.  The other three flavours have none: nothing to stage.
+template <int G>
+__device__ __forceinline__ void stage_loop_motions(const ALoopArgs &, uvs_target_motion *) {}
+template <int G>
+__device__ __forceinline__ void stage_loop_motions(const BLoopArgs &, uvs_target_motion *) {}
+template <int G>
+__device__ __forceinline__ void stage_loop_motions(const SLoopArgs &, uvs_target_motion *) {}
+template <int G>
+__device__ __forceinline__ void stage_loop_motions(const MovingBaselineArgs &a, uvs_target_motion *s_mot) {
+    stage_motions<G, kLoopThreads>(a.motion, static_cast<long long>(blockIdx.x) * G, a.T, s_mot);
+}
 
 template <int M, int N, int L, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const BaselineLoopArgs A) {
@@ -165,6 +191,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     constexpr bool SCENES = kBaselineScenes;
     __shared__ uvs_camera s_scene[SCENES ? G : 1];               // SCENES: the sensor side's cameras; the barrier before the step loop stands
     stage_loop_scenes<G>(A, s_scene);                            // between this and step 0's sines
+    constexpr bool MOVING = kBaselineMoving;
+    __shared__ uvs_target_motion s_mot[MOVING ? G : 1];          // MOVING: the motions of those trials; the same barrier covers them
+    stage_loop_motions<G>(A, s_mot);
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -216,7 +245,11 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
             joint_sincos_rows(scene, lane, q, s_sin[w], s_cos[w]);
         }
         __syncthreads();
-        if (lane < npts) project_lane_disc(scene, lane, s_sin[w], s_cos[w], s_disc[w]);
+        if constexpr (MOVING) {                                  // the disc where step k of the trial's motion has taken it
+            if (lane < npts) project_lane_disc_at(scene, lane, s_mot[ws], k, s_sin[w], s_cos[w], s_disc[w]);
+        } else {
+            if (lane < npts) project_lane_disc(scene, lane, s_sin[w], s_cos[w], s_disc[w]);
+        }
         __syncthreads();
 #pragma unroll 1
         for (int j = j_first; j < npts; j += j_step) {

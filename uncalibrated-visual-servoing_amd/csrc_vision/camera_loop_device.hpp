@@ -60,6 +60,13 @@
 // flavours read the kernel argument.  A.cam holds the launch's shape alone (n_joints, n_points, from fp) and is word 0 of every staged
 // struct.  A padding trial stages the scene of the trial it shadows; a trial whose index names no scene stages zeros and is `void` exactly as
 // one whose source index names no input trial is: FAILed by its flag, not by what the zeros give.  The step's barriers and exits are where they were.
+//
+// MOVING.  A seventh flavour: a unit that defines UVS_CAMERA_MOVING next to the other five switches (uvs_camera_moving.hip) sees
+// moving_target_kernel(MovingLoopArgs) with all six on.  The discs of a trial move: a uvs_target_motion per OUTPUT trial (velocities and one
+// window), staged once into s_mot[G] (104 B each) next to the scenes -- the barrier that covers those covers these -- and read by lanes
+// < n_points alone, where project_lane_disc_at forms the moved point in transient registers; nothing is written back to s_cam, which the four
+// wavefronts of the one-trial form share.  A padding trial stages the motion of the trial it shadows; a NULL operand stages zeros: nothing
+// moves.  The step's barriers and exits are where they were.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -104,6 +111,19 @@ struct ScenesLoopArgs : PaintedLoopArgs {
     Scenes S;
 };
 
+// uvs_camera_closed_loop_moving_f64: the scenes block and the motions, [T] by output trial or NULL; only moving_target_kernel takes it
+struct MovingLoopArgs : ScenesLoopArgs {
+    const uvs_target_motion *motion;
+};
+
+#ifdef UVS_CAMERA_MOVING
+#ifndef UVS_CAMERA_SCENES
+#error "the moving flavour is a scenes flavour: define UVS_CAMERA_SCENES (and UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
+#endif
+constexpr bool kCameraMoving = true;
+#else
+constexpr bool kCameraMoving = false;
+#endif
 #ifdef UVS_CAMERA_SCENES
 #ifndef UVS_CAMERA_PAINTED
 #error "the scenes flavour is a painted flavour: define UVS_CAMERA_PAINTED (and UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
@@ -136,7 +156,11 @@ constexpr bool kCameraOccluded = true;
 #else
 constexpr bool kCameraOccluded = false;
 #endif
-#if defined(UVS_CAMERA_SCENES)
+#if defined(UVS_CAMERA_MOVING)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = MovingLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL moving_target_kernel
+#elif defined(UVS_CAMERA_SCENES)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = ScenesLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL camera_scene_kernel
@@ -178,10 +202,14 @@ __device__ __forceinline__ const int32_t *paints_of(const PaintedLoopArgs &a) { 
 // the scenes of the launch (never called on the other five blocks: SCENES is off there)
 __device__ __forceinline__ Scenes scenes_of(const LoopArgs &) { return Scenes{nullptr, 0, nullptr}; }
 __device__ __forceinline__ Scenes scenes_of(const ScenesLoopArgs &a) { return a.S; }
+// the motions of the launch, or NULL (never called on the other six blocks: MOVING is off there)
+__device__ __forceinline__ const uvs_target_motion *motions_of(const LoopArgs &) { return nullptr; }
+__device__ __forceinline__ const uvs_target_motion *motions_of(const MovingLoopArgs &a) { return a.motion; }
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
     constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld, PAINT = kCameraPainted, SCENES = kCameraScenes;
+    constexpr bool MOVING = kCameraMoving;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -201,6 +229,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     __shared__ int s_miss[HOLD ? G : 1][kColours];               // HOLD: steps in a row, up to this one, at which the disc's pair was held
     __shared__ int s_held[HOLD ? G : 1][kColours];               // HOLD: steps at which it was held, while the trial's rows were due
     __shared__ uvs_camera s_cam[SCENES ? G : 1];                 // SCENES: the cameras that render the workgroup's trials, staged once below
+    __shared__ uvs_target_motion s_mot[MOVING ? G : 1];          // MOVING: the motions of those trials, staged next to them
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -234,6 +263,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         stage_scenes<G, kLoopThreads>(scenes_of(A), cam, static_cast<long long>(blockIdx.x) * G, T, s_cam);
         if (model_of(scenes_of(A), trial) < 0) valid = false;    // names no scene: void.  Never an address; nothing of it is stored
     }
+    if constexpr (MOVING) stage_motions<G, kLoopThreads>(motions_of(A), static_cast<long long>(blockIdx.x) * G, T, s_mot);   // by OUTPUT trial too
     const uvs_occluder *occ_at = nullptr;                        // OCC: the occluders of the OUTPUT trial (a padding wavefront: of the one it shadows)
     int n_occ = 0;
     if constexpr (OCC) occ_at = occluders_of(A, trial, n_occ);
@@ -322,7 +352,11 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
             if (seen && q_at != nullptr) *q_at = q;              // after the sines: where this text measured fastest
         }
         __syncthreads();
-        if (lane < npts) project_lane_disc(scene, lane, s_sin[w], s_cos[w], s_disc[w]);
+        if constexpr (MOVING) {                                  // the disc where step k of the trial's motion has taken it
+            if (lane < npts) project_lane_disc_at(scene, lane, s_mot[ws], k, s_sin[w], s_cos[w], s_disc[w]);
+        } else {
+            if (lane < npts) project_lane_disc(scene, lane, s_sin[w], s_cos[w], s_disc[w]);
+        }
         if constexpr (OCC) {                                     // lane o: rectangle o of this step, next to the projection
             if (lane < kOccluders) s_occ[w][lane] = lane < n_occ ? occluder_rect(occ_at[lane], k) : kNoRect;
         }

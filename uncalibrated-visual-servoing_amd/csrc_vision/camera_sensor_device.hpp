@@ -1,6 +1,6 @@
 // What the one-launch pixel loops share, written ONCE: the sensor side of a step -- joints, projection, frame-free detection, lane 0's report,
-// the epilogue's stores -- for the estimator loop (camera_loop_device.hpp, six flavours) and the baseline loop (camera_analytical_device.hpp,
-// three); the analytic initial guess of a trial for the two guess kernels; and the mapping's constants with the launch decision that goes with them.
+// the epilogue's stores -- for the estimator loop (camera_loop_device.hpp, seven flavours) and the baseline loop (camera_analytical_device.hpp,
+// four); the analytic initial guess of a trial for the two guess kernels; and the mapping's constants with the launch decision that goes with them.
 // The pieces are __device__ __forceinline__ functions over LDS row pointers and plain values: they declare no LDS and nothing is shared at
 // run time, so every kernel keeps the registers, LDS and scratch it had when the text was written out in it (a shared
 // __device__ body behind __global__ wrappers did move the allocation).  Every value is formed by the operations, in the order, of
@@ -52,6 +52,16 @@ __device__ __forceinline__ void project_lane_disc(const uvs_camera &cam, int p, 
 #pragma unroll 1                                                 // a rolled loop reads the DH table where it is used: unrolled, the whole table sits in SGPRs
     for (int i = 0; i < cam.n_joints; ++i) chain_link(cam, i, sin_row[i], cos_row[i], pose);
     project_disc(cam, p, pose, disc_row + 3 * p);
+}
+
+// The same for a MOVING target: disc p stands at step k of the trial's motion `mot` (LDS).  The moved point lives in
+// transient registers of this call alone -- nothing is written back to the staged camera, which four wavefronts may share.
+__device__ __forceinline__ void project_lane_disc_at(const uvs_camera &cam, int p, const uvs_target_motion &mot, int k, const double *sin_row,
+                                                     const double *cos_row, double *disc_row) {
+    double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
+#pragma unroll 1
+    for (int i = 0; i < cam.n_joints; ++i) chain_link(cam, i, sin_row[i], cos_row[i], pose);
+    project_moved_disc(cam, p, mot, k, pose, disc_row + 3 * p);
 }
 
 // ---- frame-free detection: feature pair j is the centre of mass of disc j's colour (npts == 1: green).  The 64 lanes walk the colour's four

@@ -421,6 +421,57 @@ __global__ __launch_bounds__(kThreads) void scene_camera_detect_kernel(const Sce
     centre_of_mass_of_block(cc, rc, n_points, noise, f_out, pixels_out);
 }
 
+// The two kernels above on MOVING targets: every disc projected where step k of its trial's motion has taken it
+// (project_moved_disc: the rule of uvs_target_motion).  motion [T] by trial, or NULL: nothing moves, and the bits are those of the kernels above.
+__global__ __launch_bounds__(kProjectThreads) void moving_project_kernel(const Scenes S, const uvs_target_motion *__restrict__ motion, int n_points,
+                                                                         int64_t T, const double *__restrict__ q_prev,
+                                                                         const double *__restrict__ dq, double dt, int k,
+                                                                         double *__restrict__ q_out, double *__restrict__ discs_out) {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * kProjectThreads + threadIdx.x;
+    if (t >= T) return;
+    const long long scene = model_of(S, t);
+    if (scene < 0) return;
+    const uvs_camera &cam = S.models[scene];
+    const uvs_target_motion *mot = motion != nullptr ? motion + t : nullptr;
+    double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
+    for (int i = 0; i < kSceneJoints; ++i) {
+        double s, c;
+        scene_joint_sincos(cam, t, i, q_prev, dq, dt, q_out, s, c);
+        chain_link(cam, i, s, c, pose);
+    }
+    for (int p = 0; p < n_points; ++p) project_moved_disc_of(cam, p, mot, k, pose, discs_out + (t * n_points + p) * 3);
+}
+
+__global__ __launch_bounds__(kThreads) void moving_detect_kernel(const Scenes S, const uvs_target_motion *__restrict__ motion, int n_points,
+                                                                 const double *__restrict__ q_prev, const double *__restrict__ dq, double dt,
+                                                                 double *__restrict__ q_out, const double *__restrict__ noise,
+                                                                 double *__restrict__ f_out, int32_t *__restrict__ pixels_out,
+                                                                 double *__restrict__ discs_out, const PaintArgs pa) {
+    __shared__ double sdisc[kColours * 3];
+    __shared__ double ssin[UVS_CAMERA_MAX_JOINTS], scos[UVS_CAMERA_MAX_JOINTS];
+    const int tid = threadIdx.x;
+    const int64_t t = blockIdx.x;
+    const long long scene = model_of(S, t);                      // the same word in all 1024 threads: the workgroup leaves as one
+    if (scene < 0) return;
+    const uvs_camera &cam = S.models[scene];
+    if (tid < kSceneJoints) scene_joint_sincos(cam, t, tid, q_prev, dq, dt, q_out, ssin[tid], scos[tid]);
+    __syncthreads();
+    if (tid < n_points) {
+        const uvs_target_motion *mot = motion != nullptr ? motion + t : nullptr;
+        double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
+        for (int i = 0; i < kSceneJoints; ++i) chain_link(cam, i, ssin[i], scos[i], pose);
+        project_moved_disc_of(cam, tid, mot, pa.oa.k, pose, &sdisc[3 * tid]);
+        if (discs_out != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) discs_out[(t * n_points + tid) * 3 + k] = sdisc[3 * tid + k];
+        }
+    }
+    __syncthreads();
+    int cc, rc;
+    painted_counts(sdisc, n_points, cc, rc, rects_of_block(pa.oa), paints_of_block(pa, n_points));
+    centre_of_mass_of_block(cc, rc, n_points, noise, f_out, pixels_out);
+}
+
 thread_local char g_err[256] = "";
 
 int fail(int code, const char *fmt, const char *detail) {
@@ -671,6 +722,42 @@ int uvs_camera_features_scenes_f64(const uvs_camera *cams, int64_t n_cams, const
                        Scenes{cams, n_cams, cam_index}, static_cast<int>(n_points), q_prev, dq, dt, q_out, noise, f_out, pixels_out, discs_out,
                        PaintArgs{{occ, n_occ, k, 0u}, paint});
     return launched("scene_camera_detect_kernel launch: %s");
+}
+
+// Moving targets: the scenes namesakes' refusals in their order; a NULL motion is legal (nothing moves).  The project call has a k of its own.
+int uvs_camera_project_moving_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, const uvs_target_motion *motion,
+                                  int32_t n_points, int64_t T, const double *q_prev, const double *dq, double dt, int32_t k, double *q_out,
+                                  double *discs_out, void *stream) {
+    g_err[0] = '\0';
+    if (discs_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL discs_out");
+    const uvs_camera shape = scene_shape(kSceneJoints, n_points);
+    if (const int rc = check_camera(&shape, T, q_prev, q_out)) return rc;
+    if (const int rc = check_scenes(cams, n_cams, cam_index, T)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (T == 0) return UVS_OK;
+    const unsigned blocks = static_cast<unsigned>((T + kProjectThreads - 1) / kProjectThreads);
+    hipLaunchKernelGGL(moving_project_kernel, dim3(blocks), dim3(kProjectThreads), 0, static_cast<hipStream_t>(stream),
+                       Scenes{cams, n_cams, cam_index}, motion, static_cast<int>(n_points), T, q_prev, dq, dt, static_cast<int>(k), q_out,
+                       discs_out);
+    return launched("moving_project_kernel launch: %s");
+}
+
+int uvs_camera_features_moving_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, const uvs_target_motion *motion,
+                                   int32_t n_points, int64_t T, const double *q_prev, const double *dq, double dt, double *q_out,
+                                   const uvs_occluder *occ, const int32_t *paint, int32_t n_occ, int32_t k, const double *noise,
+                                   double *f_out, int32_t *pixels_out, double *discs_out, void *stream) {
+    g_err[0] = '\0';
+    if (f_out == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL f_out");
+    const uvs_camera shape = scene_shape(kSceneJoints, n_points);
+    if (const int rc = check_camera(&shape, T, q_prev, q_out)) return rc;
+    if (const int rc = check_occluders(occ, n_occ)) return rc;
+    if (k < 0) return fail(UVS_ERR_ARG, "%s", "k must be >= 0");
+    if (const int rc = check_scenes(cams, n_cams, cam_index, T)) return rc;
+    if (T == 0) return UVS_OK;
+    hipLaunchKernelGGL(moving_detect_kernel, dim3(static_cast<unsigned>(T)), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       Scenes{cams, n_cams, cam_index}, motion, static_cast<int>(n_points), q_prev, dq, dt, q_out, noise, f_out, pixels_out,
+                       discs_out, PaintArgs{{occ, n_occ, k, 0u}, paint});
+    return launched("moving_detect_kernel launch: %s");
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Device code shared by all ten translation units of libuvs_vision.so (uvs_vision.hip directly, the nine loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
+// Device code shared by all twelve translation units of libuvs_vision.so (uvs_vision.hip directly, the eleven loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
 // forms its callers need, the disc geometry of the synthetic camera with its occluders and their paints, and the DH chain.  The summation order of the phase 2 is a contract
 // (see centre_of_mass): every unit that sums mask pixels goes through wave_partial and ColourSum, so they all give the same bits.
 #pragma once
@@ -529,6 +529,67 @@ __device__ __forceinline__ void stage_scenes(const Scenes &S, const uvs_camera &
         double value = model >= 0 ? reinterpret_cast<const double *>(S.models + model)[word] : 0.0;
         if (word == 0) value = reinterpret_cast<const double *>(&shape)[0];
         reinterpret_cast<double *>(s_cam)[i] = value;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- moving targets
+// THE rule of uvs_target_motion (uvs_vision.h), shared by every kernel that moves a disc.  The steps the target has moved
+// at step k, in 64-bit integers: |k - k_on| and k_off - k_on are below 2^33 for any int32 fields.
+__device__ __forceinline__ long long motion_steps(int32_t k_on, int32_t k_off, int k) {
+    const long long span = static_cast<long long>(k_off) - k_on, most = span > 0 ? span : 0;
+    const long long since = static_cast<long long>(k) - k_on, s = since > 0 ? since : 0;
+    return s < most ? s : most;
+}
+
+// One coordinate of a world point after s steps at velocity v: one rounded multiply, then one rounded add (-ffp-contract=off), as the
+// joint step; for s == 0 the coordinate itself, bits untouched -- a select over both values, so a -0.0 stays -0.0 and a velocity that is
+// not finite moves nothing.
+__device__ __forceinline__ double moved_coordinate(double x, double v, long long s) {
+    const double step = static_cast<double>(s) * v;
+    const double moved = x + step;
+    return s == 0 ? x : moved;
+}
+
+// project_disc for disc p of `cam` standing at the world point w instead of cam.points[p]: its operations in its order
+__device__ __forceinline__ void project_disc_at(const uvs_camera &cam, int p, double wx, double wy, double wz, const double (&T)[3][4], double *out) {
+    const double dx = wx - T[0][3], dy = wy - T[1][3], dz = wz - T[2][3];
+    const double xc = T[0][0] * dx + T[1][0] * dy + T[2][0] * dz;
+    const double yc = T[0][1] * dx + T[1][1] * dy + T[2][1] * dz;
+    const double zc = T[0][2] * dx + T[1][2] * dy + T[2][2] * dz;
+    out[0] = cam.center + cam.focal * xc / zc;
+    out[1] = cam.center + cam.focal * yc / zc;
+    out[2] = (zc > 0.0 && isfinite(zc)) ? cam.focal * cam.radius[p] / zc : -1.0;
+}
+
+// project_disc for disc p of `cam` at step k of the motion `mot` (global memory or LDS)
+__device__ __forceinline__ void project_moved_disc(const uvs_camera &cam, int p, const uvs_target_motion &mot, int k, const double (&T)[3][4],
+                                                   double *out) {
+    const long long s = motion_steps(mot.k_on, mot.k_off, k);
+    project_disc_at(cam, p, moved_coordinate(cam.points[p][0], mot.v[p][0], s), moved_coordinate(cam.points[p][1], mot.v[p][1], s),
+                    moved_coordinate(cam.points[p][2], mot.v[p][2], s), T, out);
+}
+
+// The same for a motion in memory that may be absent (NULL: nothing moves, s == 0 and no velocity is read)
+__device__ __forceinline__ void project_moved_disc_of(const uvs_camera &cam, int p, const uvs_target_motion *mot, int k, const double (&T)[3][4],
+                                                      double *out) {
+    const long long s = mot != nullptr ? motion_steps(mot->k_on, mot->k_off, k) : 0;
+    double w[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w[c] = moved_coordinate(cam.points[p][c], mot != nullptr ? mot->v[p][c] : 0.0, s);
+    project_disc_at(cam, p, w[0], w[1], w[2], T, out);
+}
+
+// The motions of the trials first .. first + COUNT - 1 (clamped to the last trial: padding shadows it) into s_mot[COUNT], by all THREADS
+// threads; zeros -- nothing moves -- for a NULL operand.  The caller's next barrier stands between this and the first read.
+constexpr int kMotionWords = static_cast<int>(sizeof(uvs_target_motion) / 8);
+static_assert(sizeof(uvs_target_motion) == 104, "copied as 13 eight-byte words");
+template <int COUNT, int THREADS>
+__device__ __forceinline__ void stage_motions(const uvs_target_motion *motion, long long first, long long T, uvs_target_motion *s_mot) {
+    for (int i = threadIdx.x; i < COUNT * kMotionWords; i += THREADS) {
+        const int slot = i / kMotionWords, word = i - slot * kMotionWords;
+        long long trial = first + slot;
+        if (trial >= T) trial = T - 1;
+        reinterpret_cast<uint64_t *>(s_mot)[i] = motion != nullptr ? reinterpret_cast<const uint64_t *>(motion + trial)[word] : 0ull;
     }
 }
 

@@ -364,7 +364,8 @@ def _device_of(*tensors):
     return current_device()
 
 
-def camera_project(plant, q_prev, dq=None, dt=0.0, radius=None, q_out=None, out=None, cameras=None, camera_index=None):
+def camera_project(plant, q_prev, dq=None, dt=0.0, radius=None, q_out=None, out=None, cameras=None, camera_index=None, target_motion=None,
+                   motion_window=None, k=0):
     """Disc projection of T trials on the current stream (uvs_camera_project_f64).  ``plant``: a ``SyntheticPlant`` (with ``radius`` in metres,
     default plant.DISC_RADIUS) or the ``uvs_camera`` struct of ``SyntheticPlant.to_camera``.  ``q_prev`` (T, n) fp64; with ``dq`` (T, n) the joints
     are q_prev + dq * dt, written to ``q_out`` (T, n) when given.  Returns ``out``: (T, n_points, 3) rows (u, v, r) in pixels; r = -1 for a point
@@ -372,11 +373,19 @@ def camera_project(plant, q_prev, dq=None, dt=0.0, radius=None, q_out=None, out=
     ``cameras`` (what ``camera_scenes`` returns or takes) and ``camera_index`` ((T,) integers, host or device): trial t is projected by its
     own camera (uvs_camera_project_scenes_f64) -- with an index ``cameras[camera_index[t]]``, without one the one camera there is, or
     ``cameras[t]`` of T -- and ``plant`` only gives the shape.  Trial t has the bits of the call on its camera; a trial whose device-side
-    index names no camera is left unwritten.  None (the default) is the call without the arguments."""
+    index names no camera is left unwritten.  None (the default) is the call without the arguments.
+    ``target_motion`` ((n_points, 3) or (T, n_points, 3) world metres per step, or what ``target_motions`` returns), ``motion_window``
+    (None, (2,) or (T, 2) integers (k_on, k_off)) and the step ``k``: trial t's discs where step k of its motion has taken them
+    (uvs_camera_project_moving_f64; the rule is ``plant.target_at``'s, bit for bit).  Without ``cameras`` the nominal camera is packed as
+    the one scene.  None is the call without the arguments, through the entry point it always used."""
     from . import _vision, plant as plant_mod
     if cameras is None and camera_index is not None:
         raise ValueError('camera_project: camera_index without cameras')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    motion = _check_target_motion(target_motion, motion_window, getattr(q_prev, 'shape', (0,))[0], cam.n_points, 'camera_project')
+    k = _check_step(k, 'camera_project')
+    if motion is not None and cameras is None:
+        cameras = [cam]
     if cameras is not None:
         _check_cameras(cameras, camera_index, getattr(q_prev, 'shape', (0,))[0], cam.n_points, cam.n_joints, 'camera_project')
     torch = _torch()
@@ -389,7 +398,11 @@ def camera_project(plant, q_prev, dq=None, dt=0.0, radius=None, q_out=None, out=
         rc = _vision.lib().uvs_camera_project_f64(C.byref(cam), *rest)
     else:
         scenes, _keep, _keep_index = _scene_operand(cameras, camera_index, T, cam.n_points, n, radius, _device_of(q_prev), 'camera_project')
-        rc = _vision.lib().uvs_camera_project_scenes_f64(*scenes, cam.n_points, *rest)
+        if motion is None:
+            rc = _vision.lib().uvs_camera_project_scenes_f64(*scenes, cam.n_points, *rest)
+        else:
+            mot, _keep_motion = _motion_operand(motion, _device_of(q_prev))
+            rc = _vision.lib().uvs_camera_project_moving_f64(*scenes, mot, cam.n_points, *rest[:4], k, *rest[4:])
     _vision.check(rc)
     return out
 
@@ -533,19 +546,25 @@ def disc_features(discs, n_colours=4, noise=None, out=None, pixels=None, occlude
 
 
 def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_out=None, out=None, pixels=None, discs=None, occluders=None, k=0,
-                    occluder_colours=None, cameras=None, camera_index=None):
+                    occluder_colours=None, cameras=None, camera_index=None, target_motion=None, motion_window=None):
     """``camera_project`` and ``disc_features`` in one launch (uvs_camera_features_f64), bit-identical to the two in a row: joints in, noisy
     detected features (T, 2 n_points) out.  ``discs`` (T, n_points, 3) receives the projection when given.  ``occluders`` at step ``k``:
     uvs_camera_features_occluded_f64, the two occluded calls in a row; with ``occluder_colours`` uvs_camera_features_painted_f64, the two
     painted ones.
     ``cameras`` / ``camera_index`` (as ``camera_project`` takes them): trial t on its own camera, with or without occluders and their
-    colours, in one launch (uvs_camera_features_scenes_f64); ``plant`` only gives the shape.  None is the call without the arguments."""
+    colours, in one launch (uvs_camera_features_scenes_f64); ``plant`` only gives the shape.  None is the call without the arguments.
+    ``target_motion`` / ``motion_window`` (as ``camera_project`` takes them): the detection of the frame with trial t's discs where step
+    ``k`` of its motion has taken them (uvs_camera_features_moving_f64), with or without cameras, occluders and their colours; without
+    ``cameras`` the nominal camera is packed as the one scene.  None is the call without the arguments."""
     from . import _vision, plant as plant_mod
     if cameras is None and camera_index is not None:
         raise ValueError('camera_features: camera_index without cameras')
     checked = _check_occluders(occluders, getattr(q_prev, 'shape', (0,))[0], k, who='camera_features')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
     paints = _check_occluder_colours(occluder_colours, checked, getattr(q_prev, 'shape', (0,))[0], cam.n_points, 'camera_features')
+    motion = _check_target_motion(target_motion, motion_window, getattr(q_prev, 'shape', (0,))[0], cam.n_points, 'camera_features')
+    if motion is not None and cameras is None:
+        cameras = [cam]
     if cameras is not None:
         _check_cameras(cameras, camera_index, getattr(q_prev, 'shape', (0,))[0], cam.n_points, cam.n_joints, 'camera_features')
     torch = _torch()
@@ -561,7 +580,11 @@ def camera_features(plant, q_prev, dq=None, dt=0.0, radius=None, noise=None, q_o
         scenes, _keep, _keep_index = _scene_operand(cameras, camera_index, T, npts, n, radius, dev, 'camera_features')
         occ, n_occ, _keep_occ = (None, 0, None) if checked is None else _occluder_operand(checked, dev)
         paint, _keep_paint = (None, None) if paints is None else _paint_operand(paints, dev)
-        rc = _vision.lib().uvs_camera_features_scenes_f64(*scenes, npts, *joints[1:], occ, paint, n_occ, int(k), *rest)
+        if motion is None:
+            rc = _vision.lib().uvs_camera_features_scenes_f64(*scenes, npts, *joints[1:], occ, paint, n_occ, int(k), *rest)
+        else:
+            mot, _keep_motion = _motion_operand(motion, dev)
+            rc = _vision.lib().uvs_camera_features_moving_f64(*scenes, mot, npts, *joints[1:], occ, paint, n_occ, int(k), *rest)
     elif checked is None:
         rc = _vision.lib().uvs_camera_features_f64(*joints, *rest)
     else:
@@ -759,6 +782,58 @@ def _scene_operand(cameras, camera_index, T, n_points, n_joints, radius, dev, wh
     return (cameras.data_ptr(), n, _operand(index, 'camera_index', torch.int32, (T,))), cameras, index
 
 
+def _check_target_motion(target_motion, motion_window, T, n_points, who):
+    """What can be said of a ``target_motion=`` / ``motion_window=`` pair for T output trials of n_points discs on the host alone, before any
+    device work: ValueError, or the operand -- None, the caller's own packed device (or pinned) uint8 tensor (T, 104) (what
+    ``target_motions`` returns), or the packed host uint8 array (T, 104) of ``plant.target_motion_array``."""
+    import torch                                                     # not _torch(): these refusals need no GPU
+    from . import plant as plant_mod
+    if target_motion is None:
+        if motion_window is not None:
+            raise ValueError(f'{who}: motion_window without target_motion: a window belongs to a motion')
+        return None
+    if torch.is_tensor(target_motion) and target_motion.dtype == torch.uint8:
+        if motion_window is not None:
+            raise ValueError(f'{who}: a packed target_motion carries its windows: no motion_window next to it')
+        if tuple(target_motion.shape) != (T, plant_mod.MOTION_ROW) or not target_motion.is_contiguous():
+            raise ValueError(f'{who}: a packed target_motion is what target_motions returns for these trials: a contiguous uint8 tensor '
+                             f'({T}, {plant_mod.MOTION_ROW}), got {tuple(target_motion.shape)}')
+        if not (target_motion.is_cuda or target_motion.is_pinned()):
+            raise ValueError(f'{who}: a packed target_motion is on the device (or pinned)')
+        return target_motion
+    velocity = target_motion.detach().cpu().numpy() if torch.is_tensor(target_motion) else target_motion
+    window = motion_window.detach().cpu().numpy() if torch.is_tensor(motion_window) else motion_window
+    try:
+        return plant_mod.target_motion_array(velocity, window, int(n_points), int(T))
+    except ValueError as exc:
+        raise ValueError(f'{who}: {exc}') from exc
+
+
+def target_motions(velocity, window, n_points, T, device=None):
+    """Pack target motions for the kernels (uvs_target_motion of include/uvs_vision.h; the rule: ``plant.target_at``): ``velocity``
+    (n_points, 3) or (T, n_points, 3) world metres per step, ``window`` None, (2,) or (T, 2) integers (k_on, k_off) -- the shorter forms
+    are broadcast over the trials.  Returns a contiguous uint8 tensor (T, 104) on ``device``: pack once, pass it as ``target_motion=`` to as
+    many calls as needed.  Indexed by OUTPUT trial."""
+    host = _check_target_motion(velocity, window, T, n_points, 'target_motions')
+    torch = _torch()
+    if host is None:
+        raise ValueError('target_motions: nothing to pack')
+    return host if torch.is_tensor(host) else torch.from_numpy(host).to(current_device(device))
+
+
+def _motion_operand(checked, dev):
+    """(pointer, tensor to keep alive) of what _check_target_motion returned (not None)."""
+    torch = _torch()
+    t = checked if torch.is_tensor(checked) else torch.from_numpy(np.ascontiguousarray(checked)).to(dev)
+    return t.data_ptr(), t
+
+
+def _check_step(k, who):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 2 ** 31:
+        raise ValueError(f'{who}: k is a step count, an integer >= 0, got {k!r}')
+    return int(k)
+
+
 def camera_guess(plant, q_start, f0, radius=None, out=None, believed=None, believed_index=None):
     """The analytic initial guess of T trials on the device (uvs_camera_guess_f64): what ``plant.analytic_guess`` returns per trial for the
     joints ``q_start`` (T, 6) and the detected features ``f0`` (T, 2 n_points), both cuda fp64, to about 1e-13 relative (another order of
@@ -826,16 +901,24 @@ CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
 ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
 
 
-def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=None, scenes=None):
+def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=None, scenes=None, motion=None):
     """The stepwise loops' sensor launch at step k: uvs_camera_features_f64, or its occluded namesake when ``occ`` -- None, or the
     (pointer, n_occ, tensor) of ``_occluder_operand`` -- is given.  Returns f(k, q_prev, dq_prev, q, noise, f, pixels) -> return code.
     With ``hold`` > 0 the step is that launch and uvs_hold_features_f64 behind it on the same stream, on the same rows: the callable then
     takes two more row pointers, f(..., pixels, f_prev, held), and keeps the counters of consecutive held steps (T, 4) itself.
     ``paint``: None, or the (pointer, tensor) of ``_paint_operand`` next to ``occ`` -- the launch is then uvs_camera_features_painted_f64.
     ``scenes``: None, or the (pointer, n_cams, index pointer) of ``_scene_operand`` -- the launch is then uvs_camera_features_scenes_f64 for
-    ``npts`` points, with or without ``occ`` and ``paint``, and ``cam_ref`` is not read."""
+    ``npts`` points, with or without ``occ`` and ``paint``, and ``cam_ref`` is not read.
+    ``motion``: None, or the pointer of ``_motion_operand`` next to ``scenes`` -- the launch is then uvs_camera_features_moving_f64, which
+    takes the motions and the step k."""
     from . import _vision
-    if scenes is not None:
+    if motion is not None:
+        moving = _vision.lib().uvs_camera_features_moving_f64
+        occ_ptr, n_occ = (None, 0) if occ is None else occ[:2]
+        paint_ptr = None if paint is None else paint[0]
+        detect = lambda k, q_prev, dq_prev, q, noise, f, pixels: moving(*scenes, motion, npts, T, q_prev, dq_prev, dt, q, occ_ptr, paint_ptr,   # noqa: E731
+                                                                        n_occ, k, noise, f, pixels, None, stream)
+    elif scenes is not None:
         per_scene = _vision.lib().uvs_camera_features_scenes_f64
         occ_ptr, n_occ = (None, 0) if occ is None else occ[:2]
         paint_ptr = None if paint is None else paint[0]
@@ -863,14 +946,15 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=
     return held_step
 
 
-def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None, scenes=None):
+def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None, scenes=None, motion=None):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
     ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models.
     ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none).  ``hold`` > 0 (stepwise alone): a third launch per
     step, uvs_hold_features_f64, between the two.  ``paint``: None, or the paint operand next to ``occ`` (stepwise alone).
     ``scenes``: None, or the (pointer, n_cams, index pointer) of ``_scene_operand`` -- every trial's frames come from its own camera
     (the one launch: uvs_camera_believed_loop_scenes_f64; stepwise: uvs_camera_features_scenes_f64); ``believed`` is then given, and
-    ``cam`` is the shape alone."""
+    ``cam`` is the shape alone.  ``motion``: None, or the pointer of ``_motion_operand`` next to ``scenes`` -- the sensor side's discs move
+    (the one launch: uvs_camera_believed_loop_moving_f64; stepwise: uvs_camera_features_moving_f64); the law's model does not."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -886,7 +970,9 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         stats = torch.empty((T, 3), **f64)
         pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
         outputs = (ptr('q'), ptr('f'), ptr('dq'), ptr('err'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
-        if scenes is not None:
+        if motion is not None:
+            rc = _vision.lib().uvs_camera_believed_loop_moving_f64(C.byref(fp), *scenes, motion, T, *believed, q0, noise_ptr, *outputs)
+        elif scenes is not None:
             rc = _vision.lib().uvs_camera_believed_loop_scenes_f64(C.byref(fp), *scenes, T, *believed, q0, noise_ptr, *outputs)
         elif believed is None:
             rc = _vision.lib().uvs_camera_analytical_loop_f64(C.byref(fp), C.byref(cam), T, q0, noise_ptr, *outputs)
@@ -898,7 +984,7 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, scenes)
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, scenes, motion)
     held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     if believed is None:
         step = lambda *rows: _vision.lib().uvs_camera_analytical_step_f64(fp_ref, cam_ref, T, *rows)          # noqa: E731
@@ -982,7 +1068,8 @@ def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
     return tp, keep
 
 
-def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0, paints=None, scenes=None):
+def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0, paints=None, scenes=None,
+                              motion=None):
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
     then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
     ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
@@ -991,11 +1078,17 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     ``_check_occluder_colours`` returned next to ``occluders`` -- the launch is then uvs_camera_closed_loop_painted_f64 for any hold >= 0,
     and the result has 'held' only with hold > 0.  ``scenes``: None, or the (operand, packed cameras, index tensor or None) of
     ``_scene_operand`` for the T output trials (no 'source' next to them either) -- the launch is then uvs_camera_closed_loop_scenes_f64,
-    whatever else is given; f0 comes from the step-0 frame of every trial's own scene, and x0 is given (camera_closed_loop has made it)."""
+    whatever else is given; f0 comes from the step-0 frame of every trial's own scene, and x0 is given (camera_closed_loop has made it).
+    A fourth member, True, says that the one scene is the NOMINAL camera standing in for a moving launch without ``cameras``: ``cam`` is then
+    the model of every trial, and guess='device' may still make x0 from it.
+    ``motion``: None, or the (pointer, packed tensor) of ``_motion_operand`` for the T output trials next to ``scenes`` -- the launch is
+    then uvs_camera_closed_loop_moving_f64, and f0 comes from the step-0 frame, where s(0) applies."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
     scene_kw = {} if scenes is None else dict(cameras=scenes[1], camera_index=scenes[2])
+    if motion is not None:
+        scene_kw['target_motion'] = motion[1]
     n_in, dev = q_start.shape[0], q_start.device
     T = n_in if trial_params is None else _check_camera_trial_params(trial_params, n_in)[0]
     tp, _keep = (None, ()) if trial_params is None else _camera_trial_params_struct(trial_params, T, n_in, m, dev)
@@ -1008,7 +1101,7 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     if fp.initial_guess:                                             # the step-0 frame, occluders at k = 0 and their paints included
         camera_features(cam, q_start, out=f0, occluders=None if occ is None else occ[2], occluder_colours=None if paint is None else paint[1],
                         **scene_kw)
-        if x0 is None and guess == 'device' and scenes is None:
+        if x0 is None and guess == 'device' and (scenes is None or scenes[3]):
             x0 = camera_guess(cam, q_start, f0)
     if x0 is None:
         raise ValueError("camera_closed_loop: fused=True takes x0, or guess='device' with fp.initial_guess")
@@ -1023,10 +1116,12 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
                 k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
     if scenes is not None:
         held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
-        rc = _vision.lib().uvs_camera_closed_loop_scenes_f64(C.byref(fp), *scenes[0], T, None if tp is None else C.byref(tp),
-                                                             None if occ is None else occ[0], None if paint is None else paint[0],
-                                                             0 if occ is None else occ[1], hold, *operands[:-1],
-                                                             None if held is None else held.data_ptr(), operands[-1])
+        rest = (T, None if tp is None else C.byref(tp), None if occ is None else occ[0], None if paint is None else paint[0],
+                0 if occ is None else occ[1], hold, *operands[:-1], None if held is None else held.data_ptr(), operands[-1])
+        if motion is None:
+            rc = _vision.lib().uvs_camera_closed_loop_scenes_f64(C.byref(fp), *scenes[0], *rest)
+        else:
+            rc = _vision.lib().uvs_camera_closed_loop_moving_f64(C.byref(fp), *scenes[0], motion[0], *rest)
         _vision.check(rc)
         out = dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
         return dict(out, held=held) if hold else out
@@ -1074,7 +1169,8 @@ def _gather_by_source(q_start, noise, x0, trial_params):
 
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
-                       believed_index=None, trial_params=None, occluders=None, hold=0, occluder_colours=None, cameras=None, camera_index=None):
+                       believed_index=None, trial_params=None, occluders=None, hold=0, occluder_colours=None, cameras=None, camera_index=None,
+                       target_motion=None, motion_window=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -1153,7 +1249,20 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     (uvs_camera_believed_guess_f64); guess='host' without ``x0`` next to cameras is a ValueError.  Next to trial_params['source'] the inputs
     are gathered by source before the launch, as next to occluders.  A trial whose device-side index names no camera FAILs with
     k_done = 0, alone.  ValueErrors before any device work: ``camera_index`` without ``cameras``, a host-side index out of range or of the
-    wrong length, a model whose shape is not fp's."""
+    wrong length, a model whose shape is not fp's.
+    ``target_motion`` and ``motion_window``: MOVING TARGETS, per OUTPUT trial -- (n_points, 3) or (T, n_points, 3) world velocities in
+    metres per step and None, (2,) or (T, 2) integer windows (k_on, k_off), or what ``target_motions`` returns for both.  At step k trial
+    t's discs stand where s(k) = clamp(k - k_on, 0, max(k_off - k_on, 0)) steps of its motion have taken them (the rule:
+    ``plant.target_at``; include/uvs_vision.h, uvs_target_motion); projection, pixels, occluders, paints and hold follow as they are.  The
+    controller does not know the motion: the calibrated law's model -- ``believed``, or the trial's own camera -- and every initial guess
+    keep the points where they were.  None (the default) is the call without the arguments: its routes, its entry points, its bits.
+    Without ``cameras`` the nominal camera is packed as the one scene.  fused=True with an estimator is ONE launch
+    (uvs_camera_closed_loop_moving_f64) with any of ``trial_params``, ``occluders``, ``occluder_colours``, ``hold`` and ``cameras``;
+    fused=False passes the motions and k to uvs_camera_features_moving_f64 at every step; the two return the same bits.  f0 and the
+    initial guess come from the step-0 frame, where s(0) applies.  ANALYTICAL: fused=True is uvs_camera_believed_loop_moving_f64 (with
+    occluders or hold > 0 it stays the ValueError it is), fused=False the moving features call, then uvs_camera_believed_step_f64.  Next
+    to trial_params['source'] the inputs are gathered by source before the launch, as next to occluders.  ValueErrors before any device
+    work: a wrong shape or dtype, a window without a motion, T rows of motion for a different T, window entries outside int32."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
@@ -1180,6 +1289,13 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         occluders = _check_occluders(occluders, n_out, who='camera_closed_loop: occluders')
     paints = _check_occluder_colours(occluder_colours, occluders, None if occluders is None else occluders.shape[0], fp.m // 2,
                                      'camera_closed_loop')
+    n_out = getattr(q_start, 'shape', (0,))[0]
+    if isinstance(trial_params, dict) and trial_params.get('source') is not None and (target_motion is not None or motion_window is not None):
+        n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
+    motion = _check_target_motion(target_motion, motion_window, n_out, fp.m // 2, 'camera_closed_loop')
+    nominal = motion is not None and cameras is None                 # the nominal camera stands in as the one scene of a moving launch
+    if nominal and fp.n != 6:
+        raise ValueError(f'camera_closed_loop: the moving-target kernels are built for the six-joint arms of this project, not for {fp.n} joints')
     if trial_params is not None:
         if not fused:
             raise ValueError('camera_closed_loop: trial_params needs fused=True: the two-launch step kernel has no per-trial flavour')
@@ -1208,7 +1324,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     if fused and not getattr(q_start, 'is_cuda', False):
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     torch = _torch()
-    if (occluders is not None or cameras is not None) and trial_params is not None and trial_params.get('source') is not None:
+    if (occluders is not None or cameras is not None or motion is not None) and trial_params is not None and trial_params.get('source') is not None:
         q_start, noise, x0, trial_params = _gather_by_source(q_start, noise, x0, trial_params)
     K, m, n = fp.steps, fp.m, fp.n
     T, dev = q_start.shape[0], q_start.device
@@ -1217,9 +1333,17 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     if not q_start.is_cuda:
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     scenes, scene_kw = None, {}                                      # the scene operand of the T output trials, and what the calls below take
+    if nominal:
+        cameras = [_camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)]
+        if m != 2 * cameras[0].n_points or n != cameras[0].n_joints:
+            raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cameras[0].n_points} features of '
+                             f'{cameras[0].n_joints} joints')
     if cameras is not None:
-        scenes = _scene_operand(cameras, camera_index, T, m // 2, n, radius, dev, 'camera_closed_loop')
+        scenes = _scene_operand(cameras, camera_index, T, m // 2, n, radius, dev, 'camera_closed_loop') + (nominal,)
         scene_kw = dict(cameras=scenes[1], camera_index=scenes[2])
+    mot = None if motion is None else _motion_operand(motion, dev)   # (pointer, packed tensor) of the T output trials
+    if mot is not None:
+        scene_kw['target_motion'] = mot[1]
     if analytical:
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -1233,8 +1357,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         else:
             *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
         return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold, paint=paint,
-                                              scenes=None if scenes is None else scenes[0])
-    if believed is not None or (scenes is not None and x0 is None):  # an estimator that starts from a model in memory: the believed one, or
+                                              scenes=None if scenes is None else scenes[0], motion=None if mot is None else mot[0])
+    if believed is not None or (scenes is not None and not nominal and x0 is None):  # an estimator that starts from a model in memory: the believed one, or
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)                           # its own scene; the rest is the x0= path
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
@@ -1247,7 +1371,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes, mot)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -1277,7 +1401,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
         return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2], hold,
-                                         None if paint is None else paint[1], scenes)
+                                         None if paint is None else paint[1], scenes, mot)
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
@@ -1285,7 +1409,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     dq_zero = torch.zeros((T, n), **f64)
     step = _lib.lib().uvs_rmckf_step_f64
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, None if scenes is None else scenes[0])
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, None if scenes is None else scenes[0],
+                              None if mot is None else mot[0])
     held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
     if hold:

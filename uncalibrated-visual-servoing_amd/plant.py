@@ -370,6 +370,72 @@ def miscalibrated(plant, focal_scale=1.0, point_offset=(0.0, 0.0, 0.0), joint_of
                           focal=focal, center=plant.center, fov_deg=fov_deg)
 
 
+MOTION_WINDOW = (0, 2 ** 31 - 1)        # a target that moves from step 0 on, for as long as the loop runs
+MOTION_ROW = 104                        # sizeof(uvs_target_motion): twelve doubles v[4][3], then int32 k_on, k_off
+
+
+def motion_steps(k, window=MOTION_WINDOW):
+    """s(k) of uvs_target_motion (include/uvs_vision.h): the steps a target has moved at step ``k`` >= 0 under the window (k_on, k_off),
+    clamp(k - k_on, 0, max(k_off - k_on, 0)), in Python integers -- nothing overflows, whatever the int32 fields hold."""
+    k, (k_on, k_off) = int(k), (int(w) for w in window)
+    if k < 0:
+        raise ValueError('k must be >= 0')
+    return min(max(k - k_on, 0), max(k_off - k_on, 0))
+
+
+def target_at(plant, velocity, k, window=MOTION_WINDOW):
+    """A new ``SyntheticPlant``: ``plant`` with its world points where step ``k`` of a motion has taken them -- the numpy statement of the
+    rule of uvs_target_motion (include/uvs_vision.h) that every moving-target kernel is held to.  ``velocity`` (n_points, 3): world metres
+    per step of every disc; ``window`` (k_on, k_off), one for all discs.  With s = ``motion_steps(k, window)``: if s == 0 the points are
+    the plant's own, bits untouched, with no arithmetic at all (a -0.0 stays -0.0, a velocity that is not finite moves nothing);
+    otherwise, per coordinate, points + float64(s) * velocity: one rounded multiply, then one rounded add.  One plant and a scalar ``k``:
+    not vectorised over trials."""
+    velocity = np.asarray(velocity, np.float64)
+    points = np.array(plant.points, np.float64)
+    if velocity.shape != points.shape:
+        raise ValueError(f'velocity: {points.shape} world metres per step, one row per disc, got {velocity.shape}')
+    s = motion_steps(k, window)
+    if s != 0:
+        with np.errstate(all='ignore'):
+            step = np.float64(s) * velocity
+            points = points + step
+    return SyntheticPlant(theta_offset=np.array(plant.theta_offset, float), d=np.array(plant.d, float), a=np.array(plant.a, float),
+                          alpha=np.array(plant.alpha, float), points=points, focal=plant.focal, center=plant.center, fov_deg=plant.fov_deg)
+
+
+def target_motion_array(velocity, window, n_points, T=None):
+    """``velocity`` and ``window`` as the packed rows of uvs_target_motion (include/uvs_vision.h): a uint8 host array (T, ``MOTION_ROW``),
+    row t = twelve float64 v[4][3] (rows from n_points on are zeros), then int32 k_on, k_off.  ``velocity``: (n_points, 3) -- every trial
+    the same -- or (T, n_points, 3) reals, NaN and inf allowed (the device rule is total); ``window``: None (``MOTION_WINDOW``), (2,) or
+    (T, 2) integers that are int32.  ValueError for anything else, or for T rows of either that do not match each other or ``T``."""
+    try:
+        v = np.asarray(velocity)
+    except Exception as exc:                                         # ragged lists
+        raise ValueError(f'target_motion: ({n_points}, 3) or (T, {n_points}, 3) reals, world metres per step') from exc
+    if v.dtype.kind not in 'fiu' or v.ndim not in (2, 3) or v.shape[-2:] != (n_points, 3):
+        raise ValueError(f'target_motion: ({n_points}, 3) or (T, {n_points}, 3) reals, world metres per step, got {v.dtype} {v.shape}')
+    try:
+        w = np.asarray(MOTION_WINDOW if window is None else window)
+    except Exception as exc:
+        raise ValueError('motion_window: (2,) or (T, 2) integers (k_on, k_off)') from exc
+    if w.dtype.kind not in 'iu' or w.ndim not in (1, 2) or w.shape[-1] != 2:
+        raise ValueError(f'motion_window: (2,) or (T, 2) integers (k_on, k_off), got {w.dtype} {w.shape}')
+    if w.size and (w.min() < -2 ** 31 or w.max() > 2 ** 31 - 1):
+        raise ValueError('motion_window: k_on and k_off are int32')
+    rows = {a.shape[0] for a, nd in ((v, 3), (w, 2)) if a.ndim == nd}
+    if T is not None:
+        rows.add(T)
+    if len(rows) > 1:
+        raise ValueError(f'target_motion: {sorted(rows)} trials of velocities, windows and trials do not match')
+    T = rows.pop() if rows else 1
+    out = np.zeros((T, MOTION_ROW), np.uint8)
+    vel = np.zeros((T, 4, 3), np.float64)
+    vel[:, :n_points] = v.astype(np.float64)
+    out[:, :96] = vel.reshape(T, 12).view(np.uint8)
+    out[:, 96:] = np.ascontiguousarray(np.broadcast_to(w.astype(np.int32), (T, 2))).view(np.uint8)
+    return out
+
+
 class LinearPlant:
     """Consistent linearised camera f = f0 + J (q - q0) for shapes without a DH model (BASELINE config 5: m = 32, n = 7;
     a 7-joint arm would be redundant for a 6-DoF camera pose and leave the feature Jacobian rank 6).  J, f0, q0 are uploaded
@@ -487,9 +553,14 @@ class CameraRobot:
     ``occluders``: None, or (n_occ, 8) integer rows of ``OCCLUDER_FIELDS``, drawn in ``shade`` at the robot's step count ``k`` -- 0 from
     ``start()`` on, one more with every ``step()`` after it, so that the loop's guess image and its first image are both the step-0 frame,
     as in ``engine.camera_closed_loop(occluders=...)``.  ``occluder_colours``: None, or (n_occ,) paints of those occluders
-    (``occluder_colour_array``): a painted one is a distractor of that disc's colour."""
+    (``occluder_colour_array``): a painted one is a distractor of that disc's colour.
+    ``target_motion``: None, or (n_points, 3) world velocities in metres per step, with ``motion_window`` (k_on, k_off) or None
+    (``MOTION_WINDOW``): the discs stand where step ``k`` of that motion has taken them (``target_at``), so ``discs()`` and
+    ``getCameraImage()`` show the frames ``engine.camera_closed_loop(target_motion=...)`` detects.  The robot's own kinematics -- what
+    the calibrated law reads -- keep the plant's points: the controller does not know the target's motion."""
 
-    def __init__(self, plant=None, radius=DISC_RADIUS, dt=0.05, background=96, occluders=None, shade=32, occluder_colours=None):
+    def __init__(self, plant=None, radius=DISC_RADIUS, dt=0.05, background=96, occluders=None, shade=32, occluder_colours=None,
+                 target_motion=None, motion_window=None):
         self._robot = SyntheticRobot(plant, dt)
         self.radius, self.background, self.shade = radius, background, shade
         self.occluders = None if occluders is None else occluder_array(occluders, 1)[0]
@@ -499,6 +570,15 @@ class CameraRobot:
                                                           self._robot.plant.n_points, 1)[0]
         if not 0 <= shade < 250:
             raise ValueError('shade must be 0 .. 249: 250 and above would enter a mask of the detectors')
+        if target_motion is None and motion_window is not None:
+            raise ValueError('motion_window without target_motion: a window belongs to a motion')
+        self.target_motion, self.motion_window = None, MOTION_WINDOW
+        if target_motion is not None:
+            npts = self._robot.plant.n_points
+            target_motion_array(target_motion, motion_window, npts, 1)          # its refusals
+            self.target_motion = np.array(target_motion, np.float64).reshape(npts, 3)
+            if motion_window is not None:
+                self.motion_window = tuple(int(w) for w in np.asarray(motion_window).reshape(2))
         self.k = 0
 
     def __getattr__(self, name):                                    # everything but the camera: the synthetic robot's
@@ -515,6 +595,8 @@ class CameraRobot:
         self.k += 1
 
     def discs(self):
+        if self.target_motion is not None:
+            return target_at(self._robot.plant, self.target_motion, self.k, self.motion_window).discs(self._robot.q, self.radius)
         return self._robot.plant.discs(self._robot.q, self.radius)
 
     def getCameraImage(self):
