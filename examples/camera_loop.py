@@ -41,8 +41,13 @@ method.  While the target moves, the features move and dq does not explain it --
 -- and the calibrated law's depths go stale: its model of the points stays where it was.  The chosen estimator, KF and the calibrated law on
 the same starts and noise; prints the median ISE / IAE / ITAE, the FAIL count, and the median feature error at the window's last step and
 at the last step of the run (re-convergence).
+--latency asks the textbook robustness question of visual servoing: what if the frame is old?  LATENCIES control periods between the pose a
+frame shows and the command computed from it (engine.camera_closed_loop(latency=...)), each x the trials over the same starts and noise in
+ONE launch per method: the estimators pair f_k - f_{k-1} with a regressor that is d steps too new, and the calibrated law feeds an
+interaction matrix at the current joints the features of the pose d steps ago.  Nobody is told the latency.  The chosen estimator, KF and
+the calibrated law; prints the median ISE / IAE / ITAE, the FAIL count and the median feature error at the last step, per latency.
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving]"""
+       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving] [--latency]"""
 import argparse
 import os
 import sys
@@ -338,6 +343,45 @@ def moving_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed=0,
     return lines
 
 
+LATENCIES = (0, 1, 2, 3, 4)                                          # control periods
+
+
+def latency_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed=0, latencies=LATENCIES):
+    """The latency table as a list of lines: len(latencies) x trials in ONE launch per method (engine.camera_closed_loop(latency=)).  No
+    finding is drawn here: the table is what the experiment prints."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    methods = tuple(dict.fromkeys((method, 'KF', 'ANALYTICAL')))
+    fps = {name: uvs.engine.make_params(8, 6, name, 10.0, False, 0.05, 15.0, 0.2, desired, True) for name in methods}
+    K = fps[method].steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    noise = rng.standard_normal((K, trials, 8)) * sigma
+    n = len(latencies)
+    q0_d = torch.as_tensor(np.tile(q0, (n, 1)), device='cuda')       # the same starts and the same noise at every latency
+    noise_d = torch.as_tensor(np.tile(noise, (1, n, 1)), device='cuda')
+    latency = np.repeat(np.array(latencies, np.int64), trials)
+    lines = [f'{n} camera latencies x {trials} trials of {K} steps in one launch per method, white noise {sigma} px; median over the trials that '
+             f'ran to the end',
+             f'{"":28s}{"ISE":>12s}{"IAE":>12s}{"ITAE":>12s}{"FAIL":>8s}{"|err| at step " + str(K - 1):>20s}']
+    for name, fp in fps.items():
+        kw = dict(radius=radius, fused=True, want=('err',), latency=latency)
+        if name != 'ANALYTICAL':
+            kw['guess'] = 'device'
+        out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, **kw)
+        torch.cuda.synchronize()
+        status, stats, last = out['status'].cpu().numpy(), out['stats'].cpu().numpy(), out['err'][K - 1].cpu().numpy()
+        for c, d in enumerate(latencies):
+            rows = slice(c * trials, (c + 1) * trials)
+            done = status[rows] == 0
+            med = np.median(stats[rows][done], axis=0) if done.any() else np.full(3, np.nan)
+            norm = np.median(np.linalg.norm(last[rows][done], axis=1)) if done.any() else np.nan
+            lines.append(f'{name + ", latency " + str(d):28s}{med[0]:12.3f}{med[1]:12.3f}{med[2]:12.3f}{int((~done).sum()):>8d}{norm:20.3f}')
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -359,11 +403,16 @@ def main():
                     help='N seeded true scenes x the trials in one launch per method: the estimators and the calibrated law, and nothing else')
     ap.add_argument('--moving', action='store_true',
                     help='the target moves for a window of steps after convergence: the estimator, KF and the calibrated law, and nothing else')
+    ap.add_argument('--latency', action='store_true',
+                    help='camera latencies 0 .. 4 x the trials in one launch per method: the estimator, KF and the calibrated law, and nothing else')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
     if args.hold and not args.occlusion:
         ap.error('--hold goes with --occlusion')
+    if args.latency:
+        print('\n'.join(latency_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
+        return
     if args.moving:
         print('\n'.join(moving_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
         return

@@ -553,6 +553,49 @@ int uvs_camera_believed_loop_moving_f64(const struct uvs_filter_params *fp, cons
                                         double *f_log, double *dq_log, double *err_log, int32_t *status, int32_t *k_done, double *stats,
                                         int32_t *pixels, void *stream);
 
+/*
+ * CAMERA LATENCY: the frame the detector is handed is not the newest one.  In every loop above frame k reaches the detector at step k;
+ * below each OUTPUT trial may carry a latency d, in control periods, between the pose a frame shows and the command computed from it.
+ * The rule (plant.delayed_step states it once in numpy; every kernel below is held to it bit for bit):
+ *   latency [T] int32 by output trial, in device (or pinned host) memory; NULL = none.  The device uses clamp(d, 0,
+ *     UVS_CAMERA_MAX_LATENCY): the rule is total and the operand is not validated.
+ *   At step k the detector is handed the frame of step kk = max(k - d, 0): joints q_kk, occluders and paints at kk, target motion at kk.
+ *     The delay line is primed with the step-0 frame.
+ *   Everything after the detector is the text above on that detection, in this order: the centre; plus the noise of step k (NOT kk), one
+ *     rounded add; then the hold rule on the delayed integer counts; then the estimator or the law.
+ *   The law's joints are the current q_k (encoders are not delayed), the regressor is dq_{k-1} as before: the controller is not told the
+ *     latency.  f logs the reported row; pixels is the smallest mask among the detections that were reported while the trial's rows were
+ *     due; held counts as before.  f0 and the initial guess come from the step-0 frame.  With d == 0 the pair is the one just detected.
+ * The two loops have their *_moving_* namesake's operands in its order with `latency` directly after `motion`, its refusals in their
+ * order, all before the first HIP call; T == 0 returns UVS_OK and launches nothing.  Each keeps the detections (the integer count and the
+ * two sums of a mask, before the centre is formed) of the last UVS_CAMERA_MAX_LATENCY + 1 steps in an LDS ring per disc, written and
+ * read by the one lane that holds the detection: no barrier and no exit is added.
+ * uvs_delay_features_f64 is the stepwise loops' companion, like uvs_hold_features_f64: sensed_log [K][T][2 n_points] and count_log
+ * [K][T][n_points] hold the noise-free sensed rows and mask sizes of steps 0 .. k (what the features calls write without noise); the
+ * reported row of step k is, per trial t, row max(k - d_t, 0) of the sensed log plus noise_row (step k's [T][2 n_points], or NULL: no
+ * add), and its counts those of that row.  It refuses NULL sensed_log, count_log, f_row or pixels_row, T outside 0 .. 2^31 - 1, an
+ * n_points that is not 1, 3 or 4, and k < 0, before any HIP call.  f_row and pixels_row must not overlap the logs.
+ * Bit for bit: (a) latency == NULL, or all zeros, gives the bits of the moving namesake; (b) a trial of a mixed-latency launch has the
+ * bits of the uniform launch at its own latency; (c) the one launch has the stepwise loop's bits; (d) a padding wavefront reads the
+ * latency of the trial it shadows and stores nothing; (e) void trials stay void.
+ * Built: what the moving namesakes build, each in both workgroup forms with 0 B of scratch memory.
+ */
+#define UVS_CAMERA_MAX_LATENCY 8
+
+int uvs_camera_closed_loop_delayed_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                       const uvs_target_motion *motion, const int32_t *latency, int64_t T,
+                                       const uvs_camera_trial_params *tp, const uvs_occluder *occ, const int32_t *paint, int32_t n_occ,
+                                       int32_t hold, const double *q_start, const double *noise, const double *x0, const double *f0,
+                                       double *q_log, double *f_log, double *dq_log, double *err_log, double *kappa_log, int32_t *status,
+                                       int32_t *k_done, double *stats, int32_t *pixels, int32_t *held, void *stream);
+int uvs_camera_believed_loop_delayed_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                         const uvs_target_motion *motion, const int32_t *latency, int64_t T, const uvs_camera *believed,
+                                         int64_t n_believed, const int32_t *believed_index, const double *q_start, const double *noise,
+                                         double *q_log, double *f_log, double *dq_log, double *err_log, int32_t *status, int32_t *k_done,
+                                         double *stats, int32_t *pixels, void *stream);
+int uvs_delay_features_f64(int64_t T, int32_t n_points, int32_t k, const int32_t *latency, const double *sensed_log, const int32_t *count_log,
+                           const double *noise_row, double *f_row, int32_t *pixels_row, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,7 +97,19 @@ x 299 steps, white noise 0.3 px, x0 handed in, medians of 20 with p10-p90;
       over the 16 motions in one launch.
       (mv) .. (my16) are reported, not gated.  (mv) is checked against (v), (mw) against (mx) and (mz), (my) against (y), bit for bit,
       before anything is timed.  Then the table of examples/camera_loop.py --moving.
-usage: tools/time_camera.py --moving [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --moving [--parent-lib=PATH] [out.txt]
+
+With --delayed only the camera-latency pixel loops are timed, into profiles/camera_latency_timing.txt (or the path given): GMCKF, 1 024 trials
+x 299 steps, white noise 0.3 px --
+  (e), (n), (q), (v), (w), (mv), (mw) of the sections above, each against the parent's library when --parent-lib names it (gated);
+  (dv) (mv)'s trials through delayed_frames_kernel with latency = NULL: what the kernel flavour costs;
+  (dw) 5 latencies (examples/camera_loop.py --latency) x 64 trials in ONE launch, (dx) the same as 5 launches of 64 trials, one per latency,
+      (dz) (dw) stepwise: K x (features without noise, delay, estimator step);
+  (my) the moving baseline loop with motion = NULL, (dy) its trials through delayed_baseline_kernel with latency = NULL, (dy5) the baseline
+      over the 5 latencies x 64 trials in one launch
+      -- (dv) is asserted to have the bits of (mv), (dw) those of (dx) and (dz) trial for trial, (dy) those of (my), before anything is timed.
+      Then the table of examples/camera_loop.py --latency.
+usage: tools/time_camera.py --delayed [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -113,9 +125,10 @@ ANALYTICAL, BELIEVED, GRID = '--analytical' in sys.argv[1:], '--believed' in sys
 OCCLUDED, HELD, PAINTED = '--occluded' in sys.argv[1:], '--held' in sys.argv[1:], '--painted' in sys.argv[1:]
 SCENES = '--scenes' in sys.argv[1:]
 MOVING = '--moving' in sys.argv[1:]
+DELAYED = '--delayed' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving', '--delayed') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_latency_timing.txt' if DELAYED else 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -997,6 +1010,163 @@ def moving_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def delayed_section():
+    """(e), (n), (q), (v), (w), (mv), (mw) against the parent's; (dv) .. (dy5): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T, HOLD, N = 299, 1024, 30, 16
+    LAT, PER = example.LATENCIES, 64
+    TL = len(LAT) * PER
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    fa = uvs.engine.make_params(8, 6, 'ANALYTICAL', 10.0, False, 0.05, 15.0, 0.2, DESIRED)
+    assert fp.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --delayed on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in (the nominal model\'s guess); the 12 px bar {example.BAR}, the wide '
+        f'bar {example.WIDE_BAR} with hold = {HOLD}; {N} scenes and {N} motions of examples/camera_loop.py (seed 0) x {T // N} trials; the latencies '
+        f'{LAT} x {PER} trials = {TL} trials')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+    x0 = uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+    bar, wide = uvs.engine.occluders([example.BAR], T), uvs.engine.occluders([example.WIDE_BAR], T)
+    one = uvs.engine.camera_scenes(plant)
+    scenes = uvs.engine.camera_scenes(example.scene_plants(uvs, plant, N, 0))
+    per = T // N
+    index = torch.as_tensor(np.repeat(np.arange(N, dtype=np.int32), per), device='cuda')
+    nominal = uvs.engine.believed_models(plant)
+    motions = uvs.engine.target_motions(np.repeat(example.moving_velocities(N, 4, 0), per, axis=0), example.MOVING_WINDOW, 4, T)
+    cam = plant.to_camera(uvs.plant.DISC_RADIUS)
+    scene_one = (one.data_ptr(), 1, None), one, None, True           # the nominal camera as the one scene
+    no_motion, no_latency = (None, None), (None, None)               # the entry points with motion = NULL, latency = NULL
+    # the latency experiment: the same 64 starts and noise under each of the 5 latencies
+    ql = q_d[:PER].repeat(len(LAT), 1).contiguous()
+    nl = noise[:, :PER].repeat(1, len(LAT), 1).contiguous()
+    xl = x0[:PER].repeat(len(LAT), 1).contiguous()
+    latency = np.repeat(np.array(LAT, np.int64), PER)
+    parts = [(c, slice(c * PER, (c + 1) * PER)) for c in range(len(LAT))]
+    cut = (ql[:PER].contiguous(), nl[:, :PER].contiguous(), xl[:PER].contiguous())
+
+    def baseline_null(entry, *front):                                # a baseline loop through the C ABI with NULL operands
+        import ctypes as C
+        out = {key: torch.empty((K, T, comp), dtype=torch.float64, device='cuda') for key, comp in (('q', 6), ('f', 8), ('dq', 6), ('err', 8))}
+        status, k_done = (torch.empty(T, dtype=torch.int32, device='cuda') for _ in range(2))
+        stats, pixels = torch.empty((T, 3), dtype=torch.float64, device='cuda'), torch.empty((T, 4), dtype=torch.int32, device='cuda')
+        uvs._vision.check(getattr(uvs._vision.lib(), entry)(
+            C.byref(fa), one.data_ptr(), 1, None, *front, T, nominal.data_ptr(), 1, None, q_d.data_ptr(), noise.data_ptr(), out['q'].data_ptr(),
+            out['f'].data_ptr(), out['dq'].data_ptr(), out['err'].data_ptr(), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(),
+            pixels.data_ptr(), uvs.engine._stream()))
+        return dict(out, pixels=pixels, status=status, k_done=k_done, stats=stats)
+
+    fns = {'e': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True),
+           'n': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=bar),
+           'q': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, occluders=wide, hold=HOLD),
+           'v': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, cameras=one),
+           'w': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, cameras=scenes, camera_index=index),
+           'mv': lambda: uvs.engine._camera_closed_loop_fused(fp, cam, q_d, noise, x0, 'host', uvs.engine.CAMERA_LOGS, scenes=scene_one,
+                                                              motion=no_motion),
+           'mw': lambda: loop(fp, plant, q_d, noise, x0=x0, fused=True, target_motion=motions),
+           'dv': lambda: uvs.engine._camera_closed_loop_fused(fp, cam, q_d, noise, x0, 'host', uvs.engine.CAMERA_LOGS, scenes=scene_one,
+                                                              motion=None, latency=no_latency),
+           'dw': lambda: loop(fp, plant, ql, nl, x0=xl, fused=True, latency=latency),
+           'dx': lambda: [loop(fp, plant, *cut[:2], x0=cut[2], fused=True, latency=d) for d in LAT],
+           'dz': lambda: loop(fp, plant, ql, nl, x0=xl, latency=latency),
+           'my': lambda: baseline_null('uvs_camera_believed_loop_moving_f64', None),
+           'dy': lambda: baseline_null('uvs_camera_believed_loop_delayed_f64', None, None),
+           'dy5': lambda: loop(fa, plant, ql, nl, fused=True, latency=latency)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+
+    def same(a, b, rows=slice(None), rows_b=slice(None)):
+        done = a['k_done'][rows]
+        ok = all(torch.equal(a[key][rows], b[key][rows_b]) for key in ('status', 'k_done', 'pixels'))
+        ok = ok and torch.equal(a['stats'][rows].view(torch.int64), b['stats'][rows_b].view(torch.int64))
+        ok = ok and ('held' in a) == ('held' in b) and ('held' not in a or torch.equal(a['held'][rows], b['held'][rows_b]))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):                 # the specified rows: q, f up to and including k_done, the others before it
+            if key in a:
+                spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+                ok = ok and torch.equal(a[key][:, rows].view(torch.int64)[spec], b[key][:, rows_b].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['dv'], first['mv']), 'the delayed kernel without a latency and the moving kernel disagree'
+    assert same(first['dw'], first['dz']), 'the one launch and the stepwise loop disagree'
+    assert same(first['dy'], first['my']), 'the delayed baseline without a latency and the moving baseline disagree'
+    for c, rows in parts:
+        assert same(first['dw'], first['dx'][c], rows), f'latency {LAT[c]}: the one launch and the launch per latency disagree'
+    assert not same(first['dw'], first['dx'][0], parts[1][1]), 'the latencies show'
+    gated = ('e', 'n', 'q', 'v', 'w', 'mv', 'mw')
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_delayed_f64'), 'the parent library has no camera latency'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def with_parent(fn):
+            def run():
+                mine, uvs._vision._lib = uvs._vision._lib, parent
+                try:
+                    return fn()
+                finally:
+                    uvs._vision._lib = mine
+            return run
+
+        for name in gated:
+            run = with_parent(fns[name])
+            old = run()
+            torch.cuda.synchronize()
+            assert same(first[name], old), f'this library and the parent disagree on ({name})'
+            fns[name + '_parent_a'], fns[name + '_parent_b'] = run, with_parent(fns[name])
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    say()
+    what = {'e': 'the uniform fused launch, camera_loop_kernel', 'n': 'the 12 px bar, camera_occluded_kernel', 'q': f'the wide bar, hold = {HOLD}, camera_held_kernel',
+            'v': "(e)'s trials through camera_scene_kernel, n_cams = 1", 'w': f'{N} scenes x {per} trials, one launch',
+            'mv': "(v)'s trials through moving_target_kernel, NULL", 'mw': f'{N} motions x {per} trials, one launch'}
+    passed = True
+    for name in gated:
+        say(f'  ({name}) {what[name]:52s} this library   {fmt_ms(ms[name])}   = {med[name] / K * 1e3:.1f} us per step')
+        if PARENT_LIB is not None:
+            a, b = med[name + '_parent_a'], med[name + '_parent_b']
+            say(f'  ({name}) {"":52s} the parent\'s, 1  {fmt_ms(ms[name + "_parent_a"])}')
+            say(f'  ({name}) {"":52s} the parent\'s, 2  {fmt_ms(ms[name + "_parent_b"])}')
+            ok = med[name] <= max(a, b) + abs(a - b)
+            passed = passed and ok
+            say(f'  ({name}) new / slower parent run = {med[name] / max(a, b):.4f}; the two parent runs differ by {abs(a - b) / max(a, b) * 100:.2f} %: '
+                f'{"passes" if ok else "DOES NOT pass"}; outputs bit-identical')
+    say(f'  (dv) (mv)\'s trials through delayed_frames_kernel, latency = NULL           {fmt_ms(ms["dv"])}   = {med["dv"] / K * 1e3:.1f} us per step')
+    say(f'  (dw) {len(LAT)} latencies x {PER} trials, one launch                                  {fmt_ms(ms["dw"])}   = {med["dw"] / K * 1e3:.1f} us per step')
+    say(f'  (dx) the same as {len(LAT)} launches of {PER} trials, one per latency                  {fmt_ms(ms["dx"])}')
+    say(f'  (dz) (dw) stepwise: K x (features, delay, estimator step)                  {fmt_ms(ms["dz"])}   = {med["dz"] / K * 1e3:.1f} us per step')
+    say(f'  (my) the moving baseline loop on the nominal camera, motion = NULL         {fmt_ms(ms["my"])}')
+    say(f'  (dy) (my)\'s trials through delayed_baseline_kernel, latency = NULL         {fmt_ms(ms["dy"])}')
+    say(f'  (dy5) the baseline over the {len(LAT)} latencies x {PER} trials, one launch              {fmt_ms(ms["dy5"])}')
+    say(f'  (dv) / (mv) = {med["dv"] / med["mv"]:.4f}, (dw) / (dx) = {med["dw"] / med["dx"]:.4f}, (dw) / (dz) = {med["dw"] / med["dz"]:.4f}, (dy) / (my) = '
+        f'{med["dy"] / med["my"]:.4f} (reported, not gated); (dv) has the bits of (mv), (dw) those of (dx) and of (dz), (dy) those of (my)')
+    failed = lambda out: int((out['k_done'] < K).sum())              # noqa: E731
+    say(f'  trials that FAILed: (e) {failed(first["e"])}, (dw) {failed(first["dw"])}, (my) {failed(first["my"])}, (dy5) {failed(first["dy5"])}')
+    say()
+    if PARENT_LIB is not None:
+        say(f'gate: (e), (n), (q), (v), (w), (mv), (mw) against two runs of the parent\'s library: {"pass" if passed else "DO NOT pass"}')
+        say()
+    say('# examples/camera_loop.py --latency (its defaults)')
+    for line in example.latency_table(uvs):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if DELAYED:
+    delayed_section()
+    sys.exit(0)
 if MOVING:
     moving_section()
     sys.exit(0)

@@ -11,6 +11,9 @@
 // believed one whose sensor side reads the trial's own camera as well, from a second staged array.
 // A unit that defines UVS_CAMERA_MOVING (uvs_camera_moving_baseline.hip) sees a fourth, moving_baseline_kernel(MovingBaselineArgs): the scenes
 // one whose sensor side projects every disc where its trial's motion has taken it.  The law's model does not move.
+// A unit that defines UVS_CAMERA_DELAYED on top (uvs_camera_delayed_baseline.hip) sees a fifth, delayed_baseline_kernel(DelayedBaselineArgs): the
+// moving one whose detector is handed the frame of step max(k - d, 0), d the trial's latency, through an LDS ring of detections per disc
+// (DESIGN.md 4.24).  The law's joints stay the current ones.
 // Next to them: what every entry point of the two units asks of (fp, cam, T) before its first HIP call.
 //
 // The loop's mapping is the one of camera_loop_kernel (camera_loop_device.hpp), decided and measured there -- 256 threads = one wavefront per
@@ -111,7 +114,25 @@ struct MovingBaselineArgs : SLoopArgs {
     const uvs_target_motion *motion;                             // [T] by output trial, or NULL: nothing moves
 };
 
-#if defined(UVS_CAMERA_MOVING)
+// The fifth flavour (a unit that defines UVS_CAMERA_DELAYED too, uvs_camera_delayed_baseline.hip): delayed_baseline_kernel, the
+// moving flavour with a latency per OUTPUT trial.  The detections go through s_ring; the law reads the current joints.
+struct DelayedBaselineArgs : MovingBaselineArgs {
+    const int32_t *latency;                                      // [T] by output trial, or NULL: none
+};
+
+#if defined(UVS_CAMERA_DELAYED)
+constexpr bool kBaselineDelayed = true;
+#else
+constexpr bool kBaselineDelayed = false;
+#endif
+#if defined(UVS_CAMERA_DELAYED)
+#if !defined(UVS_CAMERA_MOVING) || !defined(UVS_CAMERA_SCENES)
+#error "the delayed flavour is a moving flavour: define UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
+#endif
+constexpr bool kCameraBelieved = true, kBaselineScenes = true, kBaselineMoving = true;
+using BaselineLoopArgs = DelayedBaselineArgs;
+#define UVS_BASELINE_LOOP_KERNEL delayed_baseline_kernel
+#elif defined(UVS_CAMERA_MOVING)
 constexpr bool kCameraBelieved = true, kBaselineScenes = true, kBaselineMoving = true;
 using BaselineLoopArgs = MovingBaselineArgs;
 #define UVS_BASELINE_LOOP_KERNEL moving_baseline_kernel
@@ -172,6 +193,11 @@ template <int G>
 __device__ __forceinline__ void stage_loop_motions(const MovingBaselineArgs &a, uvs_target_motion *s_mot) {
     stage_motions<G, kLoopThreads>(a.motion, static_cast<long long>(blockIdx.x) * G, a.T, s_mot);
 }
+// The latency of `trial`.  The other four flavours have none.
+__device__ __forceinline__ int loop_latency(const ALoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_latency(const BLoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_latency(const SLoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_latency(const DelayedBaselineArgs &a, long long trial) { return latency_of(a.latency, trial); }
 
 template <int M, int N, int L, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const BaselineLoopArgs A) {
@@ -194,6 +220,8 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     constexpr bool MOVING = kBaselineMoving;
     __shared__ uvs_target_motion s_mot[MOVING ? G : 1];          // MOVING: the motions of those trials; the same barrier covers them
     stage_loop_motions<G>(A, s_mot);
+    constexpr bool DELAYED = kBaselineDelayed;
+    __shared__ DelayCell s_ring[DELAYED ? G : 1][DELAYED ? kColours : 1][DELAYED ? kDelaySlots : 1];   // DELAYED: the last nine detections of every disc
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -211,6 +239,8 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     const bool valid = trial < T;
     if (!valid) trial = T - 1;                                   // a padding wavefront shadows the last trial and stores nothing
     const bool known = has_model(A, trial);
+    int delay = 0;                                               // DELAYED: the latency of the trial (a padding wavefront: of the one it shadows)
+    if constexpr (DELAYED) delay = loop_latency(A, trial);
     double q = lane < N ? A.q_start[trial * N + lane] : 0.0;
     // this lane's own addresses in row 0 of the [K][T][comp] logs (NULL: not wanted, or nothing of this lane's), advanced by a row per step
     const long long step_rows = T;
@@ -253,8 +283,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
         __syncthreads();
 #pragma unroll 1
         for (int j = j_first; j < npts; j += j_step) {
-            const ColourSum sum = detect_pair<false>(s_disc[w], npts, j, lane);
+            ColourSum sum = detect_pair<false>(s_disc[w], npts, j, lane);
             if (lane == 0) {                                     // the lane the shuffle tree ends in
+                if constexpr (DELAYED) delay_line(s_ring[ws][j], sum, k, delay);   // in place: the detection of step max(k - delay, 0)
                 double u, v;
                 noisy_centre(sum, noise_at, j, u, v);
                 report_pair(sum.count, j, u, v, seen, s_f[ws], s_pix[ws], f_at);

@@ -67,6 +67,13 @@
 // < n_points alone, where project_lane_disc_at forms the moved point in transient registers; nothing is written back to s_cam, which the four
 // wavefronts of the one-trial form share.  A padding trial stages the motion of the trial it shadows; a NULL operand stages zeros: nothing
 // moves.  The step's barriers and exits are where they were.
+//
+// DELAYED.  An eighth flavour: a unit that defines UVS_CAMERA_DELAYED next to the other six switches (uvs_camera_delayed.hip) sees
+// delayed_frames_kernel(DelayedLoopArgs) with all seven on.  The detector is handed the frame of step max(k - d, 0), d the OUTPUT trial's latency,
+// read once before the step loop (a padding wavefront: that of the trial it shadows).  Frames are not kept: the DETECTION of every step goes
+// through s_ring[trial slot][disc][k mod 9] (delay_line, vision_device.hpp), written and read by lane 0 of the wavefront that finished
+// detect_pair for that disc -- in the one-trial form each disc still belongs to exactly one wavefront -- between detect_pair and noisy_centre.
+// Occluders, paints and motion are evaluated at step k as before; the ring carries their effect.  No barrier and no exit is added.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -116,6 +123,19 @@ struct MovingLoopArgs : ScenesLoopArgs {
     const uvs_target_motion *motion;
 };
 
+// uvs_camera_closed_loop_delayed_f64: the moving block and the latencies, [T] by output trial or NULL; only delayed_frames_kernel takes it
+struct DelayedLoopArgs : MovingLoopArgs {
+    const int32_t *latency;
+};
+
+#ifdef UVS_CAMERA_DELAYED
+#ifndef UVS_CAMERA_MOVING
+#error "the delayed flavour is a moving flavour: define UVS_CAMERA_MOVING (and UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
+#endif
+constexpr bool kCameraDelayed = true;
+#else
+constexpr bool kCameraDelayed = false;
+#endif
 #ifdef UVS_CAMERA_MOVING
 #ifndef UVS_CAMERA_SCENES
 #error "the moving flavour is a scenes flavour: define UVS_CAMERA_SCENES (and UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
@@ -156,7 +176,11 @@ constexpr bool kCameraOccluded = true;
 #else
 constexpr bool kCameraOccluded = false;
 #endif
-#if defined(UVS_CAMERA_MOVING)
+#if defined(UVS_CAMERA_DELAYED)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = DelayedLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL delayed_frames_kernel
+#elif defined(UVS_CAMERA_MOVING)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = MovingLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL moving_target_kernel
@@ -205,11 +229,14 @@ __device__ __forceinline__ Scenes scenes_of(const ScenesLoopArgs &a) { return a.
 // the motions of the launch, or NULL (never called on the other six blocks: MOVING is off there)
 __device__ __forceinline__ const uvs_target_motion *motions_of(const LoopArgs &) { return nullptr; }
 __device__ __forceinline__ const uvs_target_motion *motions_of(const MovingLoopArgs &a) { return a.motion; }
+// the latencies of the launch, or NULL (never called on the other seven blocks: DELAYED is off there)
+__device__ __forceinline__ const int32_t *latencies_of(const LoopArgs &) { return nullptr; }
+__device__ __forceinline__ const int32_t *latencies_of(const DelayedLoopArgs &a) { return a.latency; }
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
     constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld, PAINT = kCameraPainted, SCENES = kCameraScenes;
-    constexpr bool MOVING = kCameraMoving;
+    constexpr bool MOVING = kCameraMoving, DELAYED = kCameraDelayed;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -230,6 +257,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     __shared__ int s_held[HOLD ? G : 1][kColours];               // HOLD: steps at which it was held, while the trial's rows were due
     __shared__ uvs_camera s_cam[SCENES ? G : 1];                 // SCENES: the cameras that render the workgroup's trials, staged once below
     __shared__ uvs_target_motion s_mot[MOVING ? G : 1];          // MOVING: the motions of those trials, staged next to them
+    __shared__ DelayCell s_ring[DELAYED ? G : 1][DELAYED ? kColours : 1][DELAYED ? kDelaySlots : 1];   // DELAYED: the last nine detections of every disc
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -264,6 +292,8 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         if (model_of(scenes_of(A), trial) < 0) valid = false;    // names no scene: void.  Never an address; nothing of it is stored
     }
     if constexpr (MOVING) stage_motions<G, kLoopThreads>(motions_of(A), static_cast<long long>(blockIdx.x) * G, T, s_mot);   // by OUTPUT trial too
+    int delay = 0;                                               // DELAYED: the latency of the OUTPUT trial (a padding wavefront: of the one it shadows)
+    if constexpr (DELAYED) delay = latency_of(latencies_of(A), trial);
     const uvs_occluder *occ_at = nullptr;                        // OCC: the occluders of the OUTPUT trial (a padding wavefront: of the one it shadows)
     int n_occ = 0;
     if constexpr (OCC) occ_at = occluders_of(A, trial, n_occ);
@@ -377,8 +407,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         if constexpr (PAINT) paints = s_paint[w];
 #pragma unroll 1
         for (int j = j_first; j < npts; j += j_step) {
-            const ColourSum sum = detect_pair<OCC, PAINT>(s_disc[w], npts, j, lane, rects, paints);
+            ColourSum sum = detect_pair<OCC, PAINT>(s_disc[w], npts, j, lane, rects, paints);
             if (lane == 0) {                                     // the lane the shuffle tree ends in
+                if constexpr (DELAYED) delay_line(s_ring[ws][j], sum, k, delay);   // in place: the detection of step max(k - delay, 0)
                 double u, v;
                 noisy_centre(sum, noise_at, j, u, v);
                 if constexpr (HOLD) {                            // the integer count decides, never the pair

@@ -1,4 +1,4 @@
-// Device code shared by all twelve translation units of libuvs_vision.so (uvs_vision.hip directly, the eleven loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
+// Device code shared by all fourteen translation units of libuvs_vision.so (uvs_vision.hip directly, the thirteen loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
 // forms its callers need, the disc geometry of the synthetic camera with its occluders and their paints, and the DH chain.  The summation order of the phase 2 is a contract
 // (see centre_of_mass): every unit that sums mask pixels goes through wave_partial and ColourSum, so they all give the same bits.
 #pragma once
@@ -591,6 +591,36 @@ __device__ __forceinline__ void stage_motions(const uvs_target_motion *motion, l
         if (trial >= T) trial = T - 1;
         reinterpret_cast<uint64_t *>(s_mot)[i] = motion != nullptr ? reinterpret_cast<const uint64_t *>(motion + trial)[word] : 0ull;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- camera latency
+// THE rule of the latency operand (uvs_vision.h), shared by every kernel that delays a frame: the latency the device
+// uses, and the step whose frame the detector is handed at step k.
+__device__ __forceinline__ int clamped_latency(int32_t d) { return d < 0 ? 0 : (d > UVS_CAMERA_MAX_LATENCY ? UVS_CAMERA_MAX_LATENCY : d); }
+__device__ __forceinline__ int delayed_step(int k, int d) { return k - d > 0 ? k - d : 0; }
+// the latency of `trial`, clamped; NULL: none
+__device__ __forceinline__ int latency_of(const int32_t *latency, long long trial) { return latency != nullptr ? clamped_latency(latency[trial]) : 0; }
+
+// The delay line of ONE disc of one trial: the detections of the last kDelaySlots steps, slot k mod kDelaySlots.  A cell is a ColourSum as
+// three 64-bit integer words -- the bits of the two sums, and the count -- moved through plain integer pointers and replaced IN PLACE,
+// member by member.  On purpose: with a cell of doubles stored through its struct type, or the delayed detection returned by value, the
+// instantiation closest to the register limit (MCKF at (2, 6), four trials per workgroup) came out 48 registers larger and spilled 28 B
+// per lane; in this form the ring costs it nothing.  The ONE lane that holds the detection of step k writes slot k and reads slot
+// kk = delayed_step(k, d) -- its own words alone, in program order: no barrier.  k - kk <= UVS_CAMERA_MAX_LATENCY < kDelaySlots, so slot
+// kk still holds step kk's detection (d == 0: the one just written, bits untouched), and for k < d slot 0 holds step 0's: the priming.
+constexpr int kDelaySlots = UVS_CAMERA_MAX_LATENCY + 1;
+struct DelayCell {
+    long long s_u, s_v, count;
+};
+__device__ __forceinline__ void delay_line(DelayCell *ring, ColourSum &sum, int k, int d) {
+    long long *in = reinterpret_cast<long long *>(ring + k % kDelaySlots);
+    in[0] = __double_as_longlong(sum.s_u);
+    in[1] = __double_as_longlong(sum.s_v);
+    in[2] = sum.count;
+    const long long *out = reinterpret_cast<const long long *>(ring + delayed_step(k, d) % kDelaySlots);
+    sum.s_u = __longlong_as_double(out[0]);
+    sum.s_v = __longlong_as_double(out[1]);
+    sum.count = static_cast<int>(out[2]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side, shared

@@ -828,6 +828,39 @@ def _motion_operand(checked, dev):
     return t.data_ptr(), t
 
 
+MAX_LATENCY = 8                                                     # UVS_CAMERA_MAX_LATENCY of include/uvs_vision.h (plant.MAX_LATENCY)
+
+
+def _check_latency(latency, T, who):
+    """What can be said of a ``latency=`` for T output trials on the host alone, before any device work: ValueError, or the operand --
+    None, or a host int32 array (T,) of values in 0 .. MAX_LATENCY.  ``latency``: None, an integer for every trial, or T integers (a
+    sequence, an array or an integer tensor, which is brought to the host)."""
+    import torch                                                     # not _torch(): these refusals need no GPU
+    if latency is None:
+        return None
+    if torch.is_tensor(latency):
+        if latency.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64) or latency.is_complex():
+            raise ValueError(f'{who}: latency is integers, control periods, got {latency.dtype}')
+        latency = latency.detach().cpu().numpy()
+    try:
+        a = np.asarray(latency)
+    except Exception as exc:                                         # ragged lists
+        raise ValueError(f'{who}: latency is an integer or ({T},) integers') from exc
+    if a.dtype.kind not in 'iu' or a.ndim > 1:
+        raise ValueError(f'{who}: latency is an integer or ({T},) integers, control periods, got {a.dtype} {a.shape}')
+    if a.ndim == 1 and a.shape[0] != T:
+        raise ValueError(f'{who}: {a.shape[0]} latencies for {T} trials')
+    if a.size and (a.min() < 0 or a.max() > MAX_LATENCY):
+        raise ValueError(f'{who}: latency must lie in 0 .. {MAX_LATENCY} control periods, got {int(a.min())} .. {int(a.max())}')
+    return np.broadcast_to(a.astype(np.int32), (T,)).copy()
+
+
+def _latency_operand(checked, dev):
+    """(pointer, tensor to keep alive) of what _check_latency returned (not None)."""
+    t = _torch().from_numpy(checked).to(dev)
+    return t.data_ptr(), t
+
+
 def _check_step(k, who):
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 2 ** 31:
         raise ValueError(f'{who}: k is a step count, an integer >= 0, got {k!r}')
@@ -901,7 +934,7 @@ CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
 ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
 
 
-def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=None, scenes=None, motion=None):
+def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=None, scenes=None, motion=None, latency=None, steps=0):
     """The stepwise loops' sensor launch at step k: uvs_camera_features_f64, or its occluded namesake when ``occ`` -- None, or the
     (pointer, n_occ, tensor) of ``_occluder_operand`` -- is given.  Returns f(k, q_prev, dq_prev, q, noise, f, pixels) -> return code.
     With ``hold`` > 0 the step is that launch and uvs_hold_features_f64 behind it on the same stream, on the same rows: the callable then
@@ -910,7 +943,11 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=
     ``scenes``: None, or the (pointer, n_cams, index pointer) of ``_scene_operand`` -- the launch is then uvs_camera_features_scenes_f64 for
     ``npts`` points, with or without ``occ`` and ``paint``, and ``cam_ref`` is not read.
     ``motion``: None, or the pointer of ``_motion_operand`` next to ``scenes`` -- the launch is then uvs_camera_features_moving_f64, which
-    takes the motions and the step k."""
+    takes the motions and the step k.
+    ``latency``: None, or the pointer of ``_latency_operand`` for a loop of ``steps`` steps -- the sensor launch then writes the noise-free
+    detection and its mask sizes into row k of two logs the callable keeps, (steps, T, 2 npts) and (steps, T, npts), and
+    uvs_delay_features_f64 behind it forms the reported row (row max(k - d, 0) plus step k's noise) and its counts into f and pixels;
+    the hold launch, if any, follows on those."""
     from . import _vision
     if motion is not None:
         moving = _vision.lib().uvs_camera_features_moving_f64
@@ -935,6 +972,15 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=
         occluded = _vision.lib().uvs_camera_features_occluded_f64
         detect = lambda k, q_prev, dq_prev, q, noise, f, pixels: occluded(cam_ref, T, q_prev, dq_prev, dt, q, occ[0], occ[1], k, noise, f,   # noqa: E731
                                                                           pixels, None, stream)
+    if latency is not None:
+        torch = _torch()
+        sensed = torch.empty((steps, T, 2 * npts), dtype=torch.float64, device=dev)
+        counts = torch.zeros((steps, T, npts), dtype=torch.int32, device=dev)
+        sense, delay_row = detect, _vision.lib().uvs_delay_features_f64
+
+        def detect(k, q_prev, dq_prev, q, noise, f, pixels):
+            rc = sense(k, q_prev, dq_prev, q, None, sensed.data_ptr() + k * sensed.stride(0) * 8, counts.data_ptr() + k * counts.stride(0) * 4)
+            return rc if rc else delay_row(T, npts, k, latency, sensed.data_ptr(), counts.data_ptr(), noise, f, pixels, stream)
     if hold == 0:
         return detect
     miss = _torch().zeros((T, 4), dtype=_torch().int32, device=dev)
@@ -946,7 +992,8 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=
     return held_step
 
 
-def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None, scenes=None, motion=None):
+def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None, scenes=None, motion=None,
+                                   latency=None):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
     ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models.
     ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none).  ``hold`` > 0 (stepwise alone): a third launch per
@@ -954,7 +1001,10 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     ``scenes``: None, or the (pointer, n_cams, index pointer) of ``_scene_operand`` -- every trial's frames come from its own camera
     (the one launch: uvs_camera_believed_loop_scenes_f64; stepwise: uvs_camera_features_scenes_f64); ``believed`` is then given, and
     ``cam`` is the shape alone.  ``motion``: None, or the pointer of ``_motion_operand`` next to ``scenes`` -- the sensor side's discs move
-    (the one launch: uvs_camera_believed_loop_moving_f64; stepwise: uvs_camera_features_moving_f64); the law's model does not."""
+    (the one launch: uvs_camera_believed_loop_moving_f64; stepwise: uvs_camera_features_moving_f64); the law's model does not.
+    ``latency``: None, or the pointer of ``_latency_operand`` next to ``scenes`` -- the detector is handed the frame of step max(k - d, 0)
+    (the one launch: uvs_camera_believed_loop_delayed_f64, with or without ``motion``; stepwise: uvs_delay_features_f64 behind the
+    features call); the law's joints are the current ones."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -970,7 +1020,9 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         stats = torch.empty((T, 3), **f64)
         pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
         outputs = (ptr('q'), ptr('f'), ptr('dq'), ptr('err'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
-        if motion is not None:
+        if latency is not None:
+            rc = _vision.lib().uvs_camera_believed_loop_delayed_f64(C.byref(fp), *scenes, motion, latency, T, *believed, q0, noise_ptr, *outputs)
+        elif motion is not None:
             rc = _vision.lib().uvs_camera_believed_loop_moving_f64(C.byref(fp), *scenes, motion, T, *believed, q0, noise_ptr, *outputs)
         elif scenes is not None:
             rc = _vision.lib().uvs_camera_believed_loop_scenes_f64(C.byref(fp), *scenes, T, *believed, q0, noise_ptr, *outputs)
@@ -984,7 +1036,7 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
-    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, scenes, motion)
+    features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, scenes, motion, latency, K)
     held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     if believed is None:
         step = lambda *rows: _vision.lib().uvs_camera_analytical_step_f64(fp_ref, cam_ref, T, *rows)          # noqa: E731
@@ -1069,7 +1121,7 @@ def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
 
 
 def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0, paints=None, scenes=None,
-                              motion=None):
+                              motion=None, latency=None):
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
     then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
     ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
@@ -1082,7 +1134,9 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     A fourth member, True, says that the one scene is the NOMINAL camera standing in for a moving launch without ``cameras``: ``cam`` is then
     the model of every trial, and guess='device' may still make x0 from it.
     ``motion``: None, or the (pointer, packed tensor) of ``_motion_operand`` for the T output trials next to ``scenes`` -- the launch is
-    then uvs_camera_closed_loop_moving_f64, and f0 comes from the step-0 frame, where s(0) applies."""
+    then uvs_camera_closed_loop_moving_f64, and f0 comes from the step-0 frame, where s(0) applies.
+    ``latency``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the T output trials next to ``scenes`` -- the launch is
+    then uvs_camera_closed_loop_delayed_f64, with or without ``motion``; f0 still comes from the step-0 frame."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -1118,7 +1172,10 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
         held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
         rest = (T, None if tp is None else C.byref(tp), None if occ is None else occ[0], None if paint is None else paint[0],
                 0 if occ is None else occ[1], hold, *operands[:-1], None if held is None else held.data_ptr(), operands[-1])
-        if motion is None:
+        if latency is not None:
+            rc = _vision.lib().uvs_camera_closed_loop_delayed_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0], latency[0],
+                                                                  *rest)
+        elif motion is None:
             rc = _vision.lib().uvs_camera_closed_loop_scenes_f64(C.byref(fp), *scenes[0], *rest)
         else:
             rc = _vision.lib().uvs_camera_closed_loop_moving_f64(C.byref(fp), *scenes[0], motion[0], *rest)
@@ -1170,7 +1227,7 @@ def _gather_by_source(q_start, noise, x0, trial_params):
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
                        believed_index=None, trial_params=None, occluders=None, hold=0, occluder_colours=None, cameras=None, camera_index=None,
-                       target_motion=None, motion_window=None):
+                       target_motion=None, motion_window=None, latency=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -1262,7 +1319,21 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     initial guess come from the step-0 frame, where s(0) applies.  ANALYTICAL: fused=True is uvs_camera_believed_loop_moving_f64 (with
     occluders or hold > 0 it stays the ValueError it is), fused=False the moving features call, then uvs_camera_believed_step_f64.  Next
     to trial_params['source'] the inputs are gathered by source before the launch, as next to occluders.  ValueErrors before any device
-    work: a wrong shape or dtype, a window without a motion, T rows of motion for a different T, window entries outside int32."""
+    work: a wrong shape or dtype, a window without a motion, T rows of motion for a different T, window entries outside int32.
+    ``latency``: CAMERA LATENCY, per OUTPUT trial -- an integer, or T integers (a sequence, an array or an integer tensor), each in
+    0 .. ``MAX_LATENCY`` control periods.  At step k trial t's detector is handed the frame of step kk = max(k - latency[t], 0) -- the
+    joints, occluders, paints and target motion of step kk (the rule: ``plant.delayed_step``; include/uvs_vision.h, CAMERA LATENCY); the
+    noise added to that detection is step k's, and the hold rule, the estimator or the law follow on it as they are.  The controller is
+    not told: the law's joints are the current q_k, the estimators' regressor is dq_{k-1}.  'f' logs the reported rows, 'pixels' is the
+    smallest mask among the detections reported up to and including k_done.  f0 and the initial guess come from the step-0 frame.  None
+    (the default) is the call without the argument: its routes, its entry points, its bits; zeros give the same bits through the
+    delayed kernels.  Without ``cameras`` the nominal camera is packed as the one scene, as with motion.  fused=True with an estimator is
+    ONE launch (uvs_camera_closed_loop_delayed_f64) with any of ``trial_params``, ``occluders``, ``occluder_colours``, ``hold``,
+    ``cameras`` and ``target_motion``; with ANALYTICAL it is uvs_camera_believed_loop_delayed_f64 (with occluders or hold > 0 it stays the
+    ValueError it is).  fused=False, for the estimators and ANALYTICAL alike, is per step the features call without noise into a log of
+    sensed rows, uvs_delay_features_f64, then the hold call and the step as before; the two return the same bits.  Next to
+    trial_params['source'] the inputs are gathered by source before the launch, as next to occluders.  ValueErrors before any device
+    work, after the refusals above: a value outside 0 .. ``MAX_LATENCY``, a wrong length, non-integers."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
@@ -1321,10 +1392,19 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         unknown = [key for key in want if key not in ANALYTICAL_CAMERA_LOGS]
         if unknown:
             raise ValueError(f'camera_closed_loop: the calibrated baseline logs {ANALYTICAL_CAMERA_LOGS}, it has no {unknown}')
+    n_out = getattr(q_start, 'shape', (0,))[0]
+    if latency is not None and trial_params is not None and trial_params.get('source') is not None:
+        n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
+    delays = _check_latency(latency, n_out, 'camera_closed_loop')    # None, or (T,) int32 on the host, by output trial
+    if delays is not None and cameras is None and not nominal:       # the nominal camera stands in as the one scene here too
+        if fp.n != 6:
+            raise ValueError(f'camera_closed_loop: the camera-latency kernels are built for the six-joint arms of this project, not for {fp.n} joints')
+        nominal = True
     if fused and not getattr(q_start, 'is_cuda', False):
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     torch = _torch()
-    if (occluders is not None or cameras is not None or motion is not None) and trial_params is not None and trial_params.get('source') is not None:
+    if (occluders is not None or cameras is not None or motion is not None or delays is not None) and trial_params is not None \
+            and trial_params.get('source') is not None:
         q_start, noise, x0, trial_params = _gather_by_source(q_start, noise, x0, trial_params)
     K, m, n = fp.steps, fp.m, fp.n
     T, dev = q_start.shape[0], q_start.device
@@ -1344,6 +1424,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     mot = None if motion is None else _motion_operand(motion, dev)   # (pointer, packed tensor) of the T output trials
     if mot is not None:
         scene_kw['target_motion'] = mot[1]
+    lat = None if delays is None else _latency_operand(delays, dev)  # (pointer, int32 tensor) of the T output trials
     if analytical:
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -1357,7 +1438,8 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         else:
             *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
         return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold, paint=paint,
-                                              scenes=None if scenes is None else scenes[0], motion=None if mot is None else mot[0])
+                                              scenes=None if scenes is None else scenes[0], motion=None if mot is None else mot[0],
+                                              latency=None if lat is None else lat[0])
     if believed is not None or (scenes is not None and not nominal and x0 is None):  # an estimator that starts from a model in memory: the believed one, or
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)                           # its own scene; the rest is the x0= path
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -1371,7 +1453,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes, mot)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes, mot, lat)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -1401,7 +1483,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
         return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2], hold,
-                                         None if paint is None else paint[1], scenes, mot)
+                                         None if paint is None else paint[1], scenes, mot, lat)
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
@@ -1410,7 +1492,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     step = _lib.lib().uvs_rmckf_step_f64
     cam_ref, fp_ref, stream = C.byref(cam), C.byref(fp), _stream()
     features = _features_step(cam_ref, T, fp.dt, occ, stream, hold, npts, dev, paint, None if scenes is None else scenes[0],
-                              None if mot is None else mot[0])
+                              None if mot is None else mot[0], None if lat is None else lat[0], K)
     held_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev) if hold else None
     row = {key: (t.data_ptr(), t.stride(0) * t.element_size()) for key, t in dict(log, status=status_log, pixels=pixel_log).items()}
     if hold:

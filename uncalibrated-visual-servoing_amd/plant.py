@@ -436,6 +436,21 @@ def target_motion_array(velocity, window, n_points, T=None):
     return out
 
 
+MAX_LATENCY = 8                         # UVS_CAMERA_MAX_LATENCY: control periods between the pose a frame shows and the command from it
+
+
+def delayed_step(k, d):
+    """The step whose frame the detector is handed at step ``k`` >= 0 by a camera of latency ``d`` -- the numpy statement of the rule of
+    include/uvs_vision.h (CAMERA LATENCY) that every delayed kernel is held to: kk = max(k - clamp(d, 0, MAX_LATENCY), 0), in Python
+    integers.  The rule is total: a negative latency is none, a huge one is ``MAX_LATENCY``.  The frame of step kk shows joints q_kk,
+    occluders, paints and target motion at kk; the noise added to its detection is that of step k; the delay line is primed with the
+    step-0 frame."""
+    k, d = int(k), int(d)
+    if k < 0:
+        raise ValueError('k must be >= 0')
+    return max(k - min(max(d, 0), MAX_LATENCY), 0)
+
+
 class LinearPlant:
     """Consistent linearised camera f = f0 + J (q - q0) for shapes without a DH model (BASELINE config 5: m = 32, n = 7;
     a 7-joint arm would be redundant for a 6-DoF camera pose and leave the feature Jacobian rank 6).  J, f0, q0 are uploaded
@@ -557,10 +572,14 @@ class CameraRobot:
     ``target_motion``: None, or (n_points, 3) world velocities in metres per step, with ``motion_window`` (k_on, k_off) or None
     (``MOTION_WINDOW``): the discs stand where step ``k`` of that motion has taken them (``target_at``), so ``discs()`` and
     ``getCameraImage()`` show the frames ``engine.camera_closed_loop(target_motion=...)`` detects.  The robot's own kinematics -- what
-    the calibrated law reads -- keep the plant's points: the controller does not know the target's motion."""
+    the calibrated law reads -- keep the plant's points: the controller does not know the target's motion.
+    ``latency``: an integer 0 .. ``MAX_LATENCY``, the camera's latency in control periods: at step ``k`` ``discs()`` and
+    ``getCameraImage()`` show the frame of step ``delayed_step(k, latency)`` -- the joints, occluders, paints and target motion of that
+    step -- rendered on demand from the joints kept since ``start()``.  The robot's own joints, what the encoders report, are the
+    current ones.  0 (the default) is the robot without the argument."""
 
     def __init__(self, plant=None, radius=DISC_RADIUS, dt=0.05, background=96, occluders=None, shade=32, occluder_colours=None,
-                 target_motion=None, motion_window=None):
+                 target_motion=None, motion_window=None, latency=0):
         self._robot = SyntheticRobot(plant, dt)
         self.radius, self.background, self.shade = radius, background, shade
         self.occluders = None if occluders is None else occluder_array(occluders, 1)[0]
@@ -579,6 +598,10 @@ class CameraRobot:
             self.target_motion = np.array(target_motion, np.float64).reshape(npts, 3)
             if motion_window is not None:
                 self.motion_window = tuple(int(w) for w in np.asarray(motion_window).reshape(2))
+        if isinstance(latency, bool) or not isinstance(latency, (int, np.integer)) or not 0 <= latency <= MAX_LATENCY:
+            raise ValueError(f'latency is an integer 0 .. {MAX_LATENCY} control periods, got {latency!r}')
+        self.latency = int(latency)
+        self._shown = []                                            # the joints of the last latency + 1 steps, the current ones last
         self.k = 0
 
     def __getattr__(self, name):                                    # everything but the camera: the synthetic robot's
@@ -589,17 +612,27 @@ class CameraRobot:
     def start(self, q=None):
         self._robot.start(q)
         self.k = 0
+        self._shown = [np.array(self._robot.q, np.float64)]
 
     def step(self):
         self._robot.step()
         self.k += 1
+        self._shown = (self._shown + [np.array(self._robot.q, np.float64)])[-(self.latency + 1):]
+
+    def _frame_step(self):
+        """(step, joints) of the frame the camera shows now: ``delayed_step(k, latency)`` and the joints kept from it."""
+        kk = delayed_step(self.k, self.latency)
+        if kk == self.k or not self._shown:                         # no latency, or a robot that was never started: the current joints
+            return self.k, self._robot.q
+        return kk, self._shown[-1 - (self.k - kk)]
 
     def discs(self):
+        kk, q = self._frame_step()
         if self.target_motion is not None:
-            return target_at(self._robot.plant, self.target_motion, self.k, self.motion_window).discs(self._robot.q, self.radius)
-        return self._robot.plant.discs(self._robot.q, self.radius)
+            return target_at(self._robot.plant, self.target_motion, kk, self.motion_window).discs(q, self.radius)
+        return self._robot.plant.discs(q, self.radius)
 
     def getCameraImage(self):
-        frame = render_discs(self.discs(), self._robot.plant.n_points, self.background, self.occluders, self.k, self.shade,
+        frame = render_discs(self.discs(), self._robot.plant.n_points, self.background, self.occluders, self._frame_step()[0], self.shade,
                              self.occluder_colours)
         return frame, (RESOLUTION, RESOLUTION)
