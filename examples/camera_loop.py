@@ -46,8 +46,12 @@ frame shows and the command computed from it (engine.camera_closed_loop(latency=
 ONE launch per method: the estimators pair f_k - f_{k-1} with a regressor that is d steps too new, and the calibrated law feeds an
 interaction matrix at the current joints the features of the pose d steps ago.  Nobody is told the latency.  The chosen estimator, KF and
 the calibrated law; prints the median ISE / IAE / ITAE, the FAIL count and the median feature error at the last step, per latency.
+--latency --told tells the controller: LATENCIES x ASSUMED assumed latencies x the trials in ONE launch per method
+(engine.camera_closed_loop(latency=, assumed_latency=)) -- the estimators' regressor becomes the command of step k - 1 - a, the law's joints
+those of step max(k - a, 0) -- told (a > 0) and untold (a = 0) on the same starts and noise.  Prints the median ISE and the FAILs with their
+median k_done per (d, a) cell: the diagonal is what telling recovers, the rest how wrong the assumed latency may be.
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving] [--latency]"""
+       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving] [--latency [--told]]"""
 import argparse
 import os
 import sys
@@ -382,6 +386,53 @@ def latency_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed=0
     return lines
 
 
+ASSUMED = (0, 1, 2, 3, 4)                                            # control periods the controller is told
+
+
+def told_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed=0, latencies=LATENCIES, assumed=ASSUMED):
+    """The true-latency x assumed-latency grid as a list of lines: len(latencies) x len(assumed) x trials in ONE launch per method
+    (engine.camera_closed_loop(latency=, assumed_latency=)), over the same starts and noise in every cell; a = 0 is the controller that is
+    not told.  Per (d, a) cell the median ISE over the trials that ran to the end and, after the slash, the trials that did not with their
+    median k_done.  No finding is drawn here: the table is what the experiment prints."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    methods = tuple(dict.fromkeys((method, 'KF', 'ANALYTICAL')))
+    fps = {name: uvs.engine.make_params(8, 6, name, 10.0, False, 0.05, 15.0, 0.2, desired, True) for name in methods}
+    K = fps[method].steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    noise = rng.standard_normal((K, trials, 8)) * sigma
+    cells = [(d, a) for d in latencies for a in assumed]
+    n = len(cells)
+    q0_d = torch.as_tensor(np.tile(q0, (n, 1)), device='cuda')       # the same starts and the same noise in every cell
+    noise_d = torch.as_tensor(np.tile(noise, (1, n, 1)), device='cuda')
+    latency = np.repeat(np.array([d for d, _ in cells], np.int64), trials)
+    told = np.repeat(np.array([a for _, a in cells], np.int64), trials)
+    lines = [f'{len(latencies)} camera latencies x {len(assumed)} assumed latencies x {trials} trials of {K} steps in one launch per method, '
+             f'white noise {sigma} px; per cell: median ISE over the trials that ran to the end / FAILs (their median k_done)']
+    for name, fp in fps.items():
+        kw = dict(radius=radius, fused=True, want=('err',), latency=latency, assumed_latency=told)
+        if name != 'ANALYTICAL':
+            kw['guess'] = 'device'
+        out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, **kw)
+        torch.cuda.synchronize()
+        status, stats, k_done = out['status'].cpu().numpy(), out['stats'].cpu().numpy(), out['k_done'].cpu().numpy()
+        lines.append(f'{name + ": latency | told":26s}' + ''.join(f'{"a = " + str(a):>22s}' for a in assumed))
+        for i, d in enumerate(latencies):
+            row = f'{"d = " + str(d):26s}'
+            for j in range(len(assumed)):
+                c = i * len(assumed) + j
+                rows = slice(c * trials, (c + 1) * trials)
+                done = status[rows] == 0
+                ise = np.median(stats[rows][done, 0]) if done.any() else np.nan
+                fails = f'{int((~done).sum())}' + (f' ({int(np.median(k_done[rows][~done]))})' if (~done).any() else '')
+                row += f'{ise:14.3f} /{fails:>6s}'
+            lines.append(row)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -405,11 +456,19 @@ def main():
                     help='the target moves for a window of steps after convergence: the estimator, KF and the calibrated law, and nothing else')
     ap.add_argument('--latency', action='store_true',
                     help='camera latencies 0 .. 4 x the trials in one launch per method: the estimator, KF and the calibrated law, and nothing else')
+    ap.add_argument('--told', action='store_true',
+                    help='with --latency: the controller is told a latency -- latencies 0 .. 4 x assumed latencies 0 .. 4 x the trials in one '
+                         'launch per method, told and untold on the same starts and noise')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
     if args.hold and not args.occlusion:
         ap.error('--hold goes with --occlusion')
+    if args.told and not args.latency:
+        ap.error('--told goes with --latency')
+    if args.latency and args.told:
+        print('\n'.join(told_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
+        return
     if args.latency:
         print('\n'.join(latency_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
         return

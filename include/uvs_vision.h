@@ -596,6 +596,44 @@ int uvs_camera_believed_loop_delayed_f64(const struct uvs_filter_params *fp, con
 int uvs_delay_features_f64(int64_t T, int32_t n_points, int32_t k, const int32_t *latency, const double *sensed_log, const int32_t *count_log,
                            const double *noise_row, double *f_row, int32_t *pixels_row, void *stream);
 
+/*
+ * ASSUMED LATENCY: the controller is told a camera latency.  In the loops above the frame may be delayed (`latency`) but the controller is
+ * not told: the estimators pair f_k - f_{k-1} with dq_{k-1} although, at latency d, that difference belongs to dq_{k-1-d}, and the law
+ * evaluates its interaction matrix at q_k on features of q_{k-d}.  Below each OUTPUT trial also carries an ASSUMED latency a, in control
+ * periods, independent of its true latency d: a != d is the mismatch experiment, and a > 0 without any latency is legal.  The rule
+ * (plant.aligned_regressor_step and plant.delayed_step state it once in numpy; every kernel below is held to it bit for bit):
+ *   assumed [T] int32 by output trial, in device (or pinned host) memory, directly after `latency`; NULL = none.  The device uses
+ *     clamp(a, 0, UVS_CAMERA_MAX_LATENCY): the rule is total and the operand is not validated.
+ *   Estimators: the regressor of step k is the command of step k - 1 - a when k - 1 - a >= 0, and the zero vector otherwise, which goes
+ *     through the same update with h = 0 that step 0 always ran.  Everything else in the step is the text above: z, err, sigma, the
+ *     control law on the updated X, the logs, the hold rule, FAIL.  Only the regressor moves: the command integrated into the joints
+ *     stays dq_{k-1}.
+ *   Calibrated and believed law: the joints handed to the law at step k are q_{max(k - a, 0)}, so the camera Jacobian, the depths and the
+ *     interaction matrix are those of the pose the assumed frame shows.  The features stay the reported (delayed, noisy) row of step k;
+ *     the model's points do not move; the q log and the joint integration stay current.
+ * The two loops have their *_delayed_* namesake's operands in its order with `assumed` directly after `latency`, its refusals in their
+ * order, all before the first HIP call; T == 0 returns UVS_OK and launches nothing.  The estimator loop keeps the last
+ * UVS_CAMERA_MAX_LATENCY + 1 commands of every trial in an LDS ring, the baseline loop the joints of as many steps; the barriers that were
+ * there cover both: no barrier and no exit is added.  The stepwise loops gather the step call's dq_prev (or joints) row per trial from the
+ * dq (or q) log.
+ * Bit for bit: (a) assumed == NULL, or all zeros, gives the bits of the delayed namesake (with latency NULL too: of the moving one);
+ * (b) a trial of a launch that mixes (d, a) pairs has the bits of the uniform launch at its own pair; (c) the one launch has the
+ * stepwise loop's bits; (d) padding wavefronts and shadow lanes read the assumed latency of the trial they shadow and store nothing;
+ * (e) void trials stay void; (f) values outside 0 .. UVS_CAMERA_MAX_LATENCY are clamped on the device.
+ * Built: what the delayed namesakes build, each in both workgroup forms with 0 B of scratch memory.
+ */
+int uvs_camera_closed_loop_aligned_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                       const uvs_target_motion *motion, const int32_t *latency, const int32_t *assumed, int64_t T,
+                                       const uvs_camera_trial_params *tp, const uvs_occluder *occ, const int32_t *paint, int32_t n_occ,
+                                       int32_t hold, const double *q_start, const double *noise, const double *x0, const double *f0,
+                                       double *q_log, double *f_log, double *dq_log, double *err_log, double *kappa_log, int32_t *status,
+                                       int32_t *k_done, double *stats, int32_t *pixels, int32_t *held, void *stream);
+int uvs_camera_believed_loop_aligned_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                         const uvs_target_motion *motion, const int32_t *latency, const int32_t *assumed, int64_t T,
+                                         const uvs_camera *believed, int64_t n_believed, const int32_t *believed_index, const double *q_start,
+                                         const double *noise, double *q_log, double *f_log, double *dq_log, double *err_log, int32_t *status,
+                                         int32_t *k_done, double *stats, int32_t *pixels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,7 +109,20 @@ x 299 steps, white noise 0.3 px --
       over the 5 latencies x 64 trials in one launch
       -- (dv) is asserted to have the bits of (mv), (dw) those of (dx) and (dz) trial for trial, (dy) those of (my), before anything is timed.
       Then the table of examples/camera_loop.py --latency.
-usage: tools/time_camera.py --delayed [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --delayed [--parent-lib=PATH] [out.txt]
+
+With --aligned only the assumed-latency pixel loops are timed, into profiles/camera_aligned_timing.txt (or the path given): GMCKF, 1 024 trials
+x 299 steps, white noise 0.3 px --
+  (dv) the delayed loop with latency = NULL, (dy) the delayed baseline loop with latency = NULL, each also through the parent's library,
+      twice, when --parent-lib names it;
+  (av) (dv)'s trials through aligned_frames_kernel with latency = assumed = NULL, (ay) (dy)'s through aligned_baseline_kernel: against the
+      parent's (dv) and (dy) by the rule of DESIGN.md 4.20 -- no slower than the slower parent run by more than the parent runs differ;
+  (aw) 5 latencies x 5 assumed latencies (examples/camera_loop.py --latency --told) x 64 trials in ONE launch, (ax) the same as 25 launches
+      of 64 trials, one per cell, (az) (aw) stepwise: K x (features without noise, delay, gather of the regressor, estimator step);
+  (ay25) the baseline over the 25 cells x 64 trials in one launch
+      -- (av) is asserted to have the bits of (dv), (ay) those of (dy), (aw) those of (ax) and (az) trial for trial, before anything is timed.
+      Then the table of examples/camera_loop.py --latency --told.
+usage: tools/time_camera.py --aligned [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -126,9 +139,10 @@ OCCLUDED, HELD, PAINTED = '--occluded' in sys.argv[1:], '--held' in sys.argv[1:]
 SCENES = '--scenes' in sys.argv[1:]
 MOVING = '--moving' in sys.argv[1:]
 DELAYED = '--delayed' in sys.argv[1:]
+ALIGNED = '--aligned' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving', '--delayed') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_latency_timing.txt' if DELAYED else 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving', '--delayed', '--aligned') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_aligned_timing.txt' if ALIGNED else 'camera_latency_timing.txt' if DELAYED else 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -1164,6 +1178,148 @@ def delayed_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def aligned_section():
+    """(dv), (dy) against the parent's; (av) .. (ay25): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T = 299, 1024
+    LAT, TOLD, PER = example.LATENCIES, example.ASSUMED, 64
+    cells = [(d, a) for d in LAT for a in TOLD]
+    TL = len(cells) * PER
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    fa = uvs.engine.make_params(8, 6, 'ANALYTICAL', 10.0, False, 0.05, 15.0, 0.2, DESIRED)
+    assert fp.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --aligned on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in (the nominal model\'s guess); the latencies {LAT} x the assumed '
+        f'latencies {TOLD} x {PER} trials = {TL} trials')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+    x0 = uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+    one = uvs.engine.camera_scenes(plant)
+    nominal = uvs.engine.believed_models(plant)
+    cam = plant.to_camera(uvs.plant.DISC_RADIUS)
+    scene_one = (one.data_ptr(), 1, None), one, None, True           # the nominal camera as the one scene
+    null = (None, None)                                              # latency = NULL, assumed = NULL
+    # the experiment: the same 64 starts and noise in each of the 25 cells
+    ql = q_d[:PER].repeat(len(cells), 1).contiguous()
+    nl = noise[:, :PER].repeat(1, len(cells), 1).contiguous()
+    xl = x0[:PER].repeat(len(cells), 1).contiguous()
+    latency = np.repeat(np.array([d for d, _ in cells], np.int64), PER)
+    told = np.repeat(np.array([a for _, a in cells], np.int64), PER)
+    parts = [(c, slice(c * PER, (c + 1) * PER)) for c in range(len(cells))]
+    cut = (ql[:PER].contiguous(), nl[:, :PER].contiguous(), xl[:PER].contiguous())
+
+    def baseline_null(entry, *front):                                # a baseline loop through the C ABI with NULL operands
+        import ctypes as C
+        out = {key: torch.empty((K, T, comp), dtype=torch.float64, device='cuda') for key, comp in (('q', 6), ('f', 8), ('dq', 6), ('err', 8))}
+        status, k_done = (torch.empty(T, dtype=torch.int32, device='cuda') for _ in range(2))
+        stats, pixels = torch.empty((T, 3), dtype=torch.float64, device='cuda'), torch.empty((T, 4), dtype=torch.int32, device='cuda')
+        uvs._vision.check(getattr(uvs._vision.lib(), entry)(
+            C.byref(fa), one.data_ptr(), 1, None, *front, T, nominal.data_ptr(), 1, None, q_d.data_ptr(), noise.data_ptr(), out['q'].data_ptr(),
+            out['f'].data_ptr(), out['dq'].data_ptr(), out['err'].data_ptr(), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(),
+            pixels.data_ptr(), uvs.engine._stream()))
+        return dict(out, pixels=pixels, status=status, k_done=k_done, stats=stats)
+
+    fused = uvs.engine._camera_closed_loop_fused
+    fns = {'dv': lambda: fused(fp, cam, q_d, noise, x0, 'host', uvs.engine.CAMERA_LOGS, scenes=scene_one, motion=None, latency=null),
+           'av': lambda: fused(fp, cam, q_d, noise, x0, 'host', uvs.engine.CAMERA_LOGS, scenes=scene_one, motion=None, latency=None, assumed=null),
+           'dy': lambda: baseline_null('uvs_camera_believed_loop_delayed_f64', None, None),
+           'ay': lambda: baseline_null('uvs_camera_believed_loop_aligned_f64', None, None, None),
+           'aw': lambda: loop(fp, plant, ql, nl, x0=xl, fused=True, latency=latency, assumed_latency=told),
+           'ax': lambda: [loop(fp, plant, *cut[:2], x0=cut[2], fused=True, latency=d, assumed_latency=a) for d, a in cells],
+           'az': lambda: loop(fp, plant, ql, nl, x0=xl, latency=latency, assumed_latency=told),
+           'ay25': lambda: loop(fa, plant, ql, nl, fused=True, latency=latency, assumed_latency=told)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+
+    def same(a, b, rows=slice(None), rows_b=slice(None)):
+        done = a['k_done'][rows]
+        ok = all(torch.equal(a[key][rows], b[key][rows_b]) for key in ('status', 'k_done', 'pixels'))
+        ok = ok and torch.equal(a['stats'][rows].view(torch.int64), b['stats'][rows_b].view(torch.int64))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):                 # the specified rows: q, f up to and including k_done, the others before it
+            if key in a:
+                spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+                ok = ok and torch.equal(a[key][:, rows].view(torch.int64)[spec], b[key][:, rows_b].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['av'], first['dv']), 'the aligned kernel that is not told and the delayed kernel disagree'
+    assert same(first['ay'], first['dy']), 'the aligned baseline that is not told and the delayed baseline disagree'
+    assert same(first['aw'], first['az']), 'the one launch and the stepwise loop disagree'
+    for c, rows in parts:
+        assert same(first['aw'], first['ax'][c], rows), f'cell {cells[c]}: the one launch and the launch per cell disagree'
+    assert not same(first['aw'], first['ax'][0], parts[1][1]), 'telling shows'
+    gated = {'av': 'dv', 'ay': 'dy'}
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_aligned_f64'), 'the parent library has no assumed latency'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def with_parent(fn):
+            def run():
+                mine, uvs._vision._lib = uvs._vision._lib, parent
+                try:
+                    return fn()
+                finally:
+                    uvs._vision._lib = mine
+            return run
+
+        for name in gated.values():
+            run = with_parent(fns[name])
+            old = run()
+            torch.cuda.synchronize()
+            assert same(first[name], old), f'this library and the parent disagree on ({name})'
+            fns[name + '_parent_a'], fns[name + '_parent_b'] = run, with_parent(fns[name])
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    say()
+    what = {'dv': 'delayed_frames_kernel, latency = NULL', 'av': "(dv)'s trials through aligned_frames_kernel, NULL, NULL",
+            'dy': 'delayed_baseline_kernel, latency = NULL', 'ay': "(dy)'s trials through aligned_baseline_kernel, NULL, NULL"}
+    passed = True
+    for new, old in gated.items():
+        say(f'  ({old}) {what[old]:56s} this library   {fmt_ms(ms[old])}   = {med[old] / K * 1e3:.1f} us per step')
+        say(f'  ({new}) {what[new]:56s} this library   {fmt_ms(ms[new])}   = {med[new] / K * 1e3:.1f} us per step')
+        if PARENT_LIB is not None:
+            a, b = med[old + '_parent_a'], med[old + '_parent_b']
+            say(f'  ({old}) {"":56s} the parent\'s, 1  {fmt_ms(ms[old + "_parent_a"])}')
+            say(f'  ({old}) {"":56s} the parent\'s, 2  {fmt_ms(ms[old + "_parent_b"])}')
+            ok = med[new] <= max(a, b) + abs(a - b)
+            passed = passed and ok
+            say(f'  ({new}) / slower parent run of ({old}) = {med[new] / max(a, b):.4f}; the two parent runs differ by {abs(a - b) / max(a, b) * 100:.2f} %: '
+                f'{"passes" if ok else "DOES NOT pass"}; outputs bit-identical')
+    say(f'  (aw) {len(LAT)} latencies x {len(TOLD)} assumed x {PER} trials, one launch                         {fmt_ms(ms["aw"])}   = {med["aw"] / K * 1e3:.1f} us per step')
+    say(f'  (ax) the same as {len(cells)} launches of {PER} trials, one per cell                      {fmt_ms(ms["ax"])}')
+    say(f'  (az) (aw) stepwise: K x (features, delay, gather, estimator step)           {fmt_ms(ms["az"])}   = {med["az"] / K * 1e3:.1f} us per step')
+    say(f'  (ay25) the baseline over the {len(cells)} cells x {PER} trials, one launch                 {fmt_ms(ms["ay25"])}')
+    say(f'  (av) / (dv) = {med["av"] / med["dv"]:.4f}, (ay) / (dy) = {med["ay"] / med["dy"]:.4f}, (aw) / (ax) = {med["aw"] / med["ax"]:.4f}, (aw) / (az) = '
+        f'{med["aw"] / med["az"]:.4f}; (av) has the bits of (dv), (ay) those of (dy), (aw) those of (ax) and of (az)')
+    failed = lambda out: int((out['k_done'] < K).sum())              # noqa: E731
+    say(f'  trials that FAILed: (dv) {failed(first["dv"])}, (aw) {failed(first["aw"])}, (ay25) {failed(first["ay25"])}')
+    say()
+    if PARENT_LIB is not None:
+        say(f'gate (DESIGN.md 4.20): (av) against two runs of the parent\'s (dv), (ay) against two of its (dy): {"pass" if passed else "DO NOT pass"}')
+        say()
+    say('# examples/camera_loop.py --latency --told (its defaults)')
+    for line in example.told_table(uvs):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if ALIGNED:
+    aligned_section()
+    sys.exit(0)
 if DELAYED:
     delayed_section()
     sys.exit(0)

@@ -108,6 +108,9 @@ SYMBOLS = {
     'uvs_camera_believed_loop_delayed_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
     # T, n_points, k, latency, sensed_log, count_log, noise_row, f_row, pixels_row, stream
     'uvs_delay_features_f64': (C.c_int, [_I64, _I32, _I32] + [_VP] * 7),
+    # assumed latency: the two delayed loops with assumed (device int32 [T] or None) directly after latency
+    'uvs_camera_closed_loop_aligned_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
+    'uvs_camera_believed_loop_aligned_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
 }
 
 _lib = None
@@ -117,7 +120,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 14)), '-C', CSRC], check=True)        # fourteen translation units, one rule each
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 16)), '-C', CSRC], check=True)        # sixteen translation units, one rule each
     return LIB_PATH
 
 

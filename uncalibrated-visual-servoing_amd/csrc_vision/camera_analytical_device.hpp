@@ -14,6 +14,9 @@
 // A unit that defines UVS_CAMERA_DELAYED on top (uvs_camera_delayed_baseline.hip) sees a fifth, delayed_baseline_kernel(DelayedBaselineArgs): the
 // moving one whose detector is handed the frame of step max(k - d, 0), d the trial's latency, through an LDS ring of detections per disc
 // (DESIGN.md 4.24).  The law's joints stay the current ones.
+// A unit that defines UVS_CAMERA_ALIGNED on top (uvs_camera_aligned_baseline.hip) sees a sixth, aligned_baseline_kernel(AlignedBaselineArgs): the
+// delayed one whose law is told a latency -- the joints handed to analytical_step at step k are q_{max(k - a, 0)}, a the trial's ASSUMED
+// latency, through s_q as a ring of the last nine steps' joints.  The q log and the joint integration stay current.
 // Next to them: what every entry point of the two units asks of (fp, cam, T) before its first HIP call.
 //
 // The loop's mapping is the one of camera_loop_kernel (camera_loop_device.hpp), decided and measured there -- 256 threads = one wavefront per
@@ -120,6 +123,20 @@ struct DelayedBaselineArgs : MovingBaselineArgs {
     const int32_t *latency;                                      // [T] by output trial, or NULL: none
 };
 
+// The sixth flavour (a unit that defines UVS_CAMERA_ALIGNED too, uvs_camera_aligned_baseline.hip): aligned_baseline_kernel, the
+// delayed flavour with an ASSUMED latency per OUTPUT trial.  s_q is a ring; the law reads the joints of step max(k - a, 0).
+struct AlignedBaselineArgs : DelayedBaselineArgs {
+    const int32_t *assumed;                                      // [T] by output trial, or NULL: none
+};
+
+#if defined(UVS_CAMERA_ALIGNED)
+#if !defined(UVS_CAMERA_DELAYED)
+#error "the aligned flavour is a delayed flavour: define UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
+#endif
+constexpr bool kBaselineAligned = true;
+#else
+constexpr bool kBaselineAligned = false;
+#endif
 #if defined(UVS_CAMERA_DELAYED)
 constexpr bool kBaselineDelayed = true;
 #else
@@ -130,8 +147,13 @@ constexpr bool kBaselineDelayed = false;
 #error "the delayed flavour is a moving flavour: define UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
 #endif
 constexpr bool kCameraBelieved = true, kBaselineScenes = true, kBaselineMoving = true;
+#if defined(UVS_CAMERA_ALIGNED)
+using BaselineLoopArgs = AlignedBaselineArgs;
+#define UVS_BASELINE_LOOP_KERNEL aligned_baseline_kernel
+#else
 using BaselineLoopArgs = DelayedBaselineArgs;
 #define UVS_BASELINE_LOOP_KERNEL delayed_baseline_kernel
+#endif
 #elif defined(UVS_CAMERA_MOVING)
 constexpr bool kCameraBelieved = true, kBaselineScenes = true, kBaselineMoving = true;
 using BaselineLoopArgs = MovingBaselineArgs;
@@ -193,11 +215,16 @@ template <int G>
 __device__ __forceinline__ void stage_loop_motions(const MovingBaselineArgs &a, uvs_target_motion *s_mot) {
     stage_motions<G, kLoopThreads>(a.motion, static_cast<long long>(blockIdx.x) * G, a.T, s_mot);
 }
-// The latency of `trial`.  The other four flavours have none.
+// The latency of `trial`.  The first four flavours have none.
 __device__ __forceinline__ int loop_latency(const ALoopArgs &, long long) { return 0; }
 __device__ __forceinline__ int loop_latency(const BLoopArgs &, long long) { return 0; }
 __device__ __forceinline__ int loop_latency(const SLoopArgs &, long long) { return 0; }
 __device__ __forceinline__ int loop_latency(const DelayedBaselineArgs &a, long long trial) { return latency_of(a.latency, trial); }
+// The assumed latency of `trial`.  The first five flavours have none.
+__device__ __forceinline__ int loop_assumed(const ALoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_assumed(const BLoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_assumed(const SLoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_assumed(const AlignedBaselineArgs &a, long long trial) { return latency_of(a.assumed, trial); }
 
 template <int M, int N, int L, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const BaselineLoopArgs A) {
@@ -206,7 +233,8 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
     __shared__ double s_disc[W][kColours * 3];
-    __shared__ double s_q[G][N];                                 // this step's joints, sensor side -> control side
+    constexpr bool ALIGNED = kBaselineAligned;
+    __shared__ double s_q[G][ALIGNED ? kDelaySlots : 1][N];      // this step's joints, sensor side -> control side (ALIGNED: the last nine steps', slot k mod 9)
     __shared__ double s_f[G][M];                                 // this step's features, sensor side -> control side
     __shared__ double s_dq[G][N];                                // this step's command, control side -> sensor side
     __shared__ int s_alive[G];                                   // trial has not FAILed, as of the end of this step
@@ -258,6 +286,10 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     if (etrial >= T) etrial = T - 1;
     double *err_at = (evalid && A.err_log != nullptr) ? A.err_log + etrial * M + sub * R : nullptr;
     double *dq_at = (evalid && sub == 0 && A.dq_log != nullptr) ? A.dq_log + etrial * N : nullptr;
+    int assumed = 0;                                             // ALIGNED: the assumed latency of this lane's trial (a shadow lane: of the one it shadows)
+    if constexpr (ALIGNED) {
+        if (w == 0) assumed = loop_assumed(A, etrial);
+    }
     double ise[R], iae[R], itae[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) ise[r] = iae[r] = itae[r] = 0.0;
@@ -271,7 +303,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
         if (lane < N) {
             advance_joint(lane, k, s_dq[ws], fp.dt, q);
             if (seen && q_at != nullptr) *q_at = q;              // before the sines: where this text measured fastest
-            if (writer) s_q[ws][lane] = q;
+            if (writer) s_q[ws][ALIGNED ? k % kDelaySlots : 0][lane] = q;
             joint_sincos_rows(scene, lane, q, s_sin[w], s_cos[w]);
         }
         __syncthreads();
@@ -296,7 +328,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
         if (w == 0) {
             double qk[N], err[R], cmd[N];
 #pragma unroll
-            for (int j = 0; j < N; ++j) qk[j] = s_q[slot][j];
+            for (int j = 0; j < N; ++j) qk[j] = s_q[slot][ALIGNED ? delayed_step(k, assumed) % kDelaySlots : 0][j];   // ALIGNED: the joints the assumed frame shows
             uvs::Rows<M, N, L> st;
             const int bad = analytical_step<M, N, L>(s_cam[BELIEVED ? slot : 0], fp, qk, [slot](int i) { return s_f[slot][i]; }, sub, st, err, cmd);
             if (alive && bad) {                                  // FAIL at this step; the trial stops

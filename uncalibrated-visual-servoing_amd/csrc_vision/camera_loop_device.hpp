@@ -74,6 +74,21 @@
 // through s_ring[trial slot][disc][k mod 9] (delay_line, vision_device.hpp), written and read by lane 0 of the wavefront that finished
 // detect_pair for that disc -- in the one-trial form each disc still belongs to exactly one wavefront -- between detect_pair and noisy_centre.
 // Occluders, paints and motion are evaluated at step k as before; the ring carries their effect.  No barrier and no exit is added.
+//
+// ALIGNED.  A ninth flavour: a unit that defines UVS_CAMERA_ALIGNED next to the other seven switches (uvs_camera_aligned.hip) sees
+// aligned_frames_kernel(AlignedLoopArgs) with all eight on.  The controller is told a latency: each OUTPUT trial has an ASSUMED latency a (the
+// rule: plant.aligned_regressor_step), read once before the step loop by the estimator-side lanes for their etrial (lanes beyond G L and a
+// padding slot: that of the trial they shadow).  The estimator's regressor at step k is the command of step k - 1 - a, or zeros before there
+// was one; the command integrated into the joints stays dq_{k-1}.  Wavefront 0 keeps the last nine commands per trial slot in
+// s_cmd[slot][k mod 9][N], written by the trial's sub == 0 lane next to the s_dq store and read by the trial's L lanes (and their shadows)
+// before the update: the end-of-step barrier stands between a write and every later read, and for a == 8 the slot read at step k is the one
+// written at step k, after the read in the one wavefront's program order.  The regressor is formed anew in every step, so dq[N] is not
+// live across the step here.  The rings start as zeros (all 256 threads, before the barrier that precedes step 0): for k - 1 - a < 0 the slot
+// (k - 1 - a + 9) mod 9 >= k has not been written yet, so "the zero vector" is a plain read and needs no select.  The six freshly read
+// doubles cost the register allocation 12 to 15 registers against the delayed twin, whose regressor is last step's cmd left where it was
+// -- MCKF at (8,6), four trials per workgroup, spilled 36 B -- so this flavour keeps the error sums where they end up, in this lane's own
+// words of s_sum, updated by the same three operations per step: 3 R doubles fewer per lane, 0 B of scratch in all 22.  No barrier and no
+// exit is added.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -128,6 +143,19 @@ struct DelayedLoopArgs : MovingLoopArgs {
     const int32_t *latency;
 };
 
+// uvs_camera_closed_loop_aligned_f64: the delayed block and the assumed latencies, [T] by output trial or NULL; only aligned_frames_kernel takes it
+struct AlignedLoopArgs : DelayedLoopArgs {
+    const int32_t *assumed;
+};
+
+#ifdef UVS_CAMERA_ALIGNED
+#ifndef UVS_CAMERA_DELAYED
+#error "the aligned flavour is a delayed flavour: define UVS_CAMERA_DELAYED (and UVS_CAMERA_MOVING, UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
+#endif
+constexpr bool kCameraAligned = true;
+#else
+constexpr bool kCameraAligned = false;
+#endif
 #ifdef UVS_CAMERA_DELAYED
 #ifndef UVS_CAMERA_MOVING
 #error "the delayed flavour is a moving flavour: define UVS_CAMERA_MOVING (and UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
@@ -176,7 +204,11 @@ constexpr bool kCameraOccluded = true;
 #else
 constexpr bool kCameraOccluded = false;
 #endif
-#if defined(UVS_CAMERA_DELAYED)
+#if defined(UVS_CAMERA_ALIGNED)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = AlignedLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL aligned_frames_kernel
+#elif defined(UVS_CAMERA_DELAYED)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = DelayedLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL delayed_frames_kernel
@@ -229,14 +261,17 @@ __device__ __forceinline__ Scenes scenes_of(const ScenesLoopArgs &a) { return a.
 // the motions of the launch, or NULL (never called on the other six blocks: MOVING is off there)
 __device__ __forceinline__ const uvs_target_motion *motions_of(const LoopArgs &) { return nullptr; }
 __device__ __forceinline__ const uvs_target_motion *motions_of(const MovingLoopArgs &a) { return a.motion; }
-// the latencies of the launch, or NULL (never called on the other seven blocks: DELAYED is off there)
+// the latencies of the launch, or NULL (never called on the first seven blocks: DELAYED is off there)
 __device__ __forceinline__ const int32_t *latencies_of(const LoopArgs &) { return nullptr; }
 __device__ __forceinline__ const int32_t *latencies_of(const DelayedLoopArgs &a) { return a.latency; }
+// the assumed latencies of the launch, or NULL (never called on the first eight blocks: ALIGNED is off there)
+__device__ __forceinline__ const int32_t *assumed_of(const LoopArgs &) { return nullptr; }
+__device__ __forceinline__ const int32_t *assumed_of(const AlignedLoopArgs &a) { return a.assumed; }
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
     constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld, PAINT = kCameraPainted, SCENES = kCameraScenes;
-    constexpr bool MOVING = kCameraMoving, DELAYED = kCameraDelayed;
+    constexpr bool MOVING = kCameraMoving, DELAYED = kCameraDelayed, ALIGNED = kCameraAligned;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -258,6 +293,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     __shared__ uvs_camera s_cam[SCENES ? G : 1];                 // SCENES: the cameras that render the workgroup's trials, staged once below
     __shared__ uvs_target_motion s_mot[MOVING ? G : 1];          // MOVING: the motions of those trials, staged next to them
     __shared__ DelayCell s_ring[DELAYED ? G : 1][DELAYED ? kColours : 1][DELAYED ? kDelaySlots : 1];   // DELAYED: the last nine detections of every disc
+    __shared__ double s_cmd[ALIGNED ? G : 1][ALIGNED ? kDelaySlots : 1][ALIGNED ? N : 1];   // ALIGNED: the last nine commands of every trial
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -347,6 +383,12 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     double *err_at = (estore && A.err_log != nullptr) ? A.err_log + etrial * M + sub * R : nullptr;
     double *kappa_at = (estore && A.kappa_log != nullptr) ? A.kappa_log + etrial * M + sub * R : nullptr;
     double *dq_at = (estore && sub == 0 && A.dq_log != nullptr) ? A.dq_log + etrial * N : nullptr;
+    int assumed = 0;                                             // ALIGNED: the assumed latency of this lane's trial (a shadow lane: of the one it shadows)
+    if constexpr (ALIGNED) {
+        if (w == 0) assumed = latency_of(assumed_of(A), etrial);
+        // the rings start as zeros: "no such step" is then a slot that has not been written.  The step's first barrier is before the first read.
+        for (int i = threadIdx.x; i < G * kDelaySlots * N; i += kLoopThreads) (&s_cmd[0][0][0])[i] = 0;
+    }
     uvs::Rows<M, N, L> st;
     st.init_cov();
     double f_prev[R], des[R], dq[N], ise[R], iae[R], itae[R];
@@ -360,6 +402,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         }
         f_prev[r] = A.f0[esrc * M + row];
         ise[r] = iae[r] = itae[r] = 0.0;
+        if constexpr (ALIGNED) {                                 // the sums are kept where they end up, s_sum: the ring's reads take their registers
+            if (w == 0 && owner) s_sum[slot][0][row] = s_sum[slot][1][row] = s_sum[slot][2][row] = 0.0;
+        }
 #pragma unroll
         for (int j = 0; j < N; ++j) st.x[r][j] = A.x0[(esrc * M + row) * N + j];
     }
@@ -447,6 +492,12 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
                 sigma = uvs::bandwidth(fp, k);
                 gain = fp.gain;
             }
+            if constexpr (ALIGNED) {                             // the regressor: the command of step k - 1 - assumed, or zeros where there is none
+                const int kr = aligned_regressor_step(k, assumed);  // >= -kDelaySlots.  Negative: slot kr + 9 >= k has not been written: zeros
+                const double *told = s_cmd[slot][(kr + kDelaySlots) % kDelaySlots];
+#pragma unroll
+                for (int j = 0; j < N; ++j) dq[j] = told[j];
+            }
             st.template update<METHOD_T>(fpe, z, dq, sigma, kap);   // h = the previous command; zero on k = 0
             const int bad = st.any_nonfinite();
             if (alive && bad) {                                  // FAIL at this step; the trial stops
@@ -481,20 +532,34 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
                     if (err_at != nullptr) err_at[r] = err[r];
                     if (kappa_at != nullptr) kappa_at[r] = kap[r];
                     const double ae = fabs(err[r]);              // stats_kernel's sums, in its order over k
-                    ise[r] = fma(err[r], err[r], ise[r]);
-                    iae[r] += ae;
-                    itae[r] = fma(t, ae, itae[r]);
+                    if constexpr (ALIGNED) {                     // the same three operations, on this lane's own words of s_sum
+                        double *sum = &s_sum[slot][0][sub * R + r];
+                        sum[0] = fma(err[r], err[r], sum[0]);
+                        sum[M] += ae;
+                        sum[2 * M] = fma(t, ae, sum[2 * M]);
+                    } else {
+                        ise[r] = fma(err[r], err[r], ise[r]);
+                        iae[r] += ae;
+                        itae[r] = fma(t, ae, itae[r]);
+                    }
                 }
                 if (dq_at != nullptr) {
 #pragma unroll
                     for (int j = 0; j < N; ++j) dq_at[j] = cmd[j];
                 }
             }
+            if constexpr (!ALIGNED) {
 #pragma unroll
-            for (int j = 0; j < N; ++j) dq[j] = cmd[j];
+                for (int j = 0; j < N; ++j) dq[j] = cmd[j];
+            }
             if (owner && sub == 0) {
 #pragma unroll
                 for (int j = 0; j < N; ++j) s_dq[slot][j] = cmd[j];
+                if constexpr (ALIGNED) {                         // slot k mod 9 of the trial's ring; the end-of-step barrier comes before every later read
+                    double *cell = s_cmd[slot][k % kDelaySlots];
+#pragma unroll
+                    for (int j = 0; j < N; ++j) cell[j] = cmd[j];
+                }
                 s_alive[slot] = (alive && !evoid) ? 1 : 0;
             }
         }
@@ -514,11 +579,13 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     }
 
     if (w == 0 && owner) {
+        if constexpr (!ALIGNED) {                                // ALIGNED: they are there already
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            s_sum[slot][0][sub * R + r] = ise[r];
-            s_sum[slot][1][sub * R + r] = iae[r];
-            s_sum[slot][2][sub * R + r] = itae[r];
+            for (int r = 0; r < R; ++r) {
+                s_sum[slot][0][sub * R + r] = ise[r];
+                s_sum[slot][1][sub * R + r] = iae[r];
+                s_sum[slot][2][sub * R + r] = itae[r];
+            }
         }
         if (evalid && sub == 0) {
             A.status[etrial] = evoid ? UVS_STATUS_FAIL : status;

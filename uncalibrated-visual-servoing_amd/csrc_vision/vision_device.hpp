@@ -1,4 +1,4 @@
-// Device code shared by all fourteen translation units of libuvs_vision.so (uvs_vision.hip directly, the thirteen loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
+// Device code shared by all sixteen translation units of libuvs_vision.so (uvs_vision.hip directly, the fifteen loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
 // forms its callers need, the disc geometry of the synthetic camera with its occluders and their paints, and the DH chain.  The summation order of the phase 2 is a contract
 // (see centre_of_mass): every unit that sums mask pixels goes through wave_partial and ColourSum, so they all give the same bits.
 #pragma once
@@ -600,6 +600,11 @@ __device__ __forceinline__ int clamped_latency(int32_t d) { return d < 0 ? 0 : (
 __device__ __forceinline__ int delayed_step(int k, int d) { return k - d > 0 ? k - d : 0; }
 // the latency of `trial`, clamped; NULL: none
 __device__ __forceinline__ int latency_of(const int32_t *latency, long long trial) { return latency != nullptr ? clamped_latency(latency[trial]) : 0; }
+
+// THE rule of the assumed-latency operand (uvs_vision.h, ASSUMED LATENCY; plant.aligned_regressor_step): the step whose
+// command is the estimator's regressor at step k when the controller assumes latency a (clamped like d); negative: the zero vector.  The
+// law's joints at step k are those of delayed_step(k, a).
+__device__ __forceinline__ int aligned_regressor_step(int k, int a) { return k - 1 - a; }
 
 // The delay line of ONE disc of one trial: the detections of the last kDelaySlots steps, slot k mod kDelaySlots.  A cell is a ColourSum as
 // three 64-bit integer words -- the bits of the two sums, and the count -- moved through plain integer pointers and replaced IN PLACE,

@@ -831,27 +831,29 @@ def _motion_operand(checked, dev):
 MAX_LATENCY = 8                                                     # UVS_CAMERA_MAX_LATENCY of include/uvs_vision.h (plant.MAX_LATENCY)
 
 
-def _check_latency(latency, T, who):
+def _check_latency(latency, T, who, name='latency'):
     """What can be said of a ``latency=`` for T output trials on the host alone, before any device work: ValueError, or the operand --
     None, or a host int32 array (T,) of values in 0 .. MAX_LATENCY.  ``latency``: None, an integer for every trial, or T integers (a
-    sequence, an array or an integer tensor, which is brought to the host)."""
+    sequence, an array or an integer tensor, which is brought to the host).  ``name``: what the refusals call the argument
+    ('assumed_latency' has the same rule and the same messages)."""
+    many = 'latencies' if name == 'latency' else f'{name} values'
     import torch                                                     # not _torch(): these refusals need no GPU
     if latency is None:
         return None
     if torch.is_tensor(latency):
         if latency.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64) or latency.is_complex():
-            raise ValueError(f'{who}: latency is integers, control periods, got {latency.dtype}')
+            raise ValueError(f'{who}: {name} is integers, control periods, got {latency.dtype}')
         latency = latency.detach().cpu().numpy()
     try:
         a = np.asarray(latency)
     except Exception as exc:                                         # ragged lists
-        raise ValueError(f'{who}: latency is an integer or ({T},) integers') from exc
+        raise ValueError(f'{who}: {name} is an integer or ({T},) integers') from exc
     if a.dtype.kind not in 'iu' or a.ndim > 1:
-        raise ValueError(f'{who}: latency is an integer or ({T},) integers, control periods, got {a.dtype} {a.shape}')
+        raise ValueError(f'{who}: {name} is an integer or ({T},) integers, control periods, got {a.dtype} {a.shape}')
     if a.ndim == 1 and a.shape[0] != T:
-        raise ValueError(f'{who}: {a.shape[0]} latencies for {T} trials')
+        raise ValueError(f'{who}: {a.shape[0]} {many} for {T} trials')
     if a.size and (a.min() < 0 or a.max() > MAX_LATENCY):
-        raise ValueError(f'{who}: latency must lie in 0 .. {MAX_LATENCY} control periods, got {int(a.min())} .. {int(a.max())}')
+        raise ValueError(f'{who}: {name} must lie in 0 .. {MAX_LATENCY} control periods, got {int(a.min())} .. {int(a.max())}')
     return np.broadcast_to(a.astype(np.int32), (T,)).copy()
 
 
@@ -993,7 +995,7 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=
 
 
 def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None, scenes=None, motion=None,
-                                   latency=None):
+                                   latency=None, assumed=None):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
     ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models.
     ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none).  ``hold`` > 0 (stepwise alone): a third launch per
@@ -1004,7 +1006,10 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     (the one launch: uvs_camera_believed_loop_moving_f64; stepwise: uvs_camera_features_moving_f64); the law's model does not.
     ``latency``: None, or the pointer of ``_latency_operand`` next to ``scenes`` -- the detector is handed the frame of step max(k - d, 0)
     (the one launch: uvs_camera_believed_loop_delayed_f64, with or without ``motion``; stepwise: uvs_delay_features_f64 behind the
-    features call); the law's joints are the current ones."""
+    features call); the law's joints are the current ones.
+    ``assumed``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the ASSUMED latencies next to ``scenes`` -- the joints the
+    law is handed at step k are those of step max(k - a, 0) (the one launch: uvs_camera_believed_loop_aligned_f64, with or without
+    ``latency`` and ``motion``; stepwise: per trial that row of the q log, gathered by torch indexing -- a copy, no arithmetic)."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -1020,7 +1025,10 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         stats = torch.empty((T, 3), **f64)
         pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
         outputs = (ptr('q'), ptr('f'), ptr('dq'), ptr('err'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
-        if latency is not None:
+        if assumed is not None:
+            rc = _vision.lib().uvs_camera_believed_loop_aligned_f64(C.byref(fp), *scenes, motion, latency, assumed[0], T, *believed, q0, noise_ptr,
+                                                                    *outputs)
+        elif latency is not None:
             rc = _vision.lib().uvs_camera_believed_loop_delayed_f64(C.byref(fp), *scenes, motion, latency, T, *believed, q0, noise_ptr, *outputs)
         elif motion is not None:
             rc = _vision.lib().uvs_camera_believed_loop_moving_f64(C.byref(fp), *scenes, motion, T, *believed, q0, noise_ptr, *outputs)
@@ -1047,12 +1055,18 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         row['held'] = (held_log.data_ptr(), held_log.stride(0) * held_log.element_size())
     at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
     noise_row = 0 if noise is None else noise.stride(0) * 8
+    if assumed is not None:
+        told, trials = assumed[1].to(torch.int64), torch.arange(T, device=dev)
     for k in range(K):
         q_prev, dq_prev = (q0, None) if k == 0 else (at('q', k - 1), at('dq', k - 1))
         extra = (None if k == 0 else at('f', k - 1), at('held', k)) if hold else ()
         _vision.check(features(k, q_prev, dq_prev, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k), at('pixels', k),
                                *extra))
-        _vision.check(step(at('q', k), at('f', k), at('dq', k), at('err', k), None, at('status', k), stream))
+        joints = at('q', k)
+        if assumed is not None:                                      # the joints the assumed frame shows: row max(k - a_t, 0) of the q log, per trial
+            told_q = log['q'][(k - told).clamp_(min=0), trials]
+            joints = told_q.data_ptr()
+        _vision.check(step(joints, at('f', k), at('dq', k), at('err', k), None, at('status', k), stream))
     return _reduce_camera_logs(fp, log, status_log, pixel_log, want, held_log)
 
 
@@ -1121,7 +1135,7 @@ def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
 
 
 def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0, paints=None, scenes=None,
-                              motion=None, latency=None):
+                              motion=None, latency=None, assumed=None):
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
     then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
     ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
@@ -1136,7 +1150,9 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     ``motion``: None, or the (pointer, packed tensor) of ``_motion_operand`` for the T output trials next to ``scenes`` -- the launch is
     then uvs_camera_closed_loop_moving_f64, and f0 comes from the step-0 frame, where s(0) applies.
     ``latency``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the T output trials next to ``scenes`` -- the launch is
-    then uvs_camera_closed_loop_delayed_f64, with or without ``motion``; f0 still comes from the step-0 frame."""
+    then uvs_camera_closed_loop_delayed_f64, with or without ``motion``; f0 still comes from the step-0 frame.
+    ``assumed``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the ASSUMED latencies of the T output trials next to
+    ``scenes`` -- the launch is then uvs_camera_closed_loop_aligned_f64, with or without ``latency`` and ``motion``."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -1172,7 +1188,10 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
         held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
         rest = (T, None if tp is None else C.byref(tp), None if occ is None else occ[0], None if paint is None else paint[0],
                 0 if occ is None else occ[1], hold, *operands[:-1], None if held is None else held.data_ptr(), operands[-1])
-        if latency is not None:
+        if assumed is not None:
+            rc = _vision.lib().uvs_camera_closed_loop_aligned_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0],
+                                                                  None if latency is None else latency[0], assumed[0], *rest)
+        elif latency is not None:
             rc = _vision.lib().uvs_camera_closed_loop_delayed_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0], latency[0],
                                                                   *rest)
         elif motion is None:
@@ -1227,7 +1246,7 @@ def _gather_by_source(q_start, noise, x0, trial_params):
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
                        believed_index=None, trial_params=None, occluders=None, hold=0, occluder_colours=None, cameras=None, camera_index=None,
-                       target_motion=None, motion_window=None, latency=None):
+                       target_motion=None, motion_window=None, latency=None, assumed_latency=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -1333,7 +1352,20 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     ValueError it is).  fused=False, for the estimators and ANALYTICAL alike, is per step the features call without noise into a log of
     sensed rows, uvs_delay_features_f64, then the hold call and the step as before; the two return the same bits.  Next to
     trial_params['source'] the inputs are gathered by source before the launch, as next to occluders.  ValueErrors before any device
-    work, after the refusals above: a value outside 0 .. ``MAX_LATENCY``, a wrong length, non-integers."""
+    work, after the refusals above: a value outside 0 .. ``MAX_LATENCY``, a wrong length, non-integers.
+    ``assumed_latency``: ASSUMED LATENCY, per OUTPUT trial -- the controller is TOLD a latency a, in the same form and range as ``latency``
+    and independent of it: a != latency is the mismatch experiment, and a > 0 without any latency is legal.  Estimators: the regressor
+    of step k is the command of step k - 1 - a, or the zero vector where there is none (the rule: ``plant.aligned_regressor_step``;
+    include/uvs_vision.h, ASSUMED LATENCY) -- the command that caused f_k - f_{k-1} when the latency is a; the command integrated into
+    the joints stays dq_{k-1}.  ANALYTICAL (calibrated or believed): the joints the law is handed are q_{max(k - a, 0)}
+    (``plant.delayed_step(k, a)``), so its Jacobian, depths and interaction matrix are those of the pose the assumed frame shows; the
+    features stay the reported row, the 'q' log stays current.  None (the default) is the call without the argument: its routes, its
+    entry points, its bits; zeros give the same bits through the aligned kernels.  It combines with everything ``latency`` combines
+    with, in the same way: fused=True is ONE launch (uvs_camera_closed_loop_aligned_f64, or uvs_camera_believed_loop_aligned_f64 for
+    ANALYTICAL, where occluders or hold > 0 stay the ValueError they are); fused=False hands the step call, per trial, row k - 1 - a of
+    the 'dq' log (or zeros) as dq_prev, or row max(k - a, 0) of the 'q' log as joints, gathered by torch indexing; the two return the
+    same bits.  Next to trial_params['source'] it is by output trial.  ValueErrors before any device work, after the refusals above,
+    latency's included: the same as for ``latency``, naming assumed_latency."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
@@ -1396,14 +1428,17 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     if latency is not None and trial_params is not None and trial_params.get('source') is not None:
         n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
     delays = _check_latency(latency, n_out, 'camera_closed_loop')    # None, or (T,) int32 on the host, by output trial
-    if delays is not None and cameras is None and not nominal:       # the nominal camera stands in as the one scene here too
+    if assumed_latency is not None and latency is None and trial_params is not None and trial_params.get('source') is not None:
+        n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
+    tolds = _check_latency(assumed_latency, n_out, 'camera_closed_loop', 'assumed_latency')   # likewise
+    if (delays is not None or tolds is not None) and cameras is None and not nominal:   # the nominal camera stands in as the one scene here too
         if fp.n != 6:
             raise ValueError(f'camera_closed_loop: the camera-latency kernels are built for the six-joint arms of this project, not for {fp.n} joints')
         nominal = True
     if fused and not getattr(q_start, 'is_cuda', False):
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     torch = _torch()
-    if (occluders is not None or cameras is not None or motion is not None or delays is not None) and trial_params is not None \
+    if (occluders is not None or cameras is not None or motion is not None or delays is not None or tolds is not None) and trial_params is not None \
             and trial_params.get('source') is not None:
         q_start, noise, x0, trial_params = _gather_by_source(q_start, noise, x0, trial_params)
     K, m, n = fp.steps, fp.m, fp.n
@@ -1425,6 +1460,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     if mot is not None:
         scene_kw['target_motion'] = mot[1]
     lat = None if delays is None else _latency_operand(delays, dev)  # (pointer, int32 tensor) of the T output trials
+    told = None if tolds is None else _latency_operand(tolds, dev)   # likewise, the assumed latencies
     if analytical:
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -1439,7 +1475,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
             *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
         return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold, paint=paint,
                                               scenes=None if scenes is None else scenes[0], motion=None if mot is None else mot[0],
-                                              latency=None if lat is None else lat[0])
+                                              latency=None if lat is None else lat[0], assumed=told)
     if believed is not None or (scenes is not None and not nominal and x0 is None):  # an estimator that starts from a model in memory: the believed one, or
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)                           # its own scene; the rest is the x0= path
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -1453,7 +1489,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes, mot, lat)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes, mot, lat, told)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -1483,7 +1519,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
         return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2], hold,
-                                         None if paint is None else paint[1], scenes, mot, lat)
+                                         None if paint is None else paint[1], scenes, mot, lat, told)
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
@@ -1499,12 +1535,19 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         row['held'] = (held_log.data_ptr(), held_log.stride(0) * held_log.element_size())
     at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
     noise_row = 0 if noise is None else noise.stride(0) * 8
+    if told is not None:
+        assumed, trials = told[1].to(torch.int64), torch.arange(T, device=dev)
     for k in range(K):
         q_prev, dq_prev, f_old = (q0, None, f0.data_ptr()) if k == 0 else (at('q', k - 1), at('dq', k - 1), at('f', k - 1))
         extra = (None if k == 0 else f_old, at('held', k)) if hold else ()
         _vision.check(features(k, q_prev, dq_prev, at('q', k), None if noise is None else noise_ptr + k * noise_row, at('f', k), at('pixels', k),
                                *extra))
-        _lib.check(step(fp_ref, T, X.data_ptr(), P.data_ptr(), at('f', k), f_old, dq_zero.data_ptr() if k == 0 else dq_prev, int(k == 0), k,
+        regressor = dq_zero.data_ptr() if k == 0 else dq_prev
+        if told is not None and k > 0:                               # per trial row k - 1 - a_t of the dq log, or the zero row: a copy
+            rows = k - 1 - assumed
+            told_dq = torch.where((rows >= 0)[:, None], log['dq'][rows.clamp(min=0), trials], dq_zero)
+            regressor = told_dq.data_ptr()
+        _lib.check(step(fp_ref, T, X.data_ptr(), P.data_ptr(), at('f', k), f_old, regressor, int(k == 0), k,
                         at('dq', k), at('err', k), at('kappa', k), at('status', k), stream))
     return _reduce_camera_logs(fp, log, status_log, pixel_log, want, held_log)
 

@@ -451,6 +451,19 @@ def delayed_step(k, d):
     return max(k - min(max(d, 0), MAX_LATENCY), 0)
 
 
+def aligned_regressor_step(k, a):
+    """The step whose command is the estimator's regressor at step ``k`` >= 0 when the controller assumes a camera latency ``a``, or -1
+    for "the zero vector" -- the numpy statement of the rule of include/uvs_vision.h (ASSUMED LATENCY) that every aligned kernel is held
+    to: k - 1 - clamp(a, 0, MAX_LATENCY) where that is >= 0, in Python integers.  At latency d the difference f_k - f_{k-1} the
+    estimator sees was caused by the command of step k - 1 - d; an assumed latency pairs it with that command.  Only the regressor moves:
+    the command integrated into the joints stays dq_{k-1}.  The zero vector goes through the update with h = 0 that step 0 always ran.
+    The law's counterpart is ``delayed_step(k, a)``: the step whose joints the calibrated or believed law is handed."""
+    k, a = int(k), int(a)
+    if k < 0:
+        raise ValueError('k must be >= 0')
+    return max(k - 1 - min(max(a, 0), MAX_LATENCY), -1)
+
+
 class LinearPlant:
     """Consistent linearised camera f = f0 + J (q - q0) for shapes without a DH model (BASELINE config 5: m = 32, n = 7;
     a 7-joint arm would be redundant for a 6-DoF camera pose and leave the feature Jacobian rank 6).  J, f0, q0 are uploaded
