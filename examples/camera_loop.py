@@ -50,8 +50,13 @@ the calibrated law; prints the median ISE / IAE / ITAE, the FAIL count and the m
 (engine.camera_closed_loop(latency=, assumed_latency=)) -- the estimators' regressor becomes the command of step k - 1 - a, the law's joints
 those of step max(k - a, 0) -- told (a > 0) and untold (a = 0) on the same starts and noise.  Prints the median ISE and the FAILs with their
 median k_done per (d, a) cell: the diagonal is what telling recovers, the rest how wrong the assumed latency may be.
+--latency --predict lets the control law predict the features over the latency: LATENCIES x HORIZONS prediction horizons x the trials in
+ONE launch per method (engine.camera_closed_loop(latency=, assumed_latency=, predict=)), every controller told the true latency (a = d) --
+the estimators' law acts on f + X_k (dq_{k-1} + ... + dq_{k-p}), the calibrated law on f + (h(q_k) - h(q_{k-p})).  Prints per (d, p) cell
+the FAIL count, the median ISE as returned -- it is on the PREDICTED error, so it is not comparable across p -- and a "true" ISE recomputed
+from the q log with engine.camera_features at the logged joints against the target, which is.
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving] [--latency [--told]]"""
+       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving] [--latency [--told | --predict]]"""
 import argparse
 import os
 import sys
@@ -433,6 +438,62 @@ def told_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed=0, l
     return lines
 
 
+HORIZONS = (0, 1, 2, 3, 4)                                           # control periods the law predicts over
+
+
+def predicted_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed=0, latencies=LATENCIES, horizons=HORIZONS):
+    """The true-latency x prediction-horizon grid as a list of lines: len(latencies) x len(horizons) x trials in ONE launch per method
+    (engine.camera_closed_loop(latency=, assumed_latency=, predict=)), over the same starts and noise in every cell; every controller is
+    told the true latency (a = d), p = 0 is the controller that does not predict.  Per (d, p) cell: the trials that FAILed / the median
+    ISE as returned, which is on the predicted error and so not comparable across p / the median "true" ISE, recomputed from the q log
+    with engine.camera_features at the logged joints (no noise, no latency) against the target by the same sums -- both medians over the
+    trials that ran to the end.  No finding is drawn here: the table is what the experiment prints."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    methods = tuple(dict.fromkeys((method, 'KF', 'ANALYTICAL')))
+    fps = {name: uvs.engine.make_params(8, 6, name, 10.0, False, 0.05, 15.0, 0.2, desired, True) for name in methods}
+    K = fps[method].steps
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    noise = rng.standard_normal((K, trials, 8)) * sigma
+    cells = [(d, p) for d in latencies for p in horizons]
+    n = len(cells)
+    q0_d = torch.as_tensor(np.tile(q0, (n, 1)), device='cuda')       # the same starts and the same noise in every cell
+    noise_d = torch.as_tensor(np.tile(noise, (1, n, 1)), device='cuda')
+    latency = np.repeat(np.array([d for d, _ in cells], np.int64), trials)
+    ahead = np.repeat(np.array([p for _, p in cells], np.int64), trials)
+    target = torch.as_tensor(desired, device='cuda')
+    lines = [f'{len(latencies)} camera latencies x {len(horizons)} prediction horizons x {trials} trials of {K} steps in one launch per method, '
+             f'white noise {sigma} px, every controller told its latency (a = d); per cell: FAILs / median ISE as returned (on the predicted '
+             f'error) / median true ISE (from the q log), over the trials that ran to the end']
+    for name, fp in fps.items():
+        kw = dict(radius=radius, fused=True, want=('err', 'q'), latency=latency, assumed_latency=latency, predict=ahead)
+        if name != 'ANALYTICAL':
+            kw['guess'] = 'device'
+        out = uvs.engine.camera_closed_loop(fp, plant, q0_d, noise_d, **kw)
+        sums = torch.zeros((n * trials, 8), dtype=torch.float64, device='cuda')
+        for k in range(K):                                           # the features the camera would show at the logged joints, without noise
+            err = uvs.engine.camera_features(plant, out['q'][k], radius=radius) - target
+            sums += err * err
+        true_ise = sums.norm(dim=1).cpu().numpy()                    # the norm over the features of the per-feature sums, as the stats are
+        torch.cuda.synchronize()
+        status, stats = out['status'].cpu().numpy(), out['stats'].cpu().numpy()
+        lines.append(f'{name + ": latency | horizon":28s}' + ''.join(f'{"p = " + str(p):>30s}' for p in horizons))
+        for i, d in enumerate(latencies):
+            row = f'{"d = " + str(d):28s}'
+            for j in range(len(horizons)):
+                c = i * len(horizons) + j
+                rows = slice(c * trials, (c + 1) * trials)
+                done = status[rows] == 0
+                ise = np.median(stats[rows][done, 0]) if done.any() else np.nan
+                true = np.median(true_ise[rows][done]) if done.any() else np.nan
+                row += f'{int((~done).sum()):4d} /{ise:11.1f} /{true:11.1f}'
+            lines.append(row)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -459,6 +520,9 @@ def main():
     ap.add_argument('--told', action='store_true',
                     help='with --latency: the controller is told a latency -- latencies 0 .. 4 x assumed latencies 0 .. 4 x the trials in one '
                          'launch per method, told and untold on the same starts and noise')
+    ap.add_argument('--predict', action='store_true',
+                    help='with --latency: the law predicts the features over the latency -- latencies 0 .. 4 x prediction horizons 0 .. 4 x the '
+                         'trials in one launch per method, every controller told its latency; FAILs, the ISE as returned and a true ISE from the q log')
     args = ap.parse_args()
     import torch
     import uvs_amd as uvs
@@ -466,6 +530,11 @@ def main():
         ap.error('--hold goes with --occlusion')
     if args.told and not args.latency:
         ap.error('--told goes with --latency')
+    if args.predict and (not args.latency or args.told):
+        ap.error('--predict goes with --latency, and not with --told')
+    if args.latency and args.predict:
+        print('\n'.join(predicted_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
+        return
     if args.latency and args.told:
         print('\n'.join(told_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
         return

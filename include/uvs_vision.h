@@ -634,6 +634,54 @@ int uvs_camera_believed_loop_aligned_f64(const struct uvs_filter_params *fp, con
                                          const double *noise, double *q_log, double *f_log, double *dq_log, double *err_log, int32_t *status,
                                          int32_t *k_done, double *stats, int32_t *pixels, void *stream);
 
+/*
+ * FEATURE PREDICTION: the control law predicts the features over the camera latency.  Above, an assumed latency repairs the MODEL, but the
+ * law still servoes on a feature row that is d steps old.  Below each OUTPUT trial also carries a prediction HORIZON p, in control periods,
+ * independent of its latency d and its assumed latency a: p != d is the mismatch experiment, and p > 0 without any latency is legal.  The
+ * law acts on the reported row advanced by what the commands issued since that frame must have done to it (a predictor in the Smith form).
+ * The rule (plant.prediction_steps states the steps once in numpy; every kernel below is held to it bit for bit):
+ *   predict [T] int32 by output trial, in device (or pinned host) memory, directly after `assumed`; NULL = none.  The device uses
+ *     clamp(p, 0, UVS_CAMERA_MAX_LATENCY): the rule is total and the operand is not validated.
+ *   The steps whose commands count at step k, newest first: k - 1, k - 2, ..., max(k - p, 0).
+ *   Estimators, at step k after the update and before the control law:
+ *     1. s = 0, then s += cmd_{k-i} for i = 1 .. p in that order; a term with k - i < 0 is the zero vector (s is never -0.0).
+ *     2. for each row r: acc_r = sum_j X_k[r][j] s[j] as acc = fma(X_k[r][j], s[j], acc) from acc = 0 with j ascending -- the form of the
+ *        update's own dot products -- on the X just updated.
+ *     3. f^_r = f_r + acc_r, one rounded add; err_r = f^_r - desired_r.
+ *     X absorbs t_s (z = X dq), so X sum dq is the feature displacement between the frame shown and now; for k < p the frame shown is
+ *     frame 0, so dropping the missing terms is exact.  The control law, the err log and the three error sums see this err.  Everything
+ *     else is the text above: z and f_prev come from the reported row, kappa from the innovation, the f log is the reported row; the hold
+ *     rule, FAIL, the regressor (aligned to a) and the command integrated into the joints are unchanged.
+ *   Calibrated and believed law: f^ = f_reported + (h(q_k) - h(q_{max(k - p, 0)})), two rounded operations per component, the difference
+ *     first.  h(q) is the (u, v) uvs_camera_project_f64 gives for the law's own model at joints q; the model's points do not move.  The
+ *     law is handed f^ as its feature row and is otherwise untouched: the interaction matrix is evaluated at the predicted pixels, err and
+ *     the sums are f^ - f*, the joints it is handed stay q_{max(k - a, 0)}, the f log stays the reported row.  A non-finite f^ FAILs the
+ *     trial through the check that is there.
+ * The two loops have their *_aligned_* namesake's operands in its order with `predict` directly after `assumed`, its refusals in their
+ * order, all before the first HIP call; T == 0 returns UVS_OK and launches nothing.  The estimator loop forms s for the next step from its
+ * ring of commands where the command is written; the baseline loop keeps h at the joints of the last UVS_CAMERA_MAX_LATENCY + 1 steps in an
+ * LDS ring, written once per step by the projection kernel's text.  No barrier and no exit is added.  The stepwise baseline loop calls
+ * uvs_camera_project_f64 (or its scenes namesake) on rows k and max(k - p, 0) of the q log and applies the two operations.
+ * Bit for bit: (a) predict == NULL, or all zeros, gives the bits of the aligned namesake; (b) a trial of a launch that mixes (d, a, p)
+ * triples has the bits of the uniform launch at its own triple; (c) the baseline's one launch has the stepwise loop's bits; (d) padding
+ * wavefronts and shadow lanes read the horizon of the trial they shadow and store nothing; (e) void trials stay void; (f) values outside
+ * 0 .. UVS_CAMERA_MAX_LATENCY are clamped on the device.
+ * Built: what the aligned namesakes build, each in both workgroup forms with 0 B of scratch memory.
+ */
+int uvs_camera_closed_loop_predicted_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                         const uvs_target_motion *motion, const int32_t *latency, const int32_t *assumed,
+                                         const int32_t *predict, int64_t T, const uvs_camera_trial_params *tp, const uvs_occluder *occ,
+                                         const int32_t *paint, int32_t n_occ, int32_t hold, const double *q_start, const double *noise,
+                                         const double *x0, const double *f0, double *q_log, double *f_log, double *dq_log, double *err_log,
+                                         double *kappa_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, int32_t *held,
+                                         void *stream);
+int uvs_camera_believed_loop_predicted_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                           const uvs_target_motion *motion, const int32_t *latency, const int32_t *assumed,
+                                           const int32_t *predict, int64_t T, const uvs_camera *believed, int64_t n_believed,
+                                           const int32_t *believed_index, const double *q_start, const double *noise, double *q_log,
+                                           double *f_log, double *dq_log, double *err_log, int32_t *status, int32_t *k_done, double *stats,
+                                           int32_t *pixels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

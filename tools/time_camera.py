@@ -122,7 +122,20 @@ x 299 steps, white noise 0.3 px --
   (ay25) the baseline over the 25 cells x 64 trials in one launch
       -- (av) is asserted to have the bits of (dv), (ay) those of (dy), (aw) those of (ax) and (az) trial for trial, before anything is timed.
       Then the table of examples/camera_loop.py --latency --told.
-usage: tools/time_camera.py --aligned [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --aligned [--parent-lib=PATH] [out.txt]
+
+With --predicted only the feature-prediction pixel loops are timed, into profiles/camera_predicted_timing.txt (or the path given): GMCKF,
+1 024 trials x 299 steps, white noise 0.3 px --
+  (av) the aligned loop with latency = assumed = NULL, (ay) the aligned baseline loop likewise, each also through the parent's library,
+      twice, when --parent-lib names it;
+  (pv) (av)'s trials through predicted_frames_kernel with latency = assumed = predict = NULL, (py) (ay)'s through predicted_baseline_kernel:
+      the ratio against the parent's (av) and (ay) is printed next to the parent's own two-run spread; nothing is gated;
+  (a4) the aligned loop at d = a = 4, (p4) the predicted loop at d = a = p = 4, (ay4) and (py4) the baseline's likewise;
+  (pw) 5 latencies x 5 horizons (examples/camera_loop.py --latency --predict) x 64 trials in ONE launch, (px) the same as 25 launches of
+      64 trials, one per cell; (py25) the baseline over the 25 cells in one launch, (pz25) that stepwise
+      -- (pv) is asserted to have the bits of (av), (py) those of (ay), (pw) those of (px) trial for trial, (py25) those of (pz25), before
+      anything is timed.  Then the table of examples/camera_loop.py --latency --predict.
+usage: tools/time_camera.py --predicted [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -140,9 +153,10 @@ SCENES = '--scenes' in sys.argv[1:]
 MOVING = '--moving' in sys.argv[1:]
 DELAYED = '--delayed' in sys.argv[1:]
 ALIGNED = '--aligned' in sys.argv[1:]
+PREDICTED = '--predicted' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving', '--delayed', '--aligned') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_aligned_timing.txt' if ALIGNED else 'camera_latency_timing.txt' if DELAYED else 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving', '--delayed', '--aligned', '--predicted') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_predicted_timing.txt' if PREDICTED else 'camera_aligned_timing.txt' if ALIGNED else 'camera_latency_timing.txt' if DELAYED else 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -1317,6 +1331,153 @@ def aligned_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def predicted_section():
+    """(av), (ay) against the parent's; (pv) .. (pz25): see the module docstring."""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    import camera_loop as example
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T = 299, 1024
+    LAT, AHEAD, PER = example.LATENCIES, example.HORIZONS, 64
+    cells = [(d, p) for d in LAT for p in AHEAD]
+    TL = len(cells) * PER
+    fp = uvs.engine.make_params(8, 6, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    fa = uvs.engine.make_params(8, 6, 'ANALYTICAL', 10.0, False, 0.05, 15.0, 0.2, DESIRED)
+    assert fp.steps == K
+    loop = uvs.engine.camera_closed_loop
+    say(f'# tools/time_camera.py --predicted on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in (the nominal model\'s guess); the latencies {LAT} x the horizons '
+        f'{AHEAD} x {PER} trials = {TL} trials, every controller told its latency')
+    say('# host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, 8)) * 0.3, device='cuda')
+    x0 = uvs.engine.camera_guess(plant, q_d, uvs.engine.camera_features(plant, q_d))
+    one = uvs.engine.camera_scenes(plant)
+    nominal = uvs.engine.believed_models(plant)
+    cam = plant.to_camera(uvs.plant.DISC_RADIUS)
+    scene_one = (one.data_ptr(), 1, None), one, None, True           # the nominal camera as the one scene
+    null = (None, None)                                              # an operand that is NULL
+    four = uvs.engine._latency_operand(np.full(T, 4, np.int32), q_d.device)
+    # the experiment: the same 64 starts and noise in each of the 25 cells
+    ql = q_d[:PER].repeat(len(cells), 1).contiguous()
+    nl = noise[:, :PER].repeat(1, len(cells), 1).contiguous()
+    xl = x0[:PER].repeat(len(cells), 1).contiguous()
+    latency = np.repeat(np.array([d for d, _ in cells], np.int64), PER)
+    ahead = np.repeat(np.array([p for _, p in cells], np.int64), PER)
+    parts = [(c, slice(c * PER, (c + 1) * PER)) for c in range(len(cells))]
+    cut = (ql[:PER].contiguous(), nl[:, :PER].contiguous(), xl[:PER].contiguous())
+
+    def baseline(entry, *front):                                     # a baseline loop through the C ABI; front: latency, assumed[, predict]
+        import ctypes as C
+        out = {key: torch.empty((K, T, comp), dtype=torch.float64, device='cuda') for key, comp in (('q', 6), ('f', 8), ('dq', 6), ('err', 8))}
+        status, k_done = (torch.empty(T, dtype=torch.int32, device='cuda') for _ in range(2))
+        stats, pixels = torch.empty((T, 3), dtype=torch.float64, device='cuda'), torch.empty((T, 4), dtype=torch.int32, device='cuda')
+        uvs._vision.check(getattr(uvs._vision.lib(), entry)(
+            C.byref(fa), one.data_ptr(), 1, None, None, *front, T, nominal.data_ptr(), 1, None, q_d.data_ptr(), noise.data_ptr(), out['q'].data_ptr(),
+            out['f'].data_ptr(), out['dq'].data_ptr(), out['err'].data_ptr(), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(),
+            pixels.data_ptr(), uvs.engine._stream()))
+        return dict(out, pixels=pixels, status=status, k_done=k_done, stats=stats)
+
+    fused = uvs.engine._camera_closed_loop_fused
+    logs = uvs.engine.CAMERA_LOGS
+    fns = {'av': lambda: fused(fp, cam, q_d, noise, x0, 'host', logs, scenes=scene_one, motion=None, latency=None, assumed=null),
+           'pv': lambda: fused(fp, cam, q_d, noise, x0, 'host', logs, scenes=scene_one, motion=None, latency=None, assumed=None, predict=null),
+           'ay': lambda: baseline('uvs_camera_believed_loop_aligned_f64', None, None),
+           'py': lambda: baseline('uvs_camera_believed_loop_predicted_f64', None, None, None),
+           'a4': lambda: fused(fp, cam, q_d, noise, x0, 'host', logs, scenes=scene_one, motion=None, latency=four, assumed=four),
+           'p4': lambda: fused(fp, cam, q_d, noise, x0, 'host', logs, scenes=scene_one, motion=None, latency=four, assumed=four, predict=four),
+           'ay4': lambda: baseline('uvs_camera_believed_loop_aligned_f64', four[0], four[0]),
+           'py4': lambda: baseline('uvs_camera_believed_loop_predicted_f64', four[0], four[0], four[0]),
+           'pw': lambda: loop(fp, plant, ql, nl, x0=xl, fused=True, latency=latency, assumed_latency=latency, predict=ahead),
+           'px': lambda: [loop(fp, plant, *cut[:2], x0=cut[2], fused=True, latency=d, assumed_latency=d, predict=p) for d, p in cells],
+           'py25': lambda: loop(fa, plant, ql, nl, fused=True, latency=latency, assumed_latency=latency, predict=ahead),
+           'pz25': lambda: loop(fa, plant, ql, nl, fused=False, latency=latency, assumed_latency=latency, predict=ahead)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+
+    def same(a, b, rows=slice(None), rows_b=slice(None)):
+        done = a['k_done'][rows]
+        ok = all(torch.equal(a[key][rows], b[key][rows_b]) for key in ('status', 'k_done', 'pixels'))
+        ok = ok and torch.equal(a['stats'][rows].view(torch.int64), b['stats'][rows_b].view(torch.int64))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):                 # the specified rows: q, f up to and including k_done, the others before it
+            if key in a:
+                spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+                ok = ok and torch.equal(a[key][:, rows].view(torch.int64)[spec], b[key][:, rows_b].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['pv'], first['av']), 'the predicted kernel without a horizon and the aligned kernel disagree'
+    assert same(first['py'], first['ay']), 'the predicted baseline without a horizon and the aligned baseline disagree'
+    assert same(first['py25'], first['pz25']), "the baseline's one launch and its stepwise loop disagree"
+    for c, rows in parts:
+        assert same(first['pw'], first['px'][c], rows), f'cell {cells[c]}: the one launch and the launch per cell disagree'
+    assert not same(first['pw'], first['px'][0], parts[1][1]), 'predicting shows'
+    assert not same(first['p4'], first['a4']) and not same(first['py4'], first['ay4']), 'predicting shows'
+    compared = {'pv': 'av', 'py': 'ay'}
+    if PARENT_LIB is not None:
+        parent = ctypes.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_predicted_f64'), 'the parent library has no feature prediction'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+
+        def with_parent(fn):
+            def run():
+                mine, uvs._vision._lib = uvs._vision._lib, parent
+                try:
+                    return fn()
+                finally:
+                    uvs._vision._lib = mine
+            return run
+
+        for name in ('av', 'ay', 'a4', 'ay4'):
+            run = with_parent(fns[name])
+            old = run()
+            torch.cuda.synchronize()
+            assert same(first[name], old), f'this library and the parent disagree on ({name})'
+            fns[name + '_parent_a'], fns[name + '_parent_b'] = run, with_parent(fns[name])
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    say()
+    what = {'av': 'aligned_frames_kernel, NULL, NULL', 'pv': "(av)'s trials through predicted_frames_kernel, NULL x 3",
+            'ay': 'aligned_baseline_kernel, NULL, NULL', 'py': "(ay)'s trials through predicted_baseline_kernel, NULL x 3",
+            'a4': 'aligned_frames_kernel, d = a = 4', 'p4': 'predicted_frames_kernel, d = a = p = 4',
+            'ay4': 'aligned_baseline_kernel, d = a = 4', 'py4': 'predicted_baseline_kernel, d = a = p = 4'}
+    for new, old in (('pv', 'av'), ('py', 'ay'), ('p4', 'a4'), ('py4', 'ay4')):
+        say(f'  ({old}) {what[old]:58s} this library   {fmt_ms(ms[old])}   = {med[old] / K * 1e3:.1f} us per step')
+        say(f'  ({new}) {what[new]:58s} this library   {fmt_ms(ms[new])}   = {med[new] / K * 1e3:.1f} us per step')
+        if PARENT_LIB is not None:
+            a, b = med[old + '_parent_a'], med[old + '_parent_b']
+            say(f'  ({old}) {"":58s} the parent\'s, 1  {fmt_ms(ms[old + "_parent_a"])}')
+            say(f'  ({old}) {"":58s} the parent\'s, 2  {fmt_ms(ms[old + "_parent_b"])}')
+            say(f'  ({new}) / slower parent run of ({old}) = {med[new] / max(a, b):.4f}, / faster = {med[new] / min(a, b):.4f}; the two parent runs differ '
+                f'by {abs(a - b) / max(a, b) * 100:.2f} %' + ('; outputs bit-identical' if new in compared else ''))
+    say(f'  (pw) {len(LAT)} latencies x {len(AHEAD)} horizons x {PER} trials, one launch                        {fmt_ms(ms["pw"])}   = {med["pw"] / K * 1e3:.1f} us per step')
+    say(f'  (px) the same as {len(cells)} launches of {PER} trials, one per cell                      {fmt_ms(ms["px"])}')
+    say(f'  (py25) the baseline over the {len(cells)} cells x {PER} trials, one launch                 {fmt_ms(ms["py25"])}')
+    say(f'  (pz25) (py25) stepwise: K x (features, delay, gather, two projections, law)  {fmt_ms(ms["pz25"])}')
+    say(f'  (pv) / (av) = {med["pv"] / med["av"]:.4f}, (py) / (ay) = {med["py"] / med["ay"]:.4f}, (p4) / (a4) = {med["p4"] / med["a4"]:.4f}, (py4) / (ay4) = '
+        f'{med["py4"] / med["ay4"]:.4f}, (pw) / (px) = {med["pw"] / med["px"]:.4f}, (py25) / (pz25) = {med["py25"] / med["pz25"]:.4f}; (pv) has the bits '
+        f'of (av), (py) those of (ay), (pw) those of (px), (py25) those of (pz25)')
+    failed = lambda out: int((out['k_done'] < K).sum())              # noqa: E731
+    say(f'  trials that FAILed: (av) {failed(first["av"])}, (a4) {failed(first["a4"])}, (p4) {failed(first["p4"])}, (pw) {failed(first["pw"])}, '
+        f'(py25) {failed(first["py25"])}')
+    say()
+    say('# examples/camera_loop.py --latency --predict (its defaults)')
+    for line in example.predicted_table(uvs):
+        say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if PREDICTED:
+    predicted_section()
+    sys.exit(0)
 if ALIGNED:
     aligned_section()
     sys.exit(0)

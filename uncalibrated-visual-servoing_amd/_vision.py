@@ -111,6 +111,9 @@ SYMBOLS = {
     # assumed latency: the two delayed loops with assumed (device int32 [T] or None) directly after latency
     'uvs_camera_closed_loop_aligned_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
     'uvs_camera_believed_loop_aligned_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
+    # feature prediction: the two aligned loops with predict (device int32 [T] or None) directly after assumed
+    'uvs_camera_closed_loop_predicted_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
+    'uvs_camera_believed_loop_predicted_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
 }
 
 _lib = None
@@ -120,7 +123,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 16)), '-C', CSRC], check=True)        # sixteen translation units, one rule each
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 16)), '-C', CSRC], check=True)        # eighteen translation units, one rule each
     return LIB_PATH
 
 

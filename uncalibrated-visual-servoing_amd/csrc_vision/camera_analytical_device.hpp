@@ -17,6 +17,13 @@
 // A unit that defines UVS_CAMERA_ALIGNED on top (uvs_camera_aligned_baseline.hip) sees a sixth, aligned_baseline_kernel(AlignedBaselineArgs): the
 // delayed one whose law is told a latency -- the joints handed to analytical_step at step k are q_{max(k - a, 0)}, a the trial's ASSUMED
 // latency, through s_q as a ring of the last nine steps' joints.  The q log and the joint integration stay current.
+// A unit that defines UVS_CAMERA_PREDICTED on top (uvs_camera_predicted_baseline.hip) sees a seventh, predicted_baseline_kernel(PredictedBaselineArgs):
+// the aligned one whose law is handed f^ = f_reported + (h(q_k) - h(q_{max(k - p, 0)})), p the trial's prediction HORIZON and h the (u, v) the
+// projection kernel gives for the law's own model.  The sensor-side wavefront of a trial projects the law's model at q_k
+// next to the scene, once per step, into slot k mod 9 of the ring s_h -- lanes N .. 2 N - 1 take the model's sines in the sincos call that
+// lanes 0 .. N - 1 take the scene's in, lanes n_points .. 2 n_points - 1 multiply the model's links in the call the first n_points multiply
+// the scene's in (measured: 0.5 % over the aligned twin, against 6.3 % with the two done one after the other) -- and the barriers that were
+// there stand between that store and the law's reads.
 // Next to them: what every entry point of the two units asks of (fp, cam, T) before its first HIP call.
 //
 // The loop's mapping is the one of camera_loop_kernel (camera_loop_device.hpp), decided and measured there -- 256 threads = one wavefront per
@@ -129,6 +136,20 @@ struct AlignedBaselineArgs : DelayedBaselineArgs {
     const int32_t *assumed;                                      // [T] by output trial, or NULL: none
 };
 
+// The seventh flavour (a unit that defines UVS_CAMERA_PREDICTED too, uvs_camera_predicted_baseline.hip): predicted_baseline_kernel,
+// the aligned flavour with a prediction HORIZON per OUTPUT trial.  s_h is a ring of the law's model's (u, v) at the last nine steps' joints.
+struct PredictedBaselineArgs : AlignedBaselineArgs {
+    const int32_t *predict;                                      // [T] by output trial, or NULL: none
+};
+
+#if defined(UVS_CAMERA_PREDICTED)
+#if !defined(UVS_CAMERA_ALIGNED)
+#error "the predicted flavour is an aligned flavour: define UVS_CAMERA_ALIGNED, UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
+#endif
+constexpr bool kBaselinePredicted = true;
+#else
+constexpr bool kBaselinePredicted = false;
+#endif
 #if defined(UVS_CAMERA_ALIGNED)
 #if !defined(UVS_CAMERA_DELAYED)
 #error "the aligned flavour is a delayed flavour: define UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
@@ -147,7 +168,10 @@ constexpr bool kBaselineDelayed = false;
 #error "the delayed flavour is a moving flavour: define UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
 #endif
 constexpr bool kCameraBelieved = true, kBaselineScenes = true, kBaselineMoving = true;
-#if defined(UVS_CAMERA_ALIGNED)
+#if defined(UVS_CAMERA_PREDICTED)
+using BaselineLoopArgs = PredictedBaselineArgs;
+#define UVS_BASELINE_LOOP_KERNEL predicted_baseline_kernel
+#elif defined(UVS_CAMERA_ALIGNED)
 using BaselineLoopArgs = AlignedBaselineArgs;
 #define UVS_BASELINE_LOOP_KERNEL aligned_baseline_kernel
 #else
@@ -225,6 +249,21 @@ __device__ __forceinline__ int loop_assumed(const ALoopArgs &, long long) { retu
 __device__ __forceinline__ int loop_assumed(const BLoopArgs &, long long) { return 0; }
 __device__ __forceinline__ int loop_assumed(const SLoopArgs &, long long) { return 0; }
 __device__ __forceinline__ int loop_assumed(const AlignedBaselineArgs &a, long long trial) { return latency_of(a.assumed, trial); }
+// project_lane_disc_at's text (camera_sensor_device.hpp) over a chain of the launch's n joints -- a model's own n_joints word is never a
+// bound -- for the seventh flavour alone, where the lanes that project the scene and the lanes that project the law's model run it side by
+// side: a motion whose window is empty moves nothing (moved_coordinate returns the coordinate itself), so it is project_disc's bits.
+__device__ __forceinline__ void project_lane_disc_of(const uvs_camera &cam, int n, int p, const uvs_target_motion &mot, int k, const double *sin_row,
+                                                     const double *cos_row, double *out) {
+    double pose[3][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};
+#pragma unroll 1
+    for (int i = 0; i < n; ++i) chain_link(cam, i, sin_row[i], cos_row[i], pose);
+    project_moved_disc(cam, p, mot, k, pose, out);
+}
+// The prediction horizon of `trial`.  The first six flavours have none.
+__device__ __forceinline__ int loop_horizon(const ALoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_horizon(const BLoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_horizon(const SLoopArgs &, long long) { return 0; }
+__device__ __forceinline__ int loop_horizon(const PredictedBaselineArgs &a, long long trial) { return latency_of(a.predict, trial); }
 
 template <int M, int N, int L, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const BaselineLoopArgs A) {
@@ -250,6 +289,14 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     stage_loop_motions<G>(A, s_mot);
     constexpr bool DELAYED = kBaselineDelayed;
     __shared__ DelayCell s_ring[DELAYED ? G : 1][DELAYED ? kColours : 1][DELAYED ? kDelaySlots : 1];   // DELAYED: the last nine detections of every disc
+    constexpr bool PREDICTED = kBaselinePredicted;
+    __shared__ double s_msin[PREDICTED ? W : 1][UVS_CAMERA_MAX_JOINTS], s_mcos[PREDICTED ? W : 1][UVS_CAMERA_MAX_JOINTS];   // PREDICTED: the sines of the LAW's model
+    __shared__ double s_h[PREDICTED ? G : 1][PREDICTED ? kDelaySlots : 1][PREDICTED ? 3 * kColours : 1];   // PREDICTED: its (u, v, r) at the last nine steps' joints, slot k mod 9
+    __shared__ double s_hdump[PREDICTED && G == 1 ? W : 1][PREDICTED ? 3 * kColours : 1];   // PREDICTED, one trial: where the three wavefronts that do not write s_h leave theirs
+    __shared__ uvs_target_motion s_still;                        // PREDICTED: the motion that moves nothing, for the model's lanes
+    if constexpr (PREDICTED) {
+        for (int i = threadIdx.x; i < kMotionWords; i += kLoopThreads) reinterpret_cast<uint64_t *>(&s_still)[i] = 0ull;   // covered like s_mot
+    }
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -269,7 +316,10 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     const bool known = has_model(A, trial);
     int delay = 0;                                               // DELAYED: the latency of the trial (a padding wavefront: of the one it shadows)
     if constexpr (DELAYED) delay = loop_latency(A, trial);
-    double q = lane < N ? A.q_start[trial * N + lane] : 0.0;
+    // PREDICTED: lanes N .. 2 N - 1 carry the same joints through the same two operations, for the sines of the LAW's model next to the scene's
+    const int joint = (PREDICTED && lane >= N) ? lane - N : lane;
+    const int joint_lanes = PREDICTED ? 2 * N : N;
+    double q = lane < joint_lanes ? A.q_start[trial * N + joint] : 0.0;
     // this lane's own addresses in row 0 of the [K][T][comp] logs (NULL: not wanted, or nothing of this lane's), advanced by a row per step
     const long long step_rows = T;
     double *q_at = (valid && writer && lane < N && A.q_log != nullptr) ? A.q_log + trial * N + lane : nullptr;
@@ -290,6 +340,10 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
     if constexpr (ALIGNED) {
         if (w == 0) assumed = loop_assumed(A, etrial);
     }
+    int horizon = 0;                                             // PREDICTED: the prediction horizon of this lane's trial (a shadow lane: of the one it shadows)
+    if constexpr (PREDICTED) {
+        if (w == 0) horizon = loop_horizon(A, etrial);
+    }
     double ise[R], iae[R], itae[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) ise[r] = iae[r] = itae[r] = 0.0;
@@ -300,14 +354,30 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
 
     for (int k = 0; k < K; ++k) {
         // ---- the sensor side of the step (camera_sensor_device.hpp): joints, projection, detection
-        if (lane < N) {
+        if constexpr (PREDICTED) {
+            if (lane < 2 * N) {                                  // one sincos for both: lanes < N the scene's, the others the law's model's (staged
+                advance_joint(joint, k, s_dq[ws], fp.dt, q);     // before the barrier that precedes step 0)
+                if (seen && q_at != nullptr) *q_at = q;          // q_at is NULL beyond lane N - 1
+                if (writer && lane < N) s_q[ws][k % kDelaySlots][lane] = q;
+                const bool mine = lane < N;
+                joint_sincos_rows(mine ? scene : s_cam[ws], joint, q, mine ? s_sin[w] : s_msin[w], mine ? s_cos[w] : s_mcos[w]);
+            }
+        } else if (lane < N) {
             advance_joint(lane, k, s_dq[ws], fp.dt, q);
             if (seen && q_at != nullptr) *q_at = q;              // before the sines: where this text measured fastest
             if (writer) s_q[ws][ALIGNED ? k % kDelaySlots : 0][lane] = q;
             joint_sincos_rows(scene, lane, q, s_sin[w], s_cos[w]);
         }
         __syncthreads();
-        if constexpr (MOVING) {                                  // the disc where step k of the trial's motion has taken it
+        if constexpr (PREDICTED) {                               // lanes < npts: the scene's disc where the motion has taken it; the next npts lanes: h(q_k),
+            if (lane < 2 * npts) {                               // the projection kernel's text on the law's model, whose points do not move
+                const bool mine = lane < npts;
+                const int p = mine ? lane : lane - npts;
+                double *row = mine ? s_disc[w] : (writer ? s_h[ws][k % kDelaySlots] : s_hdump[G == 1 ? w : 0]);
+                project_lane_disc_of(mine ? scene : s_cam[ws], N, p, mine ? s_mot[ws] : s_still, k, mine ? s_sin[w] : s_msin[w],
+                                     mine ? s_cos[w] : s_mcos[w], row + 3 * p);
+            }
+        } else if constexpr (MOVING) {                           // the disc where step k of the trial's motion has taken it
             if (lane < npts) project_lane_disc_at(scene, lane, s_mot[ws], k, s_sin[w], s_cos[w], s_disc[w]);
         } else {
             if (lane < npts) project_lane_disc(scene, lane, s_sin[w], s_cos[w], s_disc[w]);
@@ -330,7 +400,14 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_BASELINE_LOOP_KERNEL(const B
 #pragma unroll
             for (int j = 0; j < N; ++j) qk[j] = s_q[slot][ALIGNED ? delayed_step(k, assumed) % kDelaySlots : 0][j];   // ALIGNED: the joints the assumed frame shows
             uvs::Rows<M, N, L> st;
-            const int bad = analytical_step<M, N, L>(s_cam[BELIEVED ? slot : 0], fp, qk, [slot](int i) { return s_f[slot][i]; }, sub, st, err, cmd);
+            int bad;
+            if constexpr (PREDICTED) {                           // the law on f^: the difference first, then one add -- two rounded operations
+                const double *now = s_h[slot][k % kDelaySlots], *then = s_h[slot][delayed_step(k, horizon) % kDelaySlots];
+                bad = analytical_step<M, N, L>(s_cam[BELIEVED ? slot : 0], fp, qk,
+                                               [slot, now, then](int i) { const int at = 3 * (i >> 1) + (i & 1); const double moved = now[at] - then[at]; return s_f[slot][i] + moved; }, sub, st, err, cmd);
+            } else {
+                bad = analytical_step<M, N, L>(s_cam[BELIEVED ? slot : 0], fp, qk, [slot](int i) { return s_f[slot][i]; }, sub, st, err, cmd);
+            }
             if (alive && bad) {                                  // FAIL at this step; the trial stops
                 alive = false;
                 status = UVS_STATUS_FAIL;

@@ -89,6 +89,18 @@
 // -- MCKF at (8,6), four trials per workgroup, spilled 36 B -- so this flavour keeps the error sums where they end up, in this lane's own
 // words of s_sum, updated by the same three operations per step: 3 R doubles fewer per lane, 0 B of scratch in all 22.  No barrier and no
 // exit is added.
+//
+// PREDICTED.  A tenth flavour: a unit that defines UVS_CAMERA_PREDICTED next to the other eight switches (uvs_camera_predicted.hip)
+// sees predicted_frames_kernel(PredictedLoopArgs) with all nine on.  The control law no longer servoes on a stale row: each OUTPUT trial has a
+// prediction HORIZON p (the rule: plant.prediction_steps; uvs_vision.h, FEATURE PREDICTION), read once before the step loop by the lanes
+// that read `assumed`, and after the update the error is err_r = (f_r + sum_j X_k[r][j] s[j]) - desired_r, s = cmd_{k-1} + ... + cmd_{k-p}
+// summed newest first from s = 0, a step before 0 being the zero vector -- the Smith form: X absorbs t_s, so X s is what the commands issued
+// since the frame shown must have done to the features.  The dot product is the unit's own form, acc = fma(X[r][j], s[j], acc) from acc = 0
+// with j ascending (Rows::update's); f + acc is one rounded add.  z, f_prev, kappa, the f log, the regressor and the joints are untouched.
+// The trial's sub == 0 lane forms s for step k + 1 right after it writes cmd into slot k mod 9 of the command ring -- a step before 0 is a slot
+// not written yet, zeros, so no select -- and leaves it in s_pred[slot][N]; the end-of-step barrier stands between that store and the reads
+// of step k + 1, which take one word per fma: no lane holds s in registers across the update.  The reported row is read again from s_f
+// after the update for the same reason.  No barrier and no exit is added.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -148,6 +160,19 @@ struct AlignedLoopArgs : DelayedLoopArgs {
     const int32_t *assumed;
 };
 
+// uvs_camera_closed_loop_predicted_f64: the aligned block and the prediction horizons, [T] by output trial or NULL; only predicted_frames_kernel takes it
+struct PredictedLoopArgs : AlignedLoopArgs {
+    const int32_t *predict;
+};
+
+#ifdef UVS_CAMERA_PREDICTED
+#ifndef UVS_CAMERA_ALIGNED
+#error "the predicted flavour is an aligned flavour: define UVS_CAMERA_ALIGNED (and UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING, UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
+#endif
+constexpr bool kCameraPredicted = true;
+#else
+constexpr bool kCameraPredicted = false;
+#endif
 #ifdef UVS_CAMERA_ALIGNED
 #ifndef UVS_CAMERA_DELAYED
 #error "the aligned flavour is a delayed flavour: define UVS_CAMERA_DELAYED (and UVS_CAMERA_MOVING, UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
@@ -204,7 +229,11 @@ constexpr bool kCameraOccluded = true;
 #else
 constexpr bool kCameraOccluded = false;
 #endif
-#if defined(UVS_CAMERA_ALIGNED)
+#if defined(UVS_CAMERA_PREDICTED)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = PredictedLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL predicted_frames_kernel
+#elif defined(UVS_CAMERA_ALIGNED)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = AlignedLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL aligned_frames_kernel
@@ -267,11 +296,14 @@ __device__ __forceinline__ const int32_t *latencies_of(const DelayedLoopArgs &a)
 // the assumed latencies of the launch, or NULL (never called on the first eight blocks: ALIGNED is off there)
 __device__ __forceinline__ const int32_t *assumed_of(const LoopArgs &) { return nullptr; }
 __device__ __forceinline__ const int32_t *assumed_of(const AlignedLoopArgs &a) { return a.assumed; }
+// the prediction horizons of the launch, or NULL (never called on the first nine blocks: PREDICTED is off there)
+__device__ __forceinline__ const int32_t *horizons_of(const LoopArgs &) { return nullptr; }
+__device__ __forceinline__ const int32_t *horizons_of(const PredictedLoopArgs &a) { return a.predict; }
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
     constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld, PAINT = kCameraPainted, SCENES = kCameraScenes;
-    constexpr bool MOVING = kCameraMoving, DELAYED = kCameraDelayed, ALIGNED = kCameraAligned;
+    constexpr bool MOVING = kCameraMoving, DELAYED = kCameraDelayed, ALIGNED = kCameraAligned, PREDICTED = kCameraPredicted;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -294,6 +326,7 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     __shared__ uvs_target_motion s_mot[MOVING ? G : 1];          // MOVING: the motions of those trials, staged next to them
     __shared__ DelayCell s_ring[DELAYED ? G : 1][DELAYED ? kColours : 1][DELAYED ? kDelaySlots : 1];   // DELAYED: the last nine detections of every disc
     __shared__ double s_cmd[ALIGNED ? G : 1][ALIGNED ? kDelaySlots : 1][ALIGNED ? N : 1];   // ALIGNED: the last nine commands of every trial
+    __shared__ double s_pred[PREDICTED ? G : 1][PREDICTED ? N : 1];   // PREDICTED: s of this step, the sum of the trial's last p commands
 
     const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -388,6 +421,11 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         if (w == 0) assumed = latency_of(assumed_of(A), etrial);
         // the rings start as zeros: "no such step" is then a slot that has not been written.  The step's first barrier is before the first read.
         for (int i = threadIdx.x; i < G * kDelaySlots * N; i += kLoopThreads) (&s_cmd[0][0][0])[i] = 0;
+    }
+    int horizon = 0;                                             // PREDICTED: the prediction horizon of this lane's trial (a shadow lane: of the one it shadows)
+    if constexpr (PREDICTED) {
+        if (w == 0) horizon = latency_of(horizons_of(A), etrial);
+        for (int i = threadIdx.x; i < G * N; i += kLoopThreads) (&s_pred[0][0])[i] = 0;   // step 0: no command has been issued
     }
     uvs::Rows<M, N, L> st;
     st.init_cov();
@@ -505,6 +543,17 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
                 status = UVS_STATUS_FAIL;
                 k_done = k;
             }
+            if constexpr (PREDICTED) {                           // the law's error: the reported row advanced by X_k s, against the target
+                const double *s = s_pred[slot];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    double acc = 0.0;
+#pragma unroll
+                    for (int j = 0; j < N; ++j) acc = fma(st.x[r][j], s[j], acc);
+                    const double predicted = s_f[slot][sub * R + r] + acc;
+                    err[r] = predicted - des[r];
+                }
+            }
             if constexpr (PARK) {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
@@ -559,6 +608,17 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
                     double *cell = s_cmd[slot][k % kDelaySlots];
 #pragma unroll
                     for (int j = 0; j < N; ++j) cell[j] = cmd[j];
+                }
+                if constexpr (PREDICTED) {                       // s of step k + 1: cmd_k, cmd_{k-1}, ... newest first; a slot not written yet is zeros
+                    double *s = s_pred[slot];
+#pragma unroll
+                    for (int j = 0; j < N; ++j) s[j] = 0.0;
+#pragma unroll 1
+                    for (int i = 1; i <= horizon; ++i) {
+                        const double *cell = s_cmd[slot][(k + 1 - i + kDelaySlots) % kDelaySlots];
+#pragma unroll
+                        for (int j = 0; j < N; ++j) s[j] += cell[j];
+                    }
                 }
                 s_alive[slot] = (alive && !evoid) ? 1 : 0;
             }

@@ -1,6 +1,6 @@
 // What the one-launch pixel loops share, written ONCE: the sensor side of a step -- joints, projection, frame-free detection, lane 0's report,
-// the epilogue's stores -- for the estimator loop (camera_loop_device.hpp, nine flavours) and the baseline loop (camera_analytical_device.hpp,
-// six); the analytic initial guess of a trial for the two guess kernels; and the mapping's constants with the launch decision that goes with them.
+// the epilogue's stores -- for the estimator loop (camera_loop_device.hpp, ten flavours) and the baseline loop (camera_analytical_device.hpp,
+// seven); the analytic initial guess of a trial for the two guess kernels; and the mapping's constants with the launch decision that goes with them.
 // The pieces are __device__ __forceinline__ functions over LDS row pointers and plain values: they declare no LDS and nothing is shared at
 // run time, so every kernel keeps the registers, LDS and scratch it had when the text was written out in it (a shared
 // __device__ body behind __global__ wrappers did move the allocation).  Every value is formed by the operations, in the order, of

@@ -835,7 +835,7 @@ def _check_latency(latency, T, who, name='latency'):
     """What can be said of a ``latency=`` for T output trials on the host alone, before any device work: ValueError, or the operand --
     None, or a host int32 array (T,) of values in 0 .. MAX_LATENCY.  ``latency``: None, an integer for every trial, or T integers (a
     sequence, an array or an integer tensor, which is brought to the host).  ``name``: what the refusals call the argument
-    ('assumed_latency' has the same rule and the same messages)."""
+    ('assumed_latency' and 'predict' have the same rule and the same messages)."""
     many = 'latencies' if name == 'latency' else f'{name} values'
     import torch                                                     # not _torch(): these refusals need no GPU
     if latency is None:
@@ -995,7 +995,7 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=
 
 
 def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None, scenes=None, motion=None,
-                                   latency=None, assumed=None):
+                                   latency=None, assumed=None, predict=None):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
     ``believed``: None, or the (pointer, n_believed, index pointer) of ``_believed_operand`` -- the law then runs on those models.
     ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none).  ``hold`` > 0 (stepwise alone): a third launch per
@@ -1009,7 +1009,12 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     features call); the law's joints are the current ones.
     ``assumed``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the ASSUMED latencies next to ``scenes`` -- the joints the
     law is handed at step k are those of step max(k - a, 0) (the one launch: uvs_camera_believed_loop_aligned_f64, with or without
-    ``latency`` and ``motion``; stepwise: per trial that row of the q log, gathered by torch indexing -- a copy, no arithmetic)."""
+    ``latency`` and ``motion``; stepwise: per trial that row of the q log, gathered by torch indexing -- a copy, no arithmetic).
+    ``predict``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the prediction HORIZONS next to ``scenes`` -- the law is
+    handed f^ = f + (h(q_k) - h(q_{max(k - p, 0)})), h the projection of its own model (the one launch:
+    uvs_camera_believed_loop_predicted_f64, with or without the three above; stepwise: two uvs_camera_project_scenes_f64 calls on the
+    law's models, at row k of the q log and at the per-trial gather of rows max(k - p_t, 0), and the two torch operations of the rule on
+    the launches' stream).  The f log stays the reported row."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -1025,7 +1030,10 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         stats = torch.empty((T, 3), **f64)
         pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
         outputs = (ptr('q'), ptr('f'), ptr('dq'), ptr('err'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
-        if assumed is not None:
+        if predict is not None:
+            rc = _vision.lib().uvs_camera_believed_loop_predicted_f64(C.byref(fp), *scenes, motion, latency, None if assumed is None else assumed[0],
+                                                                      predict[0], T, *believed, q0, noise_ptr, *outputs)
+        elif assumed is not None:
             rc = _vision.lib().uvs_camera_believed_loop_aligned_f64(C.byref(fp), *scenes, motion, latency, assumed[0], T, *believed, q0, noise_ptr,
                                                                     *outputs)
         elif latency is not None:
@@ -1055,8 +1063,15 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         row['held'] = (held_log.data_ptr(), held_log.stride(0) * held_log.element_size())
     at = lambda key, k: row[key][0] + k * row[key][1]                # noqa: E731
     noise_row = 0 if noise is None else noise.stride(0) * 8
+    if assumed is not None or predict is not None:
+        trials = torch.arange(T, device=dev)
     if assumed is not None:
-        told, trials = assumed[1].to(torch.int64), torch.arange(T, device=dev)
+        told = assumed[1].to(torch.int64)
+    if predict is not None:                                          # h of the law's models: zeros stay where a trial has no model (it starts FAILed)
+        horizon = predict[1].to(torch.int64)
+        h_now, h_then = (torch.zeros((T, npts, 3), **f64) for _ in range(2))
+        project = lambda joints, out: _vision.lib().uvs_camera_project_scenes_f64(*believed, npts, T, joints, None, 0.0, None, out.data_ptr(),  # noqa: E731
+                                                                                  stream)
     for k in range(K):
         q_prev, dq_prev = (q0, None) if k == 0 else (at('q', k - 1), at('dq', k - 1))
         extra = (None if k == 0 else at('f', k - 1), at('held', k)) if hold else ()
@@ -1066,7 +1081,15 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         if assumed is not None:                                      # the joints the assumed frame shows: row max(k - a_t, 0) of the q log, per trial
             told_q = log['q'][(k - told).clamp_(min=0), trials]
             joints = told_q.data_ptr()
-        _vision.check(step(joints, at('f', k), at('dq', k), at('err', k), None, at('status', k), stream))
+        feats = at('f', k)
+        if predict is not None:                                      # f^ = f + (h(q_k) - h(q_{max(k - p_t, 0)})): the difference first, then one add
+            shown_q = log['q'][(k - horizon).clamp_(min=0), trials]
+            _vision.check(project(at('q', k), h_now))
+            _vision.check(project(shown_q.data_ptr(), h_then))
+            moved = (h_now[:, :, :2] - h_then[:, :, :2]).reshape(T, m)
+            predicted = log['f'][k] + moved
+            feats = predicted.data_ptr()
+        _vision.check(step(joints, feats, at('dq', k), at('err', k), None, at('status', k), stream))
     return _reduce_camera_logs(fp, log, status_log, pixel_log, want, held_log)
 
 
@@ -1135,7 +1158,7 @@ def _camera_trial_params_struct(trial_params, T, n_in, m, dev):
 
 
 def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_params=None, occluders=None, hold=0, paints=None, scenes=None,
-                              motion=None, latency=None, assumed=None):
+                              motion=None, latency=None, assumed=None, predict=None):
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
     then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
     ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
@@ -1152,7 +1175,9 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     ``latency``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the T output trials next to ``scenes`` -- the launch is
     then uvs_camera_closed_loop_delayed_f64, with or without ``motion``; f0 still comes from the step-0 frame.
     ``assumed``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the ASSUMED latencies of the T output trials next to
-    ``scenes`` -- the launch is then uvs_camera_closed_loop_aligned_f64, with or without ``latency`` and ``motion``."""
+    ``scenes`` -- the launch is then uvs_camera_closed_loop_aligned_f64, with or without ``latency`` and ``motion``.
+    ``predict``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the prediction HORIZONS of the T output trials next to
+    ``scenes`` -- the launch is then uvs_camera_closed_loop_predicted_f64, with or without the three above."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -1188,7 +1213,11 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
         held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
         rest = (T, None if tp is None else C.byref(tp), None if occ is None else occ[0], None if paint is None else paint[0],
                 0 if occ is None else occ[1], hold, *operands[:-1], None if held is None else held.data_ptr(), operands[-1])
-        if assumed is not None:
+        if predict is not None:
+            rc = _vision.lib().uvs_camera_closed_loop_predicted_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0],
+                                                                    None if latency is None else latency[0],
+                                                                    None if assumed is None else assumed[0], predict[0], *rest)
+        elif assumed is not None:
             rc = _vision.lib().uvs_camera_closed_loop_aligned_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0],
                                                                   None if latency is None else latency[0], assumed[0], *rest)
         elif latency is not None:
@@ -1246,7 +1275,7 @@ def _gather_by_source(q_start, noise, x0, trial_params):
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
                        believed_index=None, trial_params=None, occluders=None, hold=0, occluder_colours=None, cameras=None, camera_index=None,
-                       target_motion=None, motion_window=None, latency=None, assumed_latency=None):
+                       target_motion=None, motion_window=None, latency=None, assumed_latency=None, predict=None):
     """T closed-loop trials THROUGH PIXELS: at every step the features are what the centre-of-mass detector returns for the 256 x 256 frame of the
     plant's discs (pixel quantisation included), not the ideal projection ``closed_loop`` feeds.  ``plant``: a ``SyntheticPlant``; ``radius``: disc
     radius in metres (default plant.DISC_RADIUS); ``q_start`` (T, n) cuda fp64; ``noise`` (K, T, m) cuda fp64 or None; ``x0`` (T, m*n) array-like, or
@@ -1365,7 +1394,21 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     ANALYTICAL, where occluders or hold > 0 stay the ValueError they are); fused=False hands the step call, per trial, row k - 1 - a of
     the 'dq' log (or zeros) as dq_prev, or row max(k - a, 0) of the 'q' log as joints, gathered by torch indexing; the two return the
     same bits.  Next to trial_params['source'] it is by output trial.  ValueErrors before any device work, after the refusals above,
-    latency's included: the same as for ``latency``, naming assumed_latency."""
+    latency's included: the same as for ``latency``, naming assumed_latency.
+    ``predict``: FEATURE PREDICTION, per OUTPUT trial -- a prediction HORIZON p, in the same form and range as ``latency`` and independent
+    of it and of ``assumed_latency``: p != latency is the mismatch experiment, and p > 0 without any latency is legal.  The control law
+    acts on the reported row advanced over the last p commands (the steps: ``plant.prediction_steps``; include/uvs_vision.h, FEATURE
+    PREDICTION).  Estimators: err = (f + X_k s) - desired after the update, s the sum of those commands newest first; z, kappa, the 'f'
+    log and the regressor are untouched.  ANALYTICAL: the law is handed f + (h(q_k) - h(q_{max(k - p, 0)})), h the (u, v) of
+    ``camera_project`` on its own model -- the believed model of the trial, else its scene, else the nominal camera.  The 'err' log and
+    the stats are on the PREDICTED error, so they are not comparable across p; the 'f' log stays the reported row.  None (the default)
+    is the call without the argument: its routes, its entry points, its bits; zeros give the same bits through the predicted kernels.
+    fused=True is ONE launch (uvs_camera_closed_loop_predicted_f64, or uvs_camera_believed_loop_predicted_f64 for ANALYTICAL, where
+    occluders or hold > 0 stay the ValueError they are) and combines with everything ``assumed_latency`` combines with, in the same way.
+    fused=False: ANALYTICAL projects the law's models at rows k and max(k - p, 0) of the 'q' log and applies the rule's two torch
+    operations per step, with the one launch's bits; the estimators refuse (ValueError 'predict needs fused=True': the two-launch step
+    forms err inside libuvs_rmckf.so).  Next to trial_params['source'] it is by output trial.  ValueErrors before any device work, after
+    assumed_latency's: the same as for ``latency``, naming predict."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
@@ -1431,14 +1474,20 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     if assumed_latency is not None and latency is None and trial_params is not None and trial_params.get('source') is not None:
         n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
     tolds = _check_latency(assumed_latency, n_out, 'camera_closed_loop', 'assumed_latency')   # likewise
-    if (delays is not None or tolds is not None) and cameras is None and not nominal:   # the nominal camera stands in as the one scene here too
+    if predict is not None and latency is None and assumed_latency is None and trial_params is not None and trial_params.get('source') is not None:
+        n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
+    horizons = _check_latency(predict, n_out, 'camera_closed_loop', 'predict')   # likewise
+    if horizons is not None and not analytical and not fused:
+        raise ValueError('camera_closed_loop: predict needs fused=True: the two-launch step kernel forms the error the law acts on itself')
+    if (delays is not None or tolds is not None or horizons is not None) and cameras is None and not nominal:   # the nominal camera stands in as the one scene here too
         if fp.n != 6:
             raise ValueError(f'camera_closed_loop: the camera-latency kernels are built for the six-joint arms of this project, not for {fp.n} joints')
         nominal = True
     if fused and not getattr(q_start, 'is_cuda', False):
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     torch = _torch()
-    if (occluders is not None or cameras is not None or motion is not None or delays is not None or tolds is not None) and trial_params is not None \
+    if (occluders is not None or cameras is not None or motion is not None or delays is not None or tolds is not None or horizons is not None) \
+            and trial_params is not None \
             and trial_params.get('source') is not None:
         q_start, noise, x0, trial_params = _gather_by_source(q_start, noise, x0, trial_params)
     K, m, n = fp.steps, fp.m, fp.n
@@ -1461,6 +1510,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         scene_kw['target_motion'] = mot[1]
     lat = None if delays is None else _latency_operand(delays, dev)  # (pointer, int32 tensor) of the T output trials
     told = None if tolds is None else _latency_operand(tolds, dev)   # likewise, the assumed latencies
+    ahead = None if horizons is None else _latency_operand(horizons, dev)   # likewise, the prediction horizons
     if analytical:
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -1475,7 +1525,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
             *operand, _keep = _believed_operand(believed, believed_index, T, radius, dev, 'camera_closed_loop')
         return _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, tuple(operand), occ=occ, hold=hold, paint=paint,
                                               scenes=None if scenes is None else scenes[0], motion=None if mot is None else mot[0],
-                                              latency=None if lat is None else lat[0], assumed=told)
+                                              latency=None if lat is None else lat[0], assumed=told, predict=ahead)
     if believed is not None or (scenes is not None and not nominal and x0 is None):  # an estimator that starts from a model in memory: the believed one, or
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)                           # its own scene; the rest is the x0= path
         if m != 2 * cam.n_points or n != cam.n_joints:
@@ -1489,7 +1539,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
         if m != 2 * cam.n_points or n != cam.n_joints:
             raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
-        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes, mot, lat, told)
+        return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes, mot, lat, told, ahead)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
     cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
@@ -1519,7 +1569,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     X = torch.as_tensor(x0, **f64).reshape(T, m * n).clone()
     if fused:                                                        # the host guess is in hand: the rest is the one launch
         return _camera_closed_loop_fused(fp, cam, q_start, noise, X, guess, tuple(want), trial_params, None if occ is None else occ[2], hold,
-                                         None if paint is None else paint[1], scenes, mot, lat, told)
+                                         None if paint is None else paint[1], scenes, mot, lat, told, ahead)
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)

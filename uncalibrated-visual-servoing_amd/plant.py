@@ -464,6 +464,18 @@ def aligned_regressor_step(k, a):
     return max(k - 1 - min(max(a, 0), MAX_LATENCY), -1)
 
 
+def prediction_steps(k, p):
+    """The steps whose commands the feature predictor sums at step ``k`` >= 0 with a prediction horizon ``p``, newest first -- the numpy
+    statement of the rule of include/uvs_vision.h (FEATURE PREDICTION) that every predicted kernel is held to:
+    k - 1, k - 2, ..., max(k - clamp(p, 0, MAX_LATENCY), 0), in Python integers; the empty list for p <= 0 or k == 0.  The estimators
+    advance the reported feature row by X_k times the sum of those commands; the calibrated or believed law by h(q_k) - h(q_j), j the
+    LAST step listed (or k itself where the list is empty).  For k < p the frame shown is frame 0: the missing terms are dropped."""
+    k, p = int(k), int(p)
+    if k < 0:
+        raise ValueError('k must be >= 0')
+    return list(range(k - 1, max(k - min(max(p, 0), MAX_LATENCY), 0) - 1, -1))
+
+
 class LinearPlant:
     """Consistent linearised camera f = f0 + J (q - q0) for shapes without a DH model (BASELINE config 5: m = 32, n = 7;
     a 7-joint arm would be redundant for a 6-DoF camera pose and leave the feature Jacobian rank 6).  J, f0, q0 are uploaded
