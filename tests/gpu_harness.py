@@ -1,6 +1,7 @@
 """The device side of the suites that hold the kernels to the CPU oracles (test_gpu_closed_shapes.py, test_gpu_estimator_params.py,
-test_gpu_step.py, test_gpu_grid.py): launches into poisoned buffers, the comparisons with the references of closed_shapes_common.py,
-the gates, and the generators of the single-step and replay inputs.  torch is imported inside the functions: collection on a machine
+test_gpu_step.py, test_gpu_grid.py, test_gpu_view_bounds.py): launches into poisoned buffers -- and, guarded, into windows between guard bands
+(view_arena_common.py) --, the comparisons with the references of closed_shapes_common.py, the gates, and the generators of the single-step and
+replay inputs.  torch is imported inside the functions: collection on a machine
 without a GPU imports every module that imports this one."""
 import copy
 import ctypes as C
@@ -117,9 +118,14 @@ def params(uvs, case, method, anneal, lanes=0, reserved=0, steps=None, guess=Non
     return fp
 
 
+def first_trials(a, T):
+    """The first T trials of a per-trial input of a case; beyond the case's own trials they repeat from trial 0 ('wide', T = 4, tiled to 8)."""
+    return a[:T] if T <= len(a) else a[np.arange(T) % len(a)]
+
+
 def launch(uvs, case, method, anneal, lanes=0, reserved=0, T=None, want=('x', 'err', 'q'), layout='kct', x_layout=None, final_state=False,
            steps=None, x0=None, reg=cs.REG, anneal_span=cs.ANNEAL_SPAN):
-    """One closed-loop launch (uvs_rmckf_closed_loop_ws_f64) on the first T trials of the case, fp.reg and fp.anneal_span set after
+    """One closed-loop launch (uvs_rmckf_closed_loop_ws_f64) on the first T trials of the case (first_trials), fp.reg and fp.anneal_span set after
     make_params; numpy arrays in [trial][step][component] order whatever the layout, plus what the host-side queries say about the launch.
     Launches are kept: the same one serves several tests (x0: an override, never kept)."""
     import torch
@@ -132,10 +138,10 @@ def launch(uvs, case, method, anneal, lanes=0, reserved=0, T=None, want=('x', 'e
     fp = params(uvs, case, method, anneal, lanes, reserved, steps)
     fp.reg, fp.anneal_span = reg, anneal_span
     ps = plant(uvs, case).to_struct()
-    noise = inp['noise'][:T, :steps]
+    noise = first_trials(inp['noise'], T)[:, :steps]
     noise = cuda(noise.transpose(1, 2, 0) if layout == 'kct' else noise.transpose(1, 0, 2))
-    q0 = cuda(inp['q0'][:T])
-    start = None if inp['guess'] else cuda((inp['x0'] if x0 is None else x0)[:T])
+    q0 = cuda(first_trials(inp['q0'], T))
+    start = None if inp['guess'] else cuda(first_trials(inp['x0'] if x0 is None else x0, T))
     # Every output is a buffer of this launch's, filled with NaN (-7 for the integers) beforehand: what the kernel does not store shows.
     layouts = {k: (x_layout or layout) if k == 'x' else layout for k in STREAMS}
     comps = {'x': m * n, 'err': m, 'q': n, 'f': m, 'dq': n}
@@ -275,6 +281,155 @@ def assert_replay(out, refs, worst, route, tag, skip=()):
             assert d <= tol, (key, d, t) + tuple(tag)
 
 
+# ---------------------------------------------------------------------------------------------- the view contract (view_arena_common.py)
+class Arenas:
+    """The device buffers of one guarded call: every input and every output is a window of view kind `kind` (or the kind given for it) into an
+    allocation of its own, guard bands on either side (view_arena_common.arena).  check(): no byte outside an output's window and no byte
+    of an input differs from before the call."""
+
+    def __init__(self, kind):
+        self.kind, self.items = kind, {}
+
+    def _add(self, name, T, K, comp, kind, dtype, fill, output):
+        import view_arena_common as va
+        self.items[name] = va.arena(T, K, comp, kind or self.kind, dtype=dtype, device='cuda', fill=fill) + (output,)
+        return self.items[name][1]
+
+    def input(self, name, a, kind=None, dtype=None):
+        """The window holding `a`: (T, K, comp), (T, comp) -- no step axis -- or (T,); None stays None."""
+        if a is None:
+            return None
+        a = np.asarray(a)
+        a = a.reshape(len(a), 1, -1) if a.ndim < 3 else a
+        return self._add(name, *a.shape, kind, dtype, a, False)
+
+    def output(self, name, T, K, comp, kind=None, dtype=None):
+        return self._add(name, T, K, comp, kind, dtype, None, True)
+
+    def check(self, tag):
+        import view_arena_common as va
+        for name, (whole, window, before, output) in self.items.items():
+            va.assert_only_the_window_changed(whole, window if output else None, before, (name, 'output' if output else 'input') + tuple(tag))
+
+    def host(self, name):
+        """An output window as a numpy array: (T, K, comp), or (T, comp) / (T,) for the kinds of input() without a step axis."""
+        return None if name not in self.items else np.ascontiguousarray(self.items[name][1].cpu().numpy())
+
+
+def stream(uvs, window):
+    """uvs_view of a [trial][step][comp] window (NULL for None)."""
+    return uvs._lib.NULL_VIEW if window is None else uvs._lib.View(window.data_ptr(), *window.stride())
+
+
+def flat(uvs, window):
+    """uvs_view of a per-trial window (T, 1, comp): no step stride."""
+    return uvs._lib.NULL_VIEW if window is None else uvs._lib.View(window.data_ptr(), window.stride(0), 0, window.stride(2))
+
+
+def guarded_closed(uvs, fp, ps, T, q0, noise, x0, want, kind, x_kind=None, final_state=True, trial=None, own_workspace=False, tag=()):
+    """uvs_rmckf_closed_loop_ws_f64 -- with `trial` (a dict of numpy arrays: kernel_bw, gain, reg, fpi_threshold (T,), desired (T, m), source
+    (T,) int32 over the len(q0) input trials) uvs_rmckf_closed_loop_grid_f64 -- with every input and every output in an arena of view kind
+    `kind` (the X stream: x_kind).  The per-trial pointer arguments (stats, status, k_done, the arrays of `trial`) are dense by the header and
+    get dense arenas.  own_workspace: the workspace is a byte arena of exactly uvs_rmckf_closed_loop_workspace_bytes.  After the launch: nothing
+    outside an output window and no input byte changed (the workspace's guards included), everything was stored.  The dict of launch()."""
+    import torch
+    import view_arena_common as va
+    m, n, K = fp.m, fp.n, fp.steps
+    tag = tuple(tag) + (kind, x_kind, T, want)
+    ar = Arenas(kind)
+    v_q0, v_noise, v_x0 = ar.input('q0', q0), ar.input('noise', noise), ar.input('x0', x0)
+    comps = {'x': m * n, 'err': m, 'q': n, 'f': m, 'dq': n}
+    outs = {k: ar.output(k, T, K, comps[k], x_kind if k == 'x' else None) if k in want else None for k in STREAMS}
+    stats = ar.output('stats', T, 1, 3, 'tkc')
+    status, k_done = (ar.output(k, T, 1, 1, 'tkc', torch.int32) for k in ('status', 'k_done'))
+    x_final = ar.output('x_final', T, 1, m * n) if final_state else None
+    p_final = ar.output('p_final', T, 1, m * n * n) if final_state else None
+    lib = uvs.lib()
+    need = int(lib.uvs_rmckf_closed_loop_workspace_bytes(C.byref(fp), C.byref(ps), T))
+    if own_workspace:
+        assert need > 0, ('no workspace wanted',) + tag
+        ws_whole, ws, ws_before = va.byte_arena(need, 'cuda')
+        ws_ptr = ws.data_ptr()
+    else:
+        ws_ptr, need = uvs.engine.workspace(fp, ps, T, None)
+    args = (flat(uvs, v_q0), stream(uvs, v_noise), flat(uvs, v_x0), *(stream(uvs, outs[k]) for k in STREAMS), stats.data_ptr(), status.data_ptr(),
+            k_done.data_ptr(), flat(uvs, x_final), flat(uvs, p_final), ws_ptr, need, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if trial is None:
+        rc = lib.uvs_rmckf_closed_loop_ws_f64(C.byref(fp), C.byref(ps), T, *args)
+    else:
+        tp = uvs._lib.TrialParams(None, None, None, None, uvs._lib.NULL_VIEW, None)
+        for key, a in trial.items():
+            w = ar.input('trial ' + key, a, 'tkc', torch.int32 if key == 'source' else None)
+            assert len(a) == T and w.is_contiguous()
+            if key == 'desired':
+                tp.desired = flat(uvs, w)
+            else:
+                setattr(tp, key, w.data_ptr())
+        rc = lib.uvs_rmckf_closed_loop_grid_f64(C.byref(fp), C.byref(ps), T, C.byref(tp), *args)
+    uvs._lib.check(rc)
+    torch.cuda.synchronize()
+    ar.check(tag)
+    out = {'lanes': int(lib.uvs_rmckf_closed_loop_lanes(C.byref(fp), C.byref(ps), T)),
+           'segments': int(lib.uvs_rmckf_closed_loop_segments(C.byref(fp), C.byref(ps), T)), 'workspace': need, 'fallbacks': None}
+    if own_workspace:
+        va.assert_only_the_window_changed(ws_whole, ws, ws_before, ('workspace',) + tag)
+        off = int(lib.uvs_rmckf_closed_loop_fallback_offset(C.byref(fp), C.byref(ps), T))
+        assert 0 < off <= need - 4, (off, need) + tag
+        out['fallbacks'] = int(ws[off:off + 4].view(torch.int32).item())
+    for k in STREAMS:
+        out[k] = ar.host(k)
+    out['stats'] = ar.host('stats').reshape(T, 3)
+    out['status'], out['k_done'] = ar.host('status').reshape(T), ar.host('k_done').reshape(T)
+    out['x_final'] = ar.host('x_final').reshape(T, -1) if final_state else None
+    out['p_final'] = ar.host('p_final').reshape(T, -1) if final_state else None
+    assert_everything_was_stored(out, tag)
+    return out
+
+
+def guarded_launch(uvs, case, method, anneal, lanes=0, reserved=0, T=None, want=STREAMS, kind='kct', x_kind=None, final_state=True, steps=None,
+                   x0=None, noise=None, own_workspace=False):
+    """launch()'s call -- the same parameter block, the same first T trials of the case (noise, x0: overrides) -- through guarded_closed."""
+    inp = cs.inputs(case)
+    T, steps = inp['T'] if T is None else T, inp['K'] if steps is None else steps
+    fp = params(uvs, case, method, anneal, lanes, reserved, steps)
+    start = None if inp['guess'] else first_trials(inp['x0'] if x0 is None else x0, T)
+    return guarded_closed(uvs, fp, plant(uvs, case).to_struct(), T, first_trials(inp['q0'], T), first_trials(inp['noise'] if noise is None else noise, T)[:, :steps],
+                          start, want, kind, x_kind, final_state, own_workspace=own_workspace, tag=(case, method, anneal, lanes, reserved))
+
+
+def guarded_replay(uvs, fp, f, dq, x0, want, kind, tag=()):
+    """replay()'s call with f (K + 1 rows), dq and x0 in input arenas (NaN around them) and every output in an arena of view kind `kind`:
+    nothing outside an output window and no input byte changed, everything was stored.  The dict of replay()."""
+    import torch
+    (T, K, n), m = dq.shape, f.shape[2]
+    tag = tuple(tag) + (kind, T, want)
+    ar = Arenas(kind)
+    v_f, v_dq, v_x0 = ar.input('f', f), ar.input('dq', dq), ar.input('x0', x0)
+    comps = {'x': m * n, 'err': m, 'kappa': m, 'dqcmd': n}
+    outs = {k: ar.output(k, T, K, comps[k]) if k in want else None for k in comps}
+    status, k_done = (ar.output(k, T, 1, 1, 'tkc', torch.int32) for k in ('status', 'k_done'))
+    x_final, p_final = ar.output('x_final', T, 1, m * n), ar.output('p_final', T, 1, m * n * n)
+    rc = uvs.lib().uvs_rmckf_replay_f64(C.byref(fp), T, stream(uvs, v_f), stream(uvs, v_dq), flat(uvs, v_x0), *(stream(uvs, outs[k]) for k in comps),
+                                        status.data_ptr(), k_done.data_ptr(), flat(uvs, x_final), flat(uvs, p_final),
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    uvs._lib.check(rc)
+    torch.cuda.synchronize()
+    ar.check(tag)
+    out = {k: ar.host(k) for k in comps}
+    out.update(status=ar.host('status').reshape(T), k_done=ar.host('k_done').reshape(T), x_final=ar.host('x_final').reshape(T, -1),
+               p_final=ar.host('p_final').reshape(T, -1))
+    for k, v in out.items():
+        if v is not None:
+            assert not (np.isnan(v).any() if v.dtype.kind == 'f' else (v == POISON_INT).any()), (k, 'not stored') + tag
+    return out
+
+
+def assert_same_replay(a, b, tag):
+    """Two replay launches wrote the same bits."""
+    for key in ('x', 'err', 'kappa', 'dqcmd', 'status', 'k_done', 'x_final', 'p_final'):
+        assert (a[key] is None) == (b[key] is None) and (a[key] is None or same_bits(a[key], b[key])), (key,) + tuple(tag)
+
+
 # ---------------------------------------------------------------------------------------------- single step
 def step_recipe(rng, m, n, lanes, method, k0, scale, bw, anneal, steps, default_twin=False, **estimator):
     """`steps` steps from k0 of a bank of T = 64 // L + 3 filters (two blocks, the second ragged) on the inputs of tools/fuzz_step.py: every
@@ -317,16 +472,16 @@ def step_recipe(rng, m, n, lanes, method, k0, scale, bw, anneal, steps, default_
         f_old, dq = f, np.clip(st['cmd'], -5, 5)
 
 
-def assert_step(bank, st, desired, worst, routes, tag, fresh=False):
+def assert_step(bank, st, desired, worst, routes, tag, fresh=False, put=cuda):
     """One step of step_recipe on the FilterBank `bank` -- from the oracle's state unless `fresh`, into poisoned outputs -- at STEP_GATES; the
-    deviations go to every route of `routes` in `worst`."""
+    deviations go to every route of `routes` in `worst`.  put: how an input array gets onto the device (an arena's window, say)."""
     if not fresh:
         bank.X.copy_(cuda(st['X_in']))
         bank.P.copy_(cuda(st['P_in']).reshape(bank.P.shape))
     for buf in (bank.dq, bank.err, bank.kappa):
         buf.fill_(float('nan'))
     bank.status.fill_(POISON_INT)
-    cmd, err, kappa, status = (o.cpu().numpy().copy() for o in bank.step(cuda(st['f']), cuda(st['f_old']), cuda(st['dq']), st['k']))
+    cmd, err, kappa, status = (o.cpu().numpy().copy() for o in bank.step(put(st['f']), put(st['f_old']), put(st['dq']), st['k']))
     got = {'X': bank.X.cpu().numpy(), 'P': bank.P.cpu().numpy().reshape(st['P'].shape), 'dq': cmd, 'kappa': kappa}
     assert same_bits(err, st['f'] - desired), ('err', st['k']) + tuple(tag)                 # one subtraction: the same bits
     assert np.array_equal(status == 0, st['finite']) and set(status.tolist()) <= {0, 1}, (st['k'], status.tolist()) + tuple(tag)
