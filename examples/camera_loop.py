@@ -55,8 +55,16 @@ ONE launch per method (engine.camera_closed_loop(latency=, assumed_latency=, pre
 the estimators' law acts on f + X_k (dq_{k-1} + ... + dq_{k-p}), the calibrated law on f + (h(q_k) - h(q_{k-p})).  Prints per (d, p) cell
 the FAIL count, the median ISE as returned -- it is on the PREDICTED error, so it is not comparable across p -- and a "true" ISE recomputed
 from the q log with engine.camera_features at the logged joints against the target, which is.
+--score looks at the product itself, the Jacobian estimate: KF, MCKF, IMCC-KF and GMCKF log X_k (engine.camera_closed_loop(want=
+ESTIMATOR_CAMERA_LOGS)) and engine.camera_jacobian_score scores every X_k against t_s times the TRUE image Jacobian of the trial's scene at
+q_k (engine.camera_jacobian), on the device.  Twice on the same starts and noise: from the reference's analytic guess, and from
+x0 = t_s * camera_jacobian(q_start), the correctly scaled start.  Prints per estimator the ISE of both and, at steps 0, 1, 5, 20, 100 and
+K - 1, the median over the trials of scale (the s that minimises |X - s t_s J|), cosine, rel_err and step_ratio (the share of the
+displacement X promises for dq_k that the plant delivers).  --latency (every trial at latency 2, told), --moving and --scenes N combine
+with it: the truth is then the moved target's, or the trial's own scene's.
 usage: examples/camera_loop.py [--method GMCKF] [--trials 64] [--sigma 0.3] [--radius 0.024] [--seed 0] [--fused] [--baseline] [--miscalibration]
-       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving] [--latency [--told | --predict]]"""
+       [--grid] [--occlusion [--hold N]] [--distractor [--occlusion --hold N]] [--scenes N] [--moving] [--latency [--told | --predict]]
+       [--score [--latency] [--moving] [--scenes N]]"""
 import argparse
 import os
 import sys
@@ -494,6 +502,61 @@ def predicted_table(uvs, method='GMCKF', trials=64, sigma=0.3, radius=None, seed
     return lines
 
 
+SCORE_STEPS = (0, 1, 5, 20, 100)                                     # and K - 1
+SCORE_LATENCY = 2                                                    # --score --latency: control periods, told to the controller
+
+
+def score_table(uvs, trials=64, sigma=0.3, radius=None, seed=0, latency=False, moving=False, n_scenes=0):
+    """The Jacobian-estimate table as a list of lines: the four estimators from the reference's guess and from the correctly scaled start
+    x0 = t_s * camera_jacobian(q_start), on the same starts and noise, one launch each, X_k logged and scored on the device.  No finding is
+    drawn here: the table is what the experiment prints."""
+    import torch
+    desired = np.array([149., 145., 125., 121., 101., 145., 125., 169.])
+    plant = uvs.SyntheticPlant.ur10(desired)
+    methods = ('KF', 'MCKF', 'IMCCKF', 'GMCKF')
+    fps = {method: uvs.engine.make_params(8, 6, method, 10.0, False, 0.05, 15.0, 0.2, desired, True) for method in methods}
+    K, dt = fps['GMCKF'].steps, fps['GMCKF'].dt
+    rng = np.random.default_rng(seed)
+    q0 = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (trials, 1))
+    q0[:, :2] += rng.uniform(-0.1, 0.0, (trials, 2))
+    q0_d = torch.as_tensor(q0, device='cuda')
+    noise_d = torch.as_tensor(rng.standard_normal((K, trials, 8)) * sigma, device='cuda')
+    truth, what = {}, []                                             # the scene arguments the loop and the score share
+    if n_scenes:
+        truth.update(cameras=uvs.engine.camera_scenes(scene_plants(uvs, plant, n_scenes, seed), radius),
+                     camera_index=np.arange(trials, dtype=np.int32) % n_scenes)
+        what.append(f'{n_scenes} true scenes')
+    if moving:
+        velocity = np.repeat(moving_velocities(1, 4, seed), trials, axis=0)
+        truth.update(target_motion=uvs.engine.target_motions(velocity, MOVING_WINDOW, 4, trials))
+        what.append(f'the target moves during steps {MOVING_WINDOW[0]} .. {MOVING_WINDOW[1] - 1}')
+    more = dict(latency=SCORE_LATENCY, assumed_latency=SCORE_LATENCY) if latency else {}
+    if latency:
+        what.append(f'camera latency {SCORE_LATENCY}, told')
+    steps = tuple(k for k in SCORE_STEPS if k < K - 1) + (K - 1,)
+    scaled = dt * uvs.engine.camera_jacobian(plant, q0_d, radius=radius, **truth)
+    starts = (("the reference's guess", dict(guess='device', **(dict(believed=plant) if n_scenes else {}))),
+              ('x0 = t_s J(q_start)', dict(x0=scaled.reshape(trials, -1))))
+    lines = [f'{trials} trials of {K} steps, white noise {sigma} px' + ''.join(', ' + w for w in what) + '; X_k scored against t_s times the true image '
+             f'Jacobian at q_k; median over the trials whose row is due',
+             f'{"":36s}{"ISE":>10s}{"FAIL":>6s}  ' + ''.join(f'{"step " + str(k):>31s}' for k in steps),
+             f'{"":36s}{"":16s}  ' + ''.join(f'{"scale  cos  rel_err  ratio":>31s}' for _ in steps)]
+    for method in methods:
+        for label, start in starts:
+            out = uvs.engine.camera_closed_loop(fps[method], plant, q0_d, noise_d, radius=radius, fused=True, want=uvs.engine.ESTIMATOR_CAMERA_LOGS,
+                                                **start, **truth, **more)
+            score = uvs.engine.camera_jacobian_score(plant=plant, dt=dt, radius=radius, **{k: out[k] for k in ('x', 'q', 'dq', 'k_done')}, **truth)
+            torch.cuda.synchronize()
+            done = (out['status'] == 0).cpu().numpy()
+            ise = np.median(out['stats'].cpu().numpy()[done, 0]) if done.any() else np.nan
+            cells = []
+            for k in steps:
+                med = [float(np.nanmedian(score[key][k].cpu().numpy())) for key in ('scale', 'cosine', 'rel_err', 'step_ratio')]
+                cells.append(f'{med[0]:10.3f}{med[1]:7.3f}{med[2]:8.3f}{med[3]:6.2f}')
+            lines.append(f'{method + ", " + label:36s}{ise:10.3f}{int((~done).sum()):>6d}  ' + ''.join(cells))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--method', default='GMCKF', choices=('KF', 'MCKF', 'IMCCKF', 'GMCKF'))
@@ -520,6 +583,9 @@ def main():
     ap.add_argument('--told', action='store_true',
                     help='with --latency: the controller is told a latency -- latencies 0 .. 4 x assumed latencies 0 .. 4 x the trials in one '
                          'launch per method, told and untold on the same starts and noise')
+    ap.add_argument('--score', action='store_true',
+                    help="the four estimators' X_k scored against the true image Jacobian, from the reference's guess and from the correctly scaled "
+                         'start; combines with --latency, --moving and --scenes N, and nothing else')
     ap.add_argument('--predict', action='store_true',
                     help='with --latency: the law predicts the features over the latency -- latencies 0 .. 4 x prediction horizons 0 .. 4 x the '
                          'trials in one launch per method, every controller told its latency; FAILs, the ISE as returned and a true ISE from the q log')
@@ -532,6 +598,11 @@ def main():
         ap.error('--told goes with --latency')
     if args.predict and (not args.latency or args.told):
         ap.error('--predict goes with --latency, and not with --told')
+    if args.score:
+        if args.told or args.predict:
+            ap.error('--score combines with --latency, --moving and --scenes N')
+        print('\n'.join(score_table(uvs, args.trials, args.sigma, args.radius, args.seed, args.latency, args.moving, args.scenes)))
+        return
     if args.latency and args.predict:
         print('\n'.join(predicted_table(uvs, args.method, args.trials, args.sigma, args.radius, args.seed)))
         return

@@ -682,6 +682,64 @@ int uvs_camera_believed_loop_predicted_f64(const struct uvs_filter_params *fp, c
                                            double *f_log, double *dq_log, double *err_log, int32_t *status, int32_t *k_done, double *stats,
                                            int32_t *pixels, void *stream);
 
+/*
+ * THE ESTIMATE AS A LOG: the one-launch estimator loop stores X itself.  The product of the estimators is a Jacobian estimate; above it
+ * lives in registers for all K steps and is never seen.  uvs_camera_closed_loop_logged_f64 has its *_predicted_* namesake's operands in
+ * its order with `x_log` directly after `kappa_log`, its refusals in their order, all before the first HIP call; T == 0 returns UVS_OK and
+ * launches nothing; MCKF at (6, 6) is UVS_ERR_METHOD as everywhere.
+ *   x_log [K][T][m n] doubles in device memory, or NULL.  Element i n + j of a record is X[i][j]: the layout of x0 and of the X tensor of
+ *     uvs_rmckf_step_f64.  Row k holds X_k, the matrix AFTER step k's update -- the one step k's control law (and prediction) reads.
+ *   Row k of trial t is written under the condition of the err, kappa and dq rows: k < k_done[t], t a valid trial that is not void.  Nothing
+ *     else of x_log is touched: rows from k_done on, void trials, padding wavefronts and shadow lanes store nothing.
+ * Bit for bit: (a) x_log == NULL gives the bits of the predicted namesake in every output; (b) with the log every other output keeps those
+ * bits; (c) rows k < k_done are the X tensor of the stepwise loop after its step call k.
+ * Built: what the predicted namesake builds (22 instantiations), each with 0 B of scratch memory.
+ */
+int uvs_camera_closed_loop_logged_f64(const struct uvs_filter_params *fp, const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index,
+                                      const uvs_target_motion *motion, const int32_t *latency, const int32_t *assumed,
+                                      const int32_t *predict, int64_t T, const uvs_camera_trial_params *tp, const uvs_occluder *occ,
+                                      const int32_t *paint, int32_t n_occ, int32_t hold, const double *q_start, const double *noise,
+                                      const double *x0, const double *f0, double *q_log, double *f_log, double *dq_log, double *err_log,
+                                      double *kappa_log, double *x_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels,
+                                      int32_t *held, void *stream);
+
+/*
+ * THE TRUE IMAGE JACOBIAN, and an X stream scored against it.  h(q) is the (u, v) row uvs_camera_project_moving_f64 gives for a trial's
+ * scene at joints q and step k (a moving target's points stand where step k of its motion has taken them).  The rule
+ * (plant.projection_jacobian states it once in numpy): with T6 the camera pose at q, R and c its rotation and origin, [v_j; w_j] column j
+ * of the arm's geometric Jacobian (w_j = z_{j-1}, v_j = z_{j-1} x (c - o_{j-1}), frame 0 the base), w a world point and p = R^T (w - c),
+ *   dp/dq_j = -R^T (w_j x (w - c) + v_j) = -R^T (z_{j-1} x (w - o_{j-1}))       (the device evaluates the right-hand form)
+ *   du/dq_j = focal (dp_x / p_z - p_x dp_z / p_z^2),  dv/dq_j likewise with p_y.
+ * The unit is pixels per radian: there is no t_s in it.  (The interaction row at the CENTRED pixels with the depth ALONG THE OPTICAL AXIS,
+ * applied to the camera-frame twist, is this matrix; the initial guess of the loops -- raw pixels, camera-disc distance -- is not.)
+ * The arms have six joints: q rows are six doubles, a record is [2 n_points][6], and no struct's own n_joints / n_points is read.
+ * Operand conventions are those of the scenes / moving project calls: (cams, n_cams, cam_index) picks the scene of trial t, cam_index
+ * NULL with n_cams == 1 or n_cams == T; motion [T] by trial or NULL: nothing moves.  A trial whose index names no scene gets a record of
+ * NaNs and reads no struct.
+ *
+ * uvs_camera_jacobian_f64: q [rows][T][6], j_out [rows][T][2 n_points][6].  The record at (r, t) is dh/dq at q[r][t] of trial t's scene at
+ *   step k0 + r.  Refused before any HIP call, in this order: NULL q or j_out; T outside 0 .. 2^31 - 1; rows outside 0 .. 2^31 - 1; an
+ *   n_points that is not 1, 3 or 4; the scene triple's refusals; k0 < 0 or k0 + rows > 2^31 - 1.  T == 0 or rows == 0 returns UVS_OK and
+ *   launches nothing.
+ * uvs_camera_jacobian_score_f64: x_log [K][T][2 n_points 6] (the layout of the log above), q_log [K][T][6], dq_log [K][T][6] or NULL,
+ *   k_done [T] int32 or NULL, score [K][T][6].  With J the record of the call above at (k, t) with k0 = 0, Js[i][j] = dt J[i][j] (one rounded
+ *   multiply per entry), X the record of x_log and dq that of dq_log, the six doubles of a record are
+ *     nx2 = sum X^2, nj2 = sum Js^2, dot = sum X Js, diff2 = sum (X - Js)^2, xd_xd = |X dq|^2, xd_jd = (X dq) . (Js dq)
+ *   each product and each add rounded once.  The sums over (i, j) run row-major within a disc's two rows from 0.0; the discs' partial sums
+ *   are then added in disc order from the first disc's.  (X dq)_i sums j ascending from 0.0.  dq_log == NULL: the last two are 0.0.  A record
+ *   with k >= k_done[t] is six NaNs, written without reading x_log, q_log or dq_log there.  A record does not depend on T, K or where it
+ *   stands in the launch.  Refused before any HIP call, in this order: NULL x_log, q_log or score; T outside 0 .. 2^31 - 1; K outside
+ *   0 .. 2^31 - 1; an n_points that is not 1, 3 or 4; the scene triple's refusals.  T == 0 or K == 0 returns UVS_OK and launches nothing.
+ * Either call refuses more than 2^36 records (rows T, K T) with UVS_ERR_ARG, also before any HIP call.
+ * Both kernels give four lanes to a record, one per disc: a lane reads or writes the 96 contiguous bytes of its disc's two rows, so a
+ * wavefront covers sixteen whole records; one device function forms J in both.
+ */
+int uvs_camera_jacobian_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, const uvs_target_motion *motion,
+                            int32_t n_points, int64_t T, int64_t rows, int32_t k0, const double *q, double *j_out, void *stream);
+int uvs_camera_jacobian_score_f64(const uvs_camera *cams, int64_t n_cams, const int32_t *cam_index, const uvs_target_motion *motion,
+                                  int32_t n_points, int64_t T, int64_t K, double dt, const double *x_log, const double *q_log,
+                                  const double *dq_log, const int32_t *k_done, double *score, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

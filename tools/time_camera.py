@@ -135,7 +135,17 @@ With --predicted only the feature-prediction pixel loops are timed, into profile
       64 trials, one per cell; (py25) the baseline over the 25 cells in one launch, (pz25) that stepwise
       -- (pv) is asserted to have the bits of (av), (py) those of (ay), (pw) those of (px) trial for trial, (py25) those of (pz25), before
       anything is timed.  Then the table of examples/camera_loop.py --latency --predict.
-usage: tools/time_camera.py --predicted [--parent-lib=PATH] [out.txt]"""
+usage: tools/time_camera.py --predicted [--parent-lib=PATH] [out.txt]
+
+--score: the X log, the true image Jacobian and the score, into profiles/camera_score.txt
+  (pv) the predicted loop with every optional operand NULL, 1 024 trials x 299 steps, through the C ABI -- with this library and, given
+      --parent-lib=PATH, with the parent's, twice;
+  (lv) the same trials through logged_frames_kernel with x_log = NULL: the price of the text; (lx) the same with the log: the price of
+      117 MB of stores from wavefront 0 -- (lv) is asserted to have the bits of (pv), (lx) those too in every other output, before anything
+      is timed; each ratio is printed next to the parent's own two-run spread; nothing is gated;
+  (cj) engine.camera_jacobian over the q log of (lx), (cs) engine.camera_jacobian_score over its x, q and dq logs: HIP events around the
+      calls, alternating blocks, with the bytes each moves.  Then the table of examples/camera_loop.py --score.
+usage: tools/time_camera.py --score [--parent-lib=PATH] [out.txt]"""
 import os
 import sys
 import time
@@ -154,9 +164,10 @@ MOVING = '--moving' in sys.argv[1:]
 DELAYED = '--delayed' in sys.argv[1:]
 ALIGNED = '--aligned' in sys.argv[1:]
 PREDICTED = '--predicted' in sys.argv[1:]
+SCORE = '--score' in sys.argv[1:]
 PARENT_LIB = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--parent-lib=')), None)
-ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving', '--delayed', '--aligned', '--predicted') and not a.startswith('--parent-lib=')]
-OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_predicted_timing.txt' if PREDICTED else 'camera_aligned_timing.txt' if ALIGNED else 'camera_latency_timing.txt' if DELAYED else 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
+ARGV = [a for a in sys.argv[1:] if a not in ('--analytical', '--believed', '--grid', '--occluded', '--held', '--painted', '--scenes', '--moving', '--delayed', '--aligned', '--predicted', '--score') and not a.startswith('--parent-lib=')]
+OUT = ARGV[0] if ARGV else os.path.join(ROOT, 'profiles', 'camera_score.txt' if SCORE else 'camera_predicted_timing.txt' if PREDICTED else 'camera_aligned_timing.txt' if ALIGNED else 'camera_latency_timing.txt' if DELAYED else 'camera_moving_timing.txt' if MOVING else 'camera_scenes_timing.txt' if SCENES else 'camera_painted.txt' if PAINTED else 'camera_hold.txt' if HELD else 'camera_occluded.txt' if OCCLUDED else 'camera_grid.txt' if GRID else 'camera_believed.txt' if BELIEVED else
                                         'camera_analytical.txt' if ANALYTICAL else 'camera_device.txt')
 ROUNDS, BLOCK, WARM = 5, 50, 20                      # 250 timed iterations per figure, in 5 alternating blocks
 Q_GOAL = np.array([0.0, -np.pi / 8, np.pi / 2 + np.pi / 8, 0.0, -np.pi / 2, 0.0])
@@ -1475,6 +1486,129 @@ def predicted_section():
     open(OUT, 'w').write('\n'.join(lines) + '\n')
 
 
+def score_section():
+    """(pv) against the parent's; (lv), (lx), (cj), (cs): see the module docstring."""
+    import ctypes as C
+    sys.path.insert(0, os.path.join(ROOT, 'examples'))
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import camera_loop as example
+    import kernel_resources
+    plant = uvs.SyntheticPlant.ur10()
+    rng = np.random.default_rng(2025)
+    K, T, m, n = 299, 1024, 8, 6
+    fp = uvs.engine.make_params(m, n, 'GMCKF', 10.0, False, 0.05, 15.0, 0.2, DESIRED, True)
+    assert fp.steps == K
+    say(f'# tools/time_camera.py --score on {torch.cuda.get_device_name(0)}; {uvs._vision.lib().uvs_vision_version().decode()}; '
+        f'{uvs.lib().uvs_version().decode()}')
+    say(f'# GMCKF, {T} trials x {K} steps, white noise 0.3 px, x0 handed in (the nominal model\'s guess), the nominal camera as the one scene, every '
+        f'optional operand NULL, all five logs')
+    q = np.tile(np.array([0.0, 0.0, 1.96349541, 0.0, -1.57079633, 0.0]), (T, 1))
+    q[:, :2] += rng.uniform(-0.1, 0.0, (T, 2))
+    q_d = torch.as_tensor(q, device='cuda')
+    noise = torch.as_tensor(rng.standard_normal((K, T, m)) * 0.3, device='cuda')
+    f0 = uvs.engine.camera_features(plant, q_d)
+    x0 = uvs.engine.camera_guess(plant, q_d, f0)
+    one = uvs.engine.camera_scenes(plant)
+
+    def loop(library, entry, x=None):                                # a one-launch estimator loop through the C ABI, its logs allocated here
+        f64 = dict(dtype=torch.float64, device='cuda')
+        out = {key: torch.empty((K, T, comp), **f64) for key, comp in (('q', n), ('f', m), ('dq', n), ('err', m), ('kappa', m))}
+        status, k_done = (torch.empty(T, dtype=torch.int32, device='cuda') for _ in range(2))
+        stats, pixels = torch.empty((T, 3), **f64), torch.empty((T, 4), dtype=torch.int32, device='cuda')
+        logs = [out[key].data_ptr() for key in ('q', 'f', 'dq', 'err', 'kappa')]
+        if x is not None:
+            if x:
+                out['x'] = torch.empty((K, T, m * n), **f64)
+            logs.append(out['x'].data_ptr() if x else None)
+        uvs._vision.check(getattr(library, entry)(C.byref(fp), one.data_ptr(), 1, None, None, None, None, None, T, None, None, None, 0, 0, q_d.data_ptr(),
+                                                  noise.data_ptr(), x0.data_ptr(), f0.data_ptr(), *logs, status.data_ptr(), k_done.data_ptr(),
+                                                  stats.data_ptr(), pixels.data_ptr(), None, uvs.engine._stream()))
+        return dict(out, pixels=pixels, status=status, k_done=k_done, stats=stats)
+
+    mine = uvs._vision.lib()
+    fns = {'pv': lambda: loop(mine, 'uvs_camera_closed_loop_predicted_f64'),
+           'lv': lambda: loop(mine, 'uvs_camera_closed_loop_logged_f64', False),
+           'lx': lambda: loop(mine, 'uvs_camera_closed_loop_logged_f64', True)}
+    first = {name: fn() for name, fn in fns.items()}
+    torch.cuda.synchronize()
+
+    def same(a, b):
+        done = a['k_done']
+        ok = all(torch.equal(a[key], b[key]) for key in ('status', 'k_done', 'pixels')) and torch.equal(a['stats'].view(torch.int64), b['stats'].view(torch.int64))
+        for key in ('err', 'q', 'f', 'dq', 'kappa'):
+            spec = torch.arange(K, device='cuda')[:, None] < (done[None, :] + (1 if key in ('q', 'f') else 0))
+            ok = ok and torch.equal(a[key].view(torch.int64)[spec], b[key].view(torch.int64)[spec])
+        return ok
+
+    assert same(first['lv'], first['pv']) and same(first['lx'], first['pv']), 'the logged kernel and the predicted kernel disagree'
+    if PARENT_LIB is not None:
+        parent = C.CDLL(os.path.abspath(PARENT_LIB))
+        for name, (res, args) in uvs._vision.SYMBOLS.items():
+            if hasattr(parent, name):
+                fn = getattr(parent, name)
+                fn.restype, fn.argtypes = res, args
+        assert not hasattr(parent, 'uvs_camera_closed_loop_logged_f64'), 'the parent library logs no X'
+        say(f'# parent library: {parent.uvs_vision_version().decode()}')
+        assert same(loop(parent, 'uvs_camera_closed_loop_predicted_f64'), first['pv']), 'this library and the parent disagree on (pv)'
+        fns['pv_parent_a'] = fns['pv_parent_b'] = lambda: loop(parent, 'uvs_camera_closed_loop_predicted_f64')
+        fns['pv_parent_b'] = lambda: loop(parent, 'uvs_camera_closed_loop_predicted_f64')
+    say('# (pv), (lv), (lx): host clock around synchronised calls, alternating blocks in one process, allocation of the logs included; medians of 20')
+    ms = wall_alternate(fns, rounds=5, block=4)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    say()
+    what = {'pv': 'predicted_frames_kernel, NULL x 4', 'lv': "(pv)'s trials through logged_frames_kernel, x_log = NULL",
+            'lx': f'the same with the log: {K * T * m * n * 8 / 1e6:.0f} MB of X'}
+    for name in ('pv', 'lv', 'lx'):
+        say(f'  ({name}) {what[name]:58s} this library   {fmt_ms(ms[name])}   = {med[name] / K * 1e3:.1f} us per step')
+    if PARENT_LIB is not None:
+        a, b = med['pv_parent_a'], med['pv_parent_b']
+        say(f'  (pv) {"":58s} the parent\'s, 1  {fmt_ms(ms["pv_parent_a"])}')
+        say(f'  (pv) {"":58s} the parent\'s, 2  {fmt_ms(ms["pv_parent_b"])}')
+        say(f'  the two parent runs differ by {abs(a - b) / max(a, b) * 100:.2f} %; (pv) new / slower parent run = {med["pv"] / max(a, b):.4f}, / faster = '
+            f'{med["pv"] / min(a, b):.4f}; outputs bit-identical')
+        for name in ('lv', 'lx'):
+            say(f'  ({name}) / slower parent run of (pv) = {med[name] / max(a, b):.4f}, / faster = {med[name] / min(a, b):.4f}')
+    say(f'  (lv) / (pv) = {med["lv"] / med["pv"]:.4f}: the price of the text; (lx) / (lv) = {med["lx"] / med["lv"]:.4f}, (lx) / (pv) = '
+        f'{med["lx"] / med["pv"]:.4f}: the price of the log; (lv) and (lx) have the bits of (pv) in every other output')
+    say(f'  trials that FAILed: {int((first["pv"]["k_done"] < K).sum())}')
+    say()
+    out = first['lx']
+    j_out = torch.empty((K, T, m, n), dtype=torch.float64, device='cuda')
+    kw = {key: out[key] for key in ('x', 'q', 'dq', 'k_done')}
+    us = alternate({'cj': lambda: uvs.engine.camera_jacobian(plant, out['q'], out=j_out),
+                    'cs': lambda: uvs.engine.camera_jacobian_score(plant=plant, dt=fp.dt, **kw)}, rounds=5, block=20, warm=5)
+    moved = {'cj': K * T * 8 * (n + m * n), 'cs': K * T * 8 * (m * n + 2 * n + 6)}
+    say(f'# (cj), (cs): HIP events around the engine calls (four lanes per record, one per disc), alternating blocks, {K * T} records')
+    for name, label in (('cj', 'engine.camera_jacobian over the q log'), ('cs', 'engine.camera_jacobian_score over the x, q and dq logs')):
+        mid = float(np.median(us[name]))
+        say(f'  ({name}) {label:58s} {fmt(us[name])}   {moved[name] / 1e6:.0f} MB, {moved[name] / mid / 1e3:.0f} GB/s')
+    say()
+    k = kernel_resources.kernels(uvs._vision.LIB_PATH)
+    say('# registers, LDS and scratch of the new kernels next to the predicted namesakes (tools/kernel_resources.py)')
+    short = lambda name: name.split('(')[0].replace('uvs_vision::', '').replace('void ', '')   # noqa: E731
+    for name, r in sorted(k.items()):
+        if 'logged_frames_kernel' in name:
+            twin = k[name.replace('logged_frames_kernel', 'predicted_frames_kernel').replace('LoggedLoopArgs', 'PredictedLoopArgs')]
+            say(f'  {short(name):44s} vgpr {r["vgpr"]:3d}  agpr {r["agpr"]:3d}  sgpr {r["sgpr"]:3d}  scratch {r["scratch"]} B  LDS {r["lds"]:5d} B   '
+                f'(predicted: vgpr {twin["vgpr"]:3d}  agpr {twin["agpr"]:3d}  sgpr {twin["sgpr"]:3d}  scratch {twin["scratch"]} B  LDS {twin["lds"]:5d} B)')
+        elif 'image_jacobian_kernel' in name or 'jacobian_score_kernel' in name:
+            say(f'  {short(name):44s} vgpr {r["vgpr"]:3d}  agpr {r["agpr"]:3d}  sgpr {r["sgpr"]:3d}  scratch {r["scratch"]} B  LDS {r["lds"]:5d} B')
+    say()
+    say('# examples/camera_loop.py --score (its defaults)')
+    for line in example.score_table(uvs):
+        say(line)
+    for flags, kwargs in (('--latency', dict(latency=True)), ('--moving', dict(moving=True)), ('--scenes 8', dict(n_scenes=8))):
+        say()
+        say(f'# examples/camera_loop.py --score {flags}')
+        for line in example.score_table(uvs, **kwargs):
+            say(line)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    open(OUT, 'w').write('\n'.join(lines) + '\n')
+
+
+if SCORE:
+    score_section()
+    sys.exit(0)
 if PREDICTED:
     predicted_section()
     sys.exit(0)

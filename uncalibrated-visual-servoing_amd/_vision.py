@@ -114,6 +114,12 @@ SYMBOLS = {
     # feature prediction: the two aligned loops with predict (device int32 [T] or None) directly after assumed
     'uvs_camera_closed_loop_predicted_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
     'uvs_camera_believed_loop_predicted_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
+    # the estimate as a log: the predicted estimator loop with x_log (device float64 [K][T][m n] or None) directly after kappa_log
+    'uvs_camera_closed_loop_logged_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 14 + [_VP, _VP]),
+    # the true image Jacobian: scene operand, motion, n_points, T, rows, k0, q, j_out, stream
+    'uvs_camera_jacobian_f64': (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I64, _I64, _I32, _VP, _VP, _VP]),
+    # an X stream scored against it: scene operand, motion, n_points, T, K, dt, x_log, q_log, dq_log, k_done, score, stream
+    'uvs_camera_jacobian_score_f64': (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I64, _I64, _F64, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None
@@ -123,7 +129,7 @@ def build(force=False):
     """Compile libuvs_vision.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 16)), '-C', CSRC], check=True)        # eighteen translation units, one rule each
+    subprocess.run(['make', '-j', str(min(os.cpu_count() or 4, 16)), '-C', CSRC], check=True)        # twenty translation units, one rule each
     return LIB_PATH
 
 

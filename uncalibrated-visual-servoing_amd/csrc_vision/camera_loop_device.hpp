@@ -101,6 +101,16 @@
 // not written yet, zeros, so no select -- and leaves it in s_pred[slot][N]; the end-of-step barrier stands between that store and the reads
 // of step k + 1, which take one word per fma: no lane holds s in registers across the update.  The reported row is read again from s_f
 // after the update for the same reason.  No barrier and no exit is added.
+//
+// LOGGED.  An eleventh flavour: a unit that defines UVS_CAMERA_LOGGED next to the other nine switches (uvs_camera_logged.hip) sees
+// logged_frames_kernel(LoggedLoopArgs) with all ten on.  The estimate itself is a log: x_log [K][T][M N], row k = X_k, the matrix AFTER step k's
+// update -- the one step k's law and prediction read -- element i N + j = X[i][j], the layout of x0.  Each owner lane of wavefront 0 stores the
+// R rows it holds, R N contiguous doubles, next to the step's dq row and under the condition of the err, kappa and dq rows (alive && estore:
+// rows k < k_done of valid trials that are not void); shadow lanes and padding slots store nothing.  One cursor, x_at, advances with err_at;
+// nothing else is carried across the step.  The R N stores are written as one 8-byte vector store each, in inline assembly, ON PURPOSE: as
+// plain assignments the compiler merges them into 16-byte stores, which need the rows in aligned register quadruples, and MCKF at (8,6,4)
+// -- 509 of 512 registers in the predicted flavour -- then spills 156 to 192 B per lane (and 60 B at (2,6,1)); unmerged, all 22 have 0 B.
+// No barrier, no exit and no LDS is added.  x_log == NULL: the predicted kernel's bits in every output.
 #ifndef UVS_CAMERA_LOOP_DEVICE_HPP
 #define UVS_CAMERA_LOOP_DEVICE_HPP
 
@@ -165,6 +175,19 @@ struct PredictedLoopArgs : AlignedLoopArgs {
     const int32_t *predict;
 };
 
+// uvs_camera_closed_loop_logged_f64: the predicted block and the log of the estimate, [K][T][M N] or NULL; only logged_frames_kernel takes it
+struct LoggedLoopArgs : PredictedLoopArgs {
+    double *x_log;
+};
+
+#ifdef UVS_CAMERA_LOGGED
+#ifndef UVS_CAMERA_PREDICTED
+#error "the logged flavour is a predicted flavour: define UVS_CAMERA_PREDICTED (and UVS_CAMERA_ALIGNED, UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING, UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
+#endif
+constexpr bool kCameraLogged = true;
+#else
+constexpr bool kCameraLogged = false;
+#endif
 #ifdef UVS_CAMERA_PREDICTED
 #ifndef UVS_CAMERA_ALIGNED
 #error "the predicted flavour is an aligned flavour: define UVS_CAMERA_ALIGNED (and UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING, UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
@@ -229,7 +252,11 @@ constexpr bool kCameraOccluded = true;
 #else
 constexpr bool kCameraOccluded = false;
 #endif
-#if defined(UVS_CAMERA_PREDICTED)
+#if defined(UVS_CAMERA_LOGGED)
+constexpr bool kCameraPerTrial = true;
+using CameraLoopKernelArgs = LoggedLoopArgs;
+#define UVS_CAMERA_LOOP_KERNEL logged_frames_kernel
+#elif defined(UVS_CAMERA_PREDICTED)
 constexpr bool kCameraPerTrial = true;
 using CameraLoopKernelArgs = PredictedLoopArgs;
 #define UVS_CAMERA_LOOP_KERNEL predicted_frames_kernel
@@ -299,11 +326,15 @@ __device__ __forceinline__ const int32_t *assumed_of(const AlignedLoopArgs &a) {
 // the prediction horizons of the launch, or NULL (never called on the first nine blocks: PREDICTED is off there)
 __device__ __forceinline__ const int32_t *horizons_of(const LoopArgs &) { return nullptr; }
 __device__ __forceinline__ const int32_t *horizons_of(const PredictedLoopArgs &a) { return a.predict; }
+// the log of the estimate, or NULL (never called on the first ten blocks: LOGGED is off there)
+__device__ __forceinline__ double *x_log_of(const LoopArgs &) { return nullptr; }
+__device__ __forceinline__ double *x_log_of(const LoggedLoopArgs &a) { return a.x_log; }
 
 template <int M, int N, int L, int METHOD_T, int G>
 __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const CameraLoopKernelArgs A) {
     constexpr bool PTP = kCameraPerTrial, OCC = kCameraOccluded, HOLD = kCameraHeld, PAINT = kCameraPainted, SCENES = kCameraScenes;
     constexpr bool MOVING = kCameraMoving, DELAYED = kCameraDelayed, ALIGNED = kCameraAligned, PREDICTED = kCameraPredicted;
+    constexpr bool LOGGED = kCameraLogged;
     constexpr int R = M / L, W = kLoopThreads / 64;
     static_assert((G == 1 || G == W) && W == kColours && G * L <= 64 && N <= UVS_CAMERA_MAX_JOINTS && M <= 2 * kColours, "one or four trials per workgroup");
     __shared__ double s_sin[W][UVS_CAMERA_MAX_JOINTS], s_cos[W][UVS_CAMERA_MAX_JOINTS];   // per wavefront (G = 1: four copies of one trial's)
@@ -416,6 +447,8 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
     double *err_at = (estore && A.err_log != nullptr) ? A.err_log + etrial * M + sub * R : nullptr;
     double *kappa_at = (estore && A.kappa_log != nullptr) ? A.kappa_log + etrial * M + sub * R : nullptr;
     double *dq_at = (estore && sub == 0 && A.dq_log != nullptr) ? A.dq_log + etrial * N : nullptr;
+    double *x_at = nullptr;                                      // LOGGED: this lane's R rows of X in row 0 of the log
+    if constexpr (LOGGED) x_at = (estore && x_log_of(A) != nullptr) ? x_log_of(A) + (etrial * M + sub * R) * N : nullptr;
     int assumed = 0;                                             // ALIGNED: the assumed latency of this lane's trial (a shadow lane: of the one it shadows)
     if constexpr (ALIGNED) {
         if (w == 0) assumed = latency_of(assumed_of(A), etrial);
@@ -596,6 +629,14 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
 #pragma unroll
                     for (int j = 0; j < N; ++j) dq_at[j] = cmd[j];
                 }
+                if constexpr (LOGGED) {                          // X_k, the matrix this step's update left and its law read: the lane's R rows
+                    if (x_at != nullptr) {                       // one 8-byte store each, not to be merged (see LOGGED above)
+#pragma unroll
+                        for (int r = 0; r < R; ++r)
+#pragma unroll
+                            for (int j = 0; j < N; ++j) asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(x_at + r * N + j), "v"(st.x[r][j]) : "memory");
+                    }
+                }
             }
             if constexpr (!ALIGNED) {
 #pragma unroll
@@ -631,6 +672,9 @@ __global__ __launch_bounds__(kLoopThreads) void UVS_CAMERA_LOOP_KERNEL(const Cam
         if (err_at != nullptr) err_at += step_rows * M;
         if (kappa_at != nullptr) kappa_at += step_rows * M;
         if (dq_at != nullptr) dq_at += step_rows * N;
+        if constexpr (LOGGED) {
+            if (x_at != nullptr) x_at += step_rows * (M * N);
+        }
         seen = s_alive[ws] != 0;
         int any_alive = 0;
 #pragma unroll

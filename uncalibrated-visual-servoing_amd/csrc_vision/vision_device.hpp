@@ -1,4 +1,4 @@
-// Device code shared by all eighteen translation units of libuvs_vision.so (uvs_vision.hip directly, the seventeen loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
+// Device code shared by all twenty translation units of libuvs_vision.so (uvs_vision.hip and uvs_camera_jacobian.hip directly, the eighteen loop and baseline units through camera_sensor_device.hpp): the detector's phase 2 in the two
 // forms its callers need, the disc geometry of the synthetic camera with its occluders and their paints, and the DH chain.  The summation order of the phase 2 is a contract
 // (see centre_of_mass): every unit that sums mask pixels goes through wave_partial and ColourSum, so they all give the same bits.
 #pragma once

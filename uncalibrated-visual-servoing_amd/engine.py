@@ -407,6 +407,92 @@ def camera_project(plant, q_prev, dq=None, dt=0.0, radius=None, q_out=None, out=
     return out
 
 
+def _jacobian_scene(who, plant, T, radius, cameras, camera_index, target_motion, motion_window, tensors):
+    """The refusals camera_jacobian and camera_jacobian_score share, all on the host alone and before any device work, then the operands:
+    (n_points, the scene triple, the motion pointer or None, tensors to keep alive).  Without ``cameras`` the camera of ``plant`` is packed
+    as the one scene.  ``tensors``: (name, tensor or None) pairs that must be fp64 (k_done: int32) tensors on the device."""
+    import torch                                                     # not _torch(): these refusals need no GPU
+    from . import plant as plant_mod
+    if cameras is None and camera_index is not None:
+        raise ValueError(f'{who}: camera_index without cameras')
+    cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    if cam.n_joints != 6:
+        raise ValueError(f'{who}: the image Jacobian kernels are built for the six-joint arms of this project, not for {cam.n_joints} joints')
+    motion = _check_target_motion(target_motion, motion_window, T, cam.n_points, who)
+    if cameras is None:
+        cameras = [cam]
+    _check_cameras(cameras, camera_index, T, cam.n_points, cam.n_joints, who)
+    for name, t in tensors:
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise ValueError(f'{who}: {name} is a tensor on the device')
+    dev = tensors[0][1].device
+    scenes, keep, keep_index = _scene_operand(cameras, camera_index, T, cam.n_points, cam.n_joints, radius, dev, who)
+    mot = None if motion is None else _motion_operand(motion, dev)
+    return cam.n_points, scenes, None if mot is None else mot[0], (keep, keep_index, mot)
+
+
+def camera_jacobian(plant, q, *, k=0, radius=None, cameras=None, camera_index=None, target_motion=None, motion_window=None, out=None):
+    """The TRUE image Jacobian dh/dq of the synthetic camera on the current stream (uvs_camera_jacobian_f64; the rule:
+    ``plant.projection_jacobian``), in pixels per radian -- no t_s in it; an estimator's X converges to fp.dt times it.  h is the (u, v)
+    row ``camera_project`` gives.  ``q`` (T, 6) fp64 on the device gives (T, m, 6), the Jacobian of trial t's scene at q[t] and step ``k``;
+    ``q`` (K, T, 6) -- a 'q' log -- gives (K, T, m, 6), row r at step ``k`` + r.  ``plant``, ``radius``, ``cameras`` / ``camera_index`` and
+    ``target_motion`` / ``motion_window`` are ``camera_project``'s: the scene of every trial, and where step k of its target's motion has
+    taken its points (``plant.target_at``).  Without ``cameras`` the camera of ``plant`` is the one scene.  A trial whose device-side index
+    names no camera gets NaNs.  ``out``: the tensor to fill, of the result's shape."""
+    from . import _vision
+    k = _check_step(k, 'camera_jacobian')
+    shape = tuple(getattr(q, 'shape', ()))
+    if len(shape) not in (2, 3) or shape[-1] != 6:
+        raise ValueError(f'camera_jacobian: q is (T, 6) or (K, T, 6) joints, got {shape}')
+    rows, T = (1, shape[0]) if len(shape) == 2 else shape[:2]
+    if k + rows > 2 ** 31 - 1:
+        raise ValueError(f'camera_jacobian: k + the rows of q must stay below 2^31, got {k} + {rows}')
+    npts, scenes, mot, _keep = _jacobian_scene('camera_jacobian', plant, T, radius, cameras, camera_index, target_motion, motion_window,
+                                               (('q', q), ('out', out)))
+    torch, dev = _torch(), q.device
+    result = shape[:-1] + (2 * npts, 6)
+    if out is None:
+        out = torch.empty(result, dtype=torch.float64, device=dev)
+    _vision.check(_vision.lib().uvs_camera_jacobian_f64(*scenes, mot, npts, T, rows, k, _operand(q, 'q', torch.float64, shape),
+                                                        _operand(out, 'out', torch.float64, result), _stream()))
+    return out
+
+
+SCORE_KEYS = ('rel_err', 'cosine', 'scale', 'shape_err', 'step_ratio')
+
+
+def camera_jacobian_score(x, q, plant, dt, *, dq=None, k_done=None, radius=None, cameras=None, camera_index=None, target_motion=None,
+                          motion_window=None):
+    """Score a stream of Jacobian estimates against the true image Jacobian, on the current stream (uvs_camera_jacobian_score_f64; the
+    rule: ``plant.jacobian_score`` and ``plant.score_ratios``).  ``x`` (K, T, m 6) and ``q`` (K, T, 6): the 'x' and 'q' logs of
+    ``camera_closed_loop``; ``dt``: fp.dt -- X is scored against Js = dt * ``camera_jacobian``(q), what the estimators' measurement model
+    makes it converge to; ``dq`` (K, T, 6) or None: the 'dq' log; ``k_done`` (T,) int32 or None: rows k >= k_done[t] of the logs are
+    unspecified, are not read, and score NaN.  The scene arguments are ``camera_jacobian``'s, with step k for row k.  So
+        out = camera_closed_loop(fp, plant, q0, noise, fused=True, want=ESTIMATOR_CAMERA_LOGS)
+        score = camera_jacobian_score(plant=plant, dt=fp.dt, **{k: out[k] for k in ('x', 'q', 'dq', 'k_done')})
+    Returns a dict of (K, T) tensors -- 'rel_err' = |X - Js| / |Js|; 'cosine'; 'scale' = the s minimising |X - s Js|; 'shape_err' = the
+    sine of the angle between them; 'step_ratio' = (X dq) . (Js dq) / |X dq|^2, the share of the displacement X promises that the plant
+    delivers (NaN without ``dq``, or where X dq == 0) -- and 'sums' (K, T, 6): nx2, nj2, dot, diff2, xd_xd, xd_jd as the kernel wrote them."""
+    from . import _vision, plant as plant_mod
+    shape = tuple(getattr(q, 'shape', ()))
+    if len(shape) != 3 or shape[-1] != 6:
+        raise ValueError(f'camera_jacobian_score: q is the (K, T, 6) log of the joints, got {shape}')
+    K, T = shape[:2]
+    if isinstance(dt, bool) or not isinstance(dt, (int, float, np.integer, np.floating)):
+        raise ValueError(f'camera_jacobian_score: dt is the control period, a number, got {dt!r}')
+    npts, scenes, mot, _keep = _jacobian_scene('camera_jacobian_score', plant, T, radius, cameras, camera_index, target_motion, motion_window,
+                                               (('q', q), ('x', x), ('dq', dq), ('k_done', k_done)))
+    torch, dev = _torch(), q.device
+    sums = torch.empty((K, T, 6), dtype=torch.float64, device=dev)
+    _vision.check(_vision.lib().uvs_camera_jacobian_score_f64(
+        *scenes, mot, npts, T, K, float(dt), _operand(x, 'x', torch.float64, (K, T, 2 * npts * 6)), _operand(q, 'q', torch.float64, shape),
+        _operand(dq, 'dq', torch.float64, shape, True), _operand(k_done, 'k_done', torch.int32, (T,), True), sums.data_ptr(), _stream()))
+    out = plant_mod.score_ratios(sums, torch)
+    if dq is None:
+        out['step_ratio'] = torch.full_like(out['step_ratio'], float('nan'))
+    return dict(out, sums=sums)
+
+
 def _discs_arg(discs, n_colours):
     torch = _torch()
     if not torch.is_tensor(discs) or discs.dim() != 3 or tuple(discs.shape[1:]) != (int(n_colours), 3):
@@ -934,6 +1020,7 @@ def camera_analytical_step(plant, q, f, fp, radius=None, dq=None, err=None, j=No
 
 CAMERA_LOGS = ('err', 'q', 'f', 'dq', 'kappa')
 ANALYTICAL_CAMERA_LOGS = ('err', 'q', 'f', 'dq')                    # the calibrated law has no correntropy weights
+ESTIMATOR_CAMERA_LOGS = CAMERA_LOGS + ('x',)                         # the estimators can log the estimate itself: X_k, (K, T, m n)
 
 
 def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=None, scenes=None, motion=None, latency=None, steps=0):
@@ -1177,7 +1264,9 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     ``assumed``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the ASSUMED latencies of the T output trials next to
     ``scenes`` -- the launch is then uvs_camera_closed_loop_aligned_f64, with or without ``latency`` and ``motion``.
     ``predict``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the prediction HORIZONS of the T output trials next to
-    ``scenes`` -- the launch is then uvs_camera_closed_loop_predicted_f64, with or without the three above."""
+    ``scenes`` -- the launch is then uvs_camera_closed_loop_predicted_f64, with or without the three above.
+    'x' in ``want`` (camera_closed_loop has made ``scenes``): the launch is uvs_camera_closed_loop_logged_f64, whatever else is given, and
+    the result has 'x' (K, T, m n): X_k after step k's update, rows k < k_done."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -1201,8 +1290,8 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     if x0 is None:
         raise ValueError("camera_closed_loop: fused=True takes x0, or guess='device' with fp.initial_guess")
     X0 = torch.as_tensor(x0, **f64).reshape(n_in, m * n).contiguous()
-    comps = dict(err=m, q=n, f=m, dq=n, kappa=m)
-    log = {key: torch.empty((K, T, comps[key]), **f64) for key in CAMERA_LOGS if key in want}
+    comps = dict(err=m, q=n, f=m, dq=n, kappa=m, x=m * n)
+    log = {key: torch.empty((K, T, comps[key]), **f64) for key in ESTIMATOR_CAMERA_LOGS if key in want}
     ptr = lambda key: log[key].data_ptr() if key in log else None   # noqa: E731
     status, k_done = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2))
     stats = torch.empty((T, 3), **f64)
@@ -1213,7 +1302,13 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
         held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
         rest = (T, None if tp is None else C.byref(tp), None if occ is None else occ[0], None if paint is None else paint[0],
                 0 if occ is None else occ[1], hold, *operands[:-1], None if held is None else held.data_ptr(), operands[-1])
-        if predict is not None:
+        if 'x' in log:                                               # operands[8] is kappa_log: x_log stands directly after it
+            rest = rest[:15] + (log['x'].data_ptr(),) + rest[15:]
+            rc = _vision.lib().uvs_camera_closed_loop_logged_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0],
+                                                                 None if latency is None else latency[0],
+                                                                 None if assumed is None else assumed[0],
+                                                                 None if predict is None else predict[0], *rest)
+        elif predict is not None:
             rc = _vision.lib().uvs_camera_closed_loop_predicted_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0],
                                                                     None if latency is None else latency[0],
                                                                     None if assumed is None else assumed[0], predict[0], *rest)
@@ -1408,7 +1503,16 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     fused=False: ANALYTICAL projects the law's models at rows k and max(k - p, 0) of the 'q' log and applies the rule's two torch
     operations per step, with the one launch's bits; the estimators refuse (ValueError 'predict needs fused=True': the two-launch step
     forms err inside libuvs_rmckf.so).  Next to trial_params['source'] it is by output trial.  ValueErrors before any device work, after
-    assumed_latency's: the same as for ``latency``, naming predict."""
+    assumed_latency's: the same as for ``latency``, naming predict.
+    ``'x'`` in ``want`` (``ESTIMATOR_CAMERA_LOGS`` is ``CAMERA_LOGS + ('x',)``; ``CAMERA_LOGS`` stays the default): THE ESTIMATE AS A LOG, for
+    the estimators -- the result has 'x' (K, T, m n): row k is X_k, the matrix after step k's update, the one step k's control law (and
+    prediction) read; element i n + j is X[i][j], the layout of ``x0``; rows at and after k_done are unspecified, like those of 'err'.
+    fused=True is ONE launch through uvs_camera_closed_loop_logged_f64, whatever else is given: the nominal camera stands in as the one
+    scene, exactly as for ``latency`` without ``cameras`` (six joints, or a ValueError), and ``x0`` / ``guess`` are handled as on that
+    route.  fused=False copies the step kernel's X tensor into row k after every step call; the two return the same bits.  ANALYTICAL has
+    no 'x': the ValueError it always was.  Without 'x' every call takes the route and the entry point it always took.
+    ``camera_jacobian_score`` takes the result: ``camera_jacobian_score(plant=plant, dt=fp.dt, **{k: out[k] for k in ('x', 'q', 'dq',
+    'k_done')})``."""
     from . import _vision, plant as plant_mod
     if guess not in ('host', 'device'):
         raise ValueError("camera_closed_loop: guess is 'host' or 'device'")
@@ -1482,6 +1586,11 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     if (delays is not None or tolds is not None or horizons is not None) and cameras is None and not nominal:   # the nominal camera stands in as the one scene here too
         if fp.n != 6:
             raise ValueError(f'camera_closed_loop: the camera-latency kernels are built for the six-joint arms of this project, not for {fp.n} joints')
+        nominal = True
+    want_x = not analytical and 'x' in tuple(want)                   # the estimate itself as a log: X_k of every step
+    if want_x and fused and cameras is None and not nominal:         # the one-launch X log is a scenes kernel: the nominal camera stands in here too
+        if fp.n != 6:
+            raise ValueError(f"camera_closed_loop: the kernels that log 'x' are built for the six-joint arms of this project, not for {fp.n} joints")
         nominal = True
     if fused and not getattr(q_start, 'is_cuda', False):
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
@@ -1572,6 +1681,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
                                          None if paint is None else paint[1], scenes, mot, lat, told, ahead)
     P = torch.eye(n, **f64).repeat(T, m, 1, 1).contiguous()          # P = I (experiment.py:73)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in (('err', m), ('q', n), ('f', m), ('dq', n), ('kappa', m))}
+    x_log = torch.empty((K, T, m * n), **f64) if want_x else None    # row k: the step kernel's X after step k
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
     pixel_log = torch.zeros((K, T, npts), dtype=torch.int32, device=dev)
     dq_zero = torch.zeros((T, n), **f64)
@@ -1599,6 +1709,10 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
             regressor = told_dq.data_ptr()
         _lib.check(step(fp_ref, T, X.data_ptr(), P.data_ptr(), at('f', k), f_old, regressor, int(k == 0), k,
                         at('dq', k), at('err', k), at('kappa', k), at('status', k), stream))
+        if x_log is not None:
+            x_log[k].copy_(X)
+    if x_log is not None:
+        log['x'] = x_log
     return _reduce_camera_logs(fp, log, status_log, pixel_log, want, held_log)
 
 

@@ -476,6 +476,81 @@ def prediction_steps(k, p):
     return list(range(k - 1, max(k - min(max(p, 0), MAX_LATENCY), 0) - 1, -1))
 
 
+def projection_jacobian(plant, q, points=None):
+    """The TRUE image Jacobian dh/dq of ``plant`` at joints ``q`` (6,), (2 n_points, 6) in pixels per radian -- no t_s in it: the numpy
+    statement of the rule uvs_camera_jacobian_f64 (include/uvs_vision.h) is held to.  h = ``plant.features``; ``points`` (n_points, 3)
+    replaces the plant's world points (a moved target: ``target_at(...).points``).  With T6 = fkine(q), R and c its rotation and origin,
+    [v_j; w_j] column j of ``SyntheticPlant.jacobian`` and p = R^T (w - c) for a world point w:
+        dp/dq_j = -R^T (w_j x (w - c) + v_j)
+        du/dq_j = focal (dp_x / p_z - p_x dp_z / p_z^2), dv/dq_j likewise with p_y.
+    That is the interaction row at the CENTRED pixels with the depth ALONG THE OPTICAL AXIS applied to the camera-frame twist;
+    ``analytic_guess`` (uncentred pixels, the camera-disc distance, no t_s) is not this matrix.  What an estimator's X converges to is
+    t_s times it: z = X dq with dq a velocity and q += dq t_s."""
+    q = np.asarray(q, float)
+    Ts = plant.fkine_all(q)
+    R, c = Ts[-1][:3, :3], Ts[-1][:3, 3]
+    Jg = plant.jacobian(Ts)
+    points = np.asarray(plant.points if points is None else points, float)
+    out = np.empty((2 * len(points), plant.n_joints))
+    with np.errstate(all='ignore'):
+        for i, w in enumerate(points):
+            p = R.T @ (w - c)
+            for j in range(plant.n_joints):
+                dp = -R.T @ (np.cross(Jg[3:, j], w - c) + Jg[:3, j])
+                out[2 * i, j] = plant.focal * (dp[0] / p[2] - p[0] * dp[2] / p[2] ** 2)
+                out[2 * i + 1, j] = plant.focal * (dp[1] / p[2] - p[1] * dp[2] / p[2] ** 2)
+    return out
+
+
+SCORE_SUMS = ('nx2', 'nj2', 'dot', 'diff2', 'xd_xd', 'xd_jd')
+
+
+def jacobian_score(X, Js, dq=None):
+    """The six sums uvs_camera_jacobian_score_f64 (include/uvs_vision.h) is held to, for an estimate ``X`` against a scaled true Jacobian
+    ``Js`` = t_s * ``projection_jacobian``: (..., m, n) arrays, or (..., m n) for X as the logs hold it; ``dq`` (..., n) or None.  Returns
+    (..., 6) in the order of ``SCORE_SUMS``: nx2 = sum X^2, nj2 = sum Js^2, dot = sum X Js, diff2 = sum (X - Js)^2, each over (i, j) in
+    row-major order from 0.0; xd_xd = |X dq|^2 and xd_jd = (X dq) . (Js dq), 0.0 without ``dq``.  ``score_ratios`` turns them into
+    rel_err, cosine, scale, shape_err and step_ratio."""
+    Js = np.asarray(Js, float)
+    m, n = Js.shape[-2:]
+    X = np.asarray(X, float)
+    X = X.reshape(X.shape[:-1] + (m, n)) if X.shape[-1] == m * n and X.shape[-2:] != (m, n) else X
+    X, Js = np.broadcast_arrays(X, Js)
+    out = np.zeros(X.shape[:-2] + (6,))
+    with np.errstate(all='ignore'):
+        for i in range(m):
+            for j in range(n):
+                x, js = X[..., i, j], Js[..., i, j]
+                out[..., 0] += x * x
+                out[..., 1] += js * js
+                out[..., 2] += x * js
+                out[..., 3] += (x - js) * (x - js)
+        if dq is not None:
+            dq = np.asarray(dq, float)
+            xd, jd = np.zeros(X.shape[:-1]), np.zeros(X.shape[:-1])
+            for j in range(n):
+                xd += X[..., :, j] * dq[..., None, j]
+                jd += Js[..., :, j] * dq[..., None, j]
+            for i in range(m):
+                out[..., 4] += xd[..., i] * xd[..., i]
+                out[..., 5] += xd[..., i] * jd[..., i]
+    return out
+
+
+def score_ratios(sums, xp=np):
+    """What the six sums say, as a dict of arrays of the leading shape (``xp``: numpy, or torch for tensors): rel_err = sqrt(diff2 / nj2);
+    cosine = dot / sqrt(nx2 nj2); scale = dot / nj2, the s that minimises |X - s Js|; shape_err = sqrt(max(nx2 nj2 - dot^2, 0) /
+    (nx2 nj2)), the sine of the angle between them; step_ratio = xd_jd / xd_xd, the share of the displacement X promises for dq that the
+    plant delivers (NaN where dq was not given or X dq == 0)."""
+    nx2, nj2, dot, diff2, xd_xd, xd_jd = (sums[..., i] for i in range(6))
+    with np.errstate(all='ignore'):                              # 0 / 0 is the NaN it should be
+        both = nx2 * nj2
+        gap = both - dot * dot
+        gap = xp.where(gap < 0, xp.zeros_like(gap), gap)         # keeps a NaN a NaN
+        return {'rel_err': xp.sqrt(diff2 / nj2), 'cosine': dot / xp.sqrt(both), 'scale': dot / nj2, 'shape_err': xp.sqrt(gap / both),
+                'step_ratio': xd_jd / xd_xd}
+
+
 class LinearPlant:
     """Consistent linearised camera f = f0 + J (q - q0) for shapes without a DH model (BASELINE config 5: m = 32, n = 7;
     a 7-joint arm would be redundant for a 6-DoF camera pose and leave the feature Jacobian rank 6).  J, f0, q0 are uploaded
