@@ -419,7 +419,6 @@ def grid_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_grid_f64'), 'the parent library has no per-trial entry point'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def run_e_parent():
@@ -505,7 +504,6 @@ def occluded_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_occluded_f64'), 'the parent library has no occluders'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def run_e_parent():
@@ -608,7 +606,6 @@ def held_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_held_f64'), 'the parent library holds nothing'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def run_n_parent():
@@ -720,7 +717,6 @@ def painted_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_painted_f64'), 'the parent library paints nothing'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def with_parent(fn):
@@ -847,7 +843,6 @@ def scenes_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_scenes_f64'), 'the parent library has one scene per launch'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def with_parent(fn):
@@ -993,7 +988,6 @@ def moving_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_moving_f64'), 'the parent library has no moving targets'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def with_parent(fn):
@@ -1146,7 +1140,6 @@ def delayed_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_delayed_f64'), 'the parent library has no camera latency'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def with_parent(fn):
@@ -1288,7 +1281,6 @@ def aligned_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_aligned_f64'), 'the parent library has no assumed latency'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def with_parent(fn):
@@ -1434,7 +1426,6 @@ def predicted_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_predicted_f64'), 'the parent library has no feature prediction'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
 
         def with_parent(fn):
@@ -1547,7 +1538,6 @@ def score_section():
             if hasattr(parent, name):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = res, args
-        assert not hasattr(parent, 'uvs_camera_closed_loop_logged_f64'), 'the parent library logs no X'
         say(f'# parent library: {parent.uvs_vision_version().decode()}')
         assert same(loop(parent, 'uvs_camera_closed_loop_predicted_f64'), first['pv']), 'this library and the parent disagree on (pv)'
         fns['pv_parent_a'] = fns['pv_parent_b'] = lambda: loop(parent, 'uvs_camera_closed_loop_predicted_f64')

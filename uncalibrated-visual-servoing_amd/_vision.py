@@ -60,31 +60,18 @@ SYMBOLS = {
     'uvs_render_discs_occluded_u8': (C.c_int, [_I64, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _VP, _I64, _VP]),
     'uvs_disc_features_occluded_f64': (C.c_int, [_I64, _VP, _I32, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     'uvs_camera_features_occluded_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
-    # fp (a pointer to _lib.FilterParams, passed with byref), cam, T, q_start, noise, x0, f0, five logs, status, k_done, stats, pixels, stream
-    'uvs_camera_closed_loop_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 14),
-    # the same with tp (a pointer to CameraTrialParams, passed with byref) after T
-    'uvs_camera_closed_loop_grid_f64': (C.c_int, [_VP, _CAM, _I64, _VP] + [_VP] * 14),
-    # the same with tp (or None), occ and n_occ after T
-    'uvs_camera_closed_loop_occluded_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _I32] + [_VP] * 14),
-    # the same with hold after n_occ and held (or None) after pixels
-    'uvs_camera_closed_loop_held_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
-    # the four occluded (held) calls with the paints (device int32 [T][n_occ] or None) directly after occ
+    # the three occluded calls with the paints (device int32 [T][n_occ] or None) directly after occ
     'uvs_render_discs_painted_u8': (C.c_int, [_I64, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _I32, _VP, _I64, _VP]),
     'uvs_disc_features_painted_f64': (C.c_int, [_I64, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     'uvs_camera_features_painted_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
-    'uvs_camera_closed_loop_painted_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
     # T, n_points, hold, k, f_prev_row, f_row, pixels_row, miss, held_row, stream
     'uvs_hold_features_f64': (C.c_int, [_I64, _I32, _I32, _I32] + [_VP] * 6),
     'uvs_camera_guess_f64': (C.c_int, [_CAM, _I64, _VP, _VP, _VP, _VP]),
     # fp, cam, T, q, f, dq_out, err_out, j_out, status, stream
     'uvs_camera_analytical_step_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 7),
-    # fp, cam, T, q_start, noise, four logs, status, k_done, stats, pixels, stream
-    'uvs_camera_analytical_loop_f64': (C.c_int, [_VP, _CAM, _I64] + [_VP] * 11),
     # the believed operand is (believed: device array of Camera, n_believed, believed_index: device int32 [T] or None)
     # fp, T, believed operand, q, f, dq_out, err_out, j_out, status, stream
     'uvs_camera_believed_step_f64': (C.c_int, [_VP, _I64, _VP, _I64, _VP] + [_VP] * 7),
-    # fp, cam, T, believed operand, q_start, noise, four logs, status, k_done, stats, pixels, stream
-    'uvs_camera_believed_loop_f64': (C.c_int, [_VP, _CAM, _I64, _VP, _I64, _VP] + [_VP] * 11),
     # T, n_points, believed operand, q_start, f0, x0_out, stream
     'uvs_camera_believed_guess_f64': (C.c_int, [_I64, _I32, _VP, _I64, _VP] + [_VP] * 4),
     # the scene operand is (cams: device array of Camera, n_cams, cam_index: device int32 [T] or None): it stands where the namesake has cam
@@ -92,35 +79,46 @@ SYMBOLS = {
     'uvs_camera_project_scenes_f64': (C.c_int, [_VP, _I64, _VP, _I32, _I64, _VP, _VP, _F64, _VP, _VP, _VP]),
     # scene operand, n_points, T, q_prev, dq, dt, q_out, occ, paint, n_occ, k, noise, f_out, pixels_out, discs_out, stream
     'uvs_camera_features_scenes_f64': (C.c_int, [_VP, _I64, _VP, _I32, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
-    # fp, scene operand, then uvs_camera_closed_loop_painted_f64's operands from T on
-    'uvs_camera_closed_loop_scenes_f64': (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
-    # fp, scene operand, then uvs_camera_believed_loop_f64's operands from T on
-    'uvs_camera_believed_loop_scenes_f64': (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
-    # moving targets: the four scenes calls with motion (device array of TargetMotion [T] or None) directly after the scene operand; the
+    # moving targets: the two scenes calls with motion (device array of TargetMotion [T] or None) directly after the scene operand; the
     # project call, which has no k, takes it after dt
     'uvs_camera_project_moving_f64': (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I64, _VP, _VP, _F64, _I32, _VP, _VP, _VP]),
     'uvs_camera_features_moving_f64': (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I64, _VP, _VP, _F64, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP,
                                                  _VP]),
-    'uvs_camera_closed_loop_moving_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
-    'uvs_camera_believed_loop_moving_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
-    # camera latency: the two moving loops with latency (device int32 [T] or None) directly after motion
-    'uvs_camera_closed_loop_delayed_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
-    'uvs_camera_believed_loop_delayed_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
     # T, n_points, k, latency, sensed_log, count_log, noise_row, f_row, pixels_row, stream
     'uvs_delay_features_f64': (C.c_int, [_I64, _I32, _I32] + [_VP] * 7),
-    # assumed latency: the two delayed loops with assumed (device int32 [T] or None) directly after latency
-    'uvs_camera_closed_loop_aligned_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
-    'uvs_camera_believed_loop_aligned_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
-    # feature prediction: the two aligned loops with predict (device int32 [T] or None) directly after assumed
-    'uvs_camera_closed_loop_predicted_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 13 + [_VP, _VP]),
-    'uvs_camera_believed_loop_predicted_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP] + [_VP] * 11),
-    # the estimate as a log: the predicted estimator loop with x_log (device float64 [K][T][m n] or None) directly after kappa_log
-    'uvs_camera_closed_loop_logged_f64': (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I32, _I32] + [_VP] * 14 + [_VP, _VP]),
     # the true image Jacobian: scene operand, motion, n_points, T, rows, k0, q, j_out, stream
     'uvs_camera_jacobian_f64': (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I64, _I64, _I32, _VP, _VP, _VP]),
     # an X stream scored against it: scene operand, motion, n_points, T, K, dt, x_log, q_log, dq_log, k_done, score, stream
     'uvs_camera_jacobian_score_f64': (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I64, _I64, _F64, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
+
+# The one-launch pixel loops.  A family's entry points are a chain of flavours, each the previous one plus operands (csrc_vision/
+# camera_loop_device.hpp, camera_analytical_device.hpp): entry point f of a family takes, in this order, the operands of its table whose
+# (first, last) flavours enclose f.  Pointers are device pointers or None; fp and tp are structs passed with byref, cam a Camera likewise;
+# (cams, n_cams, cam_index) is the scene operand, which stands where the lower flavours have cam; (believed, n_believed, believed_index)
+# the believed operand.
+ESTIMATOR_LOOPS = tuple('uvs_camera_closed_loop_' + flavour + 'f64' for flavour in (
+    '', 'grid_', 'occluded_', 'held_', 'painted_', 'scenes_', 'moving_', 'delayed_', 'aligned_', 'predicted_', 'logged_'))
+ESTIMATOR_LOOP_OPERANDS = (
+    ('fp', _VP, 0, 10), ('cam', _CAM, 0, 4), ('cams', _VP, 5, 10), ('n_cams', _I64, 5, 10), ('cam_index', _VP, 5, 10), ('motion', _VP, 6, 10),
+    ('latency', _VP, 7, 10), ('assumed', _VP, 8, 10), ('predict', _VP, 9, 10), ('T', _I64, 0, 10), ('tp', _VP, 1, 10), ('occ', _VP, 2, 10),
+    ('paint', _VP, 4, 10), ('n_occ', _I32, 2, 10), ('hold', _I32, 3, 10), ('q_start', _VP, 0, 10), ('noise', _VP, 0, 10), ('x0', _VP, 0, 10),
+    ('f0', _VP, 0, 10), ('q_log', _VP, 0, 10), ('f_log', _VP, 0, 10), ('dq_log', _VP, 0, 10), ('err_log', _VP, 0, 10), ('kappa_log', _VP, 0, 10),
+    ('x_log', _VP, 10, 10), ('status', _VP, 0, 10), ('k_done', _VP, 0, 10), ('stats', _VP, 0, 10), ('pixels', _VP, 0, 10), ('held', _VP, 3, 10),
+    ('stream', _VP, 0, 10))
+BASELINE_LOOPS = ('uvs_camera_analytical_loop_f64',) + tuple('uvs_camera_believed_loop_' + flavour + 'f64' for flavour in (
+    '', 'scenes_', 'moving_', 'delayed_', 'aligned_', 'predicted_'))
+BASELINE_LOOP_OPERANDS = (
+    ('fp', _VP, 0, 6), ('cam', _CAM, 0, 1), ('cams', _VP, 2, 6), ('n_cams', _I64, 2, 6), ('cam_index', _VP, 2, 6), ('motion', _VP, 3, 6),
+    ('latency', _VP, 4, 6), ('assumed', _VP, 5, 6), ('predict', _VP, 6, 6), ('T', _I64, 0, 6), ('believed', _VP, 1, 6), ('n_believed', _I64, 1, 6),
+    ('believed_index', _VP, 1, 6), ('q_start', _VP, 0, 6), ('noise', _VP, 0, 6), ('q_log', _VP, 0, 6), ('f_log', _VP, 0, 6), ('dq_log', _VP, 0, 6),
+    ('err_log', _VP, 0, 6), ('status', _VP, 0, 6), ('k_done', _VP, 0, 6), ('stats', _VP, 0, 6), ('pixels', _VP, 0, 6), ('stream', _VP, 0, 6))
+LOOP_OPERANDS = {}                                                  # entry point -> the names of its operands, in the order of its prototype
+for _names, _table in ((ESTIMATOR_LOOPS, ESTIMATOR_LOOP_OPERANDS), (BASELINE_LOOPS, BASELINE_LOOP_OPERANDS)):
+    for _flavour, _name in enumerate(_names):
+        _taken = [row for row in _table if row[2] <= _flavour <= row[3]]
+        LOOP_OPERANDS[_name] = tuple(row[0] for row in _taken)
+        SYMBOLS[_name] = (C.c_int, [row[1] for row in _taken])
 
 _lib = None
 
@@ -150,6 +148,11 @@ def lib():
             fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib
+
+
+def call_loop(name, values):
+    """Loop entry point ``name`` on the operands it takes, picked by name from ``values`` (a dict that may hold more); its return code."""
+    return getattr(lib(), name)(*(values[operand] for operand in LOOP_OPERANDS[name]))
 
 
 class UvsVisionError(UvsError):

@@ -2,22 +2,26 @@
 // frames, uniform over the launch) and uvs_camera_believed.hip (the model is a per-trial uvs_camera read from memory).  Two things live here.
 // (1) The step, analytical_step, which every kernel of the two units calls.  Both compile it with -ffp-contract=off on the same operands in
 // the same order, so a believed model that equals the true one gives the bits of the calibrated kernels.
-// (2) The pixel loop as ONE launch per batch: one kernel text in two flavours, chosen per TRANSLATION UNIT as camera_loop_device.hpp chooses
-// its four.  A unit that defines UVS_CAMERA_BELIEVED before it includes this header sees camera_believed_loop_kernel(BLoopArgs): the control
+// (2) The pixel loop as ONE launch per batch: one kernel text in seven flavours, chosen per TRANSLATION UNIT as camera_loop_device.hpp chooses
+// its eleven: a unit states ONE integer before it includes this header, #define UVS_BASELINE_FLAVOUR <0 .. 6>, a value of BaselineFlavour
+// below.  The flavours are a strict chain, so every switch of the kernel text is a comparison of that level, and the level alone picks the
+// argument block (BaselineLoopArgsList) and the kernel's name (UVS_BASELINE_KERNEL_<f>).  The host side is shared too: every loop entry
+// point fills a BaselineRequest from its parameters and calls run_baseline_loop (at the end of this header).
+// Level kBaselineCalibrated (uvs_camera_analytical.hip) is camera_analytical_loop_kernel(ALoopArgs): one model, taken from the kernel
+// argument, every trial known.  Level kBaselineWithModel (uvs_camera_believed.hip) is camera_believed_loop_kernel(BLoopArgs): the control
 // side's model of every trial is staged from memory into s_cam[G], and a trial whose index names no model starts FAILed (not alive, not seen),
-// so that it logs no row and writes status and k_done alone.  Every other unit sees camera_analytical_loop_kernel(ALoopArgs): one model, taken
-// from the kernel argument, every trial known.  Same names, argument blocks, registers and LDS as when each was written out in its unit.
-// A unit that defines UVS_CAMERA_SCENES (uvs_camera_scenes_baseline.hip) sees a third flavour, scene_baseline_loop_kernel(SLoopArgs): the
+// so that it logs no row and writes status and k_done alone.  Same names, argument blocks, registers and LDS as when each was written out in its unit.
+// Level kBaselineWithScenes (uvs_camera_scenes_baseline.hip) is a third flavour, scene_baseline_loop_kernel(SLoopArgs): the
 // believed one whose sensor side reads the trial's own camera as well, from a second staged array.
-// A unit that defines UVS_CAMERA_MOVING (uvs_camera_moving_baseline.hip) sees a fourth, moving_baseline_kernel(MovingBaselineArgs): the scenes
+// Level kBaselineWithMotion (uvs_camera_moving_baseline.hip) is a fourth, moving_baseline_kernel(MovingBaselineArgs): the scenes
 // one whose sensor side projects every disc where its trial's motion has taken it.  The law's model does not move.
-// A unit that defines UVS_CAMERA_DELAYED on top (uvs_camera_delayed_baseline.hip) sees a fifth, delayed_baseline_kernel(DelayedBaselineArgs): the
+// Level kBaselineWithLatency (uvs_camera_delayed_baseline.hip) is a fifth, delayed_baseline_kernel(DelayedBaselineArgs): the
 // moving one whose detector is handed the frame of step max(k - d, 0), d the trial's latency, through an LDS ring of detections per disc
 // (DESIGN.md 4.24).  The law's joints stay the current ones.
-// A unit that defines UVS_CAMERA_ALIGNED on top (uvs_camera_aligned_baseline.hip) sees a sixth, aligned_baseline_kernel(AlignedBaselineArgs): the
+// Level kBaselineWithAssumed (uvs_camera_aligned_baseline.hip) is a sixth, aligned_baseline_kernel(AlignedBaselineArgs): the
 // delayed one whose law is told a latency -- the joints handed to analytical_step at step k are q_{max(k - a, 0)}, a the trial's ASSUMED
 // latency, through s_q as a ring of the last nine steps' joints.  The q log and the joint integration stay current.
-// A unit that defines UVS_CAMERA_PREDICTED on top (uvs_camera_predicted_baseline.hip) sees a seventh, predicted_baseline_kernel(PredictedBaselineArgs):
+// Level kBaselineWithHorizon (uvs_camera_predicted_baseline.hip) is a seventh, predicted_baseline_kernel(PredictedBaselineArgs):
 // the aligned one whose law is handed f^ = f_reported + (h(q_k) - h(q_{max(k - p, 0)})), p the trial's prediction HORIZON and h the (u, v) the
 // projection kernel gives for the law's own model.  The sensor-side wavefront of a trial projects the law's model at q_k
 // next to the scene, once per step, into slot k mod 9 of the ring s_h -- lanes N .. 2 N - 1 take the model's sines in the sincos call that
@@ -103,7 +107,7 @@ struct BLoopArgs {
     int32_t *pixels;
 };
 
-// The third flavour (a unit that defines UVS_CAMERA_SCENES, uvs_camera_scenes_baseline.hip): scene_baseline_loop_kernel, the
+// The third flavour (level kBaselineWithScenes, uvs_camera_scenes_baseline.hip): scene_baseline_loop_kernel, the
 // believed flavour whose SENSOR side reads the trial's own camera too, from a second staged array, s_scene[G].  `cam` is the shape alone.
 struct SLoopArgs {
     uvs_filter_params fp;
@@ -118,87 +122,56 @@ struct SLoopArgs {
     int32_t *pixels;
 };
 
-// The fourth flavour (a unit that defines UVS_CAMERA_MOVING, uvs_camera_moving_baseline.hip): moving_baseline_kernel, the scenes
+// The fourth flavour (level kBaselineWithMotion, uvs_camera_moving_baseline.hip): moving_baseline_kernel, the scenes
 // flavour with a motion per OUTPUT trial, staged into s_mot[G] next to the scenes.  The SENSOR side's points move; the law's model stays.
 struct MovingBaselineArgs : SLoopArgs {
     const uvs_target_motion *motion;                             // [T] by output trial, or NULL: nothing moves
 };
 
-// The fifth flavour (a unit that defines UVS_CAMERA_DELAYED too, uvs_camera_delayed_baseline.hip): delayed_baseline_kernel, the
+// The fifth flavour (level kBaselineWithLatency, uvs_camera_delayed_baseline.hip): delayed_baseline_kernel, the
 // moving flavour with a latency per OUTPUT trial.  The detections go through s_ring; the law reads the current joints.
 struct DelayedBaselineArgs : MovingBaselineArgs {
     const int32_t *latency;                                      // [T] by output trial, or NULL: none
 };
 
-// The sixth flavour (a unit that defines UVS_CAMERA_ALIGNED too, uvs_camera_aligned_baseline.hip): aligned_baseline_kernel, the
+// The sixth flavour (level kBaselineWithAssumed, uvs_camera_aligned_baseline.hip): aligned_baseline_kernel, the
 // delayed flavour with an ASSUMED latency per OUTPUT trial.  s_q is a ring; the law reads the joints of step max(k - a, 0).
 struct AlignedBaselineArgs : DelayedBaselineArgs {
     const int32_t *assumed;                                      // [T] by output trial, or NULL: none
 };
 
-// The seventh flavour (a unit that defines UVS_CAMERA_PREDICTED too, uvs_camera_predicted_baseline.hip): predicted_baseline_kernel,
+// The seventh flavour (level kBaselineWithHorizon, uvs_camera_predicted_baseline.hip): predicted_baseline_kernel,
 // the aligned flavour with a prediction HORIZON per OUTPUT trial.  s_h is a ring of the law's model's (u, v) at the last nine steps' joints.
 struct PredictedBaselineArgs : AlignedBaselineArgs {
     const int32_t *predict;                                      // [T] by output trial, or NULL: none
 };
 
-#if defined(UVS_CAMERA_PREDICTED)
-#if !defined(UVS_CAMERA_ALIGNED)
-#error "the predicted flavour is an aligned flavour: define UVS_CAMERA_ALIGNED, UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
+// The unit's flavour: the value it gave UVS_BASELINE_FLAVOUR.  Row f of the three tables below -- level, argument block, kernel name -- is one flavour.
+enum BaselineFlavour {
+    kBaselineCalibrated, kBaselineWithModel, kBaselineWithScenes, kBaselineWithMotion, kBaselineWithLatency, kBaselineWithAssumed,
+    kBaselineWithHorizon
+};
+using BaselineLoopArgsList = std::tuple<ALoopArgs, BLoopArgs, SLoopArgs, MovingBaselineArgs, DelayedBaselineArgs, AlignedBaselineArgs,
+                                        PredictedBaselineArgs>;
+#define UVS_BASELINE_KERNEL_0 camera_analytical_loop_kernel
+#define UVS_BASELINE_KERNEL_1 camera_believed_loop_kernel
+#define UVS_BASELINE_KERNEL_2 scene_baseline_loop_kernel
+#define UVS_BASELINE_KERNEL_3 moving_baseline_kernel
+#define UVS_BASELINE_KERNEL_4 delayed_baseline_kernel
+#define UVS_BASELINE_KERNEL_5 aligned_baseline_kernel
+#define UVS_BASELINE_KERNEL_6 predicted_baseline_kernel
+
+#ifndef UVS_BASELINE_FLAVOUR
+#error "state the unit's flavour before including this header: #define UVS_BASELINE_FLAVOUR <0 .. 6>, a value of BaselineFlavour"
 #endif
-constexpr bool kBaselinePredicted = true;
-#else
-constexpr bool kBaselinePredicted = false;
-#endif
-#if defined(UVS_CAMERA_ALIGNED)
-#if !defined(UVS_CAMERA_DELAYED)
-#error "the aligned flavour is a delayed flavour: define UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
-#endif
-constexpr bool kBaselineAligned = true;
-#else
-constexpr bool kBaselineAligned = false;
-#endif
-#if defined(UVS_CAMERA_DELAYED)
-constexpr bool kBaselineDelayed = true;
-#else
-constexpr bool kBaselineDelayed = false;
-#endif
-#if defined(UVS_CAMERA_DELAYED)
-#if !defined(UVS_CAMERA_MOVING) || !defined(UVS_CAMERA_SCENES)
-#error "the delayed flavour is a moving flavour: define UVS_CAMERA_MOVING and UVS_CAMERA_SCENES too"
-#endif
-constexpr bool kCameraBelieved = true, kBaselineScenes = true, kBaselineMoving = true;
-#if defined(UVS_CAMERA_PREDICTED)
-using BaselineLoopArgs = PredictedBaselineArgs;
-#define UVS_BASELINE_LOOP_KERNEL predicted_baseline_kernel
-#elif defined(UVS_CAMERA_ALIGNED)
-using BaselineLoopArgs = AlignedBaselineArgs;
-#define UVS_BASELINE_LOOP_KERNEL aligned_baseline_kernel
-#else
-using BaselineLoopArgs = DelayedBaselineArgs;
-#define UVS_BASELINE_LOOP_KERNEL delayed_baseline_kernel
-#endif
-#elif defined(UVS_CAMERA_MOVING)
-constexpr bool kCameraBelieved = true, kBaselineScenes = true, kBaselineMoving = true;
-using BaselineLoopArgs = MovingBaselineArgs;
-#define UVS_BASELINE_LOOP_KERNEL moving_baseline_kernel
-#elif defined(UVS_CAMERA_SCENES)
-constexpr bool kBaselineMoving = false;
-constexpr bool kCameraBelieved = true, kBaselineScenes = true;
-using BaselineLoopArgs = SLoopArgs;
-#define UVS_BASELINE_LOOP_KERNEL scene_baseline_loop_kernel
-#elif defined(UVS_CAMERA_BELIEVED)
-constexpr bool kBaselineMoving = false;
-constexpr bool kCameraBelieved = true, kBaselineScenes = false;
-using BaselineLoopArgs = BLoopArgs;
-#define UVS_BASELINE_LOOP_KERNEL camera_believed_loop_kernel
-#else
-constexpr bool kBaselineMoving = false;
-constexpr bool kBaselineScenes = false;
-constexpr bool kCameraBelieved = false;
-using BaselineLoopArgs = ALoopArgs;
-#define UVS_BASELINE_LOOP_KERNEL camera_analytical_loop_kernel
-#endif
+constexpr int kBaselineFlavour = UVS_BASELINE_FLAVOUR;
+static_assert(kBaselineFlavour >= kBaselineCalibrated && kBaselineFlavour <= kBaselineWithHorizon, "UVS_BASELINE_FLAVOUR is a value of BaselineFlavour");
+constexpr bool kCameraBelieved = kBaselineFlavour >= kBaselineWithModel, kBaselineScenes = kBaselineFlavour >= kBaselineWithScenes;
+constexpr bool kBaselineMoving = kBaselineFlavour >= kBaselineWithMotion, kBaselineDelayed = kBaselineFlavour >= kBaselineWithLatency;
+constexpr bool kBaselineAligned = kBaselineFlavour >= kBaselineWithAssumed, kBaselinePredicted = kBaselineFlavour >= kBaselineWithHorizon;
+using BaselineLoopArgs = std::tuple_element_t<kBaselineFlavour, BaselineLoopArgsList>;
+#define UVS_BASELINE_LOOP_KERNEL UVS_PASTE(UVS_BASELINE_KERNEL_, UVS_BASELINE_FLAVOUR)
+
 // Has `trial` a model?  Calibrated: always, folded away.  Believed: the same word in all 64 lanes of a sensor-side wavefront.
 __device__ __forceinline__ bool has_model(const ALoopArgs &, long long) { return true; }
 __device__ __forceinline__ bool has_model(const BLoopArgs &a, long long trial) { return model_of(a.B, trial) >= 0; }
@@ -488,6 +461,85 @@ inline int check_analytical(const uvs_filter_params *fp, const uvs_camera *cam, 
     if (fp->n != cam->n_joints) return fail(UVS_ERR_SHAPE, "%s", "fp->n must be cam->n_joints");
     if (fp->n != kJoints || (fp->m != 8 && fp->m != 6 && fp->m != 2)) return fail(UVS_ERR_SHAPE, "%s", "(m, n) must be (8, 6), (6, 6) or (2, 6)");
     return UVS_OK;
+}
+
+// What the entry points ask of the believed operand; before the first HIP call.
+inline int check_believed(const uvs_camera *believed, int64_t n_believed, const int32_t *believed_index, int64_t T) {
+    if (believed == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL believed");
+    if (n_believed < 1 || n_believed > INT32_MAX) return fail(UVS_ERR_ARG, "%s", "n_believed must be 1 .. 2^31 - 1");
+    if (believed_index == nullptr && n_believed != 1 && n_believed != T)
+        return fail(UVS_ERR_ARG, "%s", "without believed_index, n_believed must be 1 or T");
+    return UVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the one host path
+// Every operand a baseline loop can take.  An entry point fills the ones it has from its parameters; the others stay NULL / 0 and are not
+// read at its unit's flavour.  `cam` belongs to the flavours below kBaselineWithScenes, (cams, n_cams, cam_index) to those from it on.
+struct BaselineRequest {
+    const uvs_filter_params *fp;
+    const uvs_camera *cam;
+    const uvs_camera *cams;
+    int64_t n_cams;
+    const int32_t *cam_index;
+    const uvs_target_motion *motion;
+    const int32_t *latency, *assumed, *predict;
+    int64_t T;
+    const uvs_camera *believed;
+    int64_t n_believed;
+    const int32_t *believed_index;
+    const double *q_start, *noise;
+    double *q_log, *f_log, *dq_log, *err_log;
+    int32_t *status, *k_done;
+    double *stats;
+    int32_t *pixels;
+    void *stream;
+};
+
+// The unit's argument block from the request, member by name; a template so that a branch for a member the block does not have is discarded.
+// `cam`: the camera of the launch, or from kBaselineWithScenes on its shape alone.  static, like run_baseline_loop below: the body reads the
+// unit's own constants.
+template <class Args>
+static void fill_baseline_args(Args &A, const BaselineRequest &r, const uvs_camera &cam) {
+    A.fp = *r.fp; A.cam = cam; A.T = r.T;
+    A.q_start = r.q_start; A.noise = r.noise;
+    A.q_log = r.q_log; A.f_log = r.f_log; A.dq_log = r.dq_log; A.err_log = r.err_log;
+    A.status = r.status; A.k_done = r.k_done; A.stats = r.stats; A.pixels = r.pixels;
+    if constexpr (kCameraBelieved) { A.B.models = r.believed; A.B.n = r.n_believed; A.B.index = r.believed_index; }
+    if constexpr (kBaselineScenes) { A.S.models = r.cams; A.S.n = r.n_cams; A.S.index = r.cam_index; }
+    if constexpr (kBaselineMoving) A.motion = r.motion;          // NULL is legal: nothing moves
+    if constexpr (kBaselineDelayed) A.latency = r.latency;       // NULL is legal: no latency
+    if constexpr (kBaselineAligned) A.assumed = r.assumed;       // NULL is legal: the law is not told
+    if constexpr (kBaselinePredicted) A.predict = r.predict;     // NULL is legal: no prediction
+}
+
+// What every baseline loop entry point does, at the unit's flavour: the refusals that apply there, in the order the entry points always made
+// them -- q_start, then the outputs, then fp -- and before the first HIP call; T == 0 is a call that does nothing; the argument block; the
+// launch.  The flavours that take scenes derive the shape from fp, as the estimator loops' do.
+// static: the body differs from unit to unit under one signature, so it must not be merged across the library's units at link time.
+static int run_baseline_loop(const BaselineRequest &r) {
+    g_err[0] = '\0';
+    if (r.q_start == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL q_start");
+    if (r.status == nullptr || r.k_done == nullptr || r.stats == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL status, k_done or stats");
+    uvs_camera shape;
+    const uvs_camera *cam = r.cam;
+    if constexpr (kBaselineScenes) {
+        if (r.fp == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL fp");
+        shape = scene_shape(r.fp->n, r.fp->m / 2);               // the shape is fp's: no struct's own n_joints / n_points is read
+        cam = &shape;
+    }
+    if (const int rc = check_analytical(r.fp, cam, r.T)) return rc;
+    if (r.fp->steps < 1) return fail(UVS_ERR_ARG, "%s", "steps must be >= 1");
+    if constexpr (kCameraBelieved) {
+        if (const int rc = check_believed(r.believed, r.n_believed, r.believed_index, r.T)) return rc;
+    }
+    if constexpr (kBaselineScenes) {
+        if (const int rc = check_scenes(r.cams, r.n_cams, r.cam_index, r.T)) return rc;
+    }
+    if (r.T == 0) return UVS_OK;
+    BaselineLoopArgs A{};
+    fill_baseline_args(A, r, *cam);
+    launch_baseline_loop(*r.fp, static_cast<hipStream_t>(r.stream), A);
+    return launched(UVS_STR(UVS_BASELINE_LOOP_KERNEL) " launch: %s");
 }
 
 }  // namespace uvs_vision

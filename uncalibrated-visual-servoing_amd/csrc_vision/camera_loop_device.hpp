@@ -1,9 +1,12 @@
-// The pixel closed loop as ONE launch per batch: the one kernel text of uvs_camera_loop.hip (camera_loop_kernel, one uvs_filter_params for the
-// batch) and of uvs_camera_grid.hip (camera_grid_kernel, per-trial estimator parameters and a source index: a hyperparameter grid in one launch).
-// One text, two flavours, chosen per TRANSLATION UNIT as ../csrc does for closed_loop_grid_kernel: a unit that defines UVS_CAMERA_PER_TRIAL
-// before it includes this header sees the kernel as camera_grid_kernel(GridLoopArgs) with the switch PTP on; every other unit sees the uniform
-// kernel it always was -- same name, same argument block, same registers, LDS and time per instantiation.  (A shared
-// __device__ body behind two __global__ wrappers moved the register allocation there; nothing here is shared at run time.)
+// The pixel closed loop as ONE launch per batch: the one kernel text of the eleven estimator loop units, uvs_camera_loop.hip (camera_loop_kernel,
+// one uvs_filter_params for the batch) to uvs_camera_logged.hip.  One text, eleven flavours, chosen per TRANSLATION UNIT as ../csrc does for
+// closed_loop_grid_kernel: a unit states ONE integer before it includes this header, #define UVS_CAMERA_FLAVOUR <0 .. 10>, a value of
+// CameraFlavour below.  The flavours are a strict chain -- level f is level f - 1 plus one capability -- so every switch of the kernel text is
+// a comparison of that level, and the level alone picks the argument block (CameraLoopArgsList) and the kernel's name (UVS_CAMERA_KERNEL_<f>).
+// Every unit keeps its kernel's name, argument block, registers, LDS and time per instantiation.  (A shared __device__ body
+// behind several __global__ wrappers moved the register allocation there; nothing here is shared at run time.)
+// The host side is shared too: every entry point fills a LoopRequest from its parameters and calls run_camera_loop (at the end of this
+// header), which refuses, fills the unit's argument block member by name and launches.
 // The estimator is the one of libuvs_rmckf.so, read from its device header (Rows::update, control_law, bandwidth, bandwidth_of); the sensor
 // side is camera_sensor_device.hpp: inlined functions over this kernel's LDS rows, which the baseline loop (camera_analytical_device.hpp)
 // calls too, together with the mapping's constants and the launch decision.  Both libraries compile with -ffp-contract=off, so every
@@ -33,27 +36,27 @@
 // the register array that held fp's.  A source index outside [0, n_in) never becomes an address: the trial is `void`, computes on input
 // trial 0 so that every barrier is still reached, counts as failed for the early exit, and stores status FAIL, k_done = 0 and nothing else.
 //
-// OCC.  A third flavour: a unit that defines UVS_CAMERA_OCCLUDED next to UVS_CAMERA_PER_TRIAL (uvs_camera_occluded.hip) sees
-// camera_occluded_kernel(OccludedLoopArgs) with both switches on.  Lane o < 4 of each sensor-side wavefront evaluates rectangle o of its OUTPUT
+// OCC.  A third flavour: a unit at level kFlavourOccluded (uvs_camera_occluded.hip) sees
+// camera_occluded_kernel(OccludedLoopArgs) with PTP and OCC on.  Lane o < 4 of each sensor-side wavefront evaluates rectangle o of its OUTPUT
 // trial for step k (occluder_rect; lanes from n_occ on write "covers nothing") into s_occ[w] next to the projection, before the second barrier;
 // the detection loop reads the four dwords from there and hands them to disc_counts_in_box<true>, which takes the unoccluded walk for every
 // disc no rectangle meets.  A padding or void trial evaluates the rectangles of the trial it shadows.  Barriers and exits are where they were.
 //
-// HOLD.  A fourth flavour: a unit that defines UVS_CAMERA_HELD next to the other two switches (uvs_camera_held.hip) sees
-// camera_held_kernel(HeldLoopArgs) with all three on.  A disc whose mask is empty at step k >= 1 keeps the pair reported at step k - 1 for up
+// HOLD.  A fourth flavour: a unit at level kFlavourHeld (uvs_camera_held.hip) sees
+// camera_held_kernel(HeldLoopArgs) with HOLD on too.  A disc whose mask is empty at step k >= 1 keeps the pair reported at step k - 1 for up
 // to `hold` steps in a row (plant.hold_features states the rule).  That pair is still in s_f[ws][2 j] when lane 0 of the sensor-side wavefront
 // is about to write disc j -- the estimator read it before the last barrier and nothing wrote it since -- so holding is "leave it there and
 // log it".  The counters of consecutive misses and of held steps sit in LDS next to s_pix, written by that lane alone (G = 1: wavefront j owns
 // colour j).  Barriers and exits are where they were; padding and void trials store nothing, `held` included.
 //
-// PAINT.  A fifth flavour: a unit that defines UVS_CAMERA_PAINTED next to the other three switches (uvs_camera_painted.hip)
-// sees camera_painted_kernel(PaintedLoopArgs) with all four on.  An occluder may be painted a disc's colour: a distractor, whose pixels enter
+// PAINT.  A fifth flavour: a unit at level kFlavourPainted (uvs_camera_painted.hip)
+// sees camera_painted_kernel(PaintedLoopArgs) with PAINT on too.  An occluder may be painted a disc's colour: a distractor, whose pixels enter
 // that colour's mask.  Lane o < 4, where it evaluates rectangle o into s_occ[w], also leaves the rectangle's paint as byte o of s_paint[w]
 // (paint_slot; opaque from n_occ on and for a NULL operand) -- one dword per trial, indexed by OUTPUT trial like the occluders -- and the
 // detection loop hands both to detect_pair<true, true>.  Barriers and exits are where they were.
 //
-// SCENES.  A sixth flavour: a unit that defines UVS_CAMERA_SCENES next to the other four switches (uvs_camera_scenes.hip) sees
-// camera_scene_kernel(ScenesLoopArgs) with all five on.  The camera that renders a trial's frames is the trial's own: a uvs_camera struct in
+// SCENES.  A sixth flavour: a unit at level kFlavourScenes (uvs_camera_scenes.hip) sees
+// camera_scene_kernel(ScenesLoopArgs) with SCENES on too.  The camera that renders a trial's frames is the trial's own: a uvs_camera struct in
 // memory, picked by OUTPUT trial through (cams, n_cams, cam_index) as the believed loop picks its models.  The workgroup's G scenes are staged
 // once, before the step loop, into s_cam[G] (472 B each, by all 256 threads; one barrier of its own, before the first step, because the first
 // reader -- the sines -- comes before the step's first barrier), and joint_sincos_rows and project_lane_disc read s_cam[ws] where the other
@@ -61,22 +64,22 @@
 // struct.  A padding trial stages the scene of the trial it shadows; a trial whose index names no scene stages zeros and is `void` exactly as
 // one whose source index names no input trial is: FAILed by its flag, not by what the zeros give.  The step's barriers and exits are where they were.
 //
-// MOVING.  A seventh flavour: a unit that defines UVS_CAMERA_MOVING next to the other five switches (uvs_camera_moving.hip) sees
-// moving_target_kernel(MovingLoopArgs) with all six on.  The discs of a trial move: a uvs_target_motion per OUTPUT trial (velocities and one
+// MOVING.  A seventh flavour: a unit at level kFlavourMoving (uvs_camera_moving.hip) sees
+// moving_target_kernel(MovingLoopArgs) with MOVING on too.  The discs of a trial move: a uvs_target_motion per OUTPUT trial (velocities and one
 // window), staged once into s_mot[G] (104 B each) next to the scenes -- the barrier that covers those covers these -- and read by lanes
 // < n_points alone, where project_lane_disc_at forms the moved point in transient registers; nothing is written back to s_cam, which the four
 // wavefronts of the one-trial form share.  A padding trial stages the motion of the trial it shadows; a NULL operand stages zeros: nothing
 // moves.  The step's barriers and exits are where they were.
 //
-// DELAYED.  An eighth flavour: a unit that defines UVS_CAMERA_DELAYED next to the other six switches (uvs_camera_delayed.hip) sees
-// delayed_frames_kernel(DelayedLoopArgs) with all seven on.  The detector is handed the frame of step max(k - d, 0), d the OUTPUT trial's latency,
+// DELAYED.  An eighth flavour: a unit at level kFlavourDelayed (uvs_camera_delayed.hip) sees
+// delayed_frames_kernel(DelayedLoopArgs) with DELAYED on too.  The detector is handed the frame of step max(k - d, 0), d the OUTPUT trial's latency,
 // read once before the step loop (a padding wavefront: that of the trial it shadows).  Frames are not kept: the DETECTION of every step goes
 // through s_ring[trial slot][disc][k mod 9] (delay_line, vision_device.hpp), written and read by lane 0 of the wavefront that finished
 // detect_pair for that disc -- in the one-trial form each disc still belongs to exactly one wavefront -- between detect_pair and noisy_centre.
 // Occluders, paints and motion are evaluated at step k as before; the ring carries their effect.  No barrier and no exit is added.
 //
-// ALIGNED.  A ninth flavour: a unit that defines UVS_CAMERA_ALIGNED next to the other seven switches (uvs_camera_aligned.hip) sees
-// aligned_frames_kernel(AlignedLoopArgs) with all eight on.  The controller is told a latency: each OUTPUT trial has an ASSUMED latency a (the
+// ALIGNED.  A ninth flavour: a unit at level kFlavourAligned (uvs_camera_aligned.hip) sees
+// aligned_frames_kernel(AlignedLoopArgs) with ALIGNED on too.  The controller is told a latency: each OUTPUT trial has an ASSUMED latency a (the
 // rule: plant.aligned_regressor_step), read once before the step loop by the estimator-side lanes for their etrial (lanes beyond G L and a
 // padding slot: that of the trial they shadow).  The estimator's regressor at step k is the command of step k - 1 - a, or zeros before there
 // was one; the command integrated into the joints stays dq_{k-1}.  Wavefront 0 keeps the last nine commands per trial slot in
@@ -90,8 +93,8 @@
 // words of s_sum, updated by the same three operations per step: 3 R doubles fewer per lane, 0 B of scratch in all 22.  No barrier and no
 // exit is added.
 //
-// PREDICTED.  A tenth flavour: a unit that defines UVS_CAMERA_PREDICTED next to the other eight switches (uvs_camera_predicted.hip)
-// sees predicted_frames_kernel(PredictedLoopArgs) with all nine on.  The control law no longer servoes on a stale row: each OUTPUT trial has a
+// PREDICTED.  A tenth flavour: a unit at level kFlavourPredicted (uvs_camera_predicted.hip)
+// sees predicted_frames_kernel(PredictedLoopArgs) with PREDICTED on too.  The control law no longer servoes on a stale row: each OUTPUT trial has a
 // prediction HORIZON p (the rule: plant.prediction_steps; uvs_vision.h, FEATURE PREDICTION), read once before the step loop by the lanes
 // that read `assumed`, and after the update the error is err_r = (f_r + sum_j X_k[r][j] s[j]) - desired_r, s = cmd_{k-1} + ... + cmd_{k-p}
 // summed newest first from s = 0, a step before 0 being the zero vector -- the Smith form: X absorbs t_s, so X s is what the commands issued
@@ -102,8 +105,8 @@
 // of step k + 1, which take one word per fma: no lane holds s in registers across the update.  The reported row is read again from s_f
 // after the update for the same reason.  No barrier and no exit is added.
 //
-// LOGGED.  An eleventh flavour: a unit that defines UVS_CAMERA_LOGGED next to the other nine switches (uvs_camera_logged.hip) sees
-// logged_frames_kernel(LoggedLoopArgs) with all ten on.  The estimate itself is a log: x_log [K][T][M N], row k = X_k, the matrix AFTER step k's
+// LOGGED.  An eleventh flavour: a unit at level kFlavourLogged (uvs_camera_logged.hip) sees
+// logged_frames_kernel(LoggedLoopArgs) with LOGGED on too: the highest level.  The estimate itself is a log: x_log [K][T][M N], row k = X_k, the matrix AFTER step k's
 // update -- the one step k's law and prediction read -- element i N + j = X[i][j], the layout of x0.  Each owner lane of wavefront 0 stores the
 // R rows it holds, R N contiguous doubles, next to the step's dq row and under the condition of the err, kappa and dq rows (alive && estore:
 // rows k < k_done of valid trials that are not void); shadow lanes and padding slots store nothing.  One cursor, x_at, advances with err_at;
@@ -180,123 +183,38 @@ struct LoggedLoopArgs : PredictedLoopArgs {
     double *x_log;
 };
 
-#ifdef UVS_CAMERA_LOGGED
-#ifndef UVS_CAMERA_PREDICTED
-#error "the logged flavour is a predicted flavour: define UVS_CAMERA_PREDICTED (and UVS_CAMERA_ALIGNED, UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING, UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
+// The unit's flavour: the value it gave UVS_CAMERA_FLAVOUR.  Row f of the three tables below -- level, argument block, kernel name -- is one flavour.
+enum CameraFlavour {
+    kFlavourUniform, kFlavourPerTrial, kFlavourOccluded, kFlavourHeld, kFlavourPainted, kFlavourScenes, kFlavourMoving, kFlavourDelayed,
+    kFlavourAligned, kFlavourPredicted, kFlavourLogged
+};
+using CameraLoopArgsList = std::tuple<LoopArgs, GridLoopArgs, OccludedLoopArgs, HeldLoopArgs, PaintedLoopArgs, ScenesLoopArgs, MovingLoopArgs,
+                                      DelayedLoopArgs, AlignedLoopArgs, PredictedLoopArgs, LoggedLoopArgs>;
+#define UVS_CAMERA_KERNEL_0 camera_loop_kernel
+#define UVS_CAMERA_KERNEL_1 camera_grid_kernel
+#define UVS_CAMERA_KERNEL_2 camera_occluded_kernel
+#define UVS_CAMERA_KERNEL_3 camera_held_kernel
+#define UVS_CAMERA_KERNEL_4 camera_painted_kernel
+#define UVS_CAMERA_KERNEL_5 camera_scene_kernel
+#define UVS_CAMERA_KERNEL_6 moving_target_kernel
+#define UVS_CAMERA_KERNEL_7 delayed_frames_kernel
+#define UVS_CAMERA_KERNEL_8 aligned_frames_kernel
+#define UVS_CAMERA_KERNEL_9 predicted_frames_kernel
+#define UVS_CAMERA_KERNEL_10 logged_frames_kernel
+
+#ifndef UVS_CAMERA_FLAVOUR
+#error "state the unit's flavour before including this header: #define UVS_CAMERA_FLAVOUR <0 .. 10>, a value of CameraFlavour"
 #endif
-constexpr bool kCameraLogged = true;
-#else
-constexpr bool kCameraLogged = false;
-#endif
-#ifdef UVS_CAMERA_PREDICTED
-#ifndef UVS_CAMERA_ALIGNED
-#error "the predicted flavour is an aligned flavour: define UVS_CAMERA_ALIGNED (and UVS_CAMERA_DELAYED, UVS_CAMERA_MOVING, UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
-#endif
-constexpr bool kCameraPredicted = true;
-#else
-constexpr bool kCameraPredicted = false;
-#endif
-#ifdef UVS_CAMERA_ALIGNED
-#ifndef UVS_CAMERA_DELAYED
-#error "the aligned flavour is a delayed flavour: define UVS_CAMERA_DELAYED (and UVS_CAMERA_MOVING, UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
-#endif
-constexpr bool kCameraAligned = true;
-#else
-constexpr bool kCameraAligned = false;
-#endif
-#ifdef UVS_CAMERA_DELAYED
-#ifndef UVS_CAMERA_MOVING
-#error "the delayed flavour is a moving flavour: define UVS_CAMERA_MOVING (and UVS_CAMERA_SCENES, UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
-#endif
-constexpr bool kCameraDelayed = true;
-#else
-constexpr bool kCameraDelayed = false;
-#endif
-#ifdef UVS_CAMERA_MOVING
-#ifndef UVS_CAMERA_SCENES
-#error "the moving flavour is a scenes flavour: define UVS_CAMERA_SCENES (and UVS_CAMERA_PAINTED, UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
-#endif
-constexpr bool kCameraMoving = true;
-#else
-constexpr bool kCameraMoving = false;
-#endif
-#ifdef UVS_CAMERA_SCENES
-#ifndef UVS_CAMERA_PAINTED
-#error "the scenes flavour is a painted flavour: define UVS_CAMERA_PAINTED (and UVS_CAMERA_HELD, UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
-#endif
-constexpr bool kCameraScenes = true;
-#else
-constexpr bool kCameraScenes = false;
-#endif
-#ifdef UVS_CAMERA_PAINTED
-#ifndef UVS_CAMERA_HELD
-#error "the painted flavour is a held flavour: define UVS_CAMERA_HELD (and UVS_CAMERA_OCCLUDED, UVS_CAMERA_PER_TRIAL) too"
-#endif
-constexpr bool kCameraPainted = true;
-#else
-constexpr bool kCameraPainted = false;
-#endif
-#ifdef UVS_CAMERA_HELD
-#ifndef UVS_CAMERA_OCCLUDED
-#error "the held flavour is an occluded flavour: define UVS_CAMERA_OCCLUDED (and UVS_CAMERA_PER_TRIAL) too"
-#endif
-constexpr bool kCameraHeld = true;
-#else
-constexpr bool kCameraHeld = false;
-#endif
-#ifdef UVS_CAMERA_OCCLUDED
-#ifndef UVS_CAMERA_PER_TRIAL
-#error "the occluded flavour is a per-trial flavour: define UVS_CAMERA_PER_TRIAL too"
-#endif
-constexpr bool kCameraOccluded = true;
-#else
-constexpr bool kCameraOccluded = false;
-#endif
-#if defined(UVS_CAMERA_LOGGED)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = LoggedLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL logged_frames_kernel
-#elif defined(UVS_CAMERA_PREDICTED)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = PredictedLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL predicted_frames_kernel
-#elif defined(UVS_CAMERA_ALIGNED)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = AlignedLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL aligned_frames_kernel
-#elif defined(UVS_CAMERA_DELAYED)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = DelayedLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL delayed_frames_kernel
-#elif defined(UVS_CAMERA_MOVING)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = MovingLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL moving_target_kernel
-#elif defined(UVS_CAMERA_SCENES)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = ScenesLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL camera_scene_kernel
-#elif defined(UVS_CAMERA_PAINTED)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = PaintedLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL camera_painted_kernel
-#elif defined(UVS_CAMERA_HELD)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = HeldLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL camera_held_kernel
-#elif defined(UVS_CAMERA_OCCLUDED)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = OccludedLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL camera_occluded_kernel
-#elif defined(UVS_CAMERA_PER_TRIAL)
-constexpr bool kCameraPerTrial = true;
-using CameraLoopKernelArgs = GridLoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL camera_grid_kernel
-#else
-constexpr bool kCameraPerTrial = false;
-using CameraLoopKernelArgs = LoopArgs;
-#define UVS_CAMERA_LOOP_KERNEL camera_loop_kernel
-#endif
+constexpr int kCameraFlavour = UVS_CAMERA_FLAVOUR;
+static_assert(kCameraFlavour >= kFlavourUniform && kCameraFlavour <= kFlavourLogged, "UVS_CAMERA_FLAVOUR is a value of CameraFlavour");
+constexpr bool kCameraPerTrial = kCameraFlavour >= kFlavourPerTrial, kCameraOccluded = kCameraFlavour >= kFlavourOccluded;
+constexpr bool kCameraHeld = kCameraFlavour >= kFlavourHeld, kCameraPainted = kCameraFlavour >= kFlavourPainted;
+constexpr bool kCameraScenes = kCameraFlavour >= kFlavourScenes, kCameraMoving = kCameraFlavour >= kFlavourMoving;
+constexpr bool kCameraDelayed = kCameraFlavour >= kFlavourDelayed, kCameraAligned = kCameraFlavour >= kFlavourAligned;
+constexpr bool kCameraPredicted = kCameraFlavour >= kFlavourPredicted, kCameraLogged = kCameraFlavour >= kFlavourLogged;
+using CameraLoopKernelArgs = std::tuple_element_t<kCameraFlavour, CameraLoopArgsList>;
+#define UVS_CAMERA_LOOP_KERNEL UVS_PASTE(UVS_CAMERA_KERNEL_, UVS_CAMERA_FLAVOUR)
+
 __device__ __forceinline__ const uvs_camera_trial_params *trial_params_of(const LoopArgs &) { return nullptr; }
 __device__ __forceinline__ const uvs_camera_trial_params *trial_params_of(const GridLoopArgs &a) { return &a.tp; }
 // the occluders of output trial `trial` and their number (never called on the other two blocks: OCC is off there)
@@ -751,6 +669,88 @@ inline bool launch_loop_shape(const uvs_filter_params &fp, hipStream_t s, const 
     if (fp.m == 6) return launch_loop<6, 6, 2, false>(fp.method, s, A);
     if (fp.m == 2) return launch_loop<2, 6, 1, true>(fp.method, s, A);
     return false;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the one host path
+// Every operand an estimator loop can take.  An entry point fills the ones it has from its parameters; the others stay NULL / 0 and are
+// not read at its unit's flavour.  `cam` belongs to the flavours below kFlavourScenes, (cams, n_cams, cam_index) to those from it on.
+struct LoopRequest {
+    const uvs_filter_params *fp;
+    const uvs_camera *cam;
+    const uvs_camera *cams;
+    int64_t n_cams;
+    const int32_t *cam_index;
+    const uvs_target_motion *motion;
+    const int32_t *latency, *assumed, *predict;
+    int64_t T;
+    const uvs_camera_trial_params *tp;
+    const uvs_occluder *occ;
+    const int32_t *paint;
+    int32_t n_occ, hold;
+    const double *q_start, *noise, *x0, *f0;
+    double *q_log, *f_log, *dq_log, *err_log, *kappa_log, *x_log;
+    int32_t *status, *k_done;
+    double *stats;
+    int32_t *pixels, *held;
+    void *stream;
+};
+
+// The unit's argument block from the request, member by name.  A template so that the members are dependent: a branch for a member the
+// unit's block does not have is discarded, not compiled.  `cam`: the camera of the launch, or from kFlavourScenes on its shape alone.
+// static, like run_camera_loop below: the body reads the unit's own constants.
+template <class Args>
+static void fill_loop_args(Args &A, const LoopRequest &r, const uvs_camera &cam) {
+    A.fp = *r.fp; A.cam = cam; A.T = r.T;
+    A.q_start = r.q_start; A.noise = r.noise; A.x0 = r.x0; A.f0 = r.f0;
+    A.q_log = r.q_log; A.f_log = r.f_log; A.dq_log = r.dq_log; A.err_log = r.err_log; A.kappa_log = r.kappa_log;
+    A.status = r.status; A.k_done = r.k_done; A.stats = r.stats; A.pixels = r.pixels;
+    if constexpr (kCameraPerTrial) A.tp = r.tp != nullptr ? *r.tp : uvs_camera_trial_params{};   // NULL tp: every member NULL
+    if constexpr (kCameraOccluded) { A.occ = r.occ; A.n_occ = r.n_occ; }
+    if constexpr (kCameraHeld) { A.hold = r.hold; A.held = r.held; }
+    if constexpr (kCameraPainted) A.paint = r.paint;             // NULL: every rectangle opaque
+    if constexpr (kCameraScenes) { A.S.models = r.cams; A.S.n = r.n_cams; A.S.index = r.cam_index; }
+    if constexpr (kCameraMoving) A.motion = r.motion;            // NULL is legal: nothing moves
+    if constexpr (kCameraDelayed) A.latency = r.latency;         // NULL is legal: no latency
+    if constexpr (kCameraAligned) A.assumed = r.assumed;         // NULL is legal: the controller is not told
+    if constexpr (kCameraPredicted) A.predict = r.predict;       // NULL is legal: no prediction
+    if constexpr (kCameraLogged) A.x_log = r.x_log;              // NULL is legal: no log of X, the predicted namesake bit for bit
+}
+
+// What every estimator loop entry point does, at the unit's flavour: the refusals that apply there, in the order the entry points always made
+// them and before the first HIP call; T == 0 is a call that does nothing; the argument block; the launch.  Two orders exist: the flavours
+// that take a `cam` hand it to check_loop_args, those that take scenes refuse a NULL fp first and derive the shape from fp.
+// static: the body differs from unit to unit under one signature, so it must not be merged across the library's units at link time.
+static int run_camera_loop(const LoopRequest &r) {
+    g_err[0] = '\0';
+    uvs_camera shape;
+    const uvs_camera *cam = r.cam;
+    if constexpr (kCameraScenes) {
+        if (r.fp == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL fp");
+        shape = scene_shape(r.fp->n, r.fp->m / 2);               // the shape is fp's: no struct's own n_joints / n_points is read
+        cam = &shape;
+    }
+    if (const int rc = check_loop_args(r.fp, cam, r.T, r.q_start, r.x0, r.f0, r.status, r.k_done, r.stats)) return rc;
+    if constexpr (kCameraFlavour == kFlavourPerTrial) {          // the grid call alone insists on its block; from kFlavourOccluded on NULL is "no block"
+        if (r.tp == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL tp (a block whose members are all NULL is the uniform call)");
+    }
+    if constexpr (kCameraPerTrial) {
+        if (r.tp != nullptr && r.tp->source != nullptr && r.tp->n_in < 1)
+            return fail(UVS_ERR_ARG, "%s", "source needs n_in >= 1: the trials q_start, noise, x0 and f0 hold");
+    }
+    if constexpr (kCameraOccluded) {
+        if (const int rc = check_occluders(r.occ, r.n_occ)) return rc;
+    }
+    if constexpr (kCameraHeld) {
+        if (r.hold < 0) return fail(UVS_ERR_ARG, "%s", "hold must be >= 0");
+    }
+    if constexpr (kCameraScenes) {
+        if (const int rc = check_scenes(r.cams, r.n_cams, r.cam_index, r.T)) return rc;
+    }
+    if (r.T == 0) return UVS_OK;
+    CameraLoopKernelArgs A{};
+    fill_loop_args(A, r, *cam);
+    if (!launch_loop_shape(*r.fp, static_cast<hipStream_t>(r.stream), A)) return fail(UVS_ERR_SHAPE, "%s", "(m, n) must be (8, 6), (6, 6) or (2, 6)");
+    return launched(UVS_STR(UVS_CAMERA_LOOP_KERNEL) " launch: %s");
 }
 
 }  // namespace uvs_vision

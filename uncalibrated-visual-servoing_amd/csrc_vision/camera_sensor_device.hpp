@@ -1,5 +1,5 @@
 // What the one-launch pixel loops share, written ONCE: the sensor side of a step -- joints, projection, frame-free detection, lane 0's report,
-// the epilogue's stores -- for the estimator loop (camera_loop_device.hpp, ten flavours) and the baseline loop (camera_analytical_device.hpp,
+// the epilogue's stores -- for the estimator loop (camera_loop_device.hpp, eleven flavours) and the baseline loop (camera_analytical_device.hpp,
 // seven); the analytic initial guess of a trial for the two guess kernels; and the mapping's constants with the launch decision that goes with them.
 // The pieces are __device__ __forceinline__ functions over LDS row pointers and plain values: they declare no LDS and nothing is shared at
 // run time, so every kernel keeps the registers, LDS and scratch it had when the text was written out in it (a shared
@@ -9,9 +9,16 @@
 #include "../csrc/rmckf_device.hpp"
 
 #include <climits>
+#include <tuple>
 
 #include "uvs_vision.h"
 #include "vision_device.hpp"
+
+// A loop header's kernel name from its table and the unit's flavour level (an integer literal), and that name as text for launched()
+#define UVS_PASTE_(a, b) a##b
+#define UVS_PASTE(a, b) UVS_PASTE_(a, b)
+#define UVS_STR_(x) #x
+#define UVS_STR(x) UVS_STR_(x)
 
 namespace uvs_vision {
 

@@ -13,7 +13,8 @@
 //   camera_analytical_step_kernel: 64 / L trials per wavefront; padding lanes shadow the last trial, so every cross-lane move of the
 //     solver sees a full wavefront, and store nothing.
 //   camera_analytical_loop_kernel: the calibrated flavour of the baseline loop's one text, which camera_analytical_device.hpp holds and
-//     describes; this unit compiles it as it is (uvs_camera_believed.hip defines UVS_CAMERA_BELIEVED and gets the other flavour).
+//     describes; this unit compiles it at level 0 (uvs_camera_believed.hip states level 1 and gets the believed flavour).
+#define UVS_BASELINE_FLAVOUR 0                                   // kBaselineCalibrated
 #include "camera_analytical_device.hpp"
 
 namespace uvs_vision {
@@ -89,15 +90,11 @@ int uvs_camera_analytical_step_f64(const uvs_filter_params *fp, const uvs_camera
 int uvs_camera_analytical_loop_f64(const uvs_filter_params *fp, const uvs_camera *cam, int64_t T, const double *q_start, const double *noise,
                                    double *q_log, double *f_log, double *dq_log, double *err_log, int32_t *status, int32_t *k_done,
                                    double *stats, int32_t *pixels, void *stream) {
-    g_err[0] = '\0';
-    if (q_start == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL q_start");
-    if (status == nullptr || k_done == nullptr || stats == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL status, k_done or stats");
-    if (const int rc = check_analytical(fp, cam, T)) return rc;
-    if (fp->steps < 1) return fail(UVS_ERR_ARG, "%s", "steps must be >= 1");
-    if (T == 0) return UVS_OK;
-    const ALoopArgs A{*fp, *cam, T, q_start, noise, q_log, f_log, dq_log, err_log, status, k_done, stats, pixels};
-    launch_baseline_loop(*fp, static_cast<hipStream_t>(stream), A);
-    return launched("camera_analytical_loop_kernel launch: %s");
+    BaselineRequest r{};
+    r.fp = fp; r.cam = cam; r.T = T;
+    r.q_start = q_start; r.noise = noise; r.q_log = q_log; r.f_log = f_log; r.dq_log = dq_log; r.err_log = err_log;
+    r.status = status; r.k_done = k_done; r.stats = stats; r.pixels = pixels; r.stream = stream;
+    return run_baseline_loop(r);
 }
 
 }  // extern "C"

@@ -12,8 +12,8 @@
 // models through LDS (472 B each) once, before the first step, and analytical_step reads s_cam[slot] where it uses a value:
 //   camera_believed_step_kernel: the mapping of camera_analytical_step_kernel (64 / L trials per wavefront, padding lanes shadow the last
 //     trial and store nothing) with the 64 / L models of the wavefront in LDS: 7 552 B, 15 104 B, 30 208 B at L = 4, 2, 1.
-//   camera_believed_loop_kernel: the believed flavour of the baseline loop's one text (camera_analytical_device.hpp; this unit defines
-//     UVS_CAMERA_BELIEVED): camera_analytical_loop_kernel with s_cam[G] staged from memory in place of its one s_cam, and a trial without
+//   camera_believed_loop_kernel: the believed flavour of the baseline loop's one text (camera_analytical_device.hpp; this unit states
+//     level 1): camera_analytical_loop_kernel with s_cam[G] staged from memory in place of its one s_cam, and a trial without
 //     a model FAILed before step 0.  The sensor side keeps reading the true camera from the kernel arguments.
 //   camera_believed_guess_kernel: camera_guess_kernel's arithmetic (guess_trial, camera_sensor_device.hpp), one lane per trial, the model
 //     read from memory where it is used.
@@ -21,7 +21,7 @@
 // An index outside [0, n_believed) never becomes an address: model_of returns -1 for it, the staging loop writes zeros in its place (the
 // lanes of that trial keep computing on them: every cross-lane move of the solver sees a full wavefront), and the trial is FAILed by the
 // flag, not by what the zeros give: status FAIL (the loop: k_done = 0) and not one other store.
-#define UVS_CAMERA_BELIEVED
+#define UVS_BASELINE_FLAVOUR 1                                   // kBaselineWithModel
 #include "camera_analytical_device.hpp"
 
 namespace uvs_vision {
@@ -84,15 +84,6 @@ __global__ __launch_bounds__(64) void camera_believed_guess_kernel(const Believe
     guess_trial(B.models[model], t, n_points, q_start, f0, x0_out);
 }
 
-// What the entry points ask of the believed operand; before the first HIP call.
-static int check_believed(const uvs_camera *believed, int64_t n_believed, const int32_t *believed_index, int64_t T) {
-    if (believed == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL believed");
-    if (n_believed < 1 || n_believed > INT32_MAX) return fail(UVS_ERR_ARG, "%s", "n_believed must be 1 .. 2^31 - 1");
-    if (believed_index == nullptr && n_believed != 1 && n_believed != T)
-        return fail(UVS_ERR_ARG, "%s", "without believed_index, n_believed must be 1 or T");
-    return UVS_OK;
-}
-
 template <int M, int N, int L>
 static void launch_bstep(hipStream_t s, const BStepArgs &A) {
     const unsigned blocks = static_cast<unsigned>((A.T * L + 63) / 64);
@@ -130,16 +121,11 @@ int uvs_camera_believed_loop_f64(const uvs_filter_params *fp, const uvs_camera *
                                  const int32_t *believed_index, const double *q_start, const double *noise, double *q_log, double *f_log,
                                  double *dq_log, double *err_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels,
                                  void *stream) {
-    g_err[0] = '\0';
-    if (q_start == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL q_start");
-    if (status == nullptr || k_done == nullptr || stats == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL status, k_done or stats");
-    if (const int rc = check_analytical(fp, cam, T)) return rc;
-    if (fp->steps < 1) return fail(UVS_ERR_ARG, "%s", "steps must be >= 1");
-    if (const int rc = check_believed(believed, n_believed, believed_index, T)) return rc;
-    if (T == 0) return UVS_OK;
-    const BLoopArgs A{*fp, *cam, {believed, n_believed, believed_index}, T, q_start, noise, q_log, f_log, dq_log, err_log, status, k_done, stats, pixels};
-    launch_baseline_loop(*fp, static_cast<hipStream_t>(stream), A);
-    return launched("camera_believed_loop_kernel launch: %s");
+    BaselineRequest r{};
+    r.fp = fp; r.cam = cam; r.T = T; r.believed = believed; r.n_believed = n_believed; r.believed_index = believed_index;
+    r.q_start = q_start; r.noise = noise; r.q_log = q_log; r.f_log = f_log; r.dq_log = dq_log; r.err_log = err_log;
+    r.status = status; r.k_done = k_done; r.stats = stats; r.pixels = pixels; r.stream = stream;
+    return run_baseline_loop(r);
 }
 
 int uvs_camera_believed_guess_f64(int64_t T, int32_t n_points, const uvs_camera *believed, int64_t n_believed, const int32_t *believed_index,

@@ -4,9 +4,7 @@
 // an LDS ring of detections per disc.  The law's joints are the current ones -- encoders are not delayed -- so an interaction matrix at
 // q_k is fed features of the pose d steps ago.  That is the experiment.  A unit of its own, so that the four other flavours keep their
 // resource figures.
-#define UVS_CAMERA_SCENES
-#define UVS_CAMERA_MOVING
-#define UVS_CAMERA_DELAYED
+#define UVS_BASELINE_FLAVOUR 4                                   // kBaselineWithLatency
 #include "camera_analytical_device.hpp"
 
 using namespace uvs_vision;
@@ -18,25 +16,12 @@ int uvs_camera_believed_loop_delayed_f64(const uvs_filter_params *fp, const uvs_
                                          int64_t n_believed, const int32_t *believed_index, const double *q_start, const double *noise,
                                          double *q_log, double *f_log, double *dq_log, double *err_log, int32_t *status, int32_t *k_done,
                                          double *stats, int32_t *pixels, void *stream) {
-    g_err[0] = '\0';
-    if (q_start == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL q_start");
-    if (status == nullptr || k_done == nullptr || stats == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL status, k_done or stats");
-    if (fp == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL fp");
-    const uvs_camera shape = scene_shape(fp->n, fp->m / 2);         // the shape is fp's: no struct's own n_joints / n_points is read
-    if (const int rc = check_analytical(fp, &shape, T)) return rc;
-    if (fp->steps < 1) return fail(UVS_ERR_ARG, "%s", "steps must be >= 1");
-    if (believed == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL believed");
-    if (n_believed < 1 || n_believed > INT32_MAX) return fail(UVS_ERR_ARG, "%s", "n_believed must be 1 .. 2^31 - 1");
-    if (believed_index == nullptr && n_believed != 1 && n_believed != T)
-        return fail(UVS_ERR_ARG, "%s", "without believed_index, n_believed must be 1 or T");
-    if (const int rc = check_scenes(cams, n_cams, cam_index, T)) return rc;
-    if (T == 0) return UVS_OK;
-    const DelayedBaselineArgs A{{{*fp, shape, {believed, n_believed, believed_index}, {cams, n_cams, cam_index}, T, q_start, noise, q_log, f_log,
-                                  dq_log, err_log, status, k_done, stats, pixels},
-                                 motion},                            // NULL is legal: nothing moves
-                                latency};                            // NULL is legal: no latency
-    launch_baseline_loop(*fp, static_cast<hipStream_t>(stream), A);
-    return launched("delayed_baseline_kernel launch: %s");
+    BaselineRequest r{};
+    r.fp = fp; r.cams = cams; r.n_cams = n_cams; r.cam_index = cam_index; r.motion = motion; r.latency = latency;
+    r.T = T; r.believed = believed; r.n_believed = n_believed; r.believed_index = believed_index;
+    r.q_start = q_start; r.noise = noise; r.q_log = q_log; r.f_log = f_log; r.dq_log = dq_log; r.err_log = err_log;
+    r.status = status; r.k_done = k_done; r.stats = stats; r.pixels = pixels; r.stream = stream;
+    return run_baseline_loop(r);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // libuvs_vision.so, second unit: the pixel closed loop (engine.camera_closed_loop) as ONE launch per batch, and its analytic initial guess.
 // The loop kernel's text, its mapping and its launcher are camera_loop_device.hpp, which this unit compiles in its uniform flavour
 // (camera_loop_kernel: one uvs_filter_params for the batch); uvs_camera_grid.hip compiles the per-trial flavour of the same text.
+#define UVS_CAMERA_FLAVOUR 0                                     // kFlavourUniform
 #include "camera_loop_device.hpp"
 
 namespace uvs_vision {
@@ -22,12 +23,12 @@ extern "C" {
 int uvs_camera_closed_loop_f64(const uvs_filter_params *fp, const uvs_camera *cam, int64_t T, const double *q_start, const double *noise,
                                const double *x0, const double *f0, double *q_log, double *f_log, double *dq_log, double *err_log,
                                double *kappa_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, void *stream) {
-    g_err[0] = '\0';
-    if (const int rc = check_loop_args(fp, cam, T, q_start, x0, f0, status, k_done, stats)) return rc;
-    if (T == 0) return UVS_OK;
-    const LoopArgs A{*fp, *cam, T, q_start, noise, x0, f0, q_log, f_log, dq_log, err_log, kappa_log, status, k_done, stats, pixels};
-    if (!launch_loop_shape(*fp, static_cast<hipStream_t>(stream), A)) return fail(UVS_ERR_SHAPE, "%s", "(m, n) must be (8, 6), (6, 6) or (2, 6)");
-    return launched("camera_loop_kernel launch: %s");
+    LoopRequest r{};
+    r.fp = fp; r.cam = cam; r.T = T;
+    r.q_start = q_start; r.noise = noise; r.x0 = x0; r.f0 = f0;
+    r.q_log = q_log; r.f_log = f_log; r.dq_log = dq_log; r.err_log = err_log; r.kappa_log = kappa_log;
+    r.status = status; r.k_done = k_done; r.stats = stats; r.pixels = pixels; r.stream = stream;
+    return run_camera_loop(r);
 }
 
 int uvs_camera_guess_f64(const uvs_camera *cam, int64_t T, const double *q_start, const double *f0, double *x0_out, void *stream) {

@@ -4,15 +4,7 @@
 // (f + X_k s) - desired, s the sum of the trial's last p commands from the command ring, p the output trial's prediction HORIZON.
 // z, f_prev, kappa, the f log, the regressor and the joints stay what they were.  A unit of its own, like uvs_camera_aligned.hip, so that
 // its 22 instantiations compile next to the others and those keep their resource figures.
-#define UVS_CAMERA_PER_TRIAL
-#define UVS_CAMERA_OCCLUDED
-#define UVS_CAMERA_HELD
-#define UVS_CAMERA_PAINTED
-#define UVS_CAMERA_SCENES
-#define UVS_CAMERA_MOVING
-#define UVS_CAMERA_DELAYED
-#define UVS_CAMERA_ALIGNED
-#define UVS_CAMERA_PREDICTED
+#define UVS_CAMERA_FLAVOUR 9                                     // kFlavourPredicted
 #include "camera_loop_device.hpp"
 
 using namespace uvs_vision;
@@ -26,29 +18,14 @@ int uvs_camera_closed_loop_predicted_f64(const uvs_filter_params *fp, const uvs_
                                          const double *x0, const double *f0, double *q_log, double *f_log, double *dq_log, double *err_log,
                                          double *kappa_log, int32_t *status, int32_t *k_done, double *stats, int32_t *pixels, int32_t *held,
                                          void *stream) {
-    g_err[0] = '\0';
-    if (fp == nullptr) return fail(UVS_ERR_ARG, "%s", "NULL fp");
-    const uvs_camera shape = scene_shape(fp->n, fp->m / 2);         // the shape is fp's: no struct's own n_joints / n_points is read
-    if (const int rc = check_loop_args(fp, &shape, T, q_start, x0, f0, status, k_done, stats)) return rc;
-    if (tp != nullptr && tp->source != nullptr && tp->n_in < 1)
-        return fail(UVS_ERR_ARG, "%s", "source needs n_in >= 1: the trials q_start, noise, x0 and f0 hold");
-    if (const int rc = check_occluders(occ, n_occ)) return rc;
-    if (hold < 0) return fail(UVS_ERR_ARG, "%s", "hold must be >= 0");
-    if (const int rc = check_scenes(cams, n_cams, cam_index, T)) return rc;
-    if (T == 0) return UVS_OK;
-    const uvs_camera_trial_params none{};                            // NULL tp: every member NULL
-    const PredictedLoopArgs A{{{{{{{{{{*fp, shape, T, q_start, noise, x0, f0, q_log, f_log, dq_log, err_log, kappa_log, status, k_done, stats, pixels},
-                                   tp != nullptr ? *tp : none},
-                                  occ, n_occ},
-                                 hold, held},
-                                paint},
-                               {cams, n_cams, cam_index}},
-                              motion},                               // NULL is legal: nothing moves
-                             latency},                               // NULL is legal: no latency
-                            assumed},                                // NULL is legal: the controller is not told
-                           predict};                                 // NULL is legal: no prediction
-    if (!launch_loop_shape(*fp, static_cast<hipStream_t>(stream), A)) return fail(UVS_ERR_SHAPE, "%s", "(m, n) must be (8, 6), (6, 6) or (2, 6)");
-    return launched("predicted_frames_kernel launch: %s");
+    LoopRequest r{};
+    r.fp = fp; r.cams = cams; r.n_cams = n_cams; r.cam_index = cam_index; r.motion = motion; r.latency = latency; r.assumed = assumed;
+    r.predict = predict;
+    r.T = T; r.tp = tp; r.occ = occ; r.paint = paint; r.n_occ = n_occ; r.hold = hold;
+    r.q_start = q_start; r.noise = noise; r.x0 = x0; r.f0 = f0;
+    r.q_log = q_log; r.f_log = f_log; r.dq_log = dq_log; r.err_log = err_log; r.kappa_log = kappa_log;
+    r.status = status; r.k_done = k_done; r.stats = stats; r.pixels = pixels; r.held = held; r.stream = stream;
+    return run_camera_loop(r);
 }
 
 }  // extern "C"

@@ -1081,6 +1081,29 @@ def _features_step(cam_ref, T, dt, occ, stream, hold=0, npts=0, dev=None, paint=
     return held_step
 
 
+# What asks for each flavour of a one-launch pixel loop, highest flavour first: the flavours are a chain, so the entry point of a call is the
+# one of the highest flavour anything given asks for (``_vision.ESTIMATOR_LOOPS`` / ``BASELINE_LOOPS`` name them, lowest first).
+ESTIMATOR_LOOP_ASKS = ('x', 'predict', 'assumed', 'latency', 'motion', 'scenes', 'paint', 'hold', 'occluders', 'trial_params')
+BASELINE_LOOP_ASKS = ('predict', 'assumed', 'latency', 'motion', 'scenes', 'believed')
+
+
+def _loop_entry(asks, entries, given):
+    flavour = max((len(asks) - rank for rank, name in enumerate(asks) if name in given), default=0)
+    return entries[flavour]
+
+
+def _estimator_loop_entry(given):
+    """The estimator loop entry point for a call in which the members of ``given`` -- names of ``ESTIMATOR_LOOP_ASKS`` -- are given ('x': in want)."""
+    from . import _vision
+    return _loop_entry(ESTIMATOR_LOOP_ASKS, _vision.ESTIMATOR_LOOPS, given)
+
+
+def _baseline_loop_entry(given):
+    """The baseline loop entry point for a call in which the members of ``given`` -- names of ``BASELINE_LOOP_ASKS`` -- are given."""
+    from . import _vision
+    return _loop_entry(BASELINE_LOOP_ASKS, _vision.BASELINE_LOOPS, given)
+
+
 def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believed=None, occ=None, hold=0, paint=None, scenes=None, motion=None,
                                    latency=None, assumed=None, predict=None):
     """camera_closed_loop for fp.method == ANALYTICAL: the one launch (fused) or K x (camera features, analytical step) on rows of the logs.
@@ -1088,20 +1111,19 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
     ``occ``: None, or the occluder operand of the stepwise loop (the one launch has none).  ``hold`` > 0 (stepwise alone): a third launch per
     step, uvs_hold_features_f64, between the two.  ``paint``: None, or the paint operand next to ``occ`` (stepwise alone).
     ``scenes``: None, or the (pointer, n_cams, index pointer) of ``_scene_operand`` -- every trial's frames come from its own camera
-    (the one launch: uvs_camera_believed_loop_scenes_f64; stepwise: uvs_camera_features_scenes_f64); ``believed`` is then given, and
+    (stepwise: uvs_camera_features_scenes_f64); ``believed`` is then given, and
     ``cam`` is the shape alone.  ``motion``: None, or the pointer of ``_motion_operand`` next to ``scenes`` -- the sensor side's discs move
-    (the one launch: uvs_camera_believed_loop_moving_f64; stepwise: uvs_camera_features_moving_f64); the law's model does not.
+    (stepwise: uvs_camera_features_moving_f64); the law's model does not.
     ``latency``: None, or the pointer of ``_latency_operand`` next to ``scenes`` -- the detector is handed the frame of step max(k - d, 0)
-    (the one launch: uvs_camera_believed_loop_delayed_f64, with or without ``motion``; stepwise: uvs_delay_features_f64 behind the
-    features call); the law's joints are the current ones.
+    (stepwise: uvs_delay_features_f64 behind the features call); the law's joints are the current ones.
     ``assumed``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the ASSUMED latencies next to ``scenes`` -- the joints the
-    law is handed at step k are those of step max(k - a, 0) (the one launch: uvs_camera_believed_loop_aligned_f64, with or without
-    ``latency`` and ``motion``; stepwise: per trial that row of the q log, gathered by torch indexing -- a copy, no arithmetic).
+    law is handed at step k are those of step max(k - a, 0) (stepwise: per trial that row of the q log, gathered by torch indexing -- a
+    copy, no arithmetic).
     ``predict``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the prediction HORIZONS next to ``scenes`` -- the law is
-    handed f^ = f + (h(q_k) - h(q_{max(k - p, 0)})), h the projection of its own model (the one launch:
-    uvs_camera_believed_loop_predicted_f64, with or without the three above; stepwise: two uvs_camera_project_scenes_f64 calls on the
-    law's models, at row k of the q log and at the per-trial gather of rows max(k - p_t, 0), and the two torch operations of the rule on
-    the launches' stream).  The f log stays the reported row."""
+    handed f^ = f + (h(q_k) - h(q_{max(k - p, 0)})), h the projection of its own model (stepwise: two uvs_camera_project_scenes_f64 calls
+    on the law's models, at row k of the q log and at the per-trial gather of rows max(k - p_t, 0), and the two torch operations of the
+    rule on the launches' stream).  The f log stays the reported row.
+    The one launch is the entry point ``_baseline_loop_entry`` names for the operands given: the highest flavour any of them needs."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -1116,24 +1138,14 @@ def _camera_closed_loop_analytical(fp, cam, q_start, noise, fused, want, believe
         status, k_done = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2))
         stats = torch.empty((T, 3), **f64)
         pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
-        outputs = (ptr('q'), ptr('f'), ptr('dq'), ptr('err'), status.data_ptr(), k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
-        if predict is not None:
-            rc = _vision.lib().uvs_camera_believed_loop_predicted_f64(C.byref(fp), *scenes, motion, latency, None if assumed is None else assumed[0],
-                                                                      predict[0], T, *believed, q0, noise_ptr, *outputs)
-        elif assumed is not None:
-            rc = _vision.lib().uvs_camera_believed_loop_aligned_f64(C.byref(fp), *scenes, motion, latency, assumed[0], T, *believed, q0, noise_ptr,
-                                                                    *outputs)
-        elif latency is not None:
-            rc = _vision.lib().uvs_camera_believed_loop_delayed_f64(C.byref(fp), *scenes, motion, latency, T, *believed, q0, noise_ptr, *outputs)
-        elif motion is not None:
-            rc = _vision.lib().uvs_camera_believed_loop_moving_f64(C.byref(fp), *scenes, motion, T, *believed, q0, noise_ptr, *outputs)
-        elif scenes is not None:
-            rc = _vision.lib().uvs_camera_believed_loop_scenes_f64(C.byref(fp), *scenes, T, *believed, q0, noise_ptr, *outputs)
-        elif believed is None:
-            rc = _vision.lib().uvs_camera_analytical_loop_f64(C.byref(fp), C.byref(cam), T, q0, noise_ptr, *outputs)
-        else:
-            rc = _vision.lib().uvs_camera_believed_loop_f64(C.byref(fp), C.byref(cam), T, *believed, q0, noise_ptr, *outputs)
-        _vision.check(rc)
+        first = lambda operand: None if operand is None else operand[0]   # noqa: E731
+        given = dict(predict=predict, assumed=assumed, latency=latency, motion=motion, scenes=scenes, believed=believed)
+        values = dict(fp=C.byref(fp), cam=C.byref(cam), motion=motion, latency=latency, assumed=first(assumed), predict=first(predict), T=T,
+                      q_start=q0, noise=noise_ptr, q_log=ptr('q'), f_log=ptr('f'), dq_log=ptr('dq'), err_log=ptr('err'), status=status.data_ptr(),
+                      k_done=k_done.data_ptr(), stats=stats.data_ptr(), pixels=pixels.data_ptr(), stream=_stream())
+        values.update(zip(('cams', 'n_cams', 'cam_index'), scenes or (None, 0, None)))
+        values.update(zip(('believed', 'n_believed', 'believed_index'), believed or (None, 0, None)))
+        _vision.check(_vision.call_loop(_baseline_loop_entry({name for name, operand in given.items() if operand is not None}), values))
         return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
     log = {key: torch.empty((K, T, comp), **f64) for key, comp in comps.items()}
     status_log = torch.zeros((K, T), dtype=torch.int32, device=dev)
@@ -1249,24 +1261,22 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     """camera_closed_loop(fused=True): at most three launches and no host loop.  ``trial_params``: None, or the dict of camera_closed_loop --
     then q_start, noise and x0 hold the n_in input trials, and T, the number of output trials, is len(source) where there is one.
     ``occluders``: None, or what ``_check_occluders`` returned for the T output trials (there is no 'source' next to them: see
-    ``_gather_by_source``) -- the launch is then uvs_camera_closed_loop_occluded_f64, with or without trial_params.  ``hold`` > 0: the launch
-    is uvs_camera_closed_loop_held_f64, with or without either, and the result has 'held'.  ``paints``: None, or what
-    ``_check_occluder_colours`` returned next to ``occluders`` -- the launch is then uvs_camera_closed_loop_painted_f64 for any hold >= 0,
-    and the result has 'held' only with hold > 0.  ``scenes``: None, or the (operand, packed cameras, index tensor or None) of
-    ``_scene_operand`` for the T output trials (no 'source' next to them either) -- the launch is then uvs_camera_closed_loop_scenes_f64,
-    whatever else is given; f0 comes from the step-0 frame of every trial's own scene, and x0 is given (camera_closed_loop has made it).
+    ``_gather_by_source``).  ``hold`` > 0: the result has 'held'.  ``paints``: None, or what ``_check_occluder_colours`` returned next to
+    ``occluders``.  ``scenes``: None, or the (operand, packed cameras, index tensor or None) of
+    ``_scene_operand`` for the T output trials (no 'source' next to them either);
+    f0 comes from the step-0 frame of every trial's own scene, and x0 is given (camera_closed_loop has made it).
     A fourth member, True, says that the one scene is the NOMINAL camera standing in for a moving launch without ``cameras``: ``cam`` is then
     the model of every trial, and guess='device' may still make x0 from it.
-    ``motion``: None, or the (pointer, packed tensor) of ``_motion_operand`` for the T output trials next to ``scenes`` -- the launch is
-    then uvs_camera_closed_loop_moving_f64, and f0 comes from the step-0 frame, where s(0) applies.
-    ``latency``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the T output trials next to ``scenes`` -- the launch is
-    then uvs_camera_closed_loop_delayed_f64, with or without ``motion``; f0 still comes from the step-0 frame.
-    ``assumed``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the ASSUMED latencies of the T output trials next to
-    ``scenes`` -- the launch is then uvs_camera_closed_loop_aligned_f64, with or without ``latency`` and ``motion``.
-    ``predict``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the prediction HORIZONS of the T output trials next to
-    ``scenes`` -- the launch is then uvs_camera_closed_loop_predicted_f64, with or without the three above.
-    'x' in ``want`` (camera_closed_loop has made ``scenes``): the launch is uvs_camera_closed_loop_logged_f64, whatever else is given, and
-    the result has 'x' (K, T, m n): X_k after step k's update, rows k < k_done."""
+    ``motion``: None, or the (pointer, packed tensor) of ``_motion_operand`` for the T output trials next to ``scenes``; f0 comes from the
+    step-0 frame, where s(0) applies.
+    ``latency``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the T output trials next to ``scenes``; f0 still comes
+    from the step-0 frame.
+    ``assumed``, ``predict``: None, or the (pointer, int32 tensor) of ``_latency_operand`` for the ASSUMED latencies and the prediction
+    HORIZONS of the T output trials next to ``scenes``.
+    'x' in ``want`` (camera_closed_loop has made ``scenes``): the result has 'x' (K, T, m n): X_k after step k's update, rows k < k_done.
+    The launch is the entry point ``_estimator_loop_entry`` names for what is given: the highest flavour any of it asks for, whatever else
+    is given or not.  ``motion``, ``latency``, ``assumed``, ``predict`` and 'x' REQUIRE ``scenes``: their entry points take the scene operand
+    where the lower ones take ``cam``, and without it the library refuses the call (NULL cams)."""
     from . import _vision
     torch = _torch()
     K, m, n, npts = fp.steps, fp.m, fp.n, cam.n_points
@@ -1296,59 +1306,19 @@ def _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, want, trial_pa
     status, k_done = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2))
     stats = torch.empty((T, 3), **f64)
     pixels = torch.empty((T, npts), dtype=torch.int32, device=dev)
-    operands = (q0, noise_ptr, X0.data_ptr(), f0.data_ptr(), ptr('q'), ptr('f'), ptr('dq'), ptr('err'), ptr('kappa'), status.data_ptr(),
-                k_done.data_ptr(), stats.data_ptr(), pixels.data_ptr(), _stream())
-    if scenes is not None:
-        held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
-        rest = (T, None if tp is None else C.byref(tp), None if occ is None else occ[0], None if paint is None else paint[0],
-                0 if occ is None else occ[1], hold, *operands[:-1], None if held is None else held.data_ptr(), operands[-1])
-        if 'x' in log:                                               # operands[8] is kappa_log: x_log stands directly after it
-            rest = rest[:15] + (log['x'].data_ptr(),) + rest[15:]
-            rc = _vision.lib().uvs_camera_closed_loop_logged_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0],
-                                                                 None if latency is None else latency[0],
-                                                                 None if assumed is None else assumed[0],
-                                                                 None if predict is None else predict[0], *rest)
-        elif predict is not None:
-            rc = _vision.lib().uvs_camera_closed_loop_predicted_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0],
-                                                                    None if latency is None else latency[0],
-                                                                    None if assumed is None else assumed[0], predict[0], *rest)
-        elif assumed is not None:
-            rc = _vision.lib().uvs_camera_closed_loop_aligned_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0],
-                                                                  None if latency is None else latency[0], assumed[0], *rest)
-        elif latency is not None:
-            rc = _vision.lib().uvs_camera_closed_loop_delayed_f64(C.byref(fp), *scenes[0], None if motion is None else motion[0], latency[0],
-                                                                  *rest)
-        elif motion is None:
-            rc = _vision.lib().uvs_camera_closed_loop_scenes_f64(C.byref(fp), *scenes[0], *rest)
-        else:
-            rc = _vision.lib().uvs_camera_closed_loop_moving_f64(C.byref(fp), *scenes[0], motion[0], *rest)
-        _vision.check(rc)
-        out = dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
-        return dict(out, held=held) if hold else out
-    if paint is not None:
-        held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
-        rc = _vision.lib().uvs_camera_closed_loop_painted_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp), occ[0], paint[0],
-                                                              occ[1], hold, *operands[:-1], None if held is None else held.data_ptr(),
-                                                              operands[-1])
-        _vision.check(rc)
-        out = dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
-        return dict(out, held=held) if hold else out
-    if hold:
-        held = torch.empty((T, npts), dtype=torch.int32, device=dev)
-        rc = _vision.lib().uvs_camera_closed_loop_held_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp),
-                                                           None if occ is None else occ[0], 0 if occ is None else occ[1], hold, *operands[:-1],
-                                                           held.data_ptr(), operands[-1])
-        _vision.check(rc)
-        return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats, held=held)
-    if occ is not None:
-        rc = _vision.lib().uvs_camera_closed_loop_occluded_f64(C.byref(fp), C.byref(cam), T, None if tp is None else C.byref(tp), occ[0], occ[1],
-                                                               *operands)
-    elif tp is None:
-        rc = _vision.lib().uvs_camera_closed_loop_f64(C.byref(fp), C.byref(cam), T, *operands)
-    else:
-        rc = _vision.lib().uvs_camera_closed_loop_grid_f64(C.byref(fp), C.byref(cam), T, C.byref(tp), *operands)
-    _vision.check(rc)
-    return dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
+    held = torch.empty((T, npts), dtype=torch.int32, device=dev) if hold else None
+    first = lambda operand: None if operand is None else operand[0]   # noqa: E731
+    given = dict(x='x' in log or None, predict=predict, assumed=assumed, latency=latency, motion=motion, scenes=scenes, paint=paint,
+                 hold=hold or None, occluders=occ, trial_params=tp)
+    values = dict(fp=C.byref(fp), cam=C.byref(cam), motion=first(motion), latency=first(latency), assumed=first(assumed), predict=first(predict),
+                  T=T, tp=None if tp is None else C.byref(tp), occ=first(occ), paint=first(paint), n_occ=0 if occ is None else occ[1], hold=hold,
+                  q_start=q0, noise=noise_ptr, x0=X0.data_ptr(), f0=f0.data_ptr(), q_log=ptr('q'), f_log=ptr('f'), dq_log=ptr('dq'),
+                  err_log=ptr('err'), kappa_log=ptr('kappa'), x_log=ptr('x'), status=status.data_ptr(), k_done=k_done.data_ptr(),
+                  stats=stats.data_ptr(), pixels=pixels.data_ptr(), held=None if held is None else held.data_ptr(), stream=_stream())
+    values.update(zip(('cams', 'n_cams', 'cam_index'), (None, 0, None) if scenes is None else scenes[0]))
+    _vision.check(_vision.call_loop(_estimator_loop_entry({name for name, operand in given.items() if operand is not None}), values))
+    out = dict(log, pixels=pixels, status=status, k_done=k_done, stats=stats)
+    return dict(out, held=held) if hold else out
 
 
 def _gather_by_source(q_start, noise, x0, trial_params):
@@ -1366,6 +1336,15 @@ def _gather_by_source(q_start, noise, x0, trial_params):
         x0 = torch.as_tensor(x0, dtype=torch.float64, device=dev).reshape(n_in, -1).index_select(0, index)
     return (q_start.index_select(0, index).contiguous(), None if noise is None else noise.index_select(1, index).contiguous(), x0,
             {key: value for key, value in trial_params.items() if key != 'source'})
+
+
+def _loop_camera(fp, plant, radius):
+    """camera_closed_loop's uvs_camera of ``plant``; ValueError unless its shape is fp's."""
+    from . import plant as plant_mod
+    cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    if fp.m != 2 * cam.n_points or fp.n != cam.n_joints:
+        raise ValueError(f'camera_closed_loop: fp is ({fp.m}, {fp.n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
+    return cam
 
 
 def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, fused=False, guess='host', want=CAMERA_LOGS, believed=None,
@@ -1417,7 +1396,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     trial_params['source'] the inputs are gathered by source before the launch (an out-of-range index is then a ValueError, also on the
     device), because the step-0 frame belongs to the output trial.
     ``hold``: an integer >= 0, one for the call: the largest number of consecutive steps for which a LOST disc's pair is held -- the rule of
-    ``plant.hold_features`` (include/uvs_vision.h, uvs_camera_closed_loop_held_f64).  A disc is lost at step k iff its mask is empty there,
+    ``plant.hold_features`` (include/uvs_vision.h, HOLDING a lost disc's last detection).  A disc is lost at step k iff its mask is empty there,
     behind an occluder or out of the frame alike; from step 1 on, and while its run of misses is shorter than ``hold``, the loop reports
     step k - 1's pair again (that step's noise in it, none of step k's) instead of NaN, and the estimator or the law takes it like any
     other.  Once the hold is used up, and at step 0, a lost disc is the NaN pair and FAIL of above.  0 (the default) is the call without
@@ -1572,15 +1551,12 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         if unknown:
             raise ValueError(f'camera_closed_loop: the calibrated baseline logs {ANALYTICAL_CAMERA_LOGS}, it has no {unknown}')
     n_out = getattr(q_start, 'shape', (0,))[0]
-    if latency is not None and trial_params is not None and trial_params.get('source') is not None:
-        n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
-    delays = _check_latency(latency, n_out, 'camera_closed_loop')    # None, or (T,) int32 on the host, by output trial
-    if assumed_latency is not None and latency is None and trial_params is not None and trial_params.get('source') is not None:
-        n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
-    tolds = _check_latency(assumed_latency, n_out, 'camera_closed_loop', 'assumed_latency')   # likewise
-    if predict is not None and latency is None and assumed_latency is None and trial_params is not None and trial_params.get('source') is not None:
-        n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
-    horizons = _check_latency(predict, n_out, 'camera_closed_loop', 'predict')   # likewise
+    checked = []                                                     # each None, or (T,) int32 on the host, by output trial
+    for name, value in (('latency', latency), ('assumed_latency', assumed_latency), ('predict', predict)):
+        if value is not None and trial_params is not None and trial_params.get('source') is not None:
+            n_out = _check_camera_trial_params(trial_params, q_start.shape[0])[0]
+        checked.append(_check_latency(value, n_out, 'camera_closed_loop', name))
+    delays, tolds, horizons = checked
     if horizons is not None and not analytical and not fused:
         raise ValueError('camera_closed_loop: predict needs fused=True: the two-launch step kernel forms the error the law acts on itself')
     if (delays is not None or tolds is not None or horizons is not None) and cameras is None and not nominal:   # the nominal camera stands in as the one scene here too
@@ -1607,10 +1583,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
         raise ValueError('camera_closed_loop: q_start must be on the device (the logs are allocated next to it)')
     scenes, scene_kw = None, {}                                      # the scene operand of the T output trials, and what the calls below take
     if nominal:
-        cameras = [_camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)]
-        if m != 2 * cameras[0].n_points or n != cameras[0].n_joints:
-            raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cameras[0].n_points} features of '
-                             f'{cameras[0].n_joints} joints')
+        cameras = [_loop_camera(fp, plant, radius)]
     if cameras is not None:
         scenes = _scene_operand(cameras, camera_index, T, m // 2, n, radius, dev, 'camera_closed_loop') + (nominal,)
         scene_kw = dict(cameras=scenes[1], camera_index=scenes[2])
@@ -1621,9 +1594,7 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
     told = None if tolds is None else _latency_operand(tolds, dev)   # likewise, the assumed latencies
     ahead = None if horizons is None else _latency_operand(horizons, dev)   # likewise, the prediction horizons
     if analytical:
-        cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
-        if m != 2 * cam.n_points or n != cam.n_joints:
-            raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
+        cam = _loop_camera(fp, plant, radius)
         occ = None if occluders is None else _occluder_operand(occluders, dev)
         paint = None if paints is None else _paint_operand(paints, dev)
         if believed is None and scenes is None:
@@ -1636,25 +1607,19 @@ def camera_closed_loop(fp, plant, q_start, noise=None, radius=None, x0=None, *, 
                                               scenes=None if scenes is None else scenes[0], motion=None if mot is None else mot[0],
                                               latency=None if lat is None else lat[0], assumed=told, predict=ahead)
     if believed is not None or (scenes is not None and not nominal and x0 is None):  # an estimator that starts from a model in memory: the believed one, or
-        cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)                           # its own scene; the rest is the x0= path
-        if m != 2 * cam.n_points or n != cam.n_joints:
-            raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
+        cam = _loop_camera(fp, plant, radius)                        # its own scene; the rest is the x0= path
         if not fp.initial_guess:
             raise ValueError('camera_closed_loop: x0 is needed when fp.initial_guess is 0 (the reference draws it unseeded, experiment.py:117)')
         models, index = (believed, believed_index) if believed is not None else (scenes[1], scenes[2])
         x0 = camera_guess(cam, q_start, camera_features(cam, q_start, occluders=occluders, occluder_colours=paints, **scene_kw), radius=radius,
                           believed=models, believed_index=index)
     if fused and (x0 is not None or guess == 'device' or not fp.initial_guess):
-        cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
-        if m != 2 * cam.n_points or n != cam.n_joints:
-            raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * cam.n_points} features of {cam.n_joints} joints')
+        cam = _loop_camera(fp, plant, radius)
         return _camera_closed_loop_fused(fp, cam, q_start, noise, x0, guess, tuple(want), trial_params, occluders, hold, paints, scenes, mot, lat, told, ahead)
     if not isinstance(plant, plant_mod.SyntheticPlant):
         raise ValueError('camera_closed_loop: plant must be a SyntheticPlant (the analytic initial guess needs its host kinematics)')
-    cam = _camera(plant, plant_mod.DISC_RADIUS if radius is None else radius)
+    cam = _loop_camera(fp, plant, radius)
     npts = cam.n_points
-    if m != 2 * npts or n != cam.n_joints:
-        raise ValueError(f'camera_closed_loop: fp is ({m}, {n}) but the camera gives {2 * npts} features of {cam.n_joints} joints')
     q0 = _operand(q_start, 'q_start', torch.float64, (T, n))
     noise_ptr = _operand(noise, 'noise', torch.float64, (K, T, m), True)
     f64 = dict(dtype=torch.float64, device=dev)
